@@ -12,8 +12,9 @@ of the gradients:
     second half of the headline metric) and for every other BASELINE config at 256 images per GPU; `values` repeats all images/s figures at top level.
 `--only W` measures a single workload (profiling runs).  Prints ONE JSON line on rank 0.
 `--gpus N` without a launcher (WORLD_SIZE unset) starts the N ranks itself (torch.distributed.run, 127.0.0.1) and relays rank 0's line.
-The timed region is repeated `--repeats` times (each EXACTLY `--steps` steps between barriers); `value` / `ms_per_step` are the MEDIAN window,
-`ms_per_step_min` the best one.
+The timed region is EXACTLY `--steps` steps after `--warmup` untimed ones (and the graph capture's own three), split into `--repeats` windows between barriers (default one); `value` /
+`ms_per_step` are the MEDIAN window, `ms_per_step_min` the best one.  `--dump-outputs DIR` saves what the last timed step computed (same inputs on every run:
+seeded weights and batch) so that two builds can be compared output for output.
 
 roofline.achieved = the dominant kernel's designed HBM bytes / its HIP-event duration (events recorded by the library on the
 launch stream around every launch).  roofline.traffic / roofline.mfma_busy come from rocprofv3 PMC passes that THIS run
@@ -103,14 +104,14 @@ def build(workload, device):
     return model, make_optimizer(model, 0.01, wd)
 
 
-REFERENCE_DIR = os.environ.get("MICRONET_REFERENCE", "/root/reference")
+REFERENCE_DIR = os.environ.get("MICRONET_REFERENCE", "")
 
 
 def cpu_baseline(workload, batch, steps, threads=0, kind="auto"):
-    """The reference's algorithm on the host cores.  kind "reference": the reference's OWN modules (imported from MICRONET_REFERENCE, default /root/reference, in a
-    child process -- its package is also called `micronet`; present in the build container only, never on the GPU box); "port": the torch-CPU oracle
+    """The reference's algorithm on the host cores.  kind "reference": the reference's OWN modules (imported from the checkout MICRONET_REFERENCE names, in a
+    child process -- its package is also called `micronet`; never on the GPU box); "port": the torch-CPU oracle
     (oracle/torch_oracle.py, bit-identical to the reference on CPU: tests/test_oracle_golden.py); "auto": the reference where it is importable, else the port."""
-    if kind in ("auto", "reference") and os.path.isdir(os.path.join(REFERENCE_DIR, "micronet")):
+    if kind in ("auto", "reference") and REFERENCE_DIR and os.path.isdir(os.path.join(REFERENCE_DIR, "micronet")):
         cmd = [sys.executable, os.path.abspath(__file__), "--cpu-ref-child", "--only", workload, "--cpu-batch", str(batch), "--cpu-steps", str(steps),
                "--cpu-threads", str(threads)]
         r = subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1800)
@@ -229,19 +230,22 @@ def measure(workload, args, world, rank, device):
 
     def one_step():
         if graphed is not None:
-            return graphed.step()[0]
-        return dp.train_step_dp(model, opt, sync, x, y)[0]
+            return graphed.step()
+        return dp.train_step_dp(model, opt, sync, x, y)
 
     for _ in range(args.warmup):
         one_step()
+    # exactly args.steps timed steps, split into --repeats windows between barriers; each window's time is scaled to args.steps steps
+    nwin = min(args.repeats, args.steps)
     windows, rank_dts = [], []
-    for _ in range(max(1, args.repeats)):
+    for i in range(nwin):
+        n = args.steps // nwin + (1 if i < args.steps % nwin else 0)
         barrier()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            loss = one_step()
+        for _ in range(n):
+            loss, logits = one_step()
         barrier()
-        dt = time.perf_counter() - t0
+        dt = (time.perf_counter() - t0) * args.steps / n
         if world > 1:
             t = torch.tensor([dt], device=device, dtype=torch.float64)
             every = [torch.empty_like(t) for _ in range(world)]
@@ -251,8 +255,9 @@ def measure(workload, args, world, rank, device):
         windows.append(dt)
     from micronet_amd import ops as _ops
     fallbacks = _ops.fallback_counts(reset=True)           # stock-operator fall-throughs seen while this workload ran (warm-up, capture, eager steps): expected {}
-    dt = sorted(windows)[len(windows) // 2]                 # the median window (an odd count by default)
+    dt = sorted(windows)[len(windows) // 2]                 # the median window
     final_loss = float(loss.detach())
+    outputs = last_step_outputs(model, loss, logits) if args.dump_outputs and rank == 0 else None
     # data-parallel runs: what the step's collectives cost by themselves -- the gradient bucket(s) all-reduced 10 times back to back, HIP events on the stream
     dp_info = None
     if dp.active() and graphed is not None and getattr(graphed, "flat", None) is not None:
@@ -312,7 +317,41 @@ def measure(workload, args, world, rank, device):
     del graphed, model, opt, sync
     torch.cuda.empty_cache()
     return dict(dt=dt, dt_min=min(windows), windows=windows, final_loss=final_loss, hip_graph=graph_err is None and not args.no_graph, graph_err=graph_err, agg=agg,
-                eager_dp=eager_dp, fallbacks=fallbacks, segments=segments, dp_info=dp_info)
+                eager_dp=eager_dp, fallbacks=fallbacks, segments=segments, dp_info=dp_info, outputs=outputs)
+
+
+DUMP_SAMPLE = 1 << 20                 # elements kept of a larger dumped array (resnet18's 11.2 M parameters): a fixed, seeded sample
+DUMP_MAX_BYTES = 64 << 20
+
+
+def last_step_outputs(model, loss, logits):
+    """What the timed step's last replay computed: the loss and logits it returns, and the parameters, gradients and floating-point buffers (BatchNorm
+    statistics, observer ranges) it left in the model -- each flattened in module order, float32 on the host."""
+    import numpy as np
+
+    def flat(ts):
+        ts = [t.detach().reshape(-1).float() for t in ts if t is not None and t.is_floating_point()]
+        return torch.cat(ts).cpu().numpy() if ts else np.zeros(0, np.float32)
+    params = list(model.parameters())
+    return {"loss": loss.detach().float().reshape(1).cpu().numpy(), "logits": logits.detach().float().cpu().numpy(), "params": flat(params),
+            "grads": flat([p.grad for p in params]), "buffers": flat(model.buffers())}
+
+
+def dump_outputs(path, outputs):
+    """`--dump-outputs`: DIR/<workload>_<name>.npy; arrays above DUMP_SAMPLE elements are cut to the same seeded DUMP_SAMPLE indices on every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for w, outs in outputs.items():
+        for name, a in outs.items():
+            if a.size > DUMP_SAMPLE:
+                a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+            arrays["%s_%s" % (w, name)] = np.ascontiguousarray(a, dtype=np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte bound" % (total, DUMP_MAX_BYTES))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def dp_single_rank(workloads, args, device):
@@ -678,7 +717,7 @@ def main():
     ap.add_argument("--batch", type=int, default=256, help="per-GPU batch")
     ap.add_argument("--workload", default="c2", choices=list(WORKLOADS), help="primary workload (value / roofline / cpu_baseline)")
     ap.add_argument("--also", default="c1_w2a2,c2b,c1,c3,c4,c5", help="comma-separated secondary workloads reported under `also` ('' = none)")
-    ap.add_argument("--repeats", type=int, default=5, help="timed windows of --steps steps each; value = the median window")
+    ap.add_argument("--repeats", type=int, default=1, help="timed windows the --steps timed steps are split into; value = the median window")
     ap.add_argument("--master-port", type=int, default=29531, help="rendezvous port when --gpus N > 1 starts its own ranks")
     ap.add_argument("--only", default=None, choices=list(WORKLOADS), help="measure this single workload (no `also`)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -700,7 +739,12 @@ def main():
     ap.add_argument("--no-dp-single", action="store_true", help="skip the single-rank data-parallel leg (dp_single_rank: the N-GPU step's own cost measured on one rank)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dp-single-child", default="", help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed step computed in its last step, per measured workload, as DIR/<workload>_{loss,logits,params,grads,buffers}.npy "
+                         "(float32; arrays above %d elements as a fixed seeded sample)" % DUMP_SAMPLE)
     args = ap.parse_args()
+    if args.steps < 1 or args.repeats < 1:
+        ap.error("--steps and --repeats must be at least 1")
 
     primary = args.only or args.workload
     also = [] if args.only else [w for w in args.also.split(",") if w and w != primary]
@@ -765,6 +809,8 @@ def main():
             if world > 1:
                 raise                   # ranks must stay in lock-step
             also_err[w] = "%s: %s" % (type(e).__name__, str(e)[:300])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {w: m.pop("outputs") for w, m in [(primary, m_primary)] + list(m_also.items())})
 
     dp1 = None
     if world == 1 and not args.only and not args.no_kernel_timing and not args.no_dp_single:

@@ -1,5 +1,5 @@
 #!/bin/bash
-# The one parameterised GPU-box runner (run through scripts/grun.sh or gpurun directly, from the repo root):
+# The one parameterised GPU-box runner (run from the repo root on a machine with an MI355X):
 #   bash scripts/gpu_check.sh [tests|parity|bench|prof]...      (default: tests bench)
 #   tests  : pytest -m gpu (whole suite)            -> gpurun_out/pytest_gpu.log
 #   parity : only tests/test_gpu_parity_full.py      -> gpurun_out/parity_r06/

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Harvest inputs where the kernels' tanh (mn_tanh_f32: the correctly rounded fp32 value, evaluated in fp64) and torch-CPU tanh (what the reference runs: MKL VML
-vsTanh, HA mode, in this torch build) differ, for tests/golden/tanh_device_vs_cpu.json (run on a GPU box: `gpurun -- python scripts/make_tanh_fixture.py`; output
+vsTanh, HA mode, in this torch build) differ, for tests/golden/tanh_device_vs_cpu.json (run on a GPU box: `python scripts/make_tanh_fixture.py`; output
 in gpurun_out/)."""
 import json
 import os

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Build a variant of libmicronet_hip.so with one source recompiled under extra -D flags (A/B inside one gpurun call via MN_LIB_PATH).
+# Build a variant of libmicronet_hip.so with one source recompiled under extra -D flags (A/B inside one GPU run via MN_LIB_PATH).
 # Usage: scripts/variant_lib.sh <tag> <source.hip> <flags...>   -> micronet_amd/lib/libmicronet_hip_<tag>.so
 set -e
 cd "$(dirname "$0")/.."

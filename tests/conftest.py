@@ -9,7 +9,6 @@ if ROOT not in sys.path:
 sys.dont_write_bytecode = True
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-REFERENCE = os.environ.get("MICRONET_REFERENCE", "/root/reference")
 
 
 def pytest_configure(config):

@@ -18,7 +18,9 @@ import sys
 
 os.environ.setdefault("PYTHONDONTWRITEBYTECODE", "1")
 sys.dont_write_bytecode = True
-REF = os.environ.get("MICRONET_REFERENCE", "/root/reference")
+REF = os.environ.get("MICRONET_REFERENCE")
+if not REF:
+    raise SystemExit("set MICRONET_REFERENCE to a checkout of the reference micronet package")
 sys.path.insert(0, REF)
 
 import numpy as np
