@@ -158,12 +158,7 @@ static inline int mn_grad_terms() { const char* e = MN_ENV("MN_GRAD_TERMS"); ret
 // The few A/B knobs that stay (each is exercised by a test or by bench.py; the tuning knobs of rounds 1-5 are gone, their findings are in profiles/README.md):
 //   MN_GRAD_TERMS=3    the exact three-term split in the dense backward kernels (tests/test_gpu_kernels.py, bench.py values_exact_terms)
 //   MN_HSIGN_FOLD=0    the per-channel constants of the sign pass from a launch of their own (tests/test_kernels_emulated.py)
-//   MN_QA_IEEE_DIV=1   the IEEE division in the DoReFa clip-STE instead of Markstein's correctly rounded quotient (bit-identical: tests/kernel_cases.py)
-//   MN_QA_NO_INTERVAL=1  element-wise ReLU / clamp masks instead of the per-channel interval (bit-identical)
-//   MN_NO_PACKED_PW=1  every conv call packs its own weight codes instead of reading the step's pre-packed image (bit-identical: check_qg_pack_multi)
-static inline float mn_qa_inv(float s) { return (s > 0.f && !MN_ENV("MN_QA_IEEE_DIV")) ? 1.0f / s : 0.f; }          // RN(1 / s) of the division-free clip-STE; 0 selects the IEEE form
-static inline int mn_qa_interval() { return MN_ENV("MN_QA_NO_INTERVAL") ? 0 : 1; }
-static inline bool mn_use_packed() { return !MN_ENV("MN_NO_PACKED_PW"); }
+static inline float mn_qa_inv(float s) { return s > 0.f ? 1.0f / s : 0.f; }          // RN(1 / s) of the division-free clip-STE; 0 (s <= 0) selects the IEEE form
 // the two term words of a pair of floats: hi = rne pair, lo = rne pair of the remainders
 __device__ __forceinline__ void mn_split2_bf16x2(float a, float b, unsigned& hi, unsigned& lo) {
     hi = mn_rne_bf16x2(a, b);
@@ -218,7 +213,7 @@ __device__ __forceinline__ float qa_dz(float gq, float a, float z, float s, int 
 // The same with the IEEE division of (g s) / s replaced by Markstein's three-instruction correctly rounded quotient (inv = RN(1 / s): q0 = RN(d inv),
 // r = d - s q0 exactly (one fma), RN(q0 + r inv)): bit-identical for every finite, normal d -- checked exhaustively-at-random on the host for the seven DoReFa
 // scales 1 / (2^a - 1), a = 2 .. 8, 3e8 gradients each over 2^-60 .. 2^60 (0 mismatches) -- at a third of the instructions; the streaming backward passes of the
-// k-bit blocks and the first-layer backward-weight that folds them are VALU-limited by that division.  inv == 0 selects the IEEE form (A/B knob MN_QA_IEEE_DIV).
+// k-bit blocks and the first-layer backward-weight that folds them are VALU-limited by that division.  inv == 0 selects the IEEE form.
 __device__ __forceinline__ float dorefa_act_grad_m(float g, float x, float s, float inv) {
     const float t = x * 0.1f;
     const float d0 = g * s;

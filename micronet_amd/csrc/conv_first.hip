@@ -52,7 +52,6 @@ struct C1Params {
     int quant;            // dq is the gradient w.r.t. the QUANTISED activation (the clip-STE is applied here)
     float qs;             // quantizer scale 1 / (2^a - 1)
     float qs_inv;         // RN(1 / qs) (qa_dz_m); 0: IEEE division
-    int interval;         // BN 2: the block's masks as one interval of y per channel (A/B knob MN_QA_NO_INTERVAL)
     // fused first block (k_c1b_fwd<MT, EPI 1 / 2>, k_c1_wgrad<MT, 3, 1>): the forward applies the BatchNorm (statistics known from the Gram data of x) and the
     // activation in its epilogue and writes CODES (1 byte) + the backward's masks (1 byte per 4 pixels) instead of y (4 bytes)
     const float* bn_save; // [2][O] mean, invstd
@@ -427,14 +426,14 @@ __global__ __launch_bounds__(256, 2) void k_c1_wgrad(const C1Params p) {
             ctab[r * 8 + 4] = p.training ? p.sums[mc] / p.n_f : 0.f;
             ctab[r * 8 + 5] = p.training ? p.sums[p.O + mc] / p.n_f : 0.f;
             ctab[r * 8 + 6] = BN == 2 ? p.chan[8 * p.O + mc] : 0.f; ctab[r * 8 + 7] = 0.f;
-            if (BN == 1 && DZ && p.interval) {          // the sign's clip-STE |z| < 1 as one interval of y per channel (as the DoReFa block below)
+            if (BN == 1 && DZ) {          // the sign's clip-STE |z| < 1 as one interval of y per channel (as the DoReFa block below)
                 const float mean = ctab[r * 8 + 0], invstd = ctab[r * 8 + 1], ga = ctab[r * 8 + 2], be = ctab[r * 8 + 3];
                 if (fabsf(mean) <= 1.0e9f && fabsf(invstd) <= 1.0e9f && fabsf(ga) <= 1.0e9f && fabsf(be) <= 1.0e9f && ga != 0.f && invstd > 0.f) {
                     const QaInterval iv = qa_mask_interval(0x7f7fffff, [&](float y) { return ((y - mean) * invstd) * ga + be; }, [](int32_t k) { return mn_keyf(k); }, 1, true);
                     ctab[r * 8 + 2] = iv.lo; ctab[r * 8 + 3] = iv.hi; ctab[r * 8 + 7] = 1.f;
                 }
             }
-            if (BN == 2 && p.interval) {
+            if (BN == 2) {
                 // the ReLU mask and the quantizer's clamp test as ONE interval of y per channel (qa_mask_interval, common.h): the per-element z, relu, 0.1 a and their
                 // selects (10 of ~21 VALU instructions per element of this VALU-bound fold) become two compares.  A channel whose constants are not finite (or
                 // gamma == 0: z is constant, an overflowing zhat would make it NaN) keeps the element-wise form (slot 7 = 0).
@@ -1034,7 +1033,7 @@ static int c1_bwd_weight_any(const mn_conv_geom* g, const float* gy, const float
     p.wp = nullptr; p.bias = nullptr; p.y = nullptr;
     p.da = gy ? nullptr : da; p.yb = yb; p.save = save; p.gamma = gamma; p.beta = beta; p.sums = sums; p.training = training;
     p.n_f = (float)g->N * (float)(g->H * g->W);
-    p.chan = gy ? nullptr : chan; p.quant = quant; p.qs = qs; p.qs_inv = mn_qa_inv(qs); p.interval = mn_qa_interval();
+    p.chan = gy ? nullptr : chan; p.quant = quant; p.qs = qs; p.qs_inv = mn_qa_inv(qs);
     mn_set_last_kernel("k_c1_wgrad<%d, %d>", pl.MT, p.da ? (p.chan ? 2 : 1) : 0);
     { const double ny = (double)g->N * g->O * g->H * g->W; mn_prof_bytes((p.da ? 8.0 : 4.0) * ny + 4.0 * g->N * g->C * g->H * g->W); }
     mn_prof_begin(s);
@@ -1104,7 +1103,7 @@ static int c1_bwd_first_any(const mn_conv_geom* g, const float* da, const float*
     p.wp = nullptr; p.bias = nullptr; p.y = nullptr;
     p.da = da; p.yb = yb; p.save = save; p.gamma = gamma; p.beta = beta; p.sums = nullptr; p.training = 0;          // (k1, k2 of the fold are not used: DZ)
     p.n_f = (float)g->N * (float)(g->H * g->W);
-    p.chan = chan; p.quant = quant; p.qs = qs; p.qs_inv = mn_qa_inv(qs); p.interval = mn_qa_interval();
+    p.chan = chan; p.quant = quant; p.qs = qs; p.qs_inv = mn_qa_inv(qs);
     p.mask4 = const_cast<uint8_t*>(mask4); p.mask_shift = (mask4 && quant) ? 4 : 0;
     mn_set_last_kernel("k_c1_wgrad<%d, %d, 1>", pl.MT, mask4 ? 3 : (chan ? 2 : 1));
     { const double ny = (double)g->N * g->O * g->H * g->W; mn_prof_bytes((mask4 ? 4.25 : 8.0) * ny + 4.0 * g->N * g->C * g->H * g->W); }

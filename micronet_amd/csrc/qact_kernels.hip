@@ -25,7 +25,6 @@ struct QaGeom {
     int64_t n8;             // 8-element groups per channel (no pool) / 4-window groups per channel (pool)
     float s;                // quantizer scale 1 / (2^a - 1)
     float inv_s;            // RN(1 / s) for the division-free clip-STE (qa_dz_m); 0: the IEEE division
-    int interval;           // backward passes: the ReLU / clamp masks as one interval of the streamed value per channel (qa_mask_interval; knob MN_QA_NO_INTERVAL)
     int nthr;               // > 0 (mn_qa_fwd on the integer stash, <= 3 bit codes): levels 2^a - 1 of the integer-threshold forward
     // the "final" step of the backward sums folded into the apply pass (mn_qa_bwd / mn_qr_bwd: one launch less per BatchNorm backward): every block of channel c sums
     // the S partial rows itself, in k_qa_final_bwd / k_qr_final_bwd's order (mn_row_sums: bit-identical statistics in all of them), block sp == 0 writes the outputs
@@ -214,12 +213,12 @@ __global__ __launch_bounds__(256) void k_qa_fwd(const QaGeom g, const void* __re
 // with non-finite (or absurd) constants, or gamma == 0, keeps the element-wise masks
 struct QaIv { float lo, hi; bool use; };
 template <int IN>
-__device__ __forceinline__ QaIv qa_block_interval(const QaGeom& g, const QaCh& k, int quant) {
+__device__ __forceinline__ QaIv qa_block_interval(const QaCh& k, int quant) {
     __shared__ float iv_[3];
     if (threadIdx.x == 0) {
         float use = 0.f;
         QaInterval r; r.lo = 1.f; r.hi = 0.f;
-        if (g.interval && qa_finite(k.alpha) && qa_finite(k.bias) && qa_finite(k.mean) && qa_finite(k.invstd) && qa_finite(k.ga) && qa_finite(k.be) && k.ga != 0.f && k.invstd > 0.f &&
+        if (qa_finite(k.alpha) && qa_finite(k.bias) && qa_finite(k.mean) && qa_finite(k.invstd) && qa_finite(k.ga) && qa_finite(k.be) && k.ga != 0.f && k.invstd > 0.f &&
             (IN == 1 || k.alpha != 0.f)) {
             auto zf = [&](float v) { float zh, z; qa_eval<IN>(v, k, zh, z); return z; };
             if (IN == 1) r = qa_mask_interval(0x7f7fffff, zf, [](int32_t w) { return mn_keyf(w); }, quant);
@@ -239,7 +238,7 @@ __global__ __launch_bounds__(256) void k_qa_partial(const QaGeom g, const void* 
     const int c = blockIdx.x, sp = blockIdx.y, S = gridDim.y;
     const QaCh k = qa_load_ch(chan, g.C, c);
     QaIv iv; iv.lo = 1.f; iv.hi = 0.f; iv.use = false;
-    if (!POOL) iv = qa_block_interval<IN>(g, k, quant);          // (the pooled pass needs the activations themselves: the window's first maximum)
+    if (!POOL) iv = qa_block_interval<IN>(k, quant);          // (the pooled pass needs the activations themselves: the window's first maximum)
     double s1 = 0.0, s2 = 0.0;
     for (int64_t i = (int64_t)sp * 256 + threadIdx.x; i < g.n8; i += (int64_t)S * 256) {
         float t1 = 0.f, t2 = 0.f;
@@ -328,7 +327,7 @@ __global__ __launch_bounds__(256) void k_qa_apply(const QaGeom g, const void* __
     } else { s1f = sums[c]; s2f = sums[g.C + c]; }
     if (training) { const float n = (float)g.N * (float)g.HW; k1 = s1f / n; k2 = s2f / n; }
     QaIv iv; iv.lo = 1.f; iv.hi = 0.f; iv.use = false;
-    if (!POOL) iv = qa_block_interval<IN>(g, k, quant);
+    if (!POOL) iv = qa_block_interval<IN>(k, quant);
     for (int64_t i = (int64_t)sp * 256 + threadIdx.x; i < g.n8; i += (int64_t)S * 256) {
         if (!POOL) {
             const int64_t off = qa_off8(g, c, (uint32_t)i);
@@ -461,7 +460,6 @@ static int qa_geom(QaGeom* g, int64_t N, int64_t C, int64_t H, int64_t W, int bi
     g->n8 = pool ? N * (H / 2) * (W / 8) : N * (HW / 8);
     g->s = dorefa_scale(bits);
     g->inv_s = mn_qa_inv(g->s);
-    g->interval = mn_qa_interval();
     g->nthr = 0;
     g->mask4 = nullptr;
     g->fin_part = nullptr; g->fin_S = 0; g->fin_dgamma = g->fin_dbeta = g->fin_sums = g->fin_dgamma_s = g->fin_dbeta_s = g->fin_sums_s = nullptr;

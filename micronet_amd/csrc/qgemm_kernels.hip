@@ -1012,7 +1012,7 @@ static int plan_pwd(const mn_conv_geom* g, PwdPlan* pl) {
 // the transposed weight codes + contraction-channel scales of this call: the step's pre-packed image (mn_wq.packed_bwd, written by mn_qg_pack_multi in the layout
 // [codes | scales at off_scale] of this very plan) or packed here into the call's workspace
 static void pwd_codes(PwdPlan& pd, const mn_wq* wq, const float* w, void* ws, hipStream_t s) {
-    if (wq->packed_bwd && mn_use_packed()) {
+    if (wq->packed_bwd) {
         pd.pk.codes = (uint16_t*)const_cast<void*>(wq->packed_bwd);
         pd.pk.scale_out = (float*)((char*)const_cast<void*>(wq->packed_bwd) + pd.off_scale);
         return;
@@ -1247,7 +1247,7 @@ static int qg_packm_plan(const mn_conv_geom* g, int which, PackParams* pk, int* 
 }
 extern "C" int64_t mn_qg_packed_bytes(const mn_conv_geom* g, int which) {
     PackParams pk; int grid; int64_t off, bytes;
-    if (!mn_use_packed() || !qg_packm_plan(g, which, &pk, &grid, &off, &bytes)) return 0;
+    if (!qg_packm_plan(g, which, &pk, &grid, &off, &bytes)) return 0;
     return (off + (int64_t)pk.G * (pk.transpose ? pk.Mgp : pk.Mpad) * 4 + 255) / 256 * 256;
 }
 extern "C" int mn_qg_pack_multi(int32_t count, const mn_conv_geom* const* g, const mn_wq* const* wq, const float* const* w, const int32_t* which, void* const* out,

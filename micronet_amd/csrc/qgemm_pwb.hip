@@ -27,7 +27,7 @@
 //   UP 2        the same for a k-bit (DoReFa) block in front: this dx is its d q; dz = clip-STE(dx) [ReLU / clamp masks of the upstream 16-bit stash, k_qa_partial's
 //               arithmetic] -- sum dz, sum dz zhat; k_qa_partial (6 B per element) is not launched (mn_conv2d_bwd_qa_up / mn_conv2d_bwd_codes_up / mn_qa_bwd_sums_final).
 // One barrier per step: barrier k publishes step k (buffer k & 1); the producers refill that buffer with step k + 2 only behind barrier k + 1, which both consumer
-// groups reach after their reads of step k.  What the timeline (PWB_TRACE) and the ablations of round 6 found on the way is in profiles/README.md: the SLP
+// groups reach after their reads of step k.  What the timeline and the ablations of round 6 found on the way is in profiles/README.md: the SLP
 // vectoriser drains the producers' software pipeline (this file is built with -fno-slp-vectorize), a memory instruction whose address / data register is rewritten
 // for the next one serialises on the memory pipeline's operand read, LDS reads issued just in time expose one round trip per MFMA group.
 #include "qgemm.h"
@@ -77,13 +77,6 @@ struct PwbParams {
 
 // 16-byte slot swizzle of a plane row: conflict-free b128 row reads (16 rows of one fragment) AND transpose reads (4 consecutive rows = 256 contiguous bytes)
 __device__ __forceinline__ uint32_t pwb_sw(uint32_t row) { return (0x1320u >> (4u * ((row >> 2) & 3u))) & 3u; }
-
-#ifdef PWB_TRACE          // s_memtime timeline of one block (scripts/variant_lib.sh trace qgemm_pwb.hip -DPWB_TRACE; MN_PWB_TRACE=1 prints steps 8..19 of the fifth call)
-__device__ unsigned long long g_pwb_trace[3 * 64 * 8];
-#define PWB_T(role_, t_, k_) do { if (blockIdx.x == 5 && wave == 1 && lane == 0 && (t_) < 64) g_pwb_trace[((role_) * 64 + (t_)) * 8 + (k_)] = clock64(); } while (0)
-#else
-#define PWB_T(role_, t_, k_) do { } while (0)
-#endif
 
 template <int BNH, int XENC, int WIDE, int UP = 0>
 __global__ __launch_bounds__(768, 1) void k_pwb(const PwbParams p) {
@@ -283,13 +276,9 @@ __global__ __launch_bounds__(768, 1) void k_pwb(const PwbParams p) {
         for (int t = 0; t < nit; t += NS) {
 #pragma unroll
             for (int u = 0; u < NS; ++u) {
-                PWB_T(0, t + u, 0);
                 commit(st[u], (t + u) & 1, t + u < n);
-                PWB_T(0, t + u, 1);
                 fetch(st[u], t + u + NS);
-                PWB_T(0, t + u, 2);
                 __syncthreads();
-                PWB_T(0, t + u, 3);
             }
         }
         __syncthreads();                                                   // the staging buffers are free (the dW waves stage their tiles through them)
@@ -314,7 +303,6 @@ __global__ __launch_bounds__(768, 1) void k_pwb(const PwbParams p) {
         __syncthreads();
         for (int t = 0; t < nit; ++t) {
             __syncthreads();
-            PWB_T(1, t, 0);
             if (t < n) {
                 const unsigned char* A = lds + (t & 1) * BUF;
                 // every LDS read of the step is issued before the first MFMA (read just in time, each group of MFMAs waits for its own LDS round trip)
@@ -326,7 +314,6 @@ __global__ __launch_bounds__(768, 1) void k_pwb(const PwbParams p) {
                 for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
                     for (int mi = 0; mi < 4; ++mi) af[pl][mi] = *reinterpret_cast<const u32x4*>(A + pl * PLANE + aoff + mi * 1024);
-                PWB_T(1, t, 1);
                 MN_SCHED_FENCE();
                 u32x4 bf[4];
 #pragma unroll
@@ -348,7 +335,6 @@ __global__ __launch_bounds__(768, 1) void k_pwb(const PwbParams p) {
                     for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
                         for (int ci = 0; ci < 4; ++ci) acc[mi][ci] = mn_mfma_bf16(af[pl][mi], bf[ci], acc[mi][ci]);
-                PWB_T(1, t, 2);
             }
         }
         __syncthreads();                                                   // every wave is done with the staging buffers
@@ -441,7 +427,6 @@ __global__ __launch_bounds__(768, 1) void k_pwb(const PwbParams p) {
         __syncthreads();
         for (int t = 0; t < nit; ++t) {
             __syncthreads();
-            PWB_T(2, t, 0);
             if (t < n) {
                 const unsigned char* A = lds + (t & 1) * BUF;
                 f32x16 a0, a1;
@@ -470,7 +455,6 @@ __global__ __launch_bounds__(768, 1) void k_pwb(const PwbParams p) {
                     if (kp + 2 < 4) { ldk(bq[(2 * kp) & 3], 2 * kp + 4); ldk(bq[(2 * kp + 1) & 3], 2 * kp + 5); }
                     MN_SCHED_FENCE();
                 }
-                PWB_T(2, t, 1);
                 const uint32_t P = (uint32_t)pwb_step(t) * 32u;
                 const uint32_t ni = fd_div(P, p.fd_hw);
                 // the 16 row segments leave from 16 DIFFERENT registers, addressed as uniform base + 32-bit lane offset: a store whose address / data register is
@@ -559,7 +543,6 @@ __global__ __launch_bounds__(768, 1) void k_pwb(const PwbParams p) {
                         }
                     }
                 }
-                PWB_T(2, t, 2);
             }
         }
         __syncthreads();
@@ -632,21 +615,6 @@ static void pwb_launch(const PwbPlan& pl, hipStream_t s) {
     raise_lds_limit((const void*)k_pwb<BNH, XENC, WIDE, UP>, lds);
     hipLaunchKernelGGL((k_pwb<BNH, XENC, WIDE, UP>), dim3(pl.grid), dim3(768), lds, s, pl.p);
 }
-#ifdef PWB_TRACE
-static void pwb_trace_dump(hipStream_t s) {
-    static int once = 0;
-    if (!MN_ENV("MN_PWB_TRACE") || once++ != 4) return;
-    (void)hipStreamSynchronize(s);
-    static unsigned long long hbuf[3 * 64 * 8];
-    (void)hipMemcpyFromSymbol(hbuf, HIP_SYMBOL(g_pwb_trace), sizeof hbuf);
-    const unsigned long long b0 = hbuf[(0 * 64 + 8) * 8 + 0];
-    for (int t = 8; t < 20; ++t) {
-        auto v = [&](int role, int k) { return (long long)(hbuf[(role * 64 + t) * 8 + k] - b0); };
-        fprintf(stderr, "t %2d  prod: top %6lld commit %6lld fetch %6lld barrier %6lld | dW: bar %6lld reads %6lld mfma %6lld | dx: bar %6lld mfma %6lld stores %6lld\n", t,
-                v(0, 0), v(0, 1), v(0, 2), v(0, 3), v(1, 0), v(1, 1), v(1, 2), v(2, 0), v(2, 1), v(2, 2));
-    }
-}
-#endif
 // mode: 1 wbwtab (h = byte stash; own != NULL: pooled), 3 DoReFa fold (h = 16 / 32-bit stash), 0 plain dy; xenc: 0 sign codes, 1 k-bit codes (dW times ascale)
 // the upstream block (UP variants): kind 1: byte stash + [8][C] constants (wbwtab); kind 2: 16-bit stash + [9][C] constants, the width of the quantizer behind it and
 // whether this dx is w.r.t. its quantised output (DoReFa); partials [C][Z][2]
@@ -660,7 +628,7 @@ static int pwb_run(const char* what, int mode, int xenc, int wide, const mn_conv
         MN_FAIL(MN_ENOTSUP, "%s: misaligned tensor", what);
     if (!ws || ws_bytes < pl.ws_bytes || !aligned16(ws)) MN_FAIL(MN_ENOSPC, "%s: workspace too small", what);
     PwbParams& p = pl.p;
-    if (wq->packed_bwd && mn_use_packed()) {
+    if (wq->packed_bwd) {
         p.wc = (const uint16_t*)wq->packed_bwd;
         p.kscale = (const float*)((const char*)wq->packed_bwd + pl.off_scale);
     } else {
@@ -704,9 +672,6 @@ static int pwb_run(const char* what, int mode, int xenc, int wide, const mn_conv
     else if (bnh == 3 && xenc) pwb_launch<3, 1, 1>(pl, s);
     else MN_FAIL(MN_ENOTSUP, "%s: variant not built", what);
     mn_prof_end(s);
-#ifdef PWB_TRACE
-    pwb_trace_dump(s);
-#endif
     qg_launch_wgrad_reduce_div(p.part, p.dbpart, dw, dbias, p.Z, p.G, 128, 128, 128, 128, ascale, p.kscale, s);
     MN_CHECK_LAUNCH(what);
     return MN_OK;

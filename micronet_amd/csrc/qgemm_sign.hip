@@ -1464,7 +1464,7 @@ static int pws_prepare(const mn_conv_geom* g, const mn_wq* wq, const int8_t* x, 
     if (!wq_codeable(wq) || !plan_pws(g, nt_max, pl)) MN_FAIL(MN_ENOTSUP, "%s: geometry / weight quantizer not covered by the fused sign kernels", what);
     if (!x || !w || (((uintptr_t)x) & 3)) MN_FAIL(MN_EINVAL, "%s: null / misaligned tensor", what);
     if (!ws || ws_bytes < pl->ws_bytes || !aligned16(ws)) MN_FAIL(MN_ENOSPC, "%s: workspace too small (%lld < %lld)", what, (long long)ws_bytes, (long long)pl->ws_bytes);
-    if (wq->packed_fwd && mn_use_packed()) {          // the step's pre-packed image (mn_qg_pack_multi: [codes | row scales at off_scale] of this plan)
+    if (wq->packed_fwd) {          // the step's pre-packed image (mn_qg_pack_multi: [codes | row scales at off_scale] of this plan)
         pl->pk.codes = (uint16_t*)const_cast<void*>(wq->packed_fwd);
         pl->pk.scale_out = (float*)((char*)const_cast<void*>(wq->packed_fwd) + pl->off_scale);
     } else {

@@ -29,10 +29,6 @@ from .sign_tensor import LazyBNAct, LazyBNGrad, LazyConvOut, LazyPoolGrad, LazyQ
 ACTQ_NONE, ACTQ_DOREFA, ACTQ_IAO, ACTQ_SIGN8, ACTQ_CODE8 = _lib.MN_ACTQ_NONE, _lib.MN_ACTQ_DOREFA, _lib.MN_ACTQ_IAO, _lib.MN_ACTQ_SIGN8, _lib.MN_ACTQ_CODE8
 WQ_REAL, WQ_TERNARY, WQ_DOREFA, WQ_IAO = _lib.MN_WQ_REAL, _lib.MN_WQ_TERNARY, _lib.MN_WQ_DOREFA, _lib.MN_WQ_IAO
 
-# algorithm used by the conv entry points; tests flip it to compare kernels (0 auto, 1 direct VALU, 2 fp32-MFMA only, 3 code-domain bf16-MFMA only)
-CONV_ALGO = _lib.MN_ALGO_AUTO
-
-
 # optional per-launch timing (bench.py): an object with .arm(which, nbytes) -> token (arms mn_profile_next with two raw HIP
 # events that the library records right around the main kernel) and .done(token, kernel_name)
 PROFILER = None
@@ -782,7 +778,7 @@ class ReluToken:
 def relu_premask_ok(x):
     """May the consumer of ``x`` (the output of a fused conv + ReLU) return its input gradient already masked by [x > 0]?  Only when nobody else can observe the
     un-masked gradient of ``x``: no tensor hooks, no retain_grad.  NOT detectable: ``torch.autograd.grad(loss, x)`` on such an intermediate (saliency / Grad-CAM in train
-    mode) -- it would receive the masked gradient; MN_NO_RELU_PREMASK=1 switches the pre-masking off for such uses (tests/test_gpu_bnfuse_block.py)."""
+    mode) -- it would receive the masked gradient; setting ``ops._NO_RELU_PREMASK = True`` switches the pre-masking off for such uses."""
     if _NO_RELU_PREMASK:
         return False
     return getattr(x, "_mn_relu_token", None) is not None and not getattr(x, "_backward_hooks", None) and not x.retains_grad
@@ -889,7 +885,7 @@ class IaoBNFusePW(Function):
         with torch.cuda.device_of(x):
             dwq, dbf = torch.empty_like(weight), torch.empty(O, dtype=torch.float32, device=dev)
             ws, nb = _ws(g, 2, dev)
-            _call("mn_conv2d_bwd_weight", C.byref(g), C.byref(aq), _p(gy), _p(x), _p(dwq), _p(dbf), _p(ws), nb, CONV_ALGO, _s())
+            _call("mn_conv2d_bwd_weight", C.byref(g), C.byref(aq), _p(gy), _p(x), _p(dwq), _p(dbf), _p(ws), nb, _lib.MN_ALGO_AUTO, _s())
             dw = torch.empty_like(weight)
             dbias = torch.empty(O, dtype=torch.float32, device=dev) if bias is not None else None
             dgamma, dbeta = torch.empty(O, dtype=torch.float32, device=dev), torch.empty(O, dtype=torch.float32, device=dev)
@@ -986,10 +982,10 @@ class IaoBNFuseGeneric(Function):
         none = ActQ(ACTQ_NONE, 0, 0, 0, None)
         # the first layer of a net (an image, <= 128 patch elements per output): the statistics of the raw convolution from the Gram matrix of the im2col matrix
         # (mn_iaobf_gram in patch mode) -- no raw convolution, no y_raw, and in the backward no raw backward-weight (same algebra as the pointwise layers)
-        gram_first = (not x.requires_grad) and CONV_ALGO == _lib.MN_ALGO_AUTO and g.KH > 1 and bool(lib.mn_iaobf_gram_supported(C.byref(g))) and \
+        gram_first = (not x.requires_grad) and g.KH > 1 and bool(lib.mn_iaobf_gram_supported(C.byref(g))) and \
             bool(lib.mn_conv2d_first_supported(C.byref(g), 0)) and bool(lib.mn_conv2d_first_supported(C.byref(g), 2))
         # a pointwise layer with <= 16 outputs (the classifier conv of nin_gc): HBM-bound streaming kernels on the vector units (csrc/iao_thin.hip)
-        thin = CONV_ALGO == _lib.MN_ALGO_AUTO and bool(lib.mn_iaobf_thin_supported(C.byref(g))) and x.requires_grad
+        thin = bool(lib.mn_iaobf_thin_supported(C.byref(g))) and x.requires_grad
         wt = qwt = None
         y_raw = vc = sx = None
         with torch.cuda.device_of(x):
@@ -1012,7 +1008,7 @@ class IaoBNFuseGeneric(Function):
                 _call("mn_iaobf_gram_stats", _p(weight), _p(bias), _p(gram), _p(sx), O, K, 1, n, _p(stats_raw), _p(vc), _s())
             else:
                 y_raw = torch.empty((g.N, O, Ho, Wo), dtype=torch.float32, device=dev)
-                _call("mn_conv2d_fwd", C.byref(g), C.byref(none), None, _p(x), _p(weight), _p(bias), _p(y_raw), _p(ws), nb, CONV_ALGO, _s())
+                _call("mn_conv2d_fwd", C.byref(g), C.byref(none), None, _p(x), _p(weight), _p(bias), _p(y_raw), _p(ws), nb, _lib.MN_ALGO_AUTO, _s())
                 wss = torch.empty(int(lib.mn_bn_stats_ws_floats(g.N, O, Ho * Wo)) + 2, dtype=torch.float32, device=dev)
                 _call("mn_bn_stats_fwd", _p(y_raw), g.N, O, Ho * Wo, _p(stats_raw), _p(wss), _s())
             first_bn = (not st.pretrained_model) and st.num_flag == 0
@@ -1033,7 +1029,7 @@ class IaoBNFuseGeneric(Function):
             st.__dict__["_mn_path"] = "thin" if thin else "generic"
             aq = ActQ(ACTQ_IAO, aq_.bits, aq_.q_type, 0, aqp.data_ptr())
             wd = WQ(WQ_IAO, wq_.bits, 0, 4, wqp.data_ptr())
-            first_layer = (not x.requires_grad) and CONV_ALGO == _lib.MN_ALGO_AUTO and bool(lib.mn_conv2d_first_supported(C.byref(g), 0)) and \
+            first_layer = (not x.requires_grad) and bool(lib.mn_conv2d_first_supported(C.byref(g), 0)) and \
                 bool(lib.mn_conv2d_first_supported(C.byref(g), 2))
             out = torch.empty((g.N, O, Ho, Wo), dtype=torch.float32, device=dev)
             xq, mm, count, relu_done = None, None, 0, False
@@ -1055,7 +1051,7 @@ class IaoBNFuseGeneric(Function):
                     _call("mn_conv2d_fwd_act", C.byref(g), C.byref(none), None, _p(xq), _p(qw), _p(bias_f), _p(out), 1, _p(mm), _p(ws), nb, _s())
                     relu_done = True
                 else:
-                    _call("mn_conv2d_fwd", C.byref(g), C.byref(none), None, _p(xq), _p(qw), _p(bias_f), _p(out), _p(ws), nb, CONV_ALGO, _s())
+                    _call("mn_conv2d_fwd", C.byref(g), C.byref(none), None, _p(xq), _p(qw), _p(bias_f), _p(out), _p(ws), nb, _lib.MN_ALGO_AUTO, _s())
             else:
                 cnt = int(lib.mn_conv2d_fwd_act_mm_count(C.byref(g), C.byref(aq), C.byref(wd))) if relu else 0
                 if cnt > 0:
@@ -1064,7 +1060,7 @@ class IaoBNFuseGeneric(Function):
                     _call("mn_conv2d_fwd_act", C.byref(g), C.byref(aq), C.byref(wd), _p(x), _p(qw), _p(bias_f), _p(out), 1, _p(mm), _p(ws), nb, _s())
                     relu_done = True
                 else:
-                    _call("mn_conv2d_fwd", C.byref(g), C.byref(aq), C.byref(wd), _p(x), _p(qw), _p(bias_f), _p(out), _p(ws), nb, CONV_ALGO, _s())
+                    _call("mn_conv2d_fwd", C.byref(g), C.byref(aq), C.byref(wd), _p(x), _p(qw), _p(bias_f), _p(out), _p(ws), nb, _lib.MN_ALGO_AUTO, _s())
             pre = None
             if relu and not relu_done:
                 # the conv kernel has no ReLU epilogue: one streaming pass (in place would lose the un-rectified output a foreign consumer may ask for -- it is
@@ -1097,11 +1093,11 @@ class IaoBNFuseGeneric(Function):
                 if thin:
                     _call("mn_iaobf_thin_fwd", C.byref(g), _p(x), _p(aqp), aq_.bits, _p(qwt), _p(bias_f), 0, _p(o2), None, _s())
                 elif first_layer:
-                    _call("mn_conv2d_fwd", C.byref(g), C.byref(ActQ(ACTQ_NONE, 0, 0, 0, None)), None, _p(xq), _p(qw), _p(bias_f), _p(o2), _p(ws2), nb2, CONV_ALGO, _s())
+                    _call("mn_conv2d_fwd", C.byref(g), C.byref(ActQ(ACTQ_NONE, 0, 0, 0, None)), None, _p(xq), _p(qw), _p(bias_f), _p(o2), _p(ws2), nb2, _lib.MN_ALGO_AUTO, _s())
                 else:
                     aq2 = ActQ(ACTQ_IAO, aq.bits, aq.q_type, 0, aqp.data_ptr())
                     wd2 = WQ(WQ_IAO, wd.bits, 0, 4, wqp.data_ptr())
-                    _call("mn_conv2d_fwd", C.byref(g), C.byref(aq2), C.byref(wd2), _p(x), _p(qw), _p(bias_f), _p(o2), _p(ws2), nb2, CONV_ALGO, _s())
+                    _call("mn_conv2d_fwd", C.byref(g), C.byref(aq2), C.byref(wd2), _p(x), _p(qw), _p(bias_f), _p(o2), _p(ws2), nb2, _lib.MN_ALGO_AUTO, _s())
             return o2
         return LazyReluConvOut(out, dict(compute=compute, mm=(mm, count) if (want_mm and mm is not None) else None))
 
@@ -1127,9 +1123,9 @@ class IaoBNFuseGeneric(Function):
             if thin:
                 _call("mn_iaobf_thin_bwd_weight", C.byref(g), _p(gy), _p(x), _p(aqp), a_bits, 0, _p(dwq), _p(dbf), _s())
             elif first_layer:
-                _call("mn_conv2d_bwd_weight", C.byref(g), C.byref(none), _p(gy), _p(xq), _p(dwq), _p(dbf), _p(ws), nb, CONV_ALGO, _s())
+                _call("mn_conv2d_bwd_weight", C.byref(g), C.byref(none), _p(gy), _p(xq), _p(dwq), _p(dbf), _p(ws), nb, _lib.MN_ALGO_AUTO, _s())
             else:
-                _call("mn_conv2d_bwd_weight", C.byref(g), C.byref(aq), _p(gy), _p(x), _p(dwq), _p(dbf), _p(ws), nb, CONV_ALGO, _s())
+                _call("mn_conv2d_bwd_weight", C.byref(g), C.byref(aq), _p(gy), _p(x), _p(dwq), _p(dbf), _p(ws), nb, _lib.MN_ALGO_AUTO, _s())
             dw = torch.empty_like(weight)
             dbias = torch.empty(O, dtype=torch.float32, device=dev) if bias is not None else None
             dgamma, dbeta = torch.empty(O, dtype=torch.float32, device=dev), torch.empty(O, dtype=torch.float32, device=dev)
@@ -1155,15 +1151,15 @@ class IaoBNFuseGeneric(Function):
             dw_raw = torch.empty_like(weight)
             if gridqp is not None:
                 aqg = ActQ(ACTQ_IAO, ctx.xgrid[0], ctx.xgrid[1], 0, gridqp.data_ptr())          # x = code * scale exactly: the codes are recovered in the kernel's prologue
-                _call("mn_conv2d_bwd_weight", C.byref(g), C.byref(aqg), _p(d_o), _p(x), _p(dw_raw), None, _p(ws), nb, CONV_ALGO, _s())
+                _call("mn_conv2d_bwd_weight", C.byref(g), C.byref(aqg), _p(d_o), _p(x), _p(dw_raw), None, _p(ws), nb, _lib.MN_ALGO_AUTO, _s())
             else:
-                _call("mn_conv2d_bwd_weight", C.byref(g), C.byref(none), _p(d_o), _p(x), _p(dw_raw), None, _p(ws), nb, CONV_ALGO, _s())
+                _call("mn_conv2d_bwd_weight", C.byref(g), C.byref(none), _p(d_o), _p(x), _p(dw_raw), None, _p(ws), nb, _lib.MN_ALGO_AUTO, _s())
             dw.add_(dw_raw)
             if ctx.needs_input_grad[0]:
                 dxq, dxr = torch.empty_like(x), torch.empty_like(x)
                 ws1, nb1 = _ws(g, 1, dev)
-                _call("mn_conv2d_bwd_data", C.byref(g), C.byref(aq), C.byref(wd), _p(gy), _p(qw), _p(x), _p(dxq), _p(ws1), nb1, CONV_ALGO, _s())
-                _call("mn_conv2d_bwd_data", C.byref(g), C.byref(none), None, _p(d_o), _p(weight), None, _p(dxr), _p(ws1), nb1, CONV_ALGO, _s())
+                _call("mn_conv2d_bwd_data", C.byref(g), C.byref(aq), C.byref(wd), _p(gy), _p(qw), _p(x), _p(dxq), _p(ws1), nb1, _lib.MN_ALGO_AUTO, _s())
+                _call("mn_conv2d_bwd_data", C.byref(g), C.byref(none), None, _p(d_o), _p(weight), None, _p(dxr), _p(ws1), nb1, _lib.MN_ALGO_AUTO, _s())
                 pre = ctx.tok_in is not None and relu_premask_ok(ctx.x_obj)
                 dx = add_relu_mask(dxq, dxr, x if pre else None)
                 if pre:
@@ -1692,8 +1688,6 @@ def iao_bn_lazy_supported(y, accstats):
 def iao_codes_bytes(x_shape, w_shape, stride, padding, dilation, groups, a_bits, w_bits, dummy):
     """bytes of the signed-code buffer the dense IAO kernels keep for a layer of this geometry (0: they do not cover it); ``dummy``: any device tensor (the descriptors
     only have to be non-NULL for the query)"""
-    if CONV_ALGO != _lib.MN_ALGO_AUTO:
-        return 0
     g = _geom(x_shape, w_shape, stride, padding, dilation, groups, 0)
     aq = ActQ(ACTQ_IAO, a_bits, 0, 0, dummy.data_ptr())
     wd = WQ(WQ_IAO, w_bits, 0, 4, dummy.data_ptr())
@@ -1959,7 +1953,7 @@ def _out_hw(g):
 
 
 def _ws(g, which, device):
-    nb = int(_lib_().mn_conv2d_ws_bytes(C.byref(g), which, CONV_ALGO))
+    nb = int(_lib_().mn_conv2d_ws_bytes(C.byref(g), which, _lib.MN_ALGO_AUTO))
     if nb < 0:
         raise MicronetHipError("invalid convolution geometry")
     return torch.empty(max(nb // 4, 4), dtype=torch.float32, device=device), nb
@@ -1994,7 +1988,6 @@ class UpSums:
 
 
 UP_SUMS_PLAIN = False          # (the k-bit hand-over also behind a plain gradient: tests only)
-UP_SUMS_3X3 = _os0.environ.get("MN_UP_SUMS_3X3", "1") != "0"          # (A/B: the hand-over behind a 3x3 block, k_pwb<1, 0, 0, 3>)
 UP_SUMS_FOLD = _os0.environ.get("MN_UP_SUMS", "1") != "0"          # (A/B and the equality test: MN_UP_SUMS=0 restores k_bnh_partial for every block)
 
 
@@ -2007,7 +2000,7 @@ class QConv2d(Function):
     def forward(ctx, x, wq, bias, stride, padding, dilation, groups, aq_mode, aq_bits, aq_qtype, qp, wdesc, aq_flags, in_shuffle=0, given=None):
         ctx.x_shape = tuple(x.shape)
         if given is not None:               # x is a LazyBNAct whose consumer-side codes + clip-STE bits are already written (iao_bn_apply_codes): fp32 x never exists and
-            if aq_mode != ACTQ_IAO or qp is None or wdesc is None or CONV_ALGO != _lib.MN_ALGO_AUTO:          # no kernel reads it; the codes stand in wherever a pointer is due
+            if aq_mode != ACTQ_IAO or qp is None or wdesc is None:          # no kernel reads it; the codes stand in wherever a pointer is due
                 raise MicronetHipError("activation codes handed over without the dense IAO path")
             xl, x = x, given[0]
         elif isinstance(x, SignTensor):     # packed +-1 activations: the kernels read the int8 codes (MN_ACTQ_SIGN8)
@@ -2028,7 +2021,7 @@ class QConv2d(Function):
         wd = _wq_desc(wdesc)
         ctx.packed = packed = getattr(wq, "_mn_packed", None) if wd is not None else None
         stats = None
-        if want_stats and aq_mode == ACTQ_IAO and wd is not None and qp is not None and CONV_ALGO == _lib.MN_ALGO_AUTO and wdesc[4] is not None:
+        if want_stats and aq_mode == ACTQ_IAO and wd is not None and qp is not None and wdesc[4] is not None:
             rows = int(_lib_().mn_conv2d_iao_stats_rows(C.byref(g), C.byref(aq), C.byref(wd)))
             if rows > 0 and x.data_ptr() % 16 == 0 and y.data_ptr() % 16 == 0:          # dense layer on the int8 matrix cores (16-byte aligned operands, as mn_conv2d_fwd asks):
                 stats = torch.empty((rows, g.O, 2), dtype=torch.float64, device=x.device)          # exact sums of acc / acc^2 per channel from the epilogue, for the BatchNorm behind the conv
@@ -2043,7 +2036,7 @@ class QConv2d(Function):
             if nc <= 0 or nc != codes.numel() or ste_mask.numel() * 8 != nc:
                 raise MicronetHipError("activation codes handed over to a layer the dense IAO kernels do not cover")
             aq.codes, aq.ste_mask, aq.flags = codes.data_ptr(), ste_mask.data_ptr(), aq.flags | _lib.MN_ACTQ_CODES_GIVEN
-        elif aq_mode == ACTQ_IAO and wd is not None and qp is not None and CONV_ALGO == _lib.MN_ALGO_AUTO and ctx.needs_input_grad[1]:
+        elif aq_mode == ACTQ_IAO and wd is not None and qp is not None and ctx.needs_input_grad[1]:
             nc = int(_lib_().mn_conv2d_iao_codes_bytes(C.byref(g), C.byref(aq), C.byref(wd)))
             if nc > 0:          # dense IAO layer: the forward's signed activation codes are kept for backward-weight (1 byte per element)
                 codes = torch.empty(nc, dtype=torch.int8, device=x.device)
@@ -2054,7 +2047,7 @@ class QConv2d(Function):
         with torch.cuda.device_of(x):
             ws, nb = _ws(g, 0, x.device)
             with _span(g, 0, 4 * (x.numel() + y.numel() + wq.numel())):
-                _call("mn_conv2d_fwd", C.byref(g), C.byref(aq), _ref(wd), _p(x), _p(wq), _p(bias), _p(y), _p(ws), nb, CONV_ALGO, _s())
+                _call("mn_conv2d_fwd", C.byref(g), C.byref(aq), _ref(wd), _p(x), _p(wq), _p(bias), _p(y), _p(ws), nb, _lib.MN_ALGO_AUTO, _s())
         wscale = wdesc[4] if wdesc is not None else None
         if (stats is not None or given is not None) and not _lib_().mn_last_kernel().decode().startswith("k_qd_fwd"):
             if given is not None:
@@ -2064,7 +2057,7 @@ class QConv2d(Function):
             _PENDING_ACCSTATS[0] = (stats, stats.shape[0], qp, wscale, int(wdesc[3]), bias, accmm)
         ctx.iao_codes, ctx.iao_mask = codes, ste_mask
         ctx.res_tok = ctx.donate_tok = None
-        if (RES_ADD_FOLD and given is None and aq_mode == ACTQ_IAO and wd is not None and qp is not None and CONV_ALGO == _lib.MN_ALGO_AUTO and ctx.needs_input_grad[0]
+        if (RES_ADD_FOLD and given is None and aq_mode == ACTQ_IAO and wd is not None and qp is not None and ctx.needs_input_grad[0]
                 and type(x) is torch.Tensor):
             prev = getattr(x, "_mn_res_token", None)
             if donate and prev is not None and not prev.claimed and not prev.consumed and prev.node is not None and prev.node() is not None:
@@ -2088,8 +2081,7 @@ class QConv2d(Function):
             if aq_mode == ACTQ_NONE and not ctx.needs_input_grad[0] and r["x"].data_ptr() == x.data_ptr() and r["w"].data_ptr() == wq.data_ptr() and \
                     tuple(r["dw"].shape) == tuple(wq.shape) and (not has_bias or r["db"] is not None):
                 return None, r["dw"], (r["db"] if has_bias else None), None, None, None, None, None, None, None, None, None, None, None, None
-        if isinstance(gy, LazyBNGrad) and gy._mn_value is None and gy._mn_recipe.get("kind") in ("bnh", "bnh_pool") and aq_mode == ACTQ_SIGN8 and wd4 is not None and \
-                CONV_ALGO == _lib.MN_ALGO_AUTO:
+        if isinstance(gy, LazyBNGrad) and gy._mn_value is None and gy._mn_recipe.get("kind") in ("bnh", "bnh_pool") and aq_mode == ACTQ_SIGN8 and wd4 is not None:
             r = gy._mn_recipe              # the fused BatchNorm+sign (+ max-pool) behind this conv: dy is formed inside backward-data / backward-weight
             pool = r.get("kind") == "bnh_pool"
             wd = _wq_desc(wd4 + (wscale,))
@@ -2110,7 +2102,7 @@ class QConv2d(Function):
                     splits, up9 = 0, False
                     if up is not None and up.kind == 1 and UP_SUMS_FOLD and tuple(up.h.shape) == tuple(x.shape) and up.h.data_ptr() % 16 == 0 and up.chan.shape[0] == 8:
                         splits = int(_lib_().mn_conv2d_bwd_bnh_up_splits(C.byref(g), _ref(wd), 1 if pool else 0, up.k))
-                    elif up is not None and up.kind == 3 and UP_SUMS_FOLD and UP_SUMS_3X3 and not pool and tuple(up.h.shape) == tuple(x.shape) and up.h.data_ptr() % 16 == 0 and \
+                    elif up is not None and up.kind == 3 and UP_SUMS_FOLD and not pool and tuple(up.h.shape) == tuple(x.shape) and up.h.data_ptr() % 16 == 0 and \
                             up.chan.shape[0] == 17:          # a 3x3 block in front: the stash offset per pixel class (k_pwb<1, 0, 0, 3>)
                         splits = int(_lib_().mn_conv2d_bwd_bnh_up9_splits(C.byref(g), _ref(wd), up.k))
                         up9 = splits > 0
@@ -2153,7 +2145,7 @@ class QConv2d(Function):
                                   _p(db), _p(ws), nb, _s())
             return dx, dw, db, None, None, None, None, None, None, None, None, None, None, None, None
         if isinstance(gy, LazyBNGrad) and gy._mn_value is None and gy._mn_recipe.get("kind") == "qa" and aq_mode == ACTQ_NONE and not ctx.needs_input_grad[0] and \
-                CONV_ALGO == _lib.MN_ALGO_AUTO and _lib_().mn_conv2d_first_supported(C.byref(g), 2):
+                _lib_().mn_conv2d_first_supported(C.byref(g), 2):
             r = gy._mn_recipe              # the DoReFa block (BatchNorm + ReLU + next quantizer) behind the first conv: dy is formed inside the backward-weight kernel
             dw = torch.empty_like(wq)
             db = torch.empty(g.O, dtype=torch.float32, device=x.device) if has_bias else None
@@ -2163,7 +2155,7 @@ class QConv2d(Function):
                       _p(x), _p(dw), _p(db), _p(ws), nb, _s())
             return None, dw, db, None, None, None, None, None, None, None, None, None, None, None, None
         if isinstance(gy, LazyBNGrad) and gy._mn_value is None and gy._mn_recipe.get("kind") not in ("bnh", "bnh_pool", "qa", "first_done") and aq_mode == ACTQ_NONE and not ctx.needs_input_grad[0] and \
-                CONV_ALGO == _lib.MN_ALGO_AUTO and _lib_().mn_conv2d_first_supported(C.byref(g), 2):
+                _lib_().mn_conv2d_first_supported(C.byref(g), 2):
             r = gy._mn_recipe              # the BatchNorm+sign behind the first conv: dy is formed inside the backward-weight kernel
             dw = torch.empty_like(wq)
             db = torch.empty(g.O, dtype=torch.float32, device=x.device) if has_bias else None
@@ -2201,7 +2193,7 @@ class QConv2d(Function):
                 if fold:
                     aq.dx_add = d_sc.data_ptr()
                 with _span(g, 1, 4 * (gy.numel() + dx.numel() + wq.numel() + (x_numel if aq_mode not in (ACTQ_NONE, ACTQ_SIGN8) else 0))):
-                    _call("mn_conv2d_bwd_data", C.byref(g), C.byref(aq), _ref(wd), _p(gy), _p(wq), _p(x), _p(dx), _p(ws), nb, CONV_ALGO, _s())
+                    _call("mn_conv2d_bwd_data", C.byref(g), C.byref(aq), _ref(wd), _p(gy), _p(wq), _p(x), _p(dx), _p(ws), nb, _lib.MN_ALGO_AUTO, _s())
                 aq.dx_add = None
                 if d_sc is not None and not fold:
                     dx.add_(d_sc)
@@ -2212,7 +2204,7 @@ class QConv2d(Function):
                 db = torch.empty(g.O, dtype=torch.float32, device=x.device) if has_bias else None
                 ws, nb = _ws(g, 2, x.device)
                 with _span(g, 2, 4 * (gy.numel() + x_numel + dw.numel())):
-                    _call("mn_conv2d_bwd_weight", C.byref(g), C.byref(aq), _p(gy), _p(x), _p(dw), _p(db), _p(ws), nb, CONV_ALGO, _s())
+                    _call("mn_conv2d_bwd_weight", C.byref(g), C.byref(aq), _p(gy), _p(x), _p(dw), _p(db), _p(ws), nb, _lib.MN_ALGO_AUTO, _s())
         dtok = getattr(ctx, "donate_tok", None)
         if dtok is not None and dx is not None and not dtok.consumed and dtok.d_sc is None and dtok.node is not None and dtok.node() is not None:
             dtok.d_sc, dx = dx, None          # (the other conv on x adds it while it stores its own d x)
@@ -2241,7 +2233,7 @@ class QConv2dLazy(Function):
             wd = _wq_desc(wdesc)
             with torch.cuda.device_of(codes):
                 ws, nb = _ws(g, 0, codes.device)
-                _call("mn_conv2d_fwd", C.byref(g), C.byref(aq), _ref(wd), _p(codes), _p(wq), _p(bias), _p(y), _p(ws), nb, CONV_ALGO, _s())
+                _call("mn_conv2d_fwd", C.byref(g), C.byref(aq), _ref(wd), _p(codes), _p(wq), _p(bias), _p(y), _p(ws), nb, _lib.MN_ALGO_AUTO, _s())
             return y
         recipe = dict(codes=codes, wq=wq, bias=bias, geom=g, wdesc=wdesc, compute=compute, packed=packed)
         return LazyConvOut((g.N, g.O, Ho, Wo), codes.device, recipe)
@@ -2252,19 +2244,17 @@ class QConv2dLazy(Function):
 
 
 def qconv_bnsign_supported(x, wq, stride, padding, dilation, groups, wdesc, in_shuffle):
-    if not isinstance(x, SignTensor) or wdesc is None or CONV_ALGO != _lib.MN_ALGO_AUTO:
+    if not isinstance(x, SignTensor) or wdesc is None:
         return False
     g = _geom(x.shape, wq.shape, stride, padding, dilation, groups, in_shuffle or 0)
     return bool(_lib_().mn_qconv_bnsign_stash_supported(C.byref(g), _ref(_wq_desc(wdesc))))
 
 
-import os as _os
 # Fold the BatchNorm+sign backward into the block's own conv backward (k_pwd / k_pws_wgrad_s form dy from (da, h) in registers / in
 # the LDS staging pass, dy is never written).  With the LDS-staged backward-weight kernel (the fold costs one pass per BLOCK there)
-# this is +3.5 % step throughput on c2 (3.25 -> 3.14 ms): ON by default, MN_BNH_FOLD=0 switches it off.
+# this is +3.5 % step throughput on c2 (3.25 -> 3.14 ms).  The 2x2 max-pool behind a block folds in as well (k_pwd<.., 2> / k_pws_wgrad_s<.., 2, ..>) wherever
+# mn_conv2d_bnh_pool_supported allows.  ON by default; tests switch it off to compare against mn_bnh_bwd_apply's dy.
 FOLD_BN_INTO_CONV_BWD = True
-# ... and the 2x2 max-pool behind a block as well (k_pwd<.., 2> / k_pws_wgrad_s<.., 2, ..>): MN_BNH_POOL_FOLD=0 restores mn_bnh_bwd_apply's full-size dy (A/B)
-FOLD_POOL_INTO_CONV_BWD = True
 
 
 class ConvBNSign(Function):
@@ -2302,7 +2292,7 @@ class ConvBNSign(Function):
         ctx.save_for_backward(h, chan, gamma, beta)
         ctx.training = int(training)
         ctx.fold_ok = FOLD_BN_INTO_CONV_BWD and bool(_lib_().mn_conv2d_bnh_supported(C.byref(g), _ref(wd)))     # the conv's own backward can form dy from (da, h)
-        ctx.fold_pool_ok = FOLD_POOL_INTO_CONV_BWD and ctx.fold_ok and bool(_lib_().mn_conv2d_bnh_pool_supported(C.byref(g), _ref(wd)))      # ... and from the POOLED gradient
+        ctx.fold_pool_ok = ctx.fold_ok and bool(_lib_().mn_conv2d_bnh_pool_supported(C.byref(g), _ref(wd)))      # ... and from the POOLED gradient
         out = SignTensor(a)
         if ap is not None:
             out._mn_pooled = ap
@@ -2364,7 +2354,7 @@ def qconv_bnq_supported(x, wq, stride, padding, dilation, groups, w_bits, in_shu
     """True when conv(x) for a ``QActTensor`` x and DoReFa weights can stay un-computed: the fused kernels (16 / 32-bit stash forward, code-reading
     backward-weight, STE-free backward-data) cover this geometry (grouped 1x1 / 3x3 stride 1: qgemm_sign / qgemm_k3s; dense layers with C, O multiples of
     64, 3x3 stride 1 / 2 and 1x1 stride 2: qgemm_dense)."""
-    if not isinstance(x, QActTensor) or CONV_ALGO != _lib.MN_ALGO_AUTO or x.dim() != 4 or not (2 <= w_bits <= 8):
+    if not isinstance(x, QActTensor) or x.dim() != 4 or not (2 <= w_bits <= 8):
         return False
     one = lambda v: v in (1, (1, 1), [1, 1])
     if not one(dilation):
@@ -2420,16 +2410,11 @@ def pack_dense_weights(mods_wq, w_bits, qps=None):
         wq._mn_packed = o
 
 
-PACK_PW_MULTI = _os.environ.get("MN_NO_PACKED_PW") is None          # (the library's own A/B knob, csrc/common.h: every conv call packs its own weight codes)
-
-
 def pack_pointwise_weights(mods_wq, wdesc):
     """The pointwise (1x1, stride 1) counterpart of ``pack_dense_weights``: the forward and backward-data weight-code images of every such conv of the step in ONE
     launch (mn_qg_pack_multi) instead of one 5 us launch per conv call and direction.  ``wdesc`` = (mode, bits, q_type, per_channel, None): ternary / binary or
     DoReFa codes.  The images ride on the quantised weight tensor (``_mn_packed`` = (forward image, backward image)); layers the code kernels do not cover are
     skipped (their calls keep packing for themselves)."""
-    if not PACK_PW_MULTI:
-        return
     lib = _lib_()
     items = []
     for m, wq in mods_wq:
@@ -2473,12 +2458,12 @@ def _code_conv_backward(g, a_bits, w_bits, codes, wq, gy, need_dx, need_dw, pack
         dq = torch.empty(codes.shape, dtype=torch.float32, device=codes.device)
         ws, nb = _ws(g, 1, codes.device)
         with _span(g, 1, 4 * (gy.numel() + dq.numel())):
-            _call("mn_conv2d_bwd_data", C.byref(g), C.byref(aq), C.byref(wd), _p(gy), _p(wq), None, _p(dq), _p(ws), nb, CONV_ALGO, _s())
+            _call("mn_conv2d_bwd_data", C.byref(g), C.byref(aq), C.byref(wd), _p(gy), _p(wq), None, _p(dq), _p(ws), nb, _lib.MN_ALGO_AUTO, _s())
     if need_dw:
         dw = torch.empty_like(wq)
         ws, nb = _ws(g, 2, codes.device)
         with _span(g, 2, 4 * gy.numel() + codes.numel() + 4 * dw.numel()):
-            _call("mn_conv2d_bwd_weight", C.byref(g), C.byref(aq), _p(gy), _p(codes), _p(dw), None, _p(ws), nb, CONV_ALGO, _s())
+            _call("mn_conv2d_bwd_weight", C.byref(g), C.byref(aq), _p(gy), _p(codes), _p(dw), None, _p(ws), nb, _lib.MN_ALGO_AUTO, _s())
     return dq, dw
 
 
@@ -2569,7 +2554,7 @@ class QConvCodeLazy(Function):
             if ctx.needs_input_grad[0]:
                 dq = torch.empty(codes.shape, dtype=torch.float32, device=codes.device)
                 ws, nb = _ws(g, 1, codes.device)
-                _call("mn_conv2d_bwd_data", C.byref(g), C.byref(aq), C.byref(wd), _p(gy), _p(wq), None, _p(dq), _p(ws), nb, CONV_ALGO, _s())
+                _call("mn_conv2d_bwd_data", C.byref(g), C.byref(aq), C.byref(wd), _p(gy), _p(wq), None, _p(dq), _p(ws), nb, _lib.MN_ALGO_AUTO, _s())
 
                 def expand(dq_):
                     return DorefaAct.backward_raw(dq_, x.materialize(), a_bits)
@@ -2578,7 +2563,7 @@ class QConvCodeLazy(Function):
                 dw = torch.empty_like(wq)
                 db = torch.empty(g.O, dtype=torch.float32, device=codes.device) if has_bias else None
                 ws, nb = _ws(g, 2, codes.device)
-                _call("mn_conv2d_bwd_weight", C.byref(g), C.byref(aq), _p(gy), _p(codes), _p(dw), _p(db), _p(ws), nb, CONV_ALGO, _s())
+                _call("mn_conv2d_bwd_weight", C.byref(g), C.byref(aq), _p(gy), _p(codes), _p(dw), _p(db), _p(ws), nb, _lib.MN_ALGO_AUTO, _s())
         ctx.x_ref = None
         return dx, dw, db, None, None, None, None, None, None
 
@@ -2790,7 +2775,7 @@ class BNReLUQ(Function):
                 with _span(None, 3, (2 if in_f32 == 0 else 4) * src.numel() + 4 * dq.numel() + 4 * dy.numel()):
                     _call("mn_qa_bwd_apply", in_f32, _p(src), _p(chan), _p(sums), _p(dq), N, Cc, H, W, qbits, pool, quant, training, _p(dy), _s())
                 return dy, dgamma, dbeta, None, None, None, None, None, None, None, None
-            if QA_BWD_TWO_LAUNCHES and not lazy_first:
+            if not lazy_first:
                 # partial sums, then the apply pass whose blocks finish the sums themselves (mn_qa_bwd: one launch less per block, bit-identical)
                 dy = torch.empty((N, Cc, H, W), dtype=torch.float32, device=dev)
                 with _span(None, 3, 2 * ((2 if in_f32 == 0 else 4) * src.numel() + 4 * dq.numel()) + 4 * dy.numel()):
@@ -2798,20 +2783,15 @@ class BNReLUQ(Function):
                 return dy, dgamma, dbeta, None, None, None, None, None, None, None, None
             with _span(None, 3, (2 if in_f32 == 0 else 4) * src.numel() + 4 * dq.numel()):
                 _call("mn_qa_bwd_sums", in_f32, _p(src), _p(chan), _p(dq), N, Cc, H, W, qbits, pool, quant, _p(dgamma), _p(dbeta), _p(sums), _p(ws), _s())
-            if lazy_first:
-                # the block behind the un-quantised first conv: d loss / d y has ONE consumer, that conv's backward-weight, which forms it from
-                # (dq, y) while they stream in (mn_conv2d_bwd_weight_first_qa) -- dy is neither written nor re-read
-                def expand(r):
-                    dy_ = torch.empty((N, Cc, H, W), dtype=torch.float32, device=dev)
-                    with torch.cuda.device(dev):
-                        _call("mn_qa_bwd_apply", 1, _p(r["y"]), _p(r["chan"]), _p(r["sums"]), _p(r["dq"]), N, Cc, H, W, r["bits"], 0, r["quant"], r["training"], _p(dy_), _s())
-                    return dy_
-                recipe = dict(kind="qa", dq=dq, y=src, chan=chan, sums=sums, bits=qbits, quant=quant, training=training)
-                return LazyBNGrad((N, Cc, H, W), dev, recipe, expand), dgamma, dbeta, None, None, None, None, None, None, None, None
-            dy = torch.empty((N, Cc, H, W), dtype=torch.float32, device=dev)
-            with _span(None, 3, (2 if in_f32 == 0 else 4) * src.numel() + 4 * dq.numel() + 4 * dy.numel()):
-                _call("mn_qa_bwd_apply", in_f32, _p(src), _p(chan), _p(sums), _p(dq), N, Cc, H, W, qbits, pool, quant, training, _p(dy), _s())
-        return dy, dgamma, dbeta, None, None, None, None, None, None, None, None
+            # the block behind the un-quantised first conv: d loss / d y has ONE consumer, that conv's backward-weight, which forms it from
+            # (dq, y) while they stream in (mn_conv2d_bwd_weight_first_qa) -- dy is neither written nor re-read
+            def expand(r):
+                dy_ = torch.empty((N, Cc, H, W), dtype=torch.float32, device=dev)
+                with torch.cuda.device(dev):
+                    _call("mn_qa_bwd_apply", 1, _p(r["y"]), _p(r["chan"]), _p(r["sums"]), _p(r["dq"]), N, Cc, H, W, r["bits"], 0, r["quant"], r["training"], _p(dy_), _s())
+                return dy_
+            recipe = dict(kind="qa", dq=dq, y=src, chan=chan, sums=sums, bits=qbits, quant=quant, training=training)
+            return LazyBNGrad((N, Cc, H, W), dev, recipe, expand), dgamma, dbeta, None, None, None, None, None, None, None, None
 
 
 class BNAddReLUQ(Function):
@@ -2887,17 +2867,9 @@ class BNAddReLUQ(Function):
         nel = N * Cc * H * W
         with torch.cuda.device(dev):
             ws = torch.empty(int(_lib_().mn_qr_ws_floats(Cc)), dtype=torch.float32, device=dev)
-            if QA_BWD_TWO_LAUNCHES:
-                with _span(None, 3, 2 * src.numel() * src.element_size() + 12 * nel):
-                    _call("mn_qr_bwd", in_kind, _p(src), _p(chan), res_kind, _p(rsrc), _p(rchan), _p(dq), _p(dq2), _p(gf), N, Cc, H, W, qbits, training, _p(du), _p(dgamma),
-                          _p(dbeta), _p(sums), _p(dgamma_s), _p(dbeta_s), _p(sums_s), _p(dy), _p(dy_s), _p(ws), _s())
-                dres = du if res_kind == 1 else dy_s
-                return (dy, dgamma, dbeta, None, None, None, None, None, None, dres, dgamma_s, dbeta_s, None, None, None, None, None, None, None)
-            with _span(None, 3, src.numel() * src.element_size() + (rsrc.numel() * rsrc.element_size() if rsrc is not None else 0) + 4 * nel * (1 + sum(t is not None for t in (dq, dq2, gf)))):
-                _call("mn_qr_bwd_sums", in_kind, _p(src), _p(chan), res_kind, _p(rsrc), _p(rchan), _p(dq), _p(dq2), _p(gf), N, Cc, H, W, qbits, _p(du), _p(dgamma), _p(dbeta),
-                      _p(sums), _p(dgamma_s), _p(dbeta_s), _p(sums_s), _p(ws), _s())
-            with _span(None, 3, src.numel() * src.element_size() + 8 * nel + ((rsrc.numel() * rsrc.element_size() + 4 * nel) if res_kind >= 2 else 0)):
-                _call("mn_qr_bwd_apply", in_kind, _p(src), _p(chan), _p(sums), res_kind, _p(rsrc), _p(rchan), _p(sums_s), _p(du), N, Cc, H, W, training, _p(dy), _p(dy_s), _s())
+            with _span(None, 3, 2 * src.numel() * src.element_size() + 12 * nel):
+                _call("mn_qr_bwd", in_kind, _p(src), _p(chan), res_kind, _p(rsrc), _p(rchan), _p(dq), _p(dq2), _p(gf), N, Cc, H, W, qbits, training, _p(du), _p(dgamma),
+                      _p(dbeta), _p(sums), _p(dgamma_s), _p(dbeta_s), _p(sums_s), _p(dy), _p(dy_s), _p(ws), _s())
         dres = du if res_kind == 1 else dy_s
         return (dy, dgamma, dbeta, None, None, None, None, None, None, dres, dgamma_s, dbeta_s, None, None, None, None, None, None, None)
 
@@ -2920,8 +2892,7 @@ def qconv2d(x, wq, bias, stride=1, padding=0, dilation=1, groups=1, aq_mode=ACTQ
         aq = ActQ(ACTQ_SIGN8 if packed else aq_mode, aq_bits, aq_qtype, 0, qp.data_ptr() if qp is not None else None)
         wd = _wq_desc(wdesc)
         lib = _lib_()
-        ok = CONV_ALGO in (_lib.MN_ALGO_AUTO, _lib.MN_ALGO_QGEMM) and all(
-            lib.mn_conv2d_qgemm_supported(C.byref(g), C.byref(aq), _ref(wd), k) for k in range(3))
+        ok = all(lib.mn_conv2d_qgemm_supported(C.byref(g), C.byref(aq), _ref(wd), k) for k in range(3))
         if not ok:                          # kernels that read neither int8 codes nor shuffled channels: hand them the plain tensor
             x = sign_to_float(x)
             if in_shuffle and in_shuffle > 1:
@@ -2973,7 +2944,7 @@ class QLinearSmall(Function):
 
 def qlinear(x, wq, bias, aq_mode=ACTQ_NONE, aq_bits=8, aq_qtype=0, qp=None, wdesc=None):
     """F.linear as a 1x1 convolution over 1x1 'images' (same kernels, same fused quantizer); few outputs: the dedicated small-linear kernels."""
-    if (CONV_ALGO == _lib.MN_ALGO_AUTO and x.dim() == 2 and type(x) is torch.Tensor and x.is_cuda and x.dtype == torch.float32 and
+    if (x.dim() == 2 and type(x) is torch.Tensor and x.is_cuda and x.dtype == torch.float32 and
             aq_mode in (ACTQ_NONE, ACTQ_DOREFA, ACTQ_IAO) and _lib_().mn_qlinear_supported(x.shape[0], x.shape[1], wq.shape[0])):
         return QLinearSmall.apply(x, wq, bias, aq_mode, aq_bits, aq_qtype, qp)
     lead = x.shape[:-1]
@@ -2999,7 +2970,7 @@ class ConvTranspose2d(Function):
         none = ActQ(ACTQ_NONE, 0, 0, 0, None)
         with torch.cuda.device_of(x):
             ws, nb = _ws(g, 1, x.device)
-            _call("mn_conv2d_bwd_data", C.byref(g), C.byref(none), None, _p(x), _p(w), None, _p(y), _p(ws), nb, CONV_ALGO, _s())
+            _call("mn_conv2d_bwd_data", C.byref(g), C.byref(none), None, _p(x), _p(w), None, _p(y), _p(ws), nb, _lib.MN_ALGO_AUTO, _s())
         if bias is not None:
             y += bias.view(1, -1, 1, 1)
         ctx.save_for_backward(x, w)
@@ -3017,17 +2988,16 @@ class ConvTranspose2d(Function):
             if ctx.needs_input_grad[0]:
                 dx = torch.empty_like(x)
                 ws, nb = _ws(g, 0, x.device)
-                _call("mn_conv2d_fwd", C.byref(g), C.byref(none), None, _p(gy), _p(w), None, _p(dx), _p(ws), nb, CONV_ALGO, _s())
+                _call("mn_conv2d_fwd", C.byref(g), C.byref(none), None, _p(gy), _p(w), None, _p(dx), _p(ws), nb, _lib.MN_ALGO_AUTO, _s())
             if ctx.needs_input_grad[1]:
                 dw = torch.empty_like(w)
                 ws, nb = _ws(g, 2, x.device)
-                _call("mn_conv2d_bwd_weight", C.byref(g), C.byref(none), _p(x), _p(gy), _p(dw), None, _p(ws), nb, CONV_ALGO, _s())
+                _call("mn_conv2d_bwd_weight", C.byref(g), C.byref(none), _p(x), _p(gy), _p(dw), None, _p(ws), nb, _lib.MN_ALGO_AUTO, _s())
             if has_bias and ctx.needs_input_grad[2]:
                 db = gy.sum(dim=(0, 2, 3))
         return dx, dw, db, None, None, None, None, None
 
 
-QA_BWD_TWO_LAUNCHES = True          # the k-bit blocks' backward: partial sums + apply (which finishes the sums) instead of partial + final + apply
 FIRST_FUSED = True          # the fused first block (round 5 A/B against conv + the BatchNorm block's own kernels: c2 111.9k -> 115.8k img/s)
 FIRST_FUSED_QA = _os0.environ.get("MN_FIRST_FUSED_QA", "0") == "1"     # ... for the DoReFa block too (off: its epilogue -- the quantizer's rounding -- makes the fused
 #                                                                         forward VALU-bound, 209 us against 110 + 58 us for conv + mn_qa_fwd_f32_mask on nin_gc at batch 256)
@@ -3051,7 +3021,7 @@ class FirstConvLazy(Function):
             aq = ActQ(ACTQ_NONE, 8, 0, 0, None)
             with torch.cuda.device_of(x):
                 ws, nb = _ws(g, 0, x.device)
-                _call("mn_conv2d_fwd", C.byref(g), C.byref(aq), None, _p(x), _p(w), _p(bias), _p(y), _p(ws), nb, CONV_ALGO, _s())
+                _call("mn_conv2d_fwd", C.byref(g), C.byref(aq), None, _p(x), _p(w), _p(bias), _p(y), _p(ws), nb, _lib.MN_ALGO_AUTO, _s())
             return y
         recipe = dict(kind="first", x=x, w=w, bias=bias, geom=g, conv=(stride, padding, dilation, groups), compute=compute)
         return LazyConvOut((g.N, g.O, Ho, Wo), x.device, recipe)
@@ -3177,15 +3147,13 @@ class FirstConvBNReLUQ(Function):
 
 def first_conv_supported(x_shape, w_shape, stride, padding, dilation, groups):
     """True when the first-layer kernels (conv_first.hip: real fp32 operands, Cin*KH*KW <= 76) cover forward and backward-weight."""
-    if CONV_ALGO != _lib.MN_ALGO_AUTO:
-        return False
     g = _geom(x_shape, w_shape, stride, padding, dilation, groups)
     lib = _lib_()
     return bool(lib.mn_conv2d_first_supported(C.byref(g), 0)) and bool(lib.mn_conv2d_first_supported(C.byref(g), 2))
 
 
 def sign_classifier_supported(x, weight, stride, padding, dilation, groups):
-    if not isinstance(x, SignTensor) or x.dim() != 4 or weight.dim() != 4 or CONV_ALGO != _lib.MN_ALGO_AUTO:
+    if not isinstance(x, SignTensor) or x.dim() != 4 or weight.dim() != 4:
         return False
     one = lambda v, k: v in (k, (k, k), [k, k])
     if not (weight.shape[2] == 1 and weight.shape[3] == 1 and one(stride, 1) and one(padding, 0) and one(dilation, 1) and groups == 1):
@@ -3231,13 +3199,13 @@ class SignClassifierConv(Function):
                 dw = torch.empty_like(weight)
                 db = torch.empty(Oc, dtype=torch.float32, device=codes.device) if ctx.has_bias else None
                 ws, nb = _ws(g, 2, codes.device)
-                _call("mn_conv2d_bwd_weight", C.byref(g), C.byref(aq), _p(gy), _p(codes), _p(dw), _p(db), _p(ws), nb, CONV_ALGO, _s())
+                _call("mn_conv2d_bwd_weight", C.byref(g), C.byref(aq), _p(gy), _p(codes), _p(dw), _p(db), _p(ws), nb, _lib.MN_ALGO_AUTO, _s())
         return dx, dw, db
 
 
 def code_classifier_supported(x, weight, stride, padding, dilation, groups):
     """True when a DoReFa QuantConv2d on a ``QActTensor`` is the small 1x1 classifier the dedicated kernels cover (O <= 16)."""
-    if not isinstance(x, QActTensor) or x.dim() != 4 or weight.dim() != 4 or CONV_ALGO != _lib.MN_ALGO_AUTO or not (2 <= x.bits <= 8):
+    if not isinstance(x, QActTensor) or x.dim() != 4 or weight.dim() != 4 or not (2 <= x.bits <= 8):
         return False
     one = lambda v, k: v in (k, (k, k), [k, k])
     if not (weight.shape[2] == 1 and weight.shape[3] == 1 and one(stride, 1) and one(padding, 0) and one(dilation, 1) and groups == 1):
@@ -3291,6 +3259,6 @@ class CodeClassifierConv(Function):
                 dw = torch.empty_like(wq)
                 db = torch.empty(Oc, dtype=torch.float32, device=codes.device) if has_bias else None
                 ws, nb = _ws(g, 2, codes.device)
-                _call("mn_conv2d_bwd_weight", C.byref(g), C.byref(aq), _p(gy), _p(codes), _p(dw), _p(db), _p(ws), nb, CONV_ALGO, _s())
+                _call("mn_conv2d_bwd_weight", C.byref(g), C.byref(aq), _p(gy), _p(codes), _p(dw), _p(db), _p(ws), nb, _lib.MN_ALGO_AUTO, _s())
         ctx.x_ref = None
         return dx, dw, db

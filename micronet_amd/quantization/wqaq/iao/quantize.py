@@ -26,9 +26,6 @@ from micronet_amd import ops
 from micronet_amd.base_module.op import Add
 
 _FUSE_G3 = os.environ.get("MN_NO_G3") is None          # A/B knob: the grouped 3 x 3 layers on the generic kernels
-_PRODUCER_MINMAX = os.environ.get("MN_NO_PRODUCER_MINMAX") is None          # A/B knob: observers read the tensor themselves
-_PRODUCER_ACCSTATS = os.environ.get("MN_NO_PRODUCER_ACCSTATS") is None      # A/B knob: the BatchNorm behind a dense conv makes its own statistics pass
-_FUSE_BNFUSE = os.environ.get("MN_NO_BNFUSE_BLOCK") is None                 # A/B knob: QuantBNFuseConv2d on the generic kernels (raw conv + statistics passes)
 _FUSE_BN_CODES = os.environ.get("MN_IAO_BN_CODES", "1") != "0"              # A/B knob (round 6): BatchNorm + ReLU + the next dense conv's activation codes in one pass (LazyBNAct)
 _FUSE_BN_ADD = os.environ.get("MN_IAO_BN_ADD", "1") != "0"                  # A/B knob (round 6): the BatchNorm(s) in front of a residual block's QuantAdd folded into its pass, both directions
 
@@ -351,7 +348,7 @@ class QuantConv2d(nn.Conv2d):
 
     def _qconv(self, input, weight, bias, quantized=True):
         from micronet_amd.sign_tensor import LazyBNAct
-        want = bool(self.emit_accstats and self.training and quantized and _PRODUCER_ACCSTATS)
+        want = bool(self.emit_accstats and self.training and quantized)
         if isinstance(input, LazyBNAct) and input._mn_value is None:
             pulled = self._pull_codes(input, quantized)
             if pulled is not None:
@@ -460,12 +457,12 @@ class QuantBNFuseConv2d(QuantConv2d):
         relu = bool(self.relu_fused)
         # relu: the result is a LazyReluConvOut -- logically the conv's output (the reference module's contract), physically the rectified tensor the block's
         # ReLUAfterFusedConv takes out of it
-        return ops.IaoBNFusePW.apply(input, self.weight, self.bias, self.gamma, self.beta, self, qp, relu, relu and _PRODUCER_MINMAX)
+        return ops.IaoBNFusePW.apply(input, self.weight, self.bias, self.gamma, self.beta, self, qp, relu, relu)
 
     def _fused_quantizers_ok(self):
         wq, aq = self.weight_quantizer, self.activation_quantizer
         wobs, aobs = wq.observer, aq.observer
-        return (_FUSE_BNFUSE and not self.bn_fuse_calib and self.padding_mode == "zeros" and not isinstance(self.padding, str)
+        return (not self.bn_fuse_calib and self.padding_mode == "zeros" and not isinstance(self.padding, str)
                 and isinstance(wobs, ObserverBase) and wobs.q_level == "C" and wobs._kind in (0, 1) and not wobs._mn_sync and wq._q_type_static == 0 and 2 <= wq.bits <= 8
                 and not wq.qaft and isinstance(aobs, ObserverBase) and aobs.q_level == "L" and aq._q_type_static == 0 and 2 <= aq.bits <= 8 and not aq.qaft and not aq.union)
 
@@ -474,20 +471,20 @@ class QuantBNFuseConv2d(QuantConv2d):
         qp = aq.qparams(input)
         aq._last_qp = qp
         relu = bool(self.relu_fused)
-        return ops.IaoBNFuseGeneric.apply(input, self.weight, self.bias, self.gamma, self.beta, self, qp, relu, relu and _PRODUCER_MINMAX)
+        return ops.IaoBNFuseGeneric.apply(input, self.weight, self.bias, self.gamma, self.beta, self, qp, relu, relu)
 
     def _forward_fused_g3(self, input):
         aq = self.activation_quantizer
         qp = aq.qparams(input)          # (the pool in front left its (min, max) partials on the tensor: no pass over it)
         aq._last_qp = qp
         relu = bool(self.relu_fused)
-        return ops.IaoBNFuseG3.apply(input, self.weight, self.bias, self.gamma, self.beta, self, qp, relu, relu and _PRODUCER_MINMAX)
+        return ops.IaoBNFuseG3.apply(input, self.weight, self.bias, self.gamma, self.beta, self, qp, relu, relu)
 
     def forward(self, input):
         training_stats = (not self.qaft) and self.training
         if training_stats and self._fused_pw_ok(input):
             return self._forward_fused_pw(input)
-        if training_stats and _FUSE_G3 and self._fused_quantizers_ok() and ops.CONV_ALGO == 0 and \
+        if training_stats and _FUSE_G3 and self._fused_quantizers_ok() and \
                 ops.iao_bnfuse_g3_supported(input, self.weight, self.stride, self.padding, self.dilation, self.groups, self.in_shuffle_groups):
             return self._forward_fused_g3(input)          # (the channel shuffle in front stays folded into the kernels' addressing)
         if self.in_shuffle_groups > 1:
@@ -496,7 +493,7 @@ class QuantBNFuseConv2d(QuantConv2d):
             input = ops.channel_shuffle(input, self.in_shuffle_groups)
             if grid is not None:
                 input._mn_qgrid = grid[:3] + (input._version,)          # a permutation of channels keeps every value on the grid
-        if training_stats and self._fused_quantizers_ok() and ops.iao_bnfuse_generic_supported(input, self.weight) and ops.CONV_ALGO == 0:
+        if training_stats and self._fused_quantizers_ok() and ops.iao_bnfuse_generic_supported(input, self.weight):
             return self._forward_fused_generic(input)
         if training_stats:
             # raw conv for the batch statistics (ref 843-855); the statistics stay in the autograd graph
@@ -592,13 +589,13 @@ class QuantMaxPool2d(nn.MaxPool2d):
 
     def forward(self, input):
         aq = self.activation_quantizer
-        if (_FUSE_BNFUSE and not self.return_indices and aq.bits != 32 and 2 <= aq.bits <= 24 and isinstance(aq.observer, (ObserverBase, HistogramObserver))
+        if (not self.return_indices and aq.bits != 32 and 2 <= aq.bits <= 24 and isinstance(aq.observer, (ObserverBase, HistogramObserver))
                 and getattr(aq.observer, "q_level", "L") == "L" and ops.iao_fq_maxpool_supported(input, self.kernel_size, self.stride, self.padding, self.dilation, self.ceil_mode)):
             # quantizer + 2 x 2 max-pool in one pass (and one in backward); leaves (min, max) partials of its output for the next layer's observer
             qp = aq.qparams(input)
             aq._last_qp = qp
             if qp is not None and qp.shape[0] == 1:
-                want_mm = self.training and _PRODUCER_MINMAX
+                want_mm = self.training
                 out = ops.IaoFakeQuantMaxPool2x2.apply(input, qp, aq.bits, aq.q_type, want_mm, self)
                 mm = self.__dict__.pop("_mn_fwd_out", None)
                 if mm is not None:
@@ -698,7 +695,7 @@ class QuantAdd(nn.Module):
                 if o.num_flag == 0:
                     o.num_flag += 1
             q._last_qp = qp
-            want_mm = bool(relu) and _PRODUCER_MINMAX
+            want_mm = bool(relu)
             tok = None if lazy_s else getattr(shortcut, "_mn_res_token", None)
             node = tok.node() if (tok is not None and tok.node is not None) else None
             if tok is not None and (tok.claimed or node is None or not torch.is_grad_enabled() or not shortcut.requires_grad or not res.requires_grad
@@ -727,7 +724,7 @@ class QuantAdd(nn.Module):
             update = (not q.qaft) and q.training
             if update:
                 q.q_type = q._q_type_static
-            pr, ps = (ops._valid_minmax(res), ops._valid_minmax(shortcut)) if (_PRODUCER_MINMAX and self.training) else (None, None)
+            pr, ps = (ops._valid_minmax(res), ops._valid_minmax(shortcut)) if self.training else (None, None)
             if _synced(obs_r):                             # data parallel: both inputs' ranges over the global batch, one collective for the two
                 cur = _global_ranges([(res, pr), (shortcut, ps)], obs_r._mn_sync_group)
                 pr, ps = (cur[0:2], 1), (cur[2:4], 1)
@@ -739,7 +736,7 @@ class QuantAdd(nn.Module):
                 if o.num_flag == 0:
                     o.num_flag += 1
             q._last_qp = qp
-            want_mm = bool(relu) and self.training and _PRODUCER_MINMAX          # (a ResNet block's output: the next block's convs observe it)
+            want_mm = bool(relu) and self.training          # (a ResNet block's output: the next block's convs observe it)
             tok = getattr(shortcut, "_mn_res_token", None)
             node = tok.node() if (tok is not None and tok.node is not None) else None
             if tok is not None and (tok.claimed or node is None or not torch.is_grad_enabled() or not shortcut.requires_grad or not res.requires_grad
@@ -794,7 +791,7 @@ def add_quant_op(module, a_bits=8, w_bits=8, q_type=0, q_level=0, weight_observe
             # same parameters / buffers / state_dict keys, isinstance contracts intact (the reference leaves nn.ReLU alone: ref 1705-1709).
             from micronet_amd.quantization.wqaq.dorefa.quantize import BatchNorm2dReLU, ReLUAfterFusedBN
             prev.__class__ = BatchNorm2dReLU
-            prev.emit_minmax = _PRODUCER_MINMAX          # the IAO conv behind it observes this activation: the fused op hands over per-block (min, max)
+            prev.emit_minmax = True          # the IAO conv behind it observes this activation: the fused op hands over per-block (min, max)
             child.__class__ = ReLUAfterFusedBN
             prev = child
             continue
@@ -873,7 +870,7 @@ def _fuse_residual_tails(model):
             for child in m.children():
                 if type(child) is nn.BatchNorm2d and child.affine and child.track_running_stats:
                     child.__class__ = BatchNorm2dPlain
-                    child.emit_minmax = _PRODUCER_MINMAX          # (an IAO QuantAdd observes this output: its two input observers then read partials only)
+                    child.emit_minmax = True          # (an IAO QuantAdd observes this output: its two input observers then read partials only)
     # conv -> BatchNorm (ours) adjacency inside a Sequential: the conv's forward hands the exact sums of its integer accumulator to that BatchNorm (dense layers)
     from micronet_amd.quantization.wqaq.dorefa.quantize import BatchNorm2dReLU
     for m in model.modules():
