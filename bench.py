@@ -1,15 +1,22 @@
 #!/usr/bin/env python
 """QAT training-step throughput of the fake-quantized conv hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W            (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--full]   (N > 1: launched by torch.distributed.run, one rank per GPU)
 
 One "step" = forward + CrossEntropy + zero_grad + backward + Adam.step on one synthetic CIFAR-10-shaped batch
-(mirror of the reference's wqaq/dorefa/main.py:77-82), data already resident in HBM.  BASELINE.json's metric names nin_gc
-under BOTH low-bit schemes, so one run measures both, batch 256 PER GPU (weak scaling), data-parallel with a RCCL all-reduce
-of the gradients:
-  * primary (`value`, `roofline`, `cpu_baseline`): configs[1] -- wbwtab W-ternary / A-binary;
-  * `also.{c1_w2a2, c1, c3, c4, c5}`: the same measurement (value, ms_per_step, roofline of its own dominant kernel) for DoReFa W2A2 on nin_gc (the
-    second half of the headline metric) and for every other BASELINE config at 256 images per GPU; `values` repeats all images/s figures at top level.
+(mirror of the reference's wqaq/dorefa/main.py:77-82), data already resident in HBM, batch 256 PER GPU (weak scaling), data-parallel
+with a RCCL all-reduce of the gradients.  The headline (`value`, `ms_per_step`) is configs[1] -- wbwtab W-ternary / A-binary on nin_gc.
+
+A plain run does only what the headline needs: set up, warm up, time the steps, write `--dump-outputs`, print the line.  What `--dump-outputs`
+writes covers every workload a --full run measures (below), so a plain run that dumps also runs the secondary workloads' warm-up and timed steps
+(nothing else of --full) and reports them under `also` / `values`.
+`--full` adds everything else the benchmark measures:
+  * `roofline` (per-kernel HIP-event pass, rocprofv3 PMC passes), `cpu_baseline` and the other CPU legs of the headline workload;
+  * `also.{c1_w2a2, c2b, c1, c3, c4, c5}`: the same measurement (value, ms_per_step, roofline of its own dominant kernel) for DoReFa W2A2 on nin_gc (the
+    second half of BASELINE.json's metric, which names nin_gc under BOTH low-bit schemes) and for every other BASELINE config at 256 images per GPU;
+    `values` repeats all images/s figures at top level (`--also` picks other secondary workloads, in a plain run too; `--also ''` none);
+  * the single-rank data-parallel leg, the exact three-term gradient figures, the eager IAO data-parallel step, the per-rank collective times at N > 1,
+    and the detail file (also written by a plain run that names `--detail`).  The `--no-*` switches trim a --full run.
 `--only W` measures a single workload (profiling runs).  Prints ONE JSON line on rank 0.
 `--gpus N` without a launcher (WORLD_SIZE unset) starts the N ranks itself (torch.distributed.run, 127.0.0.1) and relays rank 0's line.
 The timed region is EXACTLY `--steps` steps after `--warmup` untimed ones (and the graph capture's own three), split into `--repeats` windows between barriers (default one); `value` /
@@ -69,6 +76,7 @@ WORKLOAD_DESC = {
     "c5": "resnet18 CIFAR-10 IAO W4A4 per-channel + quant_add QAT (BASELINE configs[4])",
 }
 METRIC = {"c2": "QAT images/sec (nin_gc CIFAR-10, W-ternary/A-binary)", "c1_w2a2": "QAT images/sec (nin_gc CIFAR-10, DoReFa W2A2)"}
+ALSO_FULL = "c1_w2a2,c2b,c1,c3,c4,c5"     # the secondary workloads of a --full run, and of a plain one that writes --dump-outputs
 
 
 class KernelProfiler:
@@ -258,9 +266,9 @@ def measure(workload, args, world, rank, device):
     dt = sorted(windows)[len(windows) // 2]                 # the median window
     final_loss = float(loss.detach())
     outputs = last_step_outputs(model, loss, logits) if args.dump_outputs and rank == 0 else None
-    # data-parallel runs: what the step's collectives cost by themselves -- the gradient bucket(s) all-reduced 10 times back to back, HIP events on the stream
+    # data-parallel runs (--full): what the step's collectives cost by themselves -- the gradient bucket(s) all-reduced 10 times back to back, HIP events on the stream
     dp_info = None
-    if dp.active() and graphed is not None and getattr(graphed, "flat", None) is not None:
+    if args.full and dp.active() and graphed is not None and getattr(graphed, "flat", None) is not None:
         bufs = [b for b in (graphed.flat, getattr(graphed, "flat2", None)) if b is not None]
         scratch = [torch.zeros_like(b) for b in bufs]
         us = []
@@ -402,7 +410,7 @@ def dp_single_child(workloads, args):
     """dp_single_rank in a process of its own: it brings up a process group (an RCCL communicator, its watchdog thread) next to HIP-graph captures -- whatever goes wrong
     there must not cost the line of the run that asked for it."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--dp-single-child", ",".join(workloads), "--batch", str(args.batch), "--steps", str(args.steps),
-           "--warmup", str(args.warmup), "--master-port", str(args.master_port), "--no-pmc", "--no-cpu-baseline"]
+           "--warmup", str(args.warmup), "--master-port", str(args.master_port), "--full", "--no-pmc", "--no-cpu-baseline"]
     try:
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=300)
         return json.loads(r.stdout.decode().strip().splitlines()[-1])
@@ -709,14 +717,18 @@ def write_detail(detail, args):
         return "unwritten: %s" % e
 
 
-def main():
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=256, help="per-GPU batch")
     ap.add_argument("--workload", default="c2", choices=list(WORKLOADS), help="primary workload (value / roofline / cpu_baseline)")
-    ap.add_argument("--also", default="c1_w2a2,c2b,c1,c3,c4,c5", help="comma-separated secondary workloads reported under `also` ('' = none)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline too: secondary workloads, roofline (HIP-event and PMC passes), CPU baselines, "
+                         "the single-rank data-parallel leg, the exact-terms figures, the detail file")
+    ap.add_argument("--also", default=None,
+                    help="comma-separated secondary workloads reported under `also` ('' = none; default: none, with --full or --dump-outputs %s)" % ALSO_FULL)
     ap.add_argument("--repeats", type=int, default=1, help="timed windows the --steps timed steps are split into; value = the median window")
     ap.add_argument("--master-port", type=int, default=29531, help="rendezvous port when --gpus N > 1 starts its own ranks")
     ap.add_argument("--only", default=None, choices=list(WORKLOADS), help="measure this single workload (no `also`)")
@@ -742,21 +754,36 @@ def main():
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write what the timed step computed in its last step, per measured workload, as DIR/<workload>_{loss,logits,params,grads,buffers}.npy "
                          "(float32; arrays above %d elements as a fixed seeded sample)" % DUMP_SAMPLE)
-    args = ap.parse_args()
-    if args.steps < 1 or args.repeats < 1:
-        ap.error("--steps and --repeats must be at least 1")
+    return ap
 
+
+def plan(args):
+    """(primary workload, secondary workloads) of this run.  A plain run (no --full) sets up, warms up, times the steps, dumps the outputs if asked and prints
+    the line: every other leg of main() is switched off here.  Its secondary workloads are those --also names; by default none, unless it dumps: the dump
+    holds every workload --full measures."""
+    if not args.full:
+        args.no_kernel_timing = args.no_pmc = args.no_cpu_baseline = args.no_dp_single = True
     primary = args.only or args.workload
-    also = [] if args.only else [w for w in args.also.split(",") if w and w != primary]
-    if args.gpus > 1 and args.also == ap.get_default("also"):
-        # multi-GPU runs measure the scaling of the headline step: by default the two nin_gc schemes the metric names (same graphed data-parallel step), plus the
+    also_arg = args.also if args.also is not None else (ALSO_FULL if args.full or args.dump_outputs else "")
+    also = [] if args.only else [w for w in also_arg.split(",") if w and w != primary]
+    if args.gpus > 1 and args.also is None:
+        # multi-GPU --full (or dumping) runs measure the scaling of the headline step: by default the two nin_gc schemes the metric names (same graphed data-parallel step), plus the
         # BASELINE config that is DEFINED at this GPU count (configs[3]: resnet DoReFa W2A2 on 4 GPUs; configs[4]: resnet IAO W4A4 + quant_add on 8); the other
-        # configs are single-GPU lines (`also` of the --gpus 1 run) unless --also asks for them explicitly
+        # configs are single-GPU lines (`also` of the --gpus 1 --full run) unless --also asks for them explicitly
         keep = {"c1_w2a2"} | ({"c4"} if args.gpus == 4 else set()) | ({"c5"} if args.gpus == 8 else set())
         also = [w for w in also if w in keep]
     for w in also:
         if w not in WORKLOADS:
             raise SystemExit("unknown workload in --also: %s" % w)
+    return primary, also
+
+
+def main():
+    ap = arg_parser()
+    args = ap.parse_args()
+    if args.steps < 1 or args.repeats < 1:
+        ap.error("--steps and --repeats must be at least 1")
+    primary, also = plan(args)
     if args.cpu_ref_child:
         cpu_reference_child(primary, args.cpu_batch, args.cpu_steps, args.cpu_threads)
         return
@@ -840,7 +867,8 @@ def main():
             detail["values_exact_terms"] = terms3
             if len(json.dumps(out)) + len(json.dumps(terms3)) + 32 <= MAX_LINE_BYTES:
                 out["values_exact_terms"] = {w: v.get("value", v.get("error")) for w, v in terms3.items()}
-        out["detail_file"] = write_detail(detail, args)
+        if args.full or args.detail:
+            out["detail_file"] = write_detail(detail, args)
     if world > 1:
         if rank != 0:
             drain_c_stdio()          # (whatever a library buffered on the other ranks goes out BEFORE rank 0's line, not at their exit)

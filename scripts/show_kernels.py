@@ -1,4 +1,4 @@
-"""print the per-kernel table of a bench.py --detail file:  python scripts/show_kernels.py gpurun_out/quick_c2.json [top]"""
+"""print the per-kernel table of a bench.py --detail file:  python scripts/show_kernels.py out/quick_c2.json [top]"""
 import json
 import sys
 d = json.load(open(sys.argv[1]))

@@ -202,6 +202,28 @@ def test_bench_final_line_stays_parsable():
     assert set(detail["sections"]) >= {"c2", "c1", "c3", "c4", "c5"} and "kernels" in detail["sections"]["c4"]
 
 
+def test_bench_plain_run_measures_the_headline_alone():
+    """A plain `bench.py --gpus 1 --steps N --warmup W` times the headline workload and nothing else; --full brings back the secondary workloads and every
+    other leg (per-kernel timing and roofline, PMC passes, CPU baselines, single-rank data-parallel leg), and an explicit --also is honoured either way."""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("mn_bench", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    ap = bench.arg_parser()
+    legs = ("no_kernel_timing", "no_pmc", "no_cpu_baseline", "no_dp_single")
+    plain = ap.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.plan(plain) == ("c2", []) and all(getattr(plain, k) for k in legs)
+    full = ap.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    assert bench.plan(full) == ("c2", ["c1_w2a2", "c2b", "c1", "c3", "c4", "c5"]) and not any(getattr(full, k) for k in legs)
+    # --dump-outputs writes every workload of a --full run, so a plain run that dumps times them too -- and nothing else of --full
+    dump = ap.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", "d"])
+    assert bench.plan(dump) == bench.plan(ap.parse_args(["--full"])) and all(getattr(dump, k) for k in legs)
+    assert bench.plan(ap.parse_args(["--gpus", "2"]))[1] == [] and bench.plan(ap.parse_args(["--gpus", "2", "--full"]))[1] == ["c1_w2a2"]
+    assert bench.plan(ap.parse_args(["--also", "c4"]))[1] == ["c4"] and bench.plan(ap.parse_args(["--full", "--only", "c3"])) == ("c3", [])
+
+
 def test_bench_line_is_printed_behind_what_libraries_buffered_in_c_stdio():
     """Round 5: RCCL prints a version banner through C stdio when a communicator is created; on a pipe that buffer is flushed at process exit, i.e. BEHIND a line
     printed from Python -- and the driver parses the LAST stdout line.  bench.drain_c_stdio() empties the C streams first."""
