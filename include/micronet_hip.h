@@ -557,9 +557,12 @@ int mn_bnh_bwd_apply(const float* da, const uint8_t* h, const int8_t* own, const
  * splits -> sums [2][C], dgamma, dbeta (nullable) */
 int mn_bnh_bwd_sums_final(const double* part, int32_t splits, int64_t N, int64_t C, int64_t H, int64_t W, float* dgamma, float* dbeta, float* sums,
                           mn_stream_t stream);
-/* ... and the consumers of that dy can form it themselves: backward-data / backward-weight of the block's pointwise convolution whose incoming
+/* ... and the consumers of that dy can form it themselves: backward-data / backward-weight of the block's convolution whose incoming
  * gradient is the BatchNorm+sign backward of (da, h) -- evaluated in registers while da and h stream in, so dy is never written or re-read
- * (x = the block's input codes; chan, sums as above; needs mn_conv2d_bnh_supported). */
+ * (x = the block's input codes; chan, sums as above; needs mn_conv2d_bnh_supported).  Covered: the pointwise blocks, and the grouped 3x3 / stride 1 /
+ * padding 1 block on sign codes with ternary / binary weights (W = 8, 16 or 32, H >= 2, at most 32 output channels per group: k_k3s_dgrad<1>,
+ * k_k3s_wgrad<0, 1>; chan has 17 rows), where dx, dw and dbias are bit-identical to mn_bnh_bwd_apply followed by mn_conv2d_bwd_data / _weight.  da must be
+ * 16-byte and h 4-byte aligned: other operands are refused (MN_ENOTSUP). */
 int mn_conv2d_bnh_supported(const mn_conv_geom* g, const mn_wq* wq);
 int mn_conv2d_bwd_data_bnh(const mn_conv_geom* g, const mn_wq* wq, const float* da, const uint8_t* h, const float* chan, const float* sums,
                            int training, const float* w, float* dx, void* ws, int64_t ws_bytes, mn_stream_t stream);

@@ -811,13 +811,14 @@ extern "C" int mn_conv2d_bwd_data(const mn_conv_geom* g, const mn_actq* aq, cons
 
 extern "C" int mn_conv2d_bnh_supported(const mn_conv_geom* g, const mn_wq* wq) {
     if (check_geom(g, "mn_conv2d_bnh_supported") != MN_OK) return 0;
-    return pwd_supported(g, wq) && pws_wgrad_supported(g);
+    return (pwd_supported(g, wq) && pws_wgrad_supported(g)) || k3s_bnh_supported(g, wq);
 }
 extern "C" int mn_conv2d_bwd_data_bnh(const mn_conv_geom* g, const mn_wq* wq, const float* da, const uint8_t* h, const float* chan, const float* sums,
                                       int training, const float* w, float* dx, void* ws, int64_t ws_bytes, mn_stream_t stream) {
     int rc = check_geom(g, "mn_conv2d_bwd_data_bnh");
     if (rc) return rc;
     if (!da || !h || !chan || !sums || !w || !dx) MN_FAIL(MN_EINVAL, "mn_conv2d_bwd_data_bnh: null tensor");
+    if (k3s_bnh_supported(g, wq)) return k3s_bwd_data_bnh(g, wq, da, h, chan, sums, training, w, dx, (hipStream_t)stream);      // grouped 3x3 block: staged-image kernel
     return pwd_bwd_data_bnh(g, wq, da, h, chan, sums, training, w, dx, ws, ws_bytes, (hipStream_t)stream);
 }
 extern "C" int mn_conv2d_bwd_weight_bnh(const mn_conv_geom* g, const float* da, const uint8_t* h, const float* chan, const float* sums, int training,
@@ -825,6 +826,7 @@ extern "C" int mn_conv2d_bwd_weight_bnh(const mn_conv_geom* g, const float* da, 
     int rc = check_geom(g, "mn_conv2d_bwd_weight_bnh");
     if (rc) return rc;
     if (!da || !h || !chan || !sums || !x || !dw) MN_FAIL(MN_EINVAL, "mn_conv2d_bwd_weight_bnh: null tensor");
+    if (g->KH == 3 && g->KW == 3) return k3s_bwd_weight_bnh(g, da, h, chan, sums, training, x, dw, dbias, ws, ws_bytes, (hipStream_t)stream);
     return pws_bwd_weight_bnh(g, da, h, chan, sums, training, x, dw, dbias, ws, ws_bytes, (hipStream_t)stream);
 }
 // the same two behind a block whose output is MAX-POOLED (2x2 / stride 2): dpool = d loss / d pooled output [N][O][H/2][W/2], own = the block's sign output

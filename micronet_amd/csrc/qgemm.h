@@ -52,6 +52,12 @@ int pws_bwd_weight(const mn_conv_geom* g, const float* gy, const int8_t* x, floa
 // BatchNorm+sign backward folded into the consumers of dy (pointwise, sign-code activations): see k_pwd / k_pws_wgrad
 int pwd_supported(const mn_conv_geom* g, const mn_wq* wq);
 int64_t pwd_ws_bytes(const mn_conv_geom* g);
+// grouped 3 x 3 binary block (qgemm_k3s.hip) behind a BatchNorm + sign block: dy formed from (da, h) in the staging step (k_k3s_dgrad<1>, k_k3s_wgrad<0, 1>), bit-identical to k_bnh_apply<0> + the plain kernels
+int k3s_bnh_supported(const mn_conv_geom* g, const mn_wq* wq);
+int k3s_bwd_data_bnh(const mn_conv_geom* g, const mn_wq* wq, const float* da, const uint8_t* h, const float* chan, const float* sums, int training, const float* w,
+                     float* dx, hipStream_t s);
+int k3s_bwd_weight_bnh(const mn_conv_geom* g, const float* da, const uint8_t* h, const float* chan, const float* sums, int training, const int8_t* x, float* dw,
+                       float* dbias, void* ws, int64_t ws_bytes, hipStream_t s);
 int pwd_bwd_data_bnh(const mn_conv_geom* g, const mn_wq* wq, const float* da, const uint8_t* h, const float* chan, const float* sums, int training,
                      const float* w, float* dx, void* ws, int64_t ws_bytes, hipStream_t s, const int8_t* own = nullptr);
 int pws_bwd_weight_bnh(const mn_conv_geom* g, const float* da, const uint8_t* h, const float* chan, const float* sums, int training, const int8_t* x,

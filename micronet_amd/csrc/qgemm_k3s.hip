@@ -27,8 +27,54 @@
 #define K3_RSA 160            // LDS bytes per gy row (32 pixels fp32 + pad)
 #define K3_NXL 6              // code dwords a lane stages per step (W = 32: 16 channels x 3 rows x 8 dwords = 384 = 6 x 64)
 
+// ---- BNH variants of k_k3s_wgrad<0> and k_k3s_dgrad: the block behind the convolution is the fused BatchNorm + sign, and `gy` is not dy but that block's incoming
+// gradient da; the staging threads read the stash dword h of the same four pixels and form dy with the arithmetic of k_bnh_apply<0> (norm_kernels.hip), same
+// expression, same operation order (the library is built with -ffp-contract=off), so dy -- and with it dx, dw, dbias -- is bit-identical to the two-step path and dy
+// itself never exists in HBM.  The per-channel constants of the block's 32 output channels sit in LDS, K3B_CS floats per channel:
+//   [0] flip  [1] L  [2] U  [3] gi  [4] A  [5] B  [6] k1  [7] k2  [8 + 3 rc + cc] nnz of border class (rc, cc)
+// and are re-read where dy is formed (two b128 + three b32 reads per gy row of four pixels) instead of being held in registers for the whole kernel.
+#define K3B_CS 20
+struct K3Bnh {
+    const unsigned char* h;   // the byte stash, same shape as da
+    const float* chan;        // [17][O] (or [8][O]: one nnz per channel)
+    const float* sums;        // [2][O]
+    int training;
+    float n_f;                // (float)N * (float)HW, as k_bnh_apply forms it
+};
+// thread m < 32 writes the constants of channel co0 + min(m, nvalid - 1)
+__device__ __forceinline__ void k3b_fill(float* tab, const K3Bnh& q, int O, int co0, int nvalid, int m) {
+    const int co = co0 + (m < nvalid ? m : nvalid - 1);
+    float* t = tab + m * K3B_CS;
+    float k1 = 0.f, k2 = 0.f;
+    if (q.training) { k1 = q.sums[co] / q.n_f; k2 = q.sums[O + co] / q.n_f; }
+    t[0] = q.chan[O + co]; t[1] = q.chan[2 * O + co]; t[2] = q.chan[3 * O + co]; t[3] = q.chan[6 * O + co];
+    t[4] = q.chan[4 * O + co]; t[5] = q.chan[5 * O + co]; t[6] = k1; t[7] = k2;
+    const StashNnz z = stash_nnz_load(q.chan, O, co);
+    t[8] = z.v0; t[9] = z.v1; t[10] = z.v2; t[11] = z.v3; t[12] = z.v4; t[13] = z.v5; t[14] = z.v6; t[15] = z.v7; t[16] = z.v8;
+    t[17] = 0.f; t[18] = 0.f; t[19] = 0.f;
+}
+// dy of four pixels of one channel: ct = the channel's constants, nzo = 8 + 3 rc, (c0, c3) = the column class of pixels 0 / 3 (0 left, 1 middle, 2 right)
+__device__ __forceinline__ float4 k3b_dy4(const float* ct, int nzo, int c0, int c3, const float4 da, const uint32_t hb) {
+    const float4 ca = *reinterpret_cast<const float4*>(ct), cb = *reinterpret_cast<const float4*>(ct + 4);
+    const float fl = ca.x, L = ca.y, U = ca.z, gi = ca.w, A = cb.x, B = cb.y, k1 = cb.z, k2 = cb.w;
+    const float nm = ct[nzo + 1];
+    const float nz[4] = {ct[nzo + c0], nm, nm, ct[nzo + c3]};
+    const float hv[4] = {(float)(hb & 0xffu), (float)((hb >> 8) & 0xffu), (float)((hb >> 16) & 0xffu), (float)(hb >> 24)};
+    const float gv[4] = {da.x, da.y, da.z, da.w};
+    float r[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float acc = 2.f * hv[e] - nz[e];
+        const float u = acc * fl;
+        const float dz = (u >= L && u <= U) ? gv[e] : 0.f;
+        r[e] = gi * (dz - k1 - fmaf(acc, A, B) * k2);
+    }
+    return make_float4(r[0], r[1], r[2], r[3]);
+}
+
 struct K3wParams {
-    const float* gy;
+    const float* gy;          // BNH: da
+    K3Bnh bn;
     const char* x;
     float* part;      // [Z][G][Mgw][Cgw*9]
     float* dbpart;    // [Z][G][Mgw]
@@ -43,7 +89,8 @@ struct K3wParams {
 // v_perm to interleave: exact bf16 j, 8 VALU per fragment dword pair instead of 2.  The reduction multiplies by the quantizer's scale.
 // XENC 2: codes j <= 255 (a_bits 4 .. 8): same patch of raw bytes, the fragment is bf16 j = the high half of (float)j (v_cvt_f32_ubyte x 4 + 2 v_perm per
 // shifted dword).
-template <int XENC>
+// BNH 1 (XENC 0 only): gy is da of the BatchNorm+sign block behind the convolution; dy is formed in commit() (above).
+template <int XENC, int BNH>
 __global__ __launch_bounds__(256, 2) void k_k3s_wgrad(const K3wParams p) {
     HIP_DYNAMIC_SHARED(float, smem)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kg = lane >> 4;
@@ -63,6 +110,16 @@ __global__ __launch_bounds__(256, 2) void k_k3s_wgrad(const K3wParams p) {
     }
     // staging roles.  gy: row (lane >> 3) + 8 i, pixels 4 (lane & 7) ...;  codes: dword (lane + 64 u) of the [16][DPC] patch
     const int sr = lane >> 3, sq = lane & 7;
+    // BNH: the block's per-channel constants behind the four waves' images; a lane's four pixels sit in image row oh0 + blr, column class of pixels 0 / 3: bc0 / bc3
+    const float* btab = reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(smem) + 4 * (32 * K3_RSA + p.XB));
+    int bcls = 0;                                       // blr | bc0 << 8 | bc3 << 16 in one register
+    if (BNH) {
+        if (tid < 32) k3b_fill(const_cast<float*>(btab), p.bn, p.O, g * p.Mg + mb * 32, p.Mg - mb * 32, tid);
+        const uint32_t lr = fd_div(sq, p.fd_w4);
+        const int c4 = sq - (int)lr * p.W4;
+        bcls = (int)lr | (c4 == 0 ? 0 : 1) << 8 | (c4 == p.W4 - 1 ? 2 : 1) << 16;
+        __syncthreads();
+    }
     uint32_t goff[4];
     float dbacc[4];
 #pragma unroll
@@ -74,7 +131,11 @@ __global__ __launch_bounds__(256, 2) void k_k3s_wgrad(const K3wParams p) {
     }
     const int ccv = (p.Cg - cb * 16) < 16 ? (p.Cg - cb * 16) : 16;      // channels beyond Cg: zero codes
     uint32_t xoff[K3_NXL];      // byte offset of the dword inside image n, without its row
-    int xlds[K3_NXL], xpr[K3_NXL];      // LDS byte offset (-1: no item); patch row
+    // LDS byte offset (-1: no item); patch row.  BNH: both in one register ((offset + 1) << 16 | row + 1000) -- the variant has no registers to spare
+    int xlds[BNH ? 1 : K3_NXL], xpr[BNH ? 1 : K3_NXL];
+    uint32_t xpk[BNH ? K3_NXL : 1];
+    auto x_lds = [&](int u) -> int { return BNH ? (int)(xpk[u] >> 16) - 1 : xlds[u]; };
+    auto x_pr = [&](int u) -> int { return BNH ? (int)(xpk[u] & 0xffffu) - 1000 : xpr[u]; };
 #pragma unroll
     for (int u = 0; u < K3_NXL; ++u) {
         const int idx = lane + 64 * u;
@@ -84,8 +145,10 @@ __global__ __launch_bounds__(256, 2) void k_k3s_wgrad(const K3wParams p) {
         const int col4 = d - (int)pr * p.W4;
         const int cc = (int)c < ccv ? (int)c : ccv - 1;
         xoff[u] = (uint32_t)chan_phys(p.in_map, g * p.Cg + cb * 16 + cc) * HW + 4u * col4;
-        xlds[u] = (idx < 16 * p.DPC) ? (int)c * p.CS + 4 + (int)pr * (p.W + 4) + 4 * col4 : -1;
-        xpr[u] = ((int)c < ccv) ? (int)pr : -1000;      // a channel beyond Cg never has a valid row
+        const int xl = (idx < 16 * p.DPC) ? (int)c * p.CS + 4 + (int)pr * (p.W + 4) + 4 * col4 : -1;
+        const int xp = ((int)c < ccv) ? (int)pr : -1000;      // a channel beyond Cg never has a valid row
+        if (BNH) xpk[u] = ((uint32_t)(xl + 1) << 16) | (uint32_t)(xp + 1000);
+        else { xlds[u] = xl; xpr[u] = xp; }
     }
     f32x4 acc[2][9];
 #pragma unroll
@@ -93,7 +156,7 @@ __global__ __launch_bounds__(256, 2) void k_k3s_wgrad(const K3wParams p) {
 #pragma unroll
         for (int t = 0; t < 9; ++t) acc[mi][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    struct Stage { float4 gv[4]; uint32_t xv[K3_NXL]; int oh0; };
+    struct Stage { float4 gv[4]; uint32_t hv[BNH ? 4 : 1]; uint32_t xv[K3_NXL]; int oh0; };
     Stage s0, s1;
     const int st0 = z * p.st_per_z;
     const int nblk = ((st0 + p.st_per_z) < p.nsteps ? (st0 + p.st_per_z) : p.nsteps) - st0;     // steps of this block
@@ -107,16 +170,25 @@ __global__ __launch_bounds__(256, 2) void k_k3s_wgrad(const K3wParams p) {
         S.oh0 = oh0;
         const uint32_t go = n * (uint32_t)p.O * HW + (uint32_t)(oh0 * p.W);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) S.gv[i] = *reinterpret_cast<const float4*>(p.gy + (go + goff[i]));
+        for (int i = 0; i < 4; ++i) {
+            S.gv[i] = *reinterpret_cast<const float4*>(p.gy + (go + goff[i]));
+            if (BNH) S.hv[i] = *reinterpret_cast<const uint32_t*>(p.bn.h + (go + goff[i]));
+        }
         const uint32_t xo = n * (uint32_t)p.C * HW;
 #pragma unroll
         for (int u = 0; u < K3_NXL; ++u) {
-            int ir = oh0 - 1 + (xpr[u] < 0 ? 0 : xpr[u]);
+            int ir = oh0 - 1 + (x_pr(u) < 0 ? 0 : x_pr(u));
             ir = ir < 0 ? 0 : (ir < p.H ? ir : p.H - 1);          // rows outside the image: any valid address (written as zeros)
             S.xv[u] = *reinterpret_cast<const uint32_t*>(p.x + (xo + xoff[u] + (uint32_t)(ir * p.W)));
         }
     };
     auto commit = [&](Stage& S, bool valid) {
+        if (BNH) {
+            const int row = S.oh0 + (bcls & 0xff), bc0 = (bcls >> 8) & 0xff, bc3 = bcls >> 16;
+            const int nzo = 8 + 3 * (row == 0 ? 0 : (row == p.H - 1 ? 2 : 1));
+#pragma unroll
+            for (int i = 0; i < 4; ++i) S.gv[i] = k3b_dy4(btab + (sr + 8 * i) * K3B_CS, nzo, bc0, bc3, S.gv[i], S.hv[i]);
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             dbacc[i] += valid ? (S.gv[i].x + S.gv[i].y) + (S.gv[i].z + S.gv[i].w) : 0.f;
@@ -124,9 +196,9 @@ __global__ __launch_bounds__(256, 2) void k_k3s_wgrad(const K3wParams p) {
         }
 #pragma unroll
         for (int u = 0; u < K3_NXL; ++u) {
-            const int ir = S.oh0 - 1 + xpr[u];
+            const int ir = S.oh0 - 1 + x_pr(u);
             const uint32_t enc = (ir >= 0 && ir < p.H) ? (XENC ? S.xv[u] : ((S.xv[u] & 0x80808080u) | 0x3F3F3F3Fu)) : 0u;
-            if (xlds[u] >= 0) *reinterpret_cast<uint32_t*>(xsm + xlds[u]) = enc;
+            if (x_lds(u) >= 0) *reinterpret_cast<uint32_t*>(xsm + x_lds(u)) = enc;
         }
     };
     // fragment geometry of this lane: chunk a = pixels 4 kg .. + 3, chunk b = pixels 16 + 4 kg .. + 3 of the step
@@ -243,7 +315,7 @@ __global__ __launch_bounds__(256, 2) void k_k3s_wgrad(const K3wParams p) {
     if (p.want_db && cb == 0 && tid < 32) p.dbpart[((int64_t)z * p.G + g) * p.Mgw + mb * 32 + tid] = dbs[tid];
 }
 
-struct K3wPlan { K3wParams p; int grid; size_t lds; int64_t off_db, ws_bytes; };
+struct K3wPlan { K3wParams p; int grid; size_t lds, lds_wave; int64_t off_db, ws_bytes; };
 static int plan_k3s(const mn_conv_geom* g, K3wPlan* pl) {
     if (g->KH != 3 || g->KW != 3 || g->stride_h != 1 || g->stride_w != 1 || g->pad_h != 1 || g->pad_w != 1 || g->dil_h != 1 || g->dil_w != 1) return 0;
     if (g->W != 8 && g->W != 16 && g->W != 32) return 0;
@@ -271,6 +343,7 @@ static int plan_k3s(const mn_conv_geom* g, K3wPlan* pl) {
     pl->grid = (int)nb;
     size_t lds = (size_t)4 * (32 * K3_RSA + p.XB), red = (size_t)(32 * 144 + 32) * 4;
     pl->lds = lds > red ? lds : red;
+    pl->lds_wave = lds;
     const int64_t part_bytes = (int64_t)Z * p.G * p.Mgw * p.Cgw * 9 * 4;
     pl->off_db = (part_bytes + 255) / 256 * 256;
     pl->ws_bytes = pl->off_db + (int64_t)Z * p.G * p.Mgw * 4;
@@ -278,22 +351,41 @@ static int plan_k3s(const mn_conv_geom* g, K3wPlan* pl) {
 }
 int k3s_wgrad_supported(const mn_conv_geom* g) { K3wPlan pl; return plan_k3s(g, &pl); }
 int64_t k3s_wgrad_ws_bytes(const mn_conv_geom* g) { K3wPlan pl; return plan_k3s(g, &pl) ? pl.ws_bytes : 0; }
-int k3s_bwd_weight(const mn_conv_geom* g, const float* gy, const int8_t* x, float* dw, float* dbias, void* ws, int64_t ws_bytes, hipStream_t s) {
+// h != NULL: gy is da of the BatchNorm+sign block behind the convolution and dy is formed inside the kernel (k_k3s_wgrad<0, 1>); H >= 2 (k_bnh_apply's blend of a
+// row that is top and bottom at once is not reproduced)
+static int k3s_bwd_weight_any(const mn_conv_geom* g, const float* gy, const uint8_t* h, const float* chan, const float* sums, int training, const int8_t* x, float* dw,
+                              float* dbias, void* ws, int64_t ws_bytes, hipStream_t s) {
     K3wPlan pl;
-    if (!plan_k3s(g, &pl) || !aligned16(gy) || (((uintptr_t)x) & 3)) MN_FAIL(MN_ENOTSUP, "mn_conv2d_bwd_weight(sign 3x3): geometry not covered");
+    if (!plan_k3s(g, &pl) || !aligned16(gy) || (((uintptr_t)x) & 3) || (h && ((((uintptr_t)h) & 3) || g->H < 2 || !chan || !sums)))
+        MN_FAIL(MN_ENOTSUP, "mn_conv2d_bwd_weight(sign 3x3): geometry not covered");
     if (!ws || ws_bytes < pl.ws_bytes || !aligned16(ws)) MN_FAIL(MN_ENOSPC, "mn_conv2d_bwd_weight(sign 3x3): workspace too small");
     K3wParams& p = pl.p;
     p.gy = gy; p.x = (const char*)x; p.part = (float*)ws; p.dbpart = (float*)((char*)ws + pl.off_db); p.want_db = dbias != nullptr;
-    mn_set_last_kernel("k_k3s_wgrad");
-    { const double nx = (double)g->N * g->C * g->H * g->W, ny = (double)g->N * g->O * g->H * g->W; mn_prof_bytes(4.0 * ny + nx); }
+    p.bn.h = h; p.bn.chan = chan; p.bn.sums = sums; p.bn.training = training; p.bn.n_f = (float)g->N * (float)(g->H * g->W);
+    mn_set_last_kernel(h ? "k_k3s_wgrad<0, 1>" : "k_k3s_wgrad");
+    { const double nx = (double)g->N * g->C * g->H * g->W, ny = (double)g->N * g->O * g->H * g->W; mn_prof_bytes((h ? 5.0 : 4.0) * ny + nx); }
     mn_prof_begin(s);
-    raise_lds_limit((const void*)k_k3s_wgrad<0>, pl.lds);
-    hipLaunchKernelGGL(k_k3s_wgrad<0>, dim3(pl.grid), dim3(256), pl.lds, s, p);
+    if (h) {
+        const size_t lds = pl.lds_wave + (size_t)32 * K3B_CS * 4 > pl.lds ? pl.lds_wave + (size_t)32 * K3B_CS * 4 : pl.lds;      // the constants sit behind the waves' images
+        raise_lds_limit((const void*)k_k3s_wgrad<0, 1>, lds);
+        hipLaunchKernelGGL((k_k3s_wgrad<0, 1>), dim3(pl.grid), dim3(256), lds, s, p);
+    } else {
+        raise_lds_limit((const void*)k_k3s_wgrad<0, 0>, pl.lds);
+        hipLaunchKernelGGL((k_k3s_wgrad<0, 0>), dim3(pl.grid), dim3(256), pl.lds, s, p);
+    }
     mn_prof_end(s);
     // the codes were contracted as +-0.5: the reduction doubles (exact)
     qg_launch_wgrad_reduce(p.part, p.dbpart, dw, dbias, p.Z, p.G, p.Mg, p.Cg * 9, p.Mgw, p.Cgw * 9, 2.f, nullptr, s);
     MN_CHECK_LAUNCH("mn_conv2d_bwd_weight(sign 3x3)");
     return MN_OK;
+}
+int k3s_bwd_weight(const mn_conv_geom* g, const float* gy, const int8_t* x, float* dw, float* dbias, void* ws, int64_t ws_bytes, hipStream_t s) {
+    return k3s_bwd_weight_any(g, gy, nullptr, nullptr, nullptr, 0, x, dw, dbias, ws, ws_bytes, s);
+}
+int k3s_bwd_weight_bnh(const mn_conv_geom* g, const float* da, const uint8_t* h, const float* chan, const float* sums, int training, const int8_t* x, float* dw,
+                       float* dbias, void* ws, int64_t ws_bytes, hipStream_t s) {
+    if (!h) MN_FAIL(MN_EINVAL, "mn_conv2d_bwd_weight_bnh(3x3): null stash");
+    return k3s_bwd_weight_any(g, da, h, chan, sums, training, x, dw, dbias, ws, ws_bytes, s);
 }
 // 3 x 3 backward-weight on k-bit activation codes (bytes): dw = s * sum gy * j;  a_bits <= 3: the 8-entry look-up (XENC 1), else the conversion (XENC 2)
 int k3s_wgrad_code8_supported(const mn_conv_geom* g, int a_bits) { K3wPlan pl; return a_bits >= 2 && a_bits <= 8 && plan_k3s(g, &pl); }
@@ -308,11 +400,11 @@ int k3s_bwd_weight_code8(const mn_conv_geom* g, const float* gy, const uint8_t* 
     { const double nx = (double)g->N * g->C * g->H * g->W, ny = (double)g->N * g->O * g->H * g->W; mn_prof_bytes(4.0 * ny + nx); }
     mn_prof_begin(s);
     if (lut) {
-        raise_lds_limit((const void*)k_k3s_wgrad<1>, pl.lds);
-        hipLaunchKernelGGL(k_k3s_wgrad<1>, dim3(pl.grid), dim3(256), pl.lds, s, p);
+        raise_lds_limit((const void*)k_k3s_wgrad<1, 0>, pl.lds);
+        hipLaunchKernelGGL((k_k3s_wgrad<1, 0>), dim3(pl.grid), dim3(256), pl.lds, s, p);
     } else {
-        raise_lds_limit((const void*)k_k3s_wgrad<2>, pl.lds);
-        hipLaunchKernelGGL(k_k3s_wgrad<2>, dim3(pl.grid), dim3(256), pl.lds, s, p);
+        raise_lds_limit((const void*)k_k3s_wgrad<2, 0>, pl.lds);
+        hipLaunchKernelGGL((k_k3s_wgrad<2, 0>), dim3(pl.grid), dim3(256), pl.lds, s, p);
     }
     mn_prof_end(s);
     qg_launch_wgrad_reduce(p.part, p.dbpart, dw, dbias, p.Z, p.G, p.Mg, p.Cg * 9, p.Mgw, p.Cgw * 9, ascale, nullptr, s);
@@ -341,7 +433,8 @@ int k3s_bwd_weight_code8(const mn_conv_geom* g, const float* gy, const uint8_t* 
 #define K3D_MAXF4 8           // float4 a thread stages per stage: 32 rows x SP pixels / 256 threads / 4, SP <= 256
 
 struct K3dParams {
-    const float* gy;
+    const float* gy;          // BNH: da
+    K3Bnh bn;
     const float* w;           // fake-quantised weights [O][Cg][3][3]
     float* dx;
     float wn;                 // 0: ternary / binary weights (code = sign, scale = max |w| of the row);  n = 2^w_bits - 1: DoReFa weights (2k - n) / n
@@ -352,10 +445,13 @@ struct K3dParams {
     ChanMap out_map;
 };
 
+// BNH 1: gy is da of the BatchNorm+sign block behind the convolution (ternary / binary weights); dy is formed in commit() (see K3Bnh above).
+template <int BNH>
 __global__ __launch_bounds__(256, 2) void k_k3s_dgrad(const K3dParams p) {
     HIP_DYNAMIC_SHARED(float, smem)
     unsigned char* lds = reinterpret_cast<unsigned char*>(smem);
     float* alpha = reinterpret_cast<float*>(lds + 3 * p.TS);          // [32]
+    float* btab = alpha + 32;                                         // BNH: [32][K3B_CS]
     const int tid = threadIdx.x, lane = tid & 63, wave = mn_uniform(tid >> 6), j = lane & 15, kg = lane >> 4;
     uint32_t b = blockIdx.x;
     const int z = b % p.Zb; b /= p.Zb;
@@ -397,12 +493,14 @@ __global__ __launch_bounds__(256, 2) void k_k3s_dgrad(const K3dParams p) {
     __syncthreads();                                                   // everybody is done with the weight image
     for (int i = tid; i < (3 * p.TS) / 16; i += 256) *reinterpret_cast<u32x4*>(lds + 16 * i) = u32x4{0u, 0u, 0u, 0u};
     if ((tid & 7) == 0) alpha[tid >> 3] = my_alpha;
+    if (BNH && tid < 32) k3b_fill(btab, p.bn, p.O, g * p.Mg, p.Mg, tid);
     // staging roles: pair u of this thread = (chunk, sr): rows m = sr + 8 i, pixels 4 chunk .. of the stage
     const int cps = p.SP >> 2;                                         // chunks per stage
     const int npair = (p.SP * 2) >> 8;                                 // pairs per thread (1 or 2)
     int s_slot[2];                                                     // LDS byte offset of the pair's first pixel slot (+ 8 sr)
     uint32_t s_goff[2][4];                                             // element offset inside the stage's first image plane set
     float s_al[2][4];
+    int s_bt[2], s_nzo[2], s_c0[2], s_c3[2];                           // BNH: constants row of the pair's first channel; border class of its four pixels (fixed for the whole kernel)
     __syncthreads();                                                   // alpha visible
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -413,6 +511,9 @@ __global__ __launch_bounds__(256, 2) void k_k3s_dgrad(const K3dParams p) {
         const uint32_t row = fd_div(q, p.fd_w4);
         const int col = (q - (int)row * (p.W >> 2)) * 4;
         s_slot[u] = ((int)img * p.IS + ((int)row + 1) * p.WP + col + 1) * K3D_RS + 8 * (sr & 7);
+        s_bt[u] = (sr & 7) * K3B_CS;
+        s_nzo[u] = 8 + 3 * ((int)row == 0 ? 0 : ((int)row == p.H - 1 ? 2 : 1));
+        s_c0[u] = col == 0 ? 0 : 1; s_c3[u] = col == p.W - 4 ? 2 : 1;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             int m = (sr & 7) + 8 * i;
@@ -422,6 +523,7 @@ __global__ __launch_bounds__(256, 2) void k_k3s_dgrad(const K3dParams p) {
         }
     }
     float4 rg[2][4];
+    uint32_t rh[2][BNH ? 4 : 1];
     auto fetch = [&](int st) {                                         // unconditional; images past N are clamped (never stored)
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -433,6 +535,7 @@ __global__ __launch_bounds__(256, 2) void k_k3s_dgrad(const K3dParams p) {
                     int64_t off = base + s_goff[u][i];
                     off = off < lim ? off : lim;
                     rg[u][i] = *reinterpret_cast<const float4*>(p.gy + off);
+                    if (BNH) rh[u][i] = *reinterpret_cast<const uint32_t*>(p.bn.h + off);
                 }
             }
         }
@@ -444,6 +547,7 @@ __global__ __launch_bounds__(256, 2) void k_k3s_dgrad(const K3dParams p) {
                 float t0[4][4], t1[4][4], t2[4][4];                    // [i][e]
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
+                    if (BNH) rg[u][i] = k3b_dy4(btab + s_bt[u] + 8 * i * K3B_CS, s_nzo[u], s_c0[u], s_c3[u], rg[u][i], rh[u][i]);
                     const float v[4] = {rg[u][i].x * s_al[u][i], rg[u][i].y * s_al[u][i], rg[u][i].z * s_al[u][i], rg[u][i].w * s_al[u][i]};
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -520,7 +624,7 @@ __global__ __launch_bounds__(256, 2) void k_k3s_dgrad(const K3dParams p) {
 }
 
 struct K3dPlan { K3dParams p; int grid; size_t lds; };
-static int plan_k3d(const mn_conv_geom* g, const mn_wq* wq, K3dPlan* pl) {
+static int plan_k3d(const mn_conv_geom* g, const mn_wq* wq, K3dPlan* pl, int bnh = 0) {
     if (!wq || !(wq->mode == MN_WQ_TERNARY || (wq->mode == MN_WQ_DOREFA && wq->bits >= 2 && wq->bits <= 8))) return 0;
     if (g->KH != 3 || g->KW != 3 || g->stride_h != 1 || g->stride_w != 1 || g->pad_h != 1 || g->pad_w != 1 || g->dil_h != 1 || g->dil_w != 1) return 0;
     if (g->in_shuffle > 1 && g->C % g->in_shuffle) return 0;
@@ -535,7 +639,7 @@ static int plan_k3d(const mn_conv_geom* g, const mn_wq* wq, K3dPlan* pl) {
     p.N = g->N; p.C = g->C; p.H = g->H; p.W = g->W; p.O = g->O; p.Cg = Cg; p.Mg = Mg; p.G = g->groups;
     p.NI = NI; p.SP = SP; p.HW = HW; p.WP = g->W + 2; p.IS = (g->H + 2) * (g->W + 2);
     p.TS = (NI * p.IS * K3D_RS + 255) / 256 * 256;
-    pl->lds = (size_t)3 * p.TS + 128;
+    pl->lds = (size_t)3 * p.TS + 128 + (bnh ? (size_t)32 * K3B_CS * 4 : 0);
     if (pl->lds < (size_t)Mg * Cg * 9 * 4) pl->lds = (size_t)Mg * Cg * 9 * 4;          // the prologue's weight image
     if (pl->lds > 80 * 1024) return 0;
     p.nstages = (g->N + NI - 1) / NI;
@@ -559,13 +663,36 @@ int k3s_bwd_data(const mn_conv_geom* g, const mn_wq* wq, const float* gy, const 
     if (!plan_k3d(g, wq, &pl) || !aligned16(gy) || !w || !dx) MN_FAIL(MN_ENOTSUP, "mn_conv2d_bwd_data(3x3 ternary): geometry not covered");
     K3dParams& p = pl.p;
     p.gy = gy; p.w = w; p.dx = dx; p.wn = wq->mode == MN_WQ_DOREFA ? (float)((1ll << wq->bits) - 1) : 0.f;
+    p.bn.h = nullptr; p.bn.chan = nullptr; p.bn.sums = nullptr; p.bn.training = 0; p.bn.n_f = 1.f;
     mn_set_last_kernel("k_k3s_dgrad");
     { const double nx = (double)g->N * g->C * g->H * g->W, ny = (double)g->N * g->O * g->H * g->W; mn_prof_bytes(4.0 * ny + 4.0 * nx); }
     mn_prof_begin(s);
-    raise_lds_limit((const void*)k_k3s_dgrad, pl.lds);
-    hipLaunchKernelGGL(k_k3s_dgrad, dim3(pl.grid), dim3(256), pl.lds, s, p);
+    raise_lds_limit((const void*)k_k3s_dgrad<0>, pl.lds);
+    hipLaunchKernelGGL(k_k3s_dgrad<0>, dim3(pl.grid), dim3(256), pl.lds, s, p);
     mn_prof_end(s);
     MN_CHECK_LAUNCH("mn_conv2d_bwd_data(3x3 ternary)");
+    return MN_OK;
+}
+// the grouped 3 x 3 binary block (sign codes in, ternary / binary weights, BatchNorm + sign behind): both gradients form dy from (da, h) themselves
+int k3s_bnh_supported(const mn_conv_geom* g, const mn_wq* wq) {
+    K3dPlan pd; K3wPlan pw;
+    return wq && wq->mode == MN_WQ_TERNARY && g->H >= 2 && plan_k3d(g, wq, &pd, 1) && plan_k3s(g, &pw);
+}
+int k3s_bwd_data_bnh(const mn_conv_geom* g, const mn_wq* wq, const float* da, const uint8_t* h, const float* chan, const float* sums, int training, const float* w,
+                     float* dx, hipStream_t s) {
+    K3dPlan pl;
+    if (!wq || wq->mode != MN_WQ_TERNARY || g->H < 2 || !plan_k3d(g, wq, &pl, 1) || !aligned16(da) || !h || (((uintptr_t)h) & 3) || !chan || !sums || !w || !dx)
+        MN_FAIL(MN_ENOTSUP, "mn_conv2d_bwd_data_bnh(3x3 ternary): geometry / alignment not covered");
+    K3dParams& p = pl.p;
+    p.gy = da; p.w = w; p.dx = dx; p.wn = 0.f;
+    p.bn.h = h; p.bn.chan = chan; p.bn.sums = sums; p.bn.training = training; p.bn.n_f = (float)g->N * (float)(g->H * g->W);
+    mn_set_last_kernel("k_k3s_dgrad<1>");
+    { const double nx = (double)g->N * g->C * g->H * g->W, ny = (double)g->N * g->O * g->H * g->W; mn_prof_bytes(5.0 * ny + 4.0 * nx); }
+    mn_prof_begin(s);
+    raise_lds_limit((const void*)k_k3s_dgrad<1>, pl.lds);
+    hipLaunchKernelGGL(k_k3s_dgrad<1>, dim3(pl.grid), dim3(256), pl.lds, s, p);
+    mn_prof_end(s);
+    MN_CHECK_LAUNCH("mn_conv2d_bwd_data_bnh(3x3 ternary)");
     return MN_OK;
 }
 
