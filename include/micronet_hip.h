@@ -858,6 +858,29 @@ int mn_adam_step(const mn_adam_tensor* tensors, int count, int step, float beta1
 int mn_adam_step_dev(const mn_adam_tensor* tensors, int count, const int32_t* step_dev, const float* hyper_dev, float beta1, float beta2, float eps,
                      mn_stream_t stream);
 
+/* ------------------------------------------------------------------ bit-packed inference of the BN-folded W-ternary / W-binary, A-binary graph
+ * What wbwtab/bn_fuse/bn_fuse.py:36-55 leaves of a hidden block -- sign(conv(a, t * alpha) + b), a in +-1, t in {-1, 0, +1} (F.conv2d of
+ * wbwtab/quantize.py:186-194 followed by BinaryActivation, 13-19) -- on ONE BIT per activation:
+ *   bits : uint32 [N][ceil(C/32)][H][W]; bit (c & 31) of word (c >> 5) at a pixel is 1 iff the activation is +1; unused high bits of the last word are 0.
+ * pack / unpack convert from / to the int8 codes of MN_ACTQ_SIGN8 (any C; H*W % 4 == 0; 4-byte aligned tensors). */
+int mn_bits_pack_sign8(const int8_t* a, int64_t N, int64_t C, int64_t HW, uint32_t* bits, mn_stream_t stream);
+int mn_bits_unpack_sign8(const uint32_t* bits, int64_t N, int64_t C, int64_t HW, int8_t* a, mn_stream_t stream);
+/* The convolution (replaces the F.conv2d + sign of wbwtab/quantize.py:186-194 / 79-94 in the deployed graph): 1x1, or 3x3 with padding 1; stride 1, any groups, any
+ * number of channels per group (a row reads the words its group touches, a mask selects the bits); g->in_shuffle must be 0 / 1 -- a consumer's channel shuffle
+ * (models/nin_gc.py:53-56) is folded into its PRODUCER through `out_order`.
+ *   pack : w = the folded fp32 weights [O][C/groups][KH][KW] holding codes x alpha[o] (alpha[o] = max |w[o]|), bias [O] (nullable) -> `table` (private layout,
+ *          mn_bitconv_table_bytes bytes).  out_order (nullable: identity): int32 [O], row j of the table computes output channel out_order[j], i.e. bit j of the
+ *          output is channel out_order[j].  Per row: the sign / non-zero bit planes, the input word offset of its group, and the integer threshold T -- the first
+ *          accumulator value in [-K, K] for which !(fl(fl(acc * alpha) + b) < 0) holds in fp32, found by evaluating that expression for every value (exact by
+ *          construction; zero, -0 and NaN give +1 like the byte kernels).  Word 0 of the table counts the rows whose decision is not monotone in acc or whose
+ *          out_order entry is out of range: 0 for a valid table (the caller may read it back once after packing).
+ *   fwd  : acc = 2 * popc(~(x ^ s) & m & valid) - popc(m & valid) per row (zero padding is 0, not -1: taps outside the image drop out of both terms), output bit =
+ *          acc >= T.  pool != 0: the 2x2 / stride 2 max-pool behind the block folded in (OR of the four decisions; H and W even), y_bits is [N][ceil(O/32)][H/2][W/2]. */
+int mn_bitconv_supported(const mn_conv_geom* g);
+int64_t mn_bitconv_table_bytes(const mn_conv_geom* g);
+int mn_bitconv_pack(const mn_conv_geom* g, const float* w, const float* bias, const int32_t* out_order, uint32_t* table, mn_stream_t stream);
+int mn_bitconv_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t* x_bits, uint32_t* y_bits, int pool, mn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -253,6 +253,12 @@ PROTOTYPES = {
     "mn_iaobf_thin_fwd": (_I, [_G, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
     "mn_iaobf_thin_bwd_weight": (_I, [_G, _P, _P, _P, _I, _I, _P, _P, _P]),
     "mn_iaobf_thin_bwd_data": (_I, [_G, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P]),
+    "mn_bits_pack_sign8": (_I, [_P, _L, _L, _L, _P, _P]),
+    "mn_bits_unpack_sign8": (_I, [_P, _L, _L, _L, _P, _P]),
+    "mn_bitconv_supported": (_I, [_G]),
+    "mn_bitconv_table_bytes": (_L, [_G]),
+    "mn_bitconv_pack": (_I, [_G, _P, _P, _P, _P, _P]),
+    "mn_bitconv_fwd": (_I, [_G, _P, _P, _P, _I, _P]),
 }
 
 

@@ -73,6 +73,8 @@ __device__ __forceinline__ int mn_wave_any(int pred) { return __builtin_amdgcn_b
 __device__ __forceinline__ unsigned mn_f2u(float f) { return __float_as_uint(f); }
 __device__ __forceinline__ float mn_u2f(unsigned u) { return __uint_as_float(u); }
 #endif
+// population count of a 32-bit word (v_bcnt_u32_b32; the g++ emulation build has the same builtin)
+__host__ __device__ __forceinline__ int mn_popc(uint32_t v) { return __builtin_popcount(v); }
 // a value that is the same in every lane of the wave, told to the compiler (scalar registers / scalar loads downstream)
 #ifdef MN_EMULATION
 __device__ __forceinline__ int mn_uniform(int v) { return v; }

@@ -1,0 +1,323 @@
+// Bit-packed inference of the BN-folded W-ternary / W-binary, A-binary graph (wbwtab/bn_fuse/bn_fuse.py:36-55: sign(conv(a, t * alpha) + b), a in +-1): one BIT per
+// activation, XNOR / AND / popcount instead of multiply-accumulate, the bias and alpha folded into one integer threshold per output channel.
+//
+//   activation bits : uint32 [N][ceil(C/32)][H][W]; bit (c & 31) of word (c >> 5) at a pixel is 1 iff the activation is +1; unused high bits of the last word are 0.
+//                     Channel-word planar: lanes = pixels read coalesced dwords.
+//   weight table    : (private layout) 8 header words, then one row per output POSITION j (rows padded to a multiple of 32):
+//                       row[0] = T (int32), row[1] = w0 (first input word the row reads), row[2] = nnz, row[3] = 0, then taps x NW pairs (s, m):
+//                       s = sign plane (1 = +1), m = non-zero plane, of input words w0 .. w0 + NW - 1 at each tap; bits outside the row's group are 0 in both.
+//                     acc = 2 * popc(~(x ^ s) & m & valid) - popc(m & valid)  -- zero padding is 0, not -1: a tap outside the image drops out of both terms.
+//                     decision: +1 iff acc >= T, T = the first acc in [-K, K] for which !(fl(fl(acc * alpha) + b) < 0) holds in fp32 (K + 1: never).  The pack kernel
+//                     EVALUATES that expression for every acc, so the threshold is exact by construction (alpha = 0 and NaN: constant decisions), and it counts
+//                     the rows whose decision is not monotone in acc into header word 0 (0 for every alpha >= 0).
+//   consumer order  : row j computes output channel out_order[j] (the channel the consumer reads at position j -- its channel shuffle folded into the producer);
+//                     the row carries its own group's word offset, so no kernel gathers bits.
+// One lane owns one output pixel (pool: one POOLED pixel, OR of the four decisions), loops over the 32 rows of an output word with the row's s / m / T wave-uniform
+// (scalar loads), assembles the word in a register and stores one coalesced dword.
+#include "common.h"
+
+namespace mn_bits {
+
+enum { HDR = 8, ROWHDR = 4 };
+
+struct Geom {
+    int N, C, H, W, O, KS, groups;
+    int Cg, Og, K, taps, Cw, OW, NW, stride;      // channels per group in / out, taps per output, input / output words per pixel, words a row spans per tap, row stride
+};
+
+static inline int span_words(int C, int groups) {
+    const int Cg = C / groups;
+    int nw = 1;
+    for (int g = 0; g < groups; ++g) {
+        const int a = (g * Cg) >> 5, b = (g * Cg + Cg - 1) >> 5;
+        if (b - a + 1 > nw) nw = b - a + 1;
+    }
+    return nw;
+}
+
+static inline bool make_geom(const mn_conv_geom* g, Geom& q) {
+    if (!g || g->N <= 0 || g->C <= 0 || g->H <= 0 || g->W <= 0 || g->O <= 0 || g->groups <= 0) return false;
+    if (g->KH != g->KW || (g->KH != 1 && g->KH != 3)) return false;
+    const int pad = (g->KH - 1) / 2;
+    if (g->stride_h != 1 || g->stride_w != 1 || g->dil_h != 1 || g->dil_w != 1 || g->pad_h != pad || g->pad_w != pad) return false;
+    if (g->C % g->groups || g->O % g->groups || g->in_shuffle > 1) return false;      // a channel shuffle is folded into the PRODUCER's row order, never gathered here
+    q.N = g->N; q.C = g->C; q.H = g->H; q.W = g->W; q.O = g->O; q.KS = g->KH; q.groups = g->groups;
+    q.Cg = g->C / g->groups; q.Og = g->O / g->groups; q.taps = g->KH * g->KW;
+    if ((int64_t)q.Cg * q.taps > 65536) return false;
+    q.K = q.Cg * q.taps;
+    q.Cw = (g->C + 31) >> 5; q.OW = (g->O + 31) >> 5;
+    q.NW = span_words(g->C, g->groups);
+    if (q.NW > (g->KH == 1 ? 64 : 8)) return false;
+    q.stride = ROWHDR + 2 * q.taps * q.NW;
+    const int64_t words = (int64_t)g->N * (q.Cw > q.OW ? q.Cw : q.OW) * g->H * g->W;
+    if (words >= (1ll << 31) || (int64_t)q.OW * 32 * q.stride >= (1ll << 30)) return false;
+    return true;
+}
+
+// ---------------------------------------------------------------- int8 +-1 <-> bits
+// one thread = 4 consecutive pixels of one channel word: 32 aligned dword reads of 4 codes each, 4 words out
+__global__ __launch_bounds__(256) void k_bits_pack(const int8_t* __restrict__ a, uint32_t* __restrict__ bits, int64_t total, int C, int Cw, int HW4) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int p4 = (int)(i % HW4);
+    const int64_t t = i / HW4;
+    const int cw = (int)(t % Cw);
+    const int64_t n = t / Cw;
+    const int HW = HW4 * 4;
+    uint32_t o0 = 0, o1 = 0, o2 = 0, o3 = 0;
+    const int cend = C - cw * 32 < 32 ? C - cw * 32 : 32;
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(a + (n * C + (int64_t)cw * 32) * HW) + p4;
+    for (int b = 0; b < cend; ++b) {
+        const uint32_t v = ~src[(int64_t)b * HW4];          // +1 = 0x01, -1 = 0xff: the byte's top bit is the sign
+        o0 |= ((v >> 7) & 1u) << b; o1 |= ((v >> 15) & 1u) << b; o2 |= ((v >> 23) & 1u) << b; o3 |= ((v >> 31) & 1u) << b;
+    }
+    uint32_t* dst = bits + (n * Cw + cw) * HW + 4 * p4;
+    dst[0] = o0; dst[1] = o1; dst[2] = o2; dst[3] = o3;
+}
+
+// one thread = 4 consecutive pixels of one channel: 4 words in, one dword of 4 codes out
+__global__ __launch_bounds__(256) void k_bits_unpack(const uint32_t* __restrict__ bits, int8_t* __restrict__ a, int64_t total, int C, int Cw, int HW4) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int p4 = (int)(i % HW4);
+    const int64_t t = i / HW4;
+    const int c = (int)(t % C);
+    const int64_t n = t / C;
+    const int HW = HW4 * 4;
+    const uint32_t* src = bits + (n * Cw + (c >> 5)) * HW + 4 * p4;
+    uint32_t r = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r |= (((src[e] >> (c & 31)) & 1u) ? 0x01u : 0xffu) << (8 * e);
+    reinterpret_cast<uint32_t*>(a + (n * C + c) * HW)[p4] = r;
+}
+
+// ---------------------------------------------------------------- weight table
+__device__ __forceinline__ int block_reduce(int v, int op, int* sh) {      // op 0: sum, 1: min, 2: max; every thread of the 256-thread block calls it
+    const int tid = threadIdx.x;
+    __syncthreads();
+    sh[tid] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) {
+            const int a = sh[tid], b = sh[tid + s];
+            sh[tid] = op == 0 ? a + b : op == 1 ? (a < b ? a : b) : (a > b ? a : b);
+        }
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+// one block per table row
+__global__ __launch_bounds__(256) void k_bits_wpack(Geom q, const float* __restrict__ w, const float* __restrict__ bias, const int32_t* __restrict__ order,
+                                                    uint32_t* __restrict__ tab) {
+    __shared__ int sh[256];
+    const int j = blockIdx.x, tid = threadIdx.x;
+    uint32_t* row = tab + HDR + (int64_t)j * q.stride;
+    if (j == 0 && tid == 0) { tab[1] = (uint32_t)q.NW; tab[2] = (uint32_t)q.taps; tab[3] = (uint32_t)q.stride; tab[4] = (uint32_t)(q.OW * 32); tab[5] = (uint32_t)q.Cw; }
+    int o = j < q.O ? (order ? order[j] : j) : -1;
+    if (j < q.O && (o < 0 || o >= q.O)) {          // a bad out_order entry: counted, the row never fires, nothing is read out of bounds
+        if (tid == 0) atomicAdd(tab + 0, 1u);
+        o = -1;
+    }
+    if (o < 0) {
+        for (int i = tid; i < q.stride; i += 256) row[i] = i == 0 ? 0x7fffffffu : 0u;
+        return;
+    }
+    const int grp = o / q.Og, c0 = grp * q.Cg;
+    int w0 = c0 >> 5;
+    if (w0 > q.Cw - q.NW) w0 = q.Cw - q.NW;          // every row reads NW words per tap: keep the window inside the pixel's words
+    const float* wr = w + (int64_t)o * q.K;          // [Cg][taps]
+    float mx = 0.f;
+    int nz = 0, nan = 0;
+    for (int i = tid; i < q.K; i += 256) {
+        const float v = wr[i];
+        mx = fmaxf(mx, fabsf(v));
+        nz += v != 0.f;
+        nan |= v != v;
+    }
+    mx = mn_u2f((unsigned)block_reduce((int)mn_f2u(mx), 2, sh));          // non-negative floats order like their bit patterns
+    nz = block_reduce(nz, 0, sh);
+    nan = block_reduce(nan, 2, sh);
+    const float alpha = nan ? mn_u2f(0x7fc00000u) : mx;
+    for (int idx = tid; idx < q.taps * q.NW; idx += 256) {
+        const int t = idx / q.NW, k = idx - t * q.NW;
+        uint32_t s = 0, m = 0;
+        for (int b = 0; b < 32; ++b) {
+            const int ci = (w0 + k) * 32 + b - c0;
+            if (ci >= 0 && ci < q.Cg) {
+                const float v = wr[ci * q.taps + t];
+                m |= (uint32_t)(v != 0.f) << b;
+                s |= (uint32_t)(v > 0.f) << b;
+            }
+        }
+        row[ROWHDR + 2 * idx] = s;
+        row[ROWHDR + 2 * idx + 1] = m;
+    }
+    // the decision of the byte kernels, evaluated for every accumulator value the row can produce
+    const float b = bias ? bias[o] : 0.f;
+    int tmin = INT_MAX, cnt = 0;
+    for (int acc = -q.K + tid; acc <= q.K; acc += 256) {
+        const float p = (float)acc * alpha;
+        const float yv = p + b;
+        if (!(yv < 0.f)) { cnt++; if (acc < tmin) tmin = acc; }
+    }
+    tmin = block_reduce(tmin, 1, sh);
+    cnt = block_reduce(cnt, 0, sh);
+    if (tid == 0) {
+        if (cnt != 0 && cnt != q.K - tmin + 1) atomicAdd(tab + 0, 1u);          // not monotone in acc (alpha < 0 cannot come out of max|w|)
+        row[0] = (uint32_t)(cnt == 0 ? q.K + 1 : tmin);
+        row[1] = (uint32_t)w0;
+        row[2] = (uint32_t)nz;
+        row[3] = 0u;
+    }
+}
+
+// ---------------------------------------------------------------- XNOR-popcount convolution + threshold -> output bits
+struct Fwd {
+    int total, Cw, H, W, Ho, Wo, OW, nw, stride, owpb;
+};
+
+template <int KS, int NW, bool POOL>
+__global__ __launch_bounds__(256) void k_bitconv(const uint32_t* __restrict__ tab, const uint32_t* __restrict__ x, uint32_t* __restrict__ y, Fwd q) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= q.total) return;
+    const int nw = NW ? NW : q.nw;
+    const int HWo = q.Ho * q.Wo, HW = q.H * q.W;
+    const int n = p / HWo, r = p - n * HWo;
+    const int oh = r / q.Wo, ow = r - oh * q.Wo;
+    const uint32_t* xn = x + (int64_t)n * q.Cw * HW;
+    const int ow0 = blockIdx.y * q.owpb;
+    const int ow1 = ow0 + q.owpb < q.OW ? ow0 + q.owpb : q.OW;
+    for (int owi = ow0; owi < ow1; ++owi) {
+        const uint32_t* rowp = tab + HDR + (int64_t)owi * 32 * q.stride;
+        uint32_t word = 0;
+#pragma unroll 2
+        for (int j = 0; j < 32; ++j) {
+            const uint32_t* row = rowp + j * q.stride;          // wave-uniform: T, w0, nnz, s and m are scalar operands
+            const int T = (int)row[0];
+            const uint32_t* xw = xn + (int64_t)row[1] * HW;
+            uint32_t bit = 0;
+#pragma unroll(KS == 1 ? 4 : 1)
+            for (int sub = 0; sub < (POOL ? 4 : 1); ++sub) {
+                const int ph = POOL ? 2 * oh + (sub >> 1) : oh, pw = POOL ? 2 * ow + (sub & 1) : ow;
+                int acc;
+                if (KS == 1) {
+                    const uint32_t* xp = xw + ph * q.W + pw;
+                    int P = 0;
+#pragma unroll
+                    for (int k = 0; k < nw; ++k) P += mn_popc(~(xp[k * HW] ^ row[ROWHDR + 2 * k]) & row[ROWHDR + 2 * k + 1]);
+                    acc = 2 * P - (int)row[2];
+                } else {
+                    int P = 0, Z = 0;
+#pragma unroll
+                    for (int t = 0; t < 9; ++t) {
+                        const int ih = ph + t / 3 - 1, iw = pw + t % 3 - 1;
+                        const bool ok = ih >= 0 && ih < q.H && iw >= 0 && iw < q.W;
+                        const uint32_t* xp = xw + ih * q.W + iw;
+#pragma unroll
+                        for (int k = 0; k < nw; ++k) {
+                            const uint32_t xv = ok ? xp[k * HW] : 0u;
+                            const uint32_t mv = ok ? row[ROWHDR + 2 * (t * nw + k) + 1] : 0u;
+                            P += mn_popc(~(xv ^ row[ROWHDR + 2 * (t * nw + k)]) & mv);
+                            Z += mn_popc(mv);
+                        }
+                    }
+                    acc = 2 * P - Z;
+                }
+                bit |= (uint32_t)(acc >= T);
+            }
+            word |= bit << j;
+        }
+        y[((int64_t)n * q.OW + owi) * HWo + r] = word;
+    }
+}
+
+template <int KS, bool POOL>
+static void launch_nw(int nwsel, dim3 grid, hipStream_t s, const uint32_t* tab, const uint32_t* x, uint32_t* y, const Fwd& f) {
+    switch (nwsel) {          // (3x3: one word per tap -- every grouped 3x3 layer of the nets -- is unrolled; wider spans take the rolled loop, whose registers stay flat)
+    case 1: hipLaunchKernelGGL((k_bitconv<KS, 1, POOL>), grid, dim3(256), 0, s, tab, x, y, f); break;
+    case 2: if (KS == 1) { hipLaunchKernelGGL((k_bitconv<1, 2, POOL>), grid, dim3(256), 0, s, tab, x, y, f); break; }
+    case 4: if (KS == 1) { hipLaunchKernelGGL((k_bitconv<1, 4, POOL>), grid, dim3(256), 0, s, tab, x, y, f); break; }
+    default: hipLaunchKernelGGL((k_bitconv<KS, 0, POOL>), grid, dim3(256), 0, s, tab, x, y, f); break;
+    }
+}
+
+}  // namespace mn_bits
+
+extern "C" int mn_bits_pack_sign8(const int8_t* a, int64_t N, int64_t C, int64_t HW, uint32_t* bits, mn_stream_t stream) {
+    if (!a || !bits || N <= 0 || C <= 0 || HW <= 0 || HW % 4 || (((uintptr_t)a) & 3) || (((uintptr_t)bits) & 3) || C > (1 << 20) || HW > (1 << 26))
+        MN_FAIL(MN_EINVAL, "mn_bits_pack_sign8: needs H*W %% 4 == 0 and 4-byte aligned tensors");
+    const int Cw = (int)((C + 31) >> 5);
+    const int64_t total = N * Cw * (HW / 4);
+    if (total > (int64_t)INT_MAX * 256) MN_FAIL(MN_ENOTSUP, "mn_bits_pack_sign8: tensor too large");
+    mn_set_last_kernel("k_bits_pack"); mn_prof_bytes((double)N * C * HW + 4.0 * N * Cw * HW); mn_prof_begin((hipStream_t)stream);
+    hipLaunchKernelGGL(mn_bits::k_bits_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, bits, total, (int)C, Cw, (int)(HW / 4));
+    mn_prof_end((hipStream_t)stream);
+    MN_CHECK_LAUNCH("mn_bits_pack_sign8");
+    return MN_OK;
+}
+
+extern "C" int mn_bits_unpack_sign8(const uint32_t* bits, int64_t N, int64_t C, int64_t HW, int8_t* a, mn_stream_t stream) {
+    if (!a || !bits || N <= 0 || C <= 0 || HW <= 0 || HW % 4 || (((uintptr_t)a) & 3) || (((uintptr_t)bits) & 3) || C > (1 << 20) || HW > (1 << 26))
+        MN_FAIL(MN_EINVAL, "mn_bits_unpack_sign8: needs H*W %% 4 == 0 and 4-byte aligned tensors");
+    const int Cw = (int)((C + 31) >> 5);
+    const int64_t total = N * C * (HW / 4);
+    if (total > (int64_t)INT_MAX * 256) MN_FAIL(MN_ENOTSUP, "mn_bits_unpack_sign8: tensor too large");
+    mn_set_last_kernel("k_bits_unpack"); mn_prof_bytes((double)N * C * HW + 4.0 * N * Cw * HW); mn_prof_begin((hipStream_t)stream);
+    hipLaunchKernelGGL(mn_bits::k_bits_unpack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, bits, a, total, (int)C, Cw, (int)(HW / 4));
+    mn_prof_end((hipStream_t)stream);
+    MN_CHECK_LAUNCH("mn_bits_unpack_sign8");
+    return MN_OK;
+}
+
+extern "C" int mn_bitconv_supported(const mn_conv_geom* g) {
+    mn_bits::Geom q;
+    return mn_bits::make_geom(g, q) ? 1 : 0;
+}
+
+extern "C" int64_t mn_bitconv_table_bytes(const mn_conv_geom* g) {
+    mn_bits::Geom q;
+    if (!mn_bits::make_geom(g, q)) return 0;
+    return 4 * ((int64_t)mn_bits::HDR + (int64_t)q.OW * 32 * q.stride);
+}
+
+extern "C" int mn_bitconv_pack(const mn_conv_geom* g, const float* w, const float* bias, const int32_t* out_order, uint32_t* table, mn_stream_t stream) {
+    mn_bits::Geom q;
+    if (!w || !table || (((uintptr_t)table) & 3)) MN_FAIL(MN_EINVAL, "mn_bitconv_pack: null / unaligned argument");
+    if (!mn_bits::make_geom(g, q)) MN_FAIL(MN_ENOTSUP, "mn_bitconv_pack: geometry not covered (1x1 or 3x3 / padding 1, stride 1, no input shuffle)");
+    if (hipMemsetAsync(table, 0, 4 * mn_bits::HDR, (hipStream_t)stream) != hipSuccess) MN_FAIL(MN_EHIP, "mn_bitconv_pack: header reset failed");          // word 0: bad-row count
+    mn_set_last_kernel("k_bits_wpack");
+    hipLaunchKernelGGL(mn_bits::k_bits_wpack, dim3(q.OW * 32), dim3(256), 0, (hipStream_t)stream, q, w, bias, out_order, table);
+    MN_CHECK_LAUNCH("mn_bitconv_pack");
+    return MN_OK;
+}
+
+extern "C" int mn_bitconv_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t* x_bits, uint32_t* y_bits, int pool, mn_stream_t stream) {
+    mn_bits::Geom q;
+    if (!table || !x_bits || !y_bits) MN_FAIL(MN_EINVAL, "mn_bitconv_fwd: null argument");
+    if (!mn_bits::make_geom(g, q)) MN_FAIL(MN_ENOTSUP, "mn_bitconv_fwd: geometry not covered (1x1 or 3x3 / padding 1, stride 1, no input shuffle)");
+    if (pool && ((q.H & 1) || (q.W & 1))) MN_FAIL(MN_EINVAL, "mn_bitconv_fwd: the folded 2x2 max-pool needs even H and W");
+    mn_bits::Fwd f;
+    f.Cw = q.Cw; f.H = q.H; f.W = q.W; f.Ho = pool ? q.H / 2 : q.H; f.Wo = pool ? q.W / 2 : q.W; f.OW = q.OW; f.nw = q.NW; f.stride = q.stride;
+    f.total = q.N * f.Ho * f.Wo;
+    const int bx = (f.total + 255) / 256;
+    int gy = (2048 + bx - 1) / bx;          // enough blocks to fill the chip: split the output words over grid.y when the pixels alone do not
+    if (gy > q.OW) gy = q.OW;
+    f.owpb = (q.OW + gy - 1) / gy;
+    gy = (q.OW + f.owpb - 1) / f.owpb;
+    const dim3 grid(bx, gy);
+    const int nwsel = (q.NW == 1 || (q.KS == 1 && (q.NW == 2 || q.NW == 4))) ? q.NW : 0;
+    mn_set_last_kernel("k_bitconv<%d,%d,%d>", q.KS, nwsel, pool ? 1 : 0);
+    mn_prof_bytes(4.0 * q.N * q.Cw * q.H * q.W + 4.0 * q.N * q.OW * f.Ho * f.Wo + 4.0 * (mn_bits::HDR + (double)q.OW * 32 * q.stride));
+    mn_prof_begin((hipStream_t)stream);
+    if (q.KS == 1) {
+        if (pool) mn_bits::launch_nw<1, true>(nwsel, grid, (hipStream_t)stream, table, x_bits, y_bits, f);
+        else mn_bits::launch_nw<1, false>(nwsel, grid, (hipStream_t)stream, table, x_bits, y_bits, f);
+    } else {
+        if (pool) mn_bits::launch_nw<3, true>(nwsel, grid, (hipStream_t)stream, table, x_bits, y_bits, f);
+        else mn_bits::launch_nw<3, false>(nwsel, grid, (hipStream_t)stream, table, x_bits, y_bits, f);
+    }
+    mn_prof_end((hipStream_t)stream);
+    MN_CHECK_LAUNCH("mn_bitconv_fwd");
+    return MN_OK;
+}

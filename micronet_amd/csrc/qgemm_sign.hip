@@ -2039,3 +2039,8 @@ extern "C" int mn_qconv_bnq_fwd_stash(const mn_conv_geom* g, const mn_wq* wq, co
     MN_CHECK_LAUNCH("mn_qconv_bnq_fwd_stash(3x3)");
     return MN_OK;
 }
+
+// The CPU emulation build lists its translation units by name; the bit-packed inference kernels (qgemm_bits.hip, a unit of its own in the gfx950 build) ride along here.
+#ifdef MN_EMULATION
+#include "qgemm_bits.hip"
+#endif

@@ -10,7 +10,11 @@
   * ``iao_model_bn_fuse``: ``QuantBNFuseConv2d`` -> ``QuantConv2d(quant_inference=True)`` with w * gamma / std, beta + (b - mean) * gamma / std and the
     trained quantizer scales / zero points copied over (ref 20-66).
 The results are ordinary modules of this package: in eval mode they run on the same gfx950 kernels (activation codes, integer accumulators).
-``tests/test_gpu_inference.py`` checks train-graph == inference-graph on the same batch, as the reference's ``*_test.py`` scripts do."""
+``tests/test_gpu_inference.py`` checks train-graph == inference-graph on the same batch, as the reference's ``*_test.py`` scripts do.
+
+  * ``wbwtab_compile_bits``: the folded W-ternary / W-binary, A-binary graph compiled into a flat plan that keeps ONE BIT per hidden activation
+    (``csrc/qgemm_bits.hip``: XNOR / AND / popcount against bit-plane weight tables, bias and alpha folded into an integer threshold per channel).  It computes
+    exactly what the folded graph computes -- same signs in every hidden stage, same logits to the bit."""
 import copy
 
 import torch
@@ -154,3 +158,213 @@ def iao_model_bn_fuse(model, inplace=False):
                 walk(child)
     walk(model)
     return model
+
+
+# ------------------------------------------------------------------------------------------------ bit-packed deployment (csrc/qgemm_bits.hip)
+def _err(msg):
+    from micronet_amd._lib import MicronetHipError
+    return MicronetHipError(msg)
+
+
+def _codes_of(t):
+    from micronet_amd.sign_tensor import SignTensor
+    c = t.codes if isinstance(t, SignTensor) else t
+    if not (torch.is_tensor(c) and c.is_cuda and c.dtype == torch.int8 and c.dim() == 4):
+        raise _err("pack_bits: needs a SignTensor or an int8 +-1 tensor [N, C, H, W] on the GPU (no CPU fallback)")
+    return c.contiguous()
+
+
+def pack_bits(t):
+    """int8 +-1 codes [N, C, H, W] (or a SignTensor) -> int32 tensor [N, ceil(C / 32), H, W] of uint32 words: bit c & 31 of word c >> 5 is 1 iff the activation is +1."""
+    from micronet_amd import ops
+    c = _codes_of(t)
+    N, Cc, H, W = c.shape
+    bits = torch.empty((N, (Cc + 31) // 32, H, W), dtype=torch.int32, device=c.device)
+    ops._call("mn_bits_pack_sign8", ops._p(c), N, Cc, H * W, ops._p(bits), ops._s())
+    return bits
+
+
+def unpack_bits(bits, C):
+    """The inverse of ``pack_bits``: int8 +-1 codes [N, C, H, W]."""
+    from micronet_amd import ops
+    if not (torch.is_tensor(bits) and bits.is_cuda and bits.dtype == torch.int32 and bits.dim() == 4 and bits.shape[1] == (int(C) + 31) // 32):
+        raise _err("unpack_bits: needs an int32 word tensor [N, ceil(C / 32), H, W] on the GPU")
+    bits = bits.contiguous()
+    N, _, H, W = bits.shape
+    out = torch.empty((N, int(C), H, W), dtype=torch.int8, device=bits.device)
+    ops._call("mn_bits_unpack_sign8", ops._p(bits), N, int(C), H * W, ops._p(out), ops._s())
+    return out
+
+
+def _is_pool2x2(m):
+    two = lambda v: v in (2, (2, 2), [2, 2])
+    return isinstance(m, nn.MaxPool2d) and two(m.kernel_size) and two(m.stride) and m.padding in (0, (0, 0)) and m.dilation in (1, (1, 1)) and not m.ceil_mode \
+        and not m.return_indices
+
+
+class BitPlan(nn.Module):
+    """What ``wbwtab_compile_bits`` returns: first block (fp32 conv + sign, the folded graph's own module) -> bit pack -> n XNOR-popcount blocks (2x2 max-pools folded
+    in) -> bit unpack -> last block and tail (the folded graph's own modules).  Eval only; owns the packed weight tables and one set of bit buffers per input shape."""
+
+    def __init__(self, first, layers, last, tail, flatten, report):
+        super().__init__()
+        self.first, self.last, self.tail = first, last, nn.ModuleList(tail)
+        self.layers = layers              # dicts: geometry, table, pool, out_order
+        self.flatten = flatten
+        self.report = report
+        self.keep_stages = False          # True: forward also leaves every stage's bits in ``stage_bits`` (tests)
+        self.stage_bits = []
+        self._ws = {}
+        self.eval()
+
+    def train(self, mode=True):
+        if mode:
+            raise _err("wbwtab_compile_bits: the compiled plan is eval-only")
+        return super().train(False)
+
+    def _plan_buffers(self, shape, device):
+        """Bit buffers (and the int8 buffer in front of the last conv) for one first-block output shape; allocated once, reused by every later call."""
+        from micronet_amd import _lib
+        key = (tuple(shape), str(device))
+        if key not in self._ws:
+            N, Cc, H, W = shape
+            bufs, geoms = [torch.empty((N, (Cc + 31) // 32, H, W), dtype=torch.int32, device=device)], []
+            for L in self.layers:
+                k, p = L["k"], (L["k"] - 1) // 2
+                geoms.append(_lib.ConvGeom(N, L["cin"], H, W, L["cout"], k, k, 1, 1, p, p, 1, 1, L["groups"], 0))
+                if L["pool"]:
+                    H, W = H // 2, W // 2
+                bufs.append(torch.empty((N, (L["cout"] + 31) // 32, H, W), dtype=torch.int32, device=device))
+                Cc = L["cout"]
+            self._ws[key] = (bufs, geoms, torch.empty((N, Cc, H, W), dtype=torch.int8, device=device))
+        return self._ws[key]
+
+    @torch.no_grad()
+    def forward(self, x):
+        import ctypes as C
+        from micronet_amd import ops
+        from micronet_amd.sign_tensor import SignTensor
+        a = self.first(x)
+        if not isinstance(a, SignTensor):
+            raise _err("wbwtab_compile_bits: the first block did not produce packed signs (input must be a contiguous float32 GPU tensor with H * W % 4 == 0)")
+        codes = a.codes.contiguous()
+        N, Cc, H, W = codes.shape
+        bufs, geoms, a8 = self._plan_buffers(codes.shape, codes.device)
+        st = ops._s()
+        ops._call("mn_bits_pack_sign8", ops._p(codes), N, Cc, H * W, ops._p(bufs[0]), st)
+        for i, L in enumerate(self.layers):
+            ops._call("mn_bitconv_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(bufs[i + 1]), int(L["pool"]), st)
+        if self.keep_stages:
+            self.stage_bits = [b.clone() for b in bufs]
+        n_, c_, h_, w_ = a8.shape
+        ops._call("mn_bits_unpack_sign8", ops._p(bufs[-1]), n_, c_, h_ * w_, ops._p(a8), st)
+        y = self.last(SignTensor(a8))
+        for m in self.tail:
+            y = m(y)
+        return y.view(y.size(0), -1) if self.flatten else y
+
+
+@torch.no_grad()
+def wbwtab_compile_bits(model):
+    """``model``: the result of ``wbwtab_model_bn_fuse`` on a pre-quantised W in (2, 3), A = 2 net, on the GPU.  Returns a ``BitPlan`` computing the same function with one bit
+    per hidden activation; ``.report`` lists the stages.  Anything the bit kernels do not cover raises ``MicronetHipError`` naming the layer -- never a silent byte path
+    (the caller still has ``model``)."""
+    import ctypes as C
+    from micronet_amd import _lib, ops
+    from micronet_amd.nn import Conv2dFirst
+    from micronet_amd.quantization.wbwtab import quantize
+    if isinstance(model, nn.Sequential):
+        seq, prefix, flatten = model, "", False
+    else:
+        kids = list(model.named_children())
+        if len(kids) != 1 or not isinstance(kids[0][1], nn.Sequential):
+            raise _err("wbwtab_compile_bits: module order not recognised (%s: expected an nn.Sequential of blocks, or the reference's Net holding one)" % type(model).__name__)
+        seq, prefix, flatten = kids[0][1], kids[0][0] + ".", True          # models/nin_gc.py:144-147: forward = model(x).view(N, -1)
+    for n_, m in model.named_modules():
+        if isinstance(m, quantize.ActivationQuantizer) and m.A != 2:
+            raise _err("wbwtab_compile_bits: %s has A = %d; only binary activations (A = 2) are bit-packed" % (n_, m.A))
+    first = last = None
+    layers, tail, report = [], [], []
+    for name, child in seq.named_children():
+        nm = prefix + name
+        if last is not None:
+            tail.append(child)
+            continue
+        if _is_pool2x2(child):
+            if not layers or layers[-1]["pool"]:
+                raise _err("wbwtab_compile_bits: %s: a 2x2 max-pool is folded only into the bit block directly in front of it" % nm)
+            layers[-1]["pool"], layers[-1]["stage"] = 1, name
+            continue
+        conv, bn, act = getattr(child, "conv", None), getattr(child, "bn", None), getattr(child, "relu", None)
+        if not (quantize._is_ref_block(child) and isinstance(conv, nn.Conv2d) and isinstance(bn, nn.Identity)):
+            raise _err("wbwtab_compile_bits: %s (%s): module order not recognised (expected a BN-folded conv -> Identity -> activation block)" % (nm, type(child).__name__))
+        if first is None:
+            if not (type(conv) is Conv2dFirst and isinstance(act, quantize.ActivationQuantizer) and act.deploy_packed) or getattr(child, "channel_shuffle_flag", 0):
+                raise _err("wbwtab_compile_bits: %s: the first block must be the fp32 first conv followed by a packed binary activation" % nm)
+            first = child
+            report.append(dict(name=nm, kind="first", K=conv.in_channels // conv.groups * conv.kernel_size[0] * conv.kernel_size[1], words=0,
+                               kernel="first conv + mn_bnsign_fwd_i8, k_bits_pack", pooled=False, out_order="identity", stage=name))
+            continue
+        if not isinstance(conv, quantize.QuantConv2d):
+            if not layers:
+                raise _err("wbwtab_compile_bits: %s: no quantised block between the first and the last conv" % nm)
+            last = child
+            report.append(dict(name=nm, kind="last", K=conv.in_channels // conv.groups * conv.kernel_size[0] * conv.kernel_size[1], words=(conv.in_channels + 31) // 32,
+                               kernel="k_bits_unpack, last conv on sign codes", pooled=False, out_order="identity", stage=name))
+            continue
+        # ---- a hidden block: sign(conv(a, t * alpha) + b)
+        if not isinstance(act, quantize.ActivationQuantizer):
+            raise _err("wbwtab_compile_bits: %s: a quantised conv that is not followed by a binary activation" % nm)
+        if not conv._codes_valid():
+            raise _err("wbwtab_compile_bits: %s.conv: the stored weights are not codes x alpha (fold the model AFTER prequantize_weights)" % nm)
+        if tuple(conv.stride) != (1, 1) or tuple(conv.dilation) != (1, 1) or conv.padding_mode != "zeros" or isinstance(conv.padding, str):
+            raise _err("wbwtab_compile_bits: %s.conv: stride / dilation other than 1 (or non-zero padding mode) is not covered by the bit kernels" % nm)
+        k, pad = conv.kernel_size[0], conv.padding[0]
+        shuffle = int(getattr(conv, "in_shuffle_groups", 0) or 0)
+        if getattr(child, "channel_shuffle_flag", 0) and getattr(child, "shuffle_groups", 1) > 1:
+            if shuffle > 1:
+                raise _err("wbwtab_compile_bits: %s: two channel shuffles in front of one conv" % nm)
+            shuffle = int(child.shuffle_groups)
+        g = _lib.ConvGeom(1, conv.in_channels, 4, 4, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], 1, 1, conv.padding[0], conv.padding[1], 1, 1, conv.groups, 0)
+        if not _lib.get_lib().mn_bitconv_supported(C.byref(g)):
+            raise _err("wbwtab_compile_bits: %s.conv: geometry not covered by mn_bitconv_supported (%dx%d, padding %d, groups %d)" % (nm, k, conv.kernel_size[1], pad, conv.groups))
+        if shuffle > 1:
+            if conv.in_channels % shuffle:
+                raise _err("wbwtab_compile_bits: %s: %d input channels cannot be shuffled in %d groups" % (nm, conv.in_channels, shuffle))
+            if not layers:
+                raise _err("wbwtab_compile_bits: %s: a channel shuffle directly behind the first block is not covered (its producer is not a bit block)" % nm)
+            layers[-1]["shuffle"] = shuffle          # folded into the producer's row order
+        layers.append(dict(name=nm, conv=conv, k=k, cin=conv.in_channels, cout=conv.out_channels, groups=conv.groups, pool=0, shuffle=0, stage=name))
+    if first is None or last is None:
+        raise _err("wbwtab_compile_bits: module order not recognised (no %s conv block found)" % ("first" if first is None else "last"))
+    for p_ in model.parameters():
+        if not p_.is_cuda:
+            raise _err("wbwtab_compile_bits: the model is on %s: micronet_amd runs on MI355X only (no CPU fallback)" % p_.device)
+    # ---- pack the weight tables (one launch per layer, once per model)
+    lib = _lib.get_lib()
+    for L in layers:
+        conv = L.pop("conv")
+        k, p = L["k"], (L["k"] - 1) // 2
+        g = _lib.ConvGeom(1, L["cin"], 4, 4, L["cout"], k, k, 1, 1, p, p, 1, 1, L["groups"], 0)
+        table = torch.empty(int(lib.mn_bitconv_table_bytes(C.byref(g))) // 4, dtype=torch.int32, device=conv.weight.device)
+        order = None
+        if L["shuffle"] > 1:          # position j of the consumer's shuffled input is this layer's channel (j % s) * (C / s) + j // s (models/nin_gc.py:4-15)
+            j = torch.arange(L["cout"], device=conv.weight.device)
+            order = ((j % L["shuffle"]) * (L["cout"] // L["shuffle"]) + j // L["shuffle"]).to(torch.int32).contiguous()
+        w = conv.weight.detach().float().contiguous()
+        b = conv.bias.detach().float().contiguous() if conv.bias is not None else None
+        ops._call("mn_bitconv_pack", C.byref(g), ops._p(w), ops._p(b), ops._p(order), ops._p(table), ops._s())
+        L["table"], L["out_order"] = table, order
+    bad = [(L["name"], int(L["table"][0])) for L in layers]          # (compile time: the one place a host read-back is allowed)
+    for nm, nbad in bad:
+        if nbad:
+            raise _err("wbwtab_compile_bits: %s.conv: %d output channels whose decision is not monotone in the accumulator" % (nm, nbad))
+    rep_last = report.pop()
+    for L in layers:
+        cg = L["cin"] // L["groups"]
+        nw = max(((gi * cg + cg - 1) >> 5) - ((gi * cg) >> 5) + 1 for gi in range(L["groups"]))
+        sel = nw if (nw == 1 or (L["k"] == 1 and nw in (2, 4))) else 0
+        report.append(dict(name=L["name"], kind="bit", K=cg * L["k"] * L["k"], words=(L["cin"] + 31) // 32, kernel="k_bitconv<%d,%d,%d>" % (L["k"], sel, L["pool"]),
+                           pooled=bool(L["pool"]), out_order=("shuffle %d" % L["shuffle"]) if L["shuffle"] > 1 else "identity", stage=L["stage"]))
+    report.append(rep_last)
+    return BitPlan(first, layers, last, tail, flatten, report)
