@@ -875,11 +875,20 @@ int mn_bits_unpack_sign8(const uint32_t* bits, int64_t N, int64_t C, int64_t HW,
  *          construction; zero, -0 and NaN give +1 like the byte kernels).  Word 0 of the table counts the rows whose decision is not monotone in acc or whose
  *          out_order entry is out of range: 0 for a valid table (the caller may read it back once after packing).
  *   fwd  : acc = 2 * popc(~(x ^ s) & m & valid) - popc(m & valid) per row (zero padding is 0, not -1: taps outside the image drop out of both terms), output bit =
- *          acc >= T.  pool != 0: the 2x2 / stride 2 max-pool behind the block folded in (OR of the four decisions; H and W even), y_bits is [N][ceil(O/32)][H/2][W/2]. */
+ *          acc >= T.  pool == 1: the 2x2 / stride 2 max-pool behind the block folded in (OR of the four decisions; H and W even), y_bits is [N][ceil(O/32)][H/2][W/2].
+ *          pool == 2 (1x1 blocks): the 3x3 / stride 2 / padding 1 max-pool folded in (OR of the in-image decisions of the window), y_bits is
+ *          [N][ceil(O/32)][(H - 1) / 2 + 1][(W - 1) / 2 + 1].  A fold that is not covered is MN_ENOTSUP: run mn_bits_maxpool behind the block.
+ * Also covered: the dense (groups == 1) 5x5 / padding 2 block of at most 256 input channels (models/nin.py), on an LDS-resident image tile.
+ * pool | MN_BITCONV_ALT (measurement only, never part of a deployed plan): the other kernel for the same table -- the global re-read loop for the 5x5 block, the
+ * LDS-tiled kernel for a dense 3x3 block of 33 .. 256 input channels. */
+#define MN_BITCONV_ALT 0x100
 int mn_bitconv_supported(const mn_conv_geom* g);
 int64_t mn_bitconv_table_bytes(const mn_conv_geom* g);
 int mn_bitconv_pack(const mn_conv_geom* g, const float* w, const float* bias, const int32_t* out_order, uint32_t* table, mn_stream_t stream);
 int mn_bitconv_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t* x_bits, uint32_t* y_bits, int pool, mn_stream_t stream);
+/* Max-pool on bits (max over +-1 = OR; padding contributes nothing): k in {2, 3}, stride 2, pad in {0, 1}, floor mode; bits_out is
+ * [N][Cw][(H + 2 pad - k) / 2 + 1][(W + 2 pad - k) / 2 + 1]. */
+int mn_bits_maxpool(const uint32_t* bits_in, int64_t N, int64_t Cw, int64_t H, int64_t W, int k, int stride, int pad, uint32_t* bits_out, mn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -259,6 +259,7 @@ PROTOTYPES = {
     "mn_bitconv_table_bytes": (_L, [_G]),
     "mn_bitconv_pack": (_I, [_G, _P, _P, _P, _P, _P]),
     "mn_bitconv_fwd": (_I, [_G, _P, _P, _P, _I, _P]),
+    "mn_bits_maxpool": (_I, [_P, _L, _L, _L, _L, _I, _I, _I, _P, _P]),
 }
 
 

@@ -14,6 +14,14 @@
 //                     the row carries its own group's word offset, so no kernel gathers bits.
 // One lane owns one output pixel (pool: one POOLED pixel, OR of the four decisions), loops over the 32 rows of an output word with the row's s / m / T wave-uniform
 // (scalar loads), assembles the word in a register and stores one coalesced dword.
+//
+// Dense k x k blocks (groups == 1, at most 8 input words: the 5x5 / padding 2 block of nin, and the layout of a dense 3x3 with more than one word) are TILED: a block
+// stages the words of its image tile plus the halo into LDS once, halo cells as ZERO words, and the inner loop carries no border mask.  A zero word reads as 32
+// activations of -1, so a tap outside the image adds -d_t (d_t = the sum of the row's weight signs at tap t) instead of 0; the row carries the 2-D prefix sums of d_t
+// ((KS + 1)^2 words behind its planes) and a lane adds back the d_t of the taps its border class loses: four lane-indexed loads per row, 0 for an interior pixel.
+//   tiled row       : row[0..3] as above, taps x NW pairs (s, m), then S[(KS + 1)][(KS + 1)], S[a][b] = sum of d_t over taps (ty < a, tx < b).
+// The 3x3 / stride 2 / padding 1 max-pool (models/nin.py) is an OR over the in-image cells of the window: folded into a 1x1 block (one lane = one pooled pixel, up to
+// nine decisions) or a word-wise kernel of its own behind any other producer.
 #include "common.h"
 
 namespace mn_bits {
@@ -23,7 +31,10 @@ enum { HDR = 8, ROWHDR = 4 };
 struct Geom {
     int N, C, H, W, O, KS, groups;
     int Cg, Og, K, taps, Cw, OW, NW, stride;      // channels per group in / out, taps per output, input / output words per pixel, words a row spans per tap, row stride
+    int tiled;                                    // 1: the row carries the tap-sum prefix table of the LDS-tiled kernel behind its planes
 };
+
+enum { TILE_MAXW = 8, TILE_WORDS = 4 * 12 * 12 * TILE_MAXW };          // words per pixel the tiled kernel stages; its LDS image (4 images of 8 x 8 + halo 2 is the largest)
 
 static inline int span_words(int C, int groups) {
     const int Cg = C / groups;
@@ -37,7 +48,7 @@ static inline int span_words(int C, int groups) {
 
 static inline bool make_geom(const mn_conv_geom* g, Geom& q) {
     if (!g || g->N <= 0 || g->C <= 0 || g->H <= 0 || g->W <= 0 || g->O <= 0 || g->groups <= 0) return false;
-    if (g->KH != g->KW || (g->KH != 1 && g->KH != 3)) return false;
+    if (g->KH != g->KW || (g->KH != 1 && g->KH != 3 && g->KH != 5)) return false;
     const int pad = (g->KH - 1) / 2;
     if (g->stride_h != 1 || g->stride_w != 1 || g->dil_h != 1 || g->dil_w != 1 || g->pad_h != pad || g->pad_w != pad) return false;
     if (g->C % g->groups || g->O % g->groups || g->in_shuffle > 1) return false;      // a channel shuffle is folded into the PRODUCER's row order, never gathered here
@@ -48,7 +59,10 @@ static inline bool make_geom(const mn_conv_geom* g, Geom& q) {
     q.Cw = (g->C + 31) >> 5; q.OW = (g->O + 31) >> 5;
     q.NW = span_words(g->C, g->groups);
     if (q.NW > (g->KH == 1 ? 64 : 8)) return false;
-    q.stride = ROWHDR + 2 * q.taps * q.NW;
+    q.tiled = g->KH > 1 && g->groups == 1 && q.Cw > 1 && q.Cw <= TILE_MAXW;
+    if (g->KH == 5 && !(g->groups == 1 && q.Cw <= TILE_MAXW)) return false;          // 5x5: the tiled kernel only (dense, C <= 256)
+    if (g->KH == 5) q.tiled = 1;
+    q.stride = ROWHDR + 2 * q.taps * q.NW + (q.tiled ? (g->KH + 1) * (g->KH + 1) : 0);
     const int64_t words = (int64_t)g->N * (q.Cw > q.OW ? q.Cw : q.OW) * g->H * g->W;
     if (words >= (1ll << 31) || (int64_t)q.OW * 32 * q.stride >= (1ll << 30)) return false;
     return true;
@@ -113,7 +127,7 @@ __global__ __launch_bounds__(256) void k_bits_wpack(Geom q, const float* __restr
     __shared__ int sh[256];
     const int j = blockIdx.x, tid = threadIdx.x;
     uint32_t* row = tab + HDR + (int64_t)j * q.stride;
-    if (j == 0 && tid == 0) { tab[1] = (uint32_t)q.NW; tab[2] = (uint32_t)q.taps; tab[3] = (uint32_t)q.stride; tab[4] = (uint32_t)(q.OW * 32); tab[5] = (uint32_t)q.Cw; }
+    if (j == 0 && tid == 0) { tab[1] = (uint32_t)q.NW; tab[2] = (uint32_t)q.taps; tab[3] = (uint32_t)q.stride; tab[4] = (uint32_t)(q.OW * 32); tab[5] = (uint32_t)q.Cw; tab[6] = (uint32_t)q.tiled; }
     int o = j < q.O ? (order ? order[j] : j) : -1;
     if (j < q.O && (o < 0 || o >= q.O)) {          // a bad out_order entry: counted, the row never fires, nothing is read out of bounds
         if (tid == 0) atomicAdd(tab + 0, 1u);
@@ -152,6 +166,26 @@ __global__ __launch_bounds__(256) void k_bits_wpack(Geom q, const float* __restr
         }
         row[ROWHDR + 2 * idx] = s;
         row[ROWHDR + 2 * idx + 1] = m;
+    }
+    if (q.tiled) {          // S[a][b] = sum over taps (ty < a, tx < b) of d_t, d_t = sum of the row's weight signs at tap t (what a zero halo word wrongly subtracts)
+        __shared__ int dt[32];
+        if (tid < q.taps) {
+            int d = 0;
+            for (int ci = 0; ci < q.Cg; ++ci) {
+                const float v = wr[ci * q.taps + tid];
+                d += (v > 0.f) - (v < 0.f);
+            }
+            dt[tid] = d;
+        }
+        __syncthreads();
+        const int S1 = q.KS + 1;
+        if (tid < S1 * S1) {
+            const int a = tid / S1, c = tid - a * S1;
+            int v = 0;
+            for (int ty = 0; ty < a; ++ty)
+                for (int tx = 0; tx < c; ++tx) v += dt[ty * q.KS + tx];
+            row[ROWHDR + 2 * q.taps * q.NW + tid] = (uint32_t)v;
+        }
     }
     // the decision of the byte kernels, evaluated for every accumulator value the row can produce
     const float b = bias ? bias[o] : 0.f;
@@ -242,6 +276,194 @@ static void launch_nw(int nwsel, dim3 grid, hipStream_t s, const uint32_t* tab, 
     }
 }
 
+
+// ---------------------------------------------------------------- dense k x k on an LDS-resident tile
+struct Tile {
+    int N, Cw, H, W, OW, stride, owpb, tw, th, ipb, tx, ty;          // tile width / height (8 or 16), images per block (256 / (tw * th)), tiles per image row / column
+};
+
+// NW > 0: Cw == NW, the lane's KS x KS x NW window is read from LDS into registers once; NW == 0: any Cw <= TILE_MAXW, the window is read from LDS for every row.
+template <int KS, int NW>
+__global__ __launch_bounds__(256) void k_bitconv_tile(const uint32_t* __restrict__ tab, const uint32_t* __restrict__ x, uint32_t* __restrict__ y, Tile q) {
+    __shared__ uint32_t sx[TILE_WORDS];
+    constexpr int P = (KS - 1) / 2, S1 = KS + 1;
+    const int nw = NW ? NW : q.Cw;
+    const int tid = threadIdx.x;
+    const int pw = q.tw + 2 * P, cells = (q.th + 2 * P) * pw;
+    int b = blockIdx.x;
+    const int bx = b % q.tx; b /= q.tx;
+    const int by = b % q.ty;
+    const int n0 = (b / q.ty) * q.ipb, h0 = by * q.th, w0 = bx * q.tw;
+    const int HW = q.H * q.W;
+    const int tot = q.ipb * nw * cells;          // <= TILE_WORDS (checked by the host)
+    for (int i = tid; i < tot; i += 256) {
+        const int c = i % cells, r = i / cells;
+        const int k = r % nw, n = n0 + r / nw;
+        const int ih = h0 + c / pw - P, iw = w0 + c % pw - P;
+        uint32_t v = 0u;          // halo and everything outside the batch: zero words
+        if (n < q.N && ih >= 0 && ih < q.H && iw >= 0 && iw < q.W) v = x[((int64_t)n * q.Cw + k) * HW + ih * q.W + iw];
+        sx[i] = v;
+    }
+    __syncthreads();
+    const int per = q.tw * q.th;
+    const int im = tid / per, r = tid - im * per;
+    const int ly = r / q.tw, lx = r - ly * q.tw;
+    const int n = n0 + im, oh = h0 + ly, ow = w0 + lx;
+    if (n >= q.N || oh >= q.H || ow >= q.W) return;
+    // the taps inside the image are ty in [y0, y1), tx in [x0, x1): the lane's border class, as four offsets into the row's prefix table
+    const int y0 = P - oh > 0 ? P - oh : 0, y1 = q.H + P - oh < KS ? q.H + P - oh : KS;
+    const int x0 = P - ow > 0 ? P - ow : 0, x1 = q.W + P - ow < KS ? q.W + P - ow : KS;
+    const int i11 = y1 * S1 + x1, i01 = y0 * S1 + x1, i10 = y1 * S1 + x0, i00 = y0 * S1 + x0;
+    const uint32_t* xs = sx + im * nw * cells + ly * pw + lx;
+    uint32_t xr[NW ? KS * KS * NW : 1];
+    if (NW) {
+#pragma unroll
+        for (int t = 0; t < KS * KS; ++t)
+#pragma unroll
+            for (int k = 0; k < NW; ++k) xr[t * NW + k] = xs[k * cells + (t / KS) * pw + t % KS];
+    }
+    const int ow0 = blockIdx.y * q.owpb;
+    const int ow1 = ow0 + q.owpb < q.OW ? ow0 + q.owpb : q.OW;
+    for (int owi = ow0; owi < ow1; ++owi) {
+        const uint32_t* rowp = tab + HDR + (int64_t)owi * 32 * q.stride;
+        uint32_t word = 0;
+        for (int j = 0; j < 32; ++j) {
+            const uint32_t* row = rowp + j * q.stride;          // wave-uniform
+            const uint32_t* sp = row + ROWHDR + 2 * KS * KS * nw;
+            const int lost = (int)sp[S1 * S1 - 1] - ((int)sp[i11] - (int)sp[i01] - (int)sp[i10] + (int)sp[i00]);          // sum of d_t over the taps outside the image
+            int Pc = 0;
+            if (NW) {
+#pragma unroll
+                for (int t = 0; t < KS * KS * NW; ++t) Pc += mn_popc(~(xr[t] ^ row[ROWHDR + 2 * t]) & row[ROWHDR + 2 * t + 1]);
+            } else {
+#pragma unroll
+                for (int t = 0; t < KS * KS; ++t) {
+                    const uint32_t* xp = xs + (t / KS) * pw + t % KS;
+                    for (int k = 0; k < nw; ++k) Pc += mn_popc(~(xp[k * cells] ^ row[ROWHDR + 2 * (t * nw + k)]) & row[ROWHDR + 2 * (t * nw + k) + 1]);
+                }
+            }
+            const int acc = 2 * Pc - (int)row[2] + lost;
+            word |= (uint32_t)(acc >= (int)row[0]) << j;
+        }
+        y[((int64_t)n * q.OW + owi) * HW + oh * q.W + ow] = word;
+    }
+}
+
+// MEASUREMENT ONLY (never dispatched by a plan): the global re-read loop of k_bitconv at any odd KS, on the same table -- what the tiled kernel is compared against.
+template <int KS>
+__global__ __launch_bounds__(256) void k_bitconv_direct(const uint32_t* __restrict__ tab, const uint32_t* __restrict__ x, uint32_t* __restrict__ y, Fwd q) {
+    constexpr int P = (KS - 1) / 2;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= q.total) return;
+    const int HW = q.H * q.W;
+    const int n = p / HW, r = p - n * HW;
+    const int oh = r / q.W, ow = r - oh * q.W;
+    const uint32_t* xn = x + (int64_t)n * q.Cw * HW;
+    const int ow0 = blockIdx.y * q.owpb;
+    const int ow1 = ow0 + q.owpb < q.OW ? ow0 + q.owpb : q.OW;
+    for (int owi = ow0; owi < ow1; ++owi) {
+        const uint32_t* rowp = tab + HDR + (int64_t)owi * 32 * q.stride;
+        uint32_t word = 0;
+        for (int j = 0; j < 32; ++j) {
+            const uint32_t* row = rowp + j * q.stride;
+            int Pc = 0, Z = 0;
+#pragma unroll
+            for (int t = 0; t < KS * KS; ++t) {
+                const int ih = oh + t / KS - P, iw = ow + t % KS - P;
+                const bool ok = ih >= 0 && ih < q.H && iw >= 0 && iw < q.W;
+                const uint32_t* xp = xn + ih * q.W + iw;
+                for (int k = 0; k < q.nw; ++k) {
+                    const uint32_t xv = ok ? xp[k * HW] : 0u;
+                    const uint32_t mv = ok ? row[ROWHDR + 2 * (t * q.nw + k) + 1] : 0u;
+                    Pc += mn_popc(~(xv ^ row[ROWHDR + 2 * (t * q.nw + k)]) & mv);
+                    Z += mn_popc(mv);
+                }
+            }
+            word |= (uint32_t)(2 * Pc - Z >= (int)row[0]) << j;
+        }
+        y[((int64_t)n * q.OW + owi) * HW + r] = word;
+    }
+}
+
+// ---------------------------------------------------------------- 1x1 block + the 3x3 / stride 2 / padding 1 max-pool behind it
+// One lane owns one POOLED pixel: OR of the decisions of the (up to nine) in-image cells of its window.  NWMAX > 0: dense (every row reads words 0 .. Cw - 1, Cw <=
+// NWMAX), the window's words are held in registers; NWMAX == 0: any 1x1 geometry, the words are re-read per row.
+template <int NWMAX>
+__global__ __launch_bounds__(256) void k_bitconv1_pool3(const uint32_t* __restrict__ tab, const uint32_t* __restrict__ x, uint32_t* __restrict__ y, Fwd q) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= q.total) return;
+    const int HWo = q.Ho * q.Wo, HW = q.H * q.W;
+    const int n = p / HWo, r = p - n * HWo;
+    const int oh = r / q.Wo, ow = r - oh * q.Wo;
+    const uint32_t* xn = x + (int64_t)n * q.Cw * HW;
+    uint32_t okm = 0;
+    int off[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) {
+        const int ih = 2 * oh - 1 + c / 3, iw = 2 * ow - 1 + c % 3;
+        const bool ok = ih >= 0 && ih < q.H && iw >= 0 && iw < q.W;
+        okm |= (uint32_t)ok << c;
+        off[c] = ok ? ih * q.W + iw : 0;          // (a cell outside the image is never read)
+    }
+    uint32_t xr[NWMAX ? 9 * NWMAX : 1];
+    if (NWMAX) {
+#pragma unroll
+        for (int c = 0; c < 9; ++c)
+#pragma unroll
+            for (int k = 0; k < NWMAX; ++k) xr[c * NWMAX + k] = (k < q.nw && ((okm >> c) & 1u)) ? xn[k * HW + off[c]] : 0u;
+    }
+    const int ow0 = blockIdx.y * q.owpb;
+    const int ow1 = ow0 + q.owpb < q.OW ? ow0 + q.owpb : q.OW;
+    for (int owi = ow0; owi < ow1; ++owi) {
+        const uint32_t* rowp = tab + HDR + (int64_t)owi * 32 * q.stride;
+        uint32_t word = 0;
+        for (int j = 0; j < 32; ++j) {
+            const uint32_t* row = rowp + j * q.stride;          // wave-uniform
+            const int T = (int)row[0] + (int)row[2];          // 2 * P - nnz >= T
+            uint32_t hit = 0;
+            if (NWMAX) {
+#pragma unroll
+                for (int c = 0; c < 9; ++c) {
+                    int Pc = 0;
+#pragma unroll
+                    for (int k = 0; k < NWMAX; ++k)
+                        if (k < q.nw) Pc += mn_popc(~(xr[c * NWMAX + k] ^ row[ROWHDR + 2 * k]) & row[ROWHDR + 2 * k + 1]);
+                    hit |= (uint32_t)(2 * Pc >= T) << c;
+                }
+            } else {
+                const uint32_t* xw = xn + (int64_t)row[1] * HW;
+#pragma unroll
+                for (int c = 0; c < 9; ++c) {
+                    int Pc = 0;
+                    if ((okm >> c) & 1u)
+                        for (int k = 0; k < q.nw; ++k) Pc += mn_popc(~(xw[k * HW + off[c]] ^ row[ROWHDR + 2 * k]) & row[ROWHDR + 2 * k + 1]);
+                    hit |= (uint32_t)(2 * Pc >= T) << c;
+                }
+            }
+            word |= (uint32_t)((hit & okm) != 0u) << j;
+        }
+        y[((int64_t)n * q.OW + owi) * HWo + r] = word;
+    }
+}
+
+// ---------------------------------------------------------------- max-pool on bits: OR over the in-image cells of the window, one thread per output word
+__global__ __launch_bounds__(256) void k_bits_maxpool(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, int64_t total, int H, int W, int Ho, int Wo, int k, int s,
+                                                      int pad) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int ow = (int)(i % Wo);
+    const int64_t t = i / Wo;
+    const int oh = (int)(t % Ho);
+    const uint32_t* src = in + (t / Ho) * H * W;
+    uint32_t v = 0;
+    for (int dy = 0; dy < k; ++dy)
+        for (int dx = 0; dx < k; ++dx) {
+            const int ih = oh * s - pad + dy, iw = ow * s - pad + dx;
+            if (ih >= 0 && ih < H && iw >= 0 && iw < W) v |= src[ih * W + iw];
+        }
+    out[i] = v;
+}
+
 }  // namespace mn_bits
 
 extern "C" int mn_bits_pack_sign8(const int8_t* a, int64_t N, int64_t C, int64_t HW, uint32_t* bits, mn_stream_t stream) {
@@ -284,7 +506,7 @@ extern "C" int64_t mn_bitconv_table_bytes(const mn_conv_geom* g) {
 extern "C" int mn_bitconv_pack(const mn_conv_geom* g, const float* w, const float* bias, const int32_t* out_order, uint32_t* table, mn_stream_t stream) {
     mn_bits::Geom q;
     if (!w || !table || (((uintptr_t)table) & 3)) MN_FAIL(MN_EINVAL, "mn_bitconv_pack: null / unaligned argument");
-    if (!mn_bits::make_geom(g, q)) MN_FAIL(MN_ENOTSUP, "mn_bitconv_pack: geometry not covered (1x1 or 3x3 / padding 1, stride 1, no input shuffle)");
+    if (!mn_bits::make_geom(g, q)) MN_FAIL(MN_ENOTSUP, "mn_bitconv_pack: geometry not covered (1x1, 3x3 / padding 1 or dense 5x5 / padding 2 of at most 256 channels; stride 1, no input shuffle)");
     if (hipMemsetAsync(table, 0, 4 * mn_bits::HDR, (hipStream_t)stream) != hipSuccess) MN_FAIL(MN_EHIP, "mn_bitconv_pack: header reset failed");          // word 0: bad-row count
     mn_set_last_kernel("k_bits_wpack");
     hipLaunchKernelGGL(mn_bits::k_bits_wpack, dim3(q.OW * 32), dim3(256), 0, (hipStream_t)stream, q, w, bias, out_order, table);
@@ -295,29 +517,82 @@ extern "C" int mn_bitconv_pack(const mn_conv_geom* g, const float* w, const floa
 extern "C" int mn_bitconv_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t* x_bits, uint32_t* y_bits, int pool, mn_stream_t stream) {
     mn_bits::Geom q;
     if (!table || !x_bits || !y_bits) MN_FAIL(MN_EINVAL, "mn_bitconv_fwd: null argument");
-    if (!mn_bits::make_geom(g, q)) MN_FAIL(MN_ENOTSUP, "mn_bitconv_fwd: geometry not covered (1x1 or 3x3 / padding 1, stride 1, no input shuffle)");
-    if (pool && ((q.H & 1) || (q.W & 1))) MN_FAIL(MN_EINVAL, "mn_bitconv_fwd: the folded 2x2 max-pool needs even H and W");
+    if (!mn_bits::make_geom(g, q)) MN_FAIL(MN_ENOTSUP, "mn_bitconv_fwd: geometry not covered (1x1, 3x3 / padding 1 or dense 5x5 / padding 2 of at most 256 channels; stride 1, no input shuffle)");
+    const int alt = pool & MN_BITCONV_ALT;          // measurement only: the other kernel for the same table (tiled <-> global re-read)
+    pool &= ~MN_BITCONV_ALT;
+    if (pool < 0 || pool > 2) MN_FAIL(MN_EINVAL, "mn_bitconv_fwd: pool must be 0, 1 (2x2 / stride 2) or 2 (3x3 / stride 2 / padding 1)");
+    if (pool == 1 && q.KS == 5) MN_FAIL(MN_ENOTSUP, "mn_bitconv_fwd: a max-pool is not folded into the 5x5 block (use mn_bits_maxpool behind it)");
+    if (pool == 2 && q.KS != 1) MN_FAIL(MN_ENOTSUP, "mn_bitconv_fwd: the 3x3 / stride 2 max-pool is folded into 1x1 blocks only (use mn_bits_maxpool behind it)");
+    if (alt && (pool || !q.tiled)) MN_FAIL(MN_ENOTSUP, "mn_bitconv_fwd: no alternative kernel for this geometry");
+    if (pool == 1 && ((q.H & 1) || (q.W & 1))) MN_FAIL(MN_EINVAL, "mn_bitconv_fwd: the folded 2x2 max-pool needs even H and W");
     mn_bits::Fwd f;
-    f.Cw = q.Cw; f.H = q.H; f.W = q.W; f.Ho = pool ? q.H / 2 : q.H; f.Wo = pool ? q.W / 2 : q.W; f.OW = q.OW; f.nw = q.NW; f.stride = q.stride;
+    f.Cw = q.Cw; f.H = q.H; f.W = q.W; f.OW = q.OW; f.nw = q.NW; f.stride = q.stride;
+    f.Ho = pool == 1 ? q.H / 2 : pool == 2 ? (q.H - 1) / 2 + 1 : q.H;
+    f.Wo = pool == 1 ? q.W / 2 : pool == 2 ? (q.W - 1) / 2 + 1 : q.W;
     f.total = q.N * f.Ho * f.Wo;
-    const int bx = (f.total + 255) / 256;
+    const bool tile = q.tiled && (q.KS == 5) != (alt != 0);          // 5x5: always; the dense 3x3 with several words: only when asked for
+    mn_bits::Tile t;
+    int bx = (f.total + 255) / 256;
+    if (tile) {
+        t.N = q.N; t.Cw = q.Cw; t.H = q.H; t.W = q.W; t.OW = q.OW; t.stride = q.stride;
+        t.tw = q.W <= 8 ? 8 : 16; t.th = q.H <= 8 ? 8 : 16; t.ipb = 256 / (t.tw * t.th);
+        t.tx = (q.W + t.tw - 1) / t.tw; t.ty = (q.H + t.th - 1) / t.th;
+        const int64_t blocks = (int64_t)((q.N + t.ipb - 1) / t.ipb) * t.tx * t.ty;
+        if (blocks > INT_MAX || t.ipb * q.Cw * (t.tw + q.KS - 1) * (t.th + q.KS - 1) > mn_bits::TILE_WORDS) MN_FAIL(MN_ENOTSUP, "mn_bitconv_fwd: tile does not fit");
+        bx = (int)blocks;
+    }
     int gy = (2048 + bx - 1) / bx;          // enough blocks to fill the chip: split the output words over grid.y when the pixels alone do not
     if (gy > q.OW) gy = q.OW;
     f.owpb = (q.OW + gy - 1) / gy;
     gy = (q.OW + f.owpb - 1) / f.owpb;
+    t.owpb = f.owpb;
     const dim3 grid(bx, gy);
+    const hipStream_t s = (hipStream_t)stream;
     const int nwsel = (q.NW == 1 || (q.KS == 1 && (q.NW == 2 || q.NW == 4))) ? q.NW : 0;
-    mn_set_last_kernel("k_bitconv<%d,%d,%d>", q.KS, nwsel, pool ? 1 : 0);
+    const int tsel = q.KS == 5 ? (q.Cw == 3 ? 3 : 0) : (q.Cw == 6 ? 6 : 0);
+    const int psel = (q.groups == 1 && q.Cw <= 8) ? 8 : 0;
+    if (tile) mn_set_last_kernel("k_bitconv_tile<%d,%d>", q.KS, tsel);
+    else if (alt) mn_set_last_kernel("k_bitconv_direct<%d>", q.KS);
+    else if (pool == 2) mn_set_last_kernel("k_bitconv1_pool3<%d>", psel);
+    else mn_set_last_kernel("k_bitconv<%d,%d,%d>", q.KS, nwsel, pool ? 1 : 0);
     mn_prof_bytes(4.0 * q.N * q.Cw * q.H * q.W + 4.0 * q.N * q.OW * f.Ho * f.Wo + 4.0 * (mn_bits::HDR + (double)q.OW * 32 * q.stride));
-    mn_prof_begin((hipStream_t)stream);
-    if (q.KS == 1) {
-        if (pool) mn_bits::launch_nw<1, true>(nwsel, grid, (hipStream_t)stream, table, x_bits, y_bits, f);
-        else mn_bits::launch_nw<1, false>(nwsel, grid, (hipStream_t)stream, table, x_bits, y_bits, f);
+    mn_prof_begin(s);
+    if (tile) {
+        if (q.KS == 5) {
+            if (tsel) hipLaunchKernelGGL((mn_bits::k_bitconv_tile<5, 3>), grid, dim3(256), 0, s, table, x_bits, y_bits, t);
+            else hipLaunchKernelGGL((mn_bits::k_bitconv_tile<5, 0>), grid, dim3(256), 0, s, table, x_bits, y_bits, t);
+        } else {
+            if (tsel) hipLaunchKernelGGL((mn_bits::k_bitconv_tile<3, 6>), grid, dim3(256), 0, s, table, x_bits, y_bits, t);
+            else hipLaunchKernelGGL((mn_bits::k_bitconv_tile<3, 0>), grid, dim3(256), 0, s, table, x_bits, y_bits, t);
+        }
+    } else if (alt) {
+        hipLaunchKernelGGL((mn_bits::k_bitconv_direct<5>), grid, dim3(256), 0, s, table, x_bits, y_bits, f);
+    } else if (pool == 2) {
+        if (psel) hipLaunchKernelGGL((mn_bits::k_bitconv1_pool3<8>), grid, dim3(256), 0, s, table, x_bits, y_bits, f);
+        else hipLaunchKernelGGL((mn_bits::k_bitconv1_pool3<0>), grid, dim3(256), 0, s, table, x_bits, y_bits, f);
+    } else if (q.KS == 1) {
+        if (pool) mn_bits::launch_nw<1, true>(nwsel, grid, s, table, x_bits, y_bits, f);
+        else mn_bits::launch_nw<1, false>(nwsel, grid, s, table, x_bits, y_bits, f);
     } else {
-        if (pool) mn_bits::launch_nw<3, true>(nwsel, grid, (hipStream_t)stream, table, x_bits, y_bits, f);
-        else mn_bits::launch_nw<3, false>(nwsel, grid, (hipStream_t)stream, table, x_bits, y_bits, f);
+        if (pool) mn_bits::launch_nw<3, true>(nwsel, grid, s, table, x_bits, y_bits, f);
+        else mn_bits::launch_nw<3, false>(nwsel, grid, s, table, x_bits, y_bits, f);
     }
-    mn_prof_end((hipStream_t)stream);
+    mn_prof_end(s);
     MN_CHECK_LAUNCH("mn_bitconv_fwd");
+    return MN_OK;
+}
+
+extern "C" int mn_bits_maxpool(const uint32_t* bits_in, int64_t N, int64_t Cw, int64_t H, int64_t W, int k, int stride, int pad, uint32_t* bits_out, mn_stream_t stream) {
+    if (!bits_in || !bits_out || N <= 0 || Cw <= 0 || H <= 0 || W <= 0 || H > (1 << 15) || W > (1 << 15)) MN_FAIL(MN_EINVAL, "mn_bits_maxpool: null / empty argument");
+    if ((k != 2 && k != 3) || stride != 2 || pad < 0 || pad > 1) MN_FAIL(MN_ENOTSUP, "mn_bits_maxpool: window not covered (k in {2, 3}, stride 2, padding in {0, 1}, floor mode)");
+    if (H + 2 * pad < k || W + 2 * pad < k) MN_FAIL(MN_EINVAL, "mn_bits_maxpool: image smaller than the window");
+    const int Ho = (int)((H + 2 * pad - k) / stride + 1), Wo = (int)((W + 2 * pad - k) / stride + 1);
+    const int64_t total = N * Cw * Ho * Wo;
+    if (N * Cw * H * W >= (1ll << 31)) MN_FAIL(MN_ENOTSUP, "mn_bits_maxpool: tensor too large");
+    mn_set_last_kernel("k_bits_maxpool"); mn_prof_bytes(4.0 * N * Cw * H * W + 4.0 * total); mn_prof_begin((hipStream_t)stream);
+    hipLaunchKernelGGL(mn_bits::k_bits_maxpool, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, bits_in, bits_out, total, (int)H, (int)W, Ho, Wo, k,
+                       stride, pad);
+    mn_prof_end((hipStream_t)stream);
+    MN_CHECK_LAUNCH("mn_bits_maxpool");
     return MN_OK;
 }

@@ -196,15 +196,31 @@ def unpack_bits(bits, C):
     return out
 
 
-def _is_pool2x2(m):
-    two = lambda v: v in (2, (2, 2), [2, 2])
-    return isinstance(m, nn.MaxPool2d) and two(m.kernel_size) and two(m.stride) and m.padding in (0, (0, 0)) and m.dilation in (1, (1, 1)) and not m.ceil_mode \
-        and not m.return_indices
+def _pool_kind(m):
+    """(kernel, stride, padding) of a max-pool the bit kernels cover -- 2x2 / 2 / 0 (models/nin_gc.py) and 3x3 / 2 / 1 (models/nin.py), floor mode -- else None."""
+    if not isinstance(m, nn.MaxPool2d) or m.ceil_mode or m.return_indices or m.dilation not in (1, (1, 1), [1, 1]):
+        return None
+    one = lambda v: v if isinstance(v, int) else (v[0] if len(v) == 2 and v[0] == v[1] else None)
+    ksp = (one(m.kernel_size), one(m.stride if m.stride is not None else m.kernel_size), one(m.padding))
+    return ksp if ksp in ((2, 2, 0), (3, 2, 1)) else None
+
+
+def _conv_kernel_name(k, cin, groups, fold):
+    """The kernel mn_bitconv_fwd launches for a hidden block (csrc/qgemm_bits.hip: the dispatch at the end of the file); fold: 0, 1 (2x2 / 2) or 2 (3x3 / 2 / 1)."""
+    cw, cg = (cin + 31) // 32, cin // groups
+    if k == 5:
+        return "k_bitconv_tile<5,%d>" % (3 if cw == 3 else 0)
+    if fold == 2:
+        return "k_bitconv1_pool3<%d>" % (8 if groups == 1 and cw <= 8 else 0)
+    nw = max(((gi * cg + cg - 1) >> 5) - ((gi * cg) >> 5) + 1 for gi in range(groups))
+    sel = nw if (nw == 1 or (k == 1 and nw in (2, 4))) else 0
+    return "k_bitconv<%d,%d,%d>" % (k, sel, fold)
 
 
 class BitPlan(nn.Module):
-    """What ``wbwtab_compile_bits`` returns: first block (fp32 conv + sign, the folded graph's own module) -> bit pack -> n XNOR-popcount blocks (2x2 max-pools folded
-    in) -> bit unpack -> last block and tail (the folded graph's own modules).  Eval only; owns the packed weight tables and one set of bit buffers per input shape."""
+    """What ``wbwtab_compile_bits`` returns: first block (fp32 conv + sign, the folded graph's own module) -> bit pack -> n XNOR-popcount blocks (max-pools folded in,
+    or run on the bits behind a block that cannot fold them) -> bit unpack -> last block and tail (the folded graph's own modules).  Eval only; owns the packed weight
+    tables and one set of bit buffers per input shape."""
 
     def __init__(self, first, layers, last, tail, flatten, report):
         super().__init__()
@@ -229,14 +245,23 @@ class BitPlan(nn.Module):
         if key not in self._ws:
             N, Cc, H, W = shape
             bufs, geoms = [torch.empty((N, (Cc + 31) // 32, H, W), dtype=torch.int32, device=device)], []
+            mids = []
             for L in self.layers:
-                k, p = L["k"], (L["k"] - 1) // 2
+                k, p = L["k"], L["pad"]
                 geoms.append(_lib.ConvGeom(N, L["cin"], H, W, L["cout"], k, k, 1, 1, p, p, 1, 1, L["groups"], 0))
-                if L["pool"]:
-                    H, W = H // 2, W // 2
+                H, W = H + 2 * p - k + 1, W + 2 * p - k + 1
+                pool = L["pool_ksp"]
+                if pool and (min(H, W) + 2 * pool[2] < pool[0] or (L["pool"] == 1 and (H % 2 or W % 2))):
+                    raise _err("wbwtab_compile_bits: %s: the max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
+                mids.append(torch.empty((N, (L["cout"] + 31) // 32, H, W), dtype=torch.int32, device=device) if pool and not L["pool"] else None)
+                if pool:
+                    H, W = (H + 2 * pool[2] - pool[0]) // pool[1] + 1, (W + 2 * pool[2] - pool[0]) // pool[1] + 1
                 bufs.append(torch.empty((N, (L["cout"] + 31) // 32, H, W), dtype=torch.int32, device=device))
                 Cc = L["cout"]
-            self._ws[key] = (bufs, geoms, torch.empty((N, Cc, H, W), dtype=torch.int8, device=device))
+            if (H * W) % 4:
+                raise _err("wbwtab_compile_bits: %s: its %d x %d output cannot be unpacked for the last conv (mn_bits_unpack_sign8 needs H * W %% 4 == 0)"
+                           % (self.layers[-1]["name"], H, W))
+            self._ws[key] = (bufs, geoms, torch.empty((N, Cc, H, W), dtype=torch.int8, device=device), mids)
         return self._ws[key]
 
     @torch.no_grad()
@@ -249,11 +274,16 @@ class BitPlan(nn.Module):
             raise _err("wbwtab_compile_bits: the first block did not produce packed signs (input must be a contiguous float32 GPU tensor with H * W % 4 == 0)")
         codes = a.codes.contiguous()
         N, Cc, H, W = codes.shape
-        bufs, geoms, a8 = self._plan_buffers(codes.shape, codes.device)
+        bufs, geoms, a8, mids = self._plan_buffers(codes.shape, codes.device)
         st = ops._s()
         ops._call("mn_bits_pack_sign8", ops._p(codes), N, Cc, H * W, ops._p(bufs[0]), st)
         for i, L in enumerate(self.layers):
-            ops._call("mn_bitconv_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(bufs[i + 1]), int(L["pool"]), st)
+            if mids[i] is None:
+                ops._call("mn_bitconv_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(bufs[i + 1]), int(L["pool"]), st)
+            else:          # a pool the block cannot fold: the block at full size, then the word-wise OR
+                m, (pk, ps, pp) = mids[i], L["pool_ksp"]
+                ops._call("mn_bitconv_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(m), 0, st)
+                ops._call("mn_bits_maxpool", ops._p(m), m.shape[0], m.shape[1], m.shape[2], m.shape[3], pk, ps, pp, ops._p(bufs[i + 1]), st)
         if self.keep_stages:
             self.stage_bits = [b.clone() for b in bufs]
         n_, c_, h_, w_ = a8.shape
@@ -264,13 +294,10 @@ class BitPlan(nn.Module):
         return y.view(y.size(0), -1) if self.flatten else y
 
 
-@torch.no_grad()
-def wbwtab_compile_bits(model):
-    """``model``: the result of ``wbwtab_model_bn_fuse`` on a pre-quantised W in (2, 3), A = 2 net, on the GPU.  Returns a ``BitPlan`` computing the same function with one bit
-    per hidden activation; ``.report`` lists the stages.  Anything the bit kernels do not cover raises ``MicronetHipError`` naming the layer -- never a silent byte path
-    (the caller still has ``model``)."""
+def _walk_bits(model):
+    """The graph walk of ``wbwtab_compile_bits`` (no GPU needed): (first, layers, last, tail, flatten, report)."""
     import ctypes as C
-    from micronet_amd import _lib, ops
+    from micronet_amd import _lib
     from micronet_amd.nn import Conv2dFirst
     from micronet_amd.quantization.wbwtab import quantize
     if isinstance(model, nn.Sequential):
@@ -290,10 +317,17 @@ def wbwtab_compile_bits(model):
         if last is not None:
             tail.append(child)
             continue
-        if _is_pool2x2(child):
-            if not layers or layers[-1]["pool"]:
-                raise _err("wbwtab_compile_bits: %s: a 2x2 max-pool is folded only into the bit block directly in front of it" % nm)
-            layers[-1]["pool"], layers[-1]["stage"] = 1, name
+        if isinstance(child, nn.MaxPool2d):
+            ksp = _pool_kind(child)
+            if ksp is None:
+                raise _err("wbwtab_compile_bits: %s: max-pool (kernel %s, stride %s, padding %s, ceil_mode %s) is not covered by the bit kernels (2x2 / 2 / 0 and 3x3 / 2 / 1, "
+                           "floor mode)" % (nm, child.kernel_size, child.stride, child.padding, child.ceil_mode))
+            if not layers or layers[-1]["pool_ksp"]:
+                raise _err("wbwtab_compile_bits: %s: a %dx%d max-pool is folded only into the bit block directly in front of it" % (nm, ksp[0], ksp[0]))
+            L = layers[-1]
+            # folded where the block's kernel can own a pooled pixel (2x2: 1x1 and 3x3 blocks; 3x3 / 2: 1x1 blocks), else mn_bits_maxpool behind the block
+            L["pool"] = (1 if L["k"] in (1, 3) else 0) if ksp == (2, 2, 0) else (2 if L["k"] == 1 else 0)
+            L["pool_ksp"], L["stage"] = ksp, name
             continue
         conv, bn, act = getattr(child, "conv", None), getattr(child, "bn", None), getattr(child, "relu", None)
         if not (quantize._is_ref_block(child) and isinstance(conv, nn.Conv2d) and isinstance(bn, nn.Identity)):
@@ -334,9 +368,37 @@ def wbwtab_compile_bits(model):
             if not layers:
                 raise _err("wbwtab_compile_bits: %s: a channel shuffle directly behind the first block is not covered (its producer is not a bit block)" % nm)
             layers[-1]["shuffle"] = shuffle          # folded into the producer's row order
-        layers.append(dict(name=nm, conv=conv, k=k, cin=conv.in_channels, cout=conv.out_channels, groups=conv.groups, pool=0, shuffle=0, stage=name))
+        layers.append(dict(name=nm, conv=conv, k=k, pad=pad, cin=conv.in_channels, cout=conv.out_channels, groups=conv.groups, pool=0, pool_ksp=None, shuffle=0, stage=name))
     if first is None or last is None:
         raise _err("wbwtab_compile_bits: module order not recognised (no %s conv block found)" % ("first" if first is None else "last"))
+    rep_last = report.pop()
+    for L in layers:
+        kern = _conv_kernel_name(L["k"], L["cin"], L["groups"], L["pool"])
+        pooled = bool(L["pool"])
+        if L["pool"] == 2:
+            pooled = "folded 3x3/2"
+        elif L["pool_ksp"] and not L["pool"]:
+            kern, pooled = kern + ", k_bits_maxpool", "standalone"
+        report.append(dict(name=L["name"], kind="bit", K=L["cin"] // L["groups"] * L["k"] * L["k"], words=(L["cin"] + 31) // 32, kernel=kern, pooled=pooled,
+                           out_order=("shuffle %d" % L["shuffle"]) if L["shuffle"] > 1 else "identity", stage=L["stage"]))
+    report.append(rep_last)
+    return first, layers, last, tail, flatten, report
+
+
+def wbwtab_bits_report(model):
+    """The ``report`` ``wbwtab_compile_bits(model)`` would carry -- one row per stage: kernel, K, words, how a max-pool behind it is done -- from the graph walk alone:
+    no GPU, nothing packed.  Raises like ``wbwtab_compile_bits`` for whatever the bit kernels do not cover."""
+    return _walk_bits(model)[5]
+
+
+@torch.no_grad()
+def wbwtab_compile_bits(model):
+    """``model``: the result of ``wbwtab_model_bn_fuse`` on a pre-quantised W in (2, 3), A = 2 net, on the GPU (the reference's ``nin`` and ``nin_gc``).  Returns a ``BitPlan``
+    computing the same function with one bit per hidden activation; ``.report`` lists the stages.  Anything the bit kernels do not cover raises ``MicronetHipError``
+    naming the layer -- never a silent byte path (the caller still has ``model``)."""
+    import ctypes as C
+    from micronet_amd import _lib, ops
+    first, layers, last, tail, flatten, report = _walk_bits(model)
     for p_ in model.parameters():
         if not p_.is_cuda:
             raise _err("wbwtab_compile_bits: the model is on %s: micronet_amd runs on MI355X only (no CPU fallback)" % p_.device)
@@ -344,7 +406,7 @@ def wbwtab_compile_bits(model):
     lib = _lib.get_lib()
     for L in layers:
         conv = L.pop("conv")
-        k, p = L["k"], (L["k"] - 1) // 2
+        k, p = L["k"], L["pad"]
         g = _lib.ConvGeom(1, L["cin"], 4, 4, L["cout"], k, k, 1, 1, p, p, 1, 1, L["groups"], 0)
         table = torch.empty(int(lib.mn_bitconv_table_bytes(C.byref(g))) // 4, dtype=torch.int32, device=conv.weight.device)
         order = None
@@ -359,12 +421,4 @@ def wbwtab_compile_bits(model):
     for nm, nbad in bad:
         if nbad:
             raise _err("wbwtab_compile_bits: %s.conv: %d output channels whose decision is not monotone in the accumulator" % (nm, nbad))
-    rep_last = report.pop()
-    for L in layers:
-        cg = L["cin"] // L["groups"]
-        nw = max(((gi * cg + cg - 1) >> 5) - ((gi * cg) >> 5) + 1 for gi in range(L["groups"]))
-        sel = nw if (nw == 1 or (L["k"] == 1 and nw in (2, 4))) else 0
-        report.append(dict(name=L["name"], kind="bit", K=cg * L["k"] * L["k"], words=(L["cin"] + 31) // 32, kernel="k_bitconv<%d,%d,%d>" % (L["k"], sel, L["pool"]),
-                           pooled=bool(L["pool"]), out_order=("shuffle %d" % L["shuffle"]) if L["shuffle"] > 1 else "identity", stage=L["stage"]))
-    report.append(rep_last)
     return BitPlan(first, layers, last, tail, flatten, report)

@@ -1,10 +1,11 @@
-"""Byte path vs bit path of the deployed (BN-folded, pre-quantised) W-ternary / A-binary nin_gc: images/s of the folded graph ``F`` (one byte per activation, the
+"""Byte path vs bit path of the deployed (BN-folded, pre-quantised) W-ternary / A-binary nin_gc (or, --model nin, the plain nin): images/s of the folded graph ``F`` (one byte per activation, the
 training kernels in eval mode) and of ``B = inference.wbwtab_compile_bits(F)`` (one bit per hidden activation), alternated in ONE process, HIP events.
 
-    python scripts/kbench_bits.py [--batches 256,1024] [--warmup 5] [--iters 20] [--out profiles/bits_inference.json]
+    python scripts/kbench_bits.py [--model nin_gc|nin] [--batches 256,1024] [--warmup 5] [--iters 20] [--out profiles/bits_inference[_nin].json]
 
 Per batch: median / min of the timed forwards of each, the spread of F's own runs, B's per-kernel time from the library's profile hooks, and the designed HBM
-bytes per image per layer (each operand read or written once)."""
+bytes per image per layer (each operand read or written once).  --model nin adds the design comparison of its two dense blocks, kernel against kernel on the
+same table: the LDS-tiled 5x5 against the global re-read loop at KS = 5, and the rolled 3x3 the plan uses against the LDS-tiled kernel (MN_BITCONV_ALT)."""
 import argparse
 import json
 import os
@@ -41,7 +42,8 @@ def designed_bytes_per_image(B, hw=32):
     """First block: image in, int8 signs out, bits out.  Bit blocks: input words + output words.  Last: bits in, int8 out and in, fp32 logit maps out."""
     rows, h = [], hw
     for r, L in zip(B.report[1:-1], B.layers):
-        ho = h // 2 if L["pool"] else h
+        pk = L["pool_ksp"]
+        ho = (h + 2 * pk[2] - pk[0]) // pk[1] + 1 if pk else h
         rows.append(dict(name=r["name"], kernel=r["kernel"], bits_bytes=4 * ((L["cin"] + 31) // 32) * h * h + 4 * ((L["cout"] + 31) // 32) * ho * ho,
                          byte_path_bytes=L["cin"] * h * h + 2 * L["cout"] * h * h))          # byte path: codes in, codes + stash out
         h = ho
@@ -52,24 +54,55 @@ def designed_bytes_per_image(B, hw=32):
     return [first] + rows + [last]
 
 
+def kernel_ab(lib, _lib, bs, cin, cout, k, hw, iters, warmup):
+    """The two kernels that can run one dense block (plan's choice first, MN_BITCONV_ALT second), alternated: per-launch HIP-event times in ms."""
+    import ctypes as C
+    from micronet_amd import ops
+    g = _lib.ConvGeom(bs, cin, hw, hw, cout, k, k, 1, 1, (k - 1) // 2, (k - 1) // 2, 1, 1, 1, 0)
+    gen = torch.Generator(device="cuda").manual_seed(k)
+    w = (torch.randint(-1, 2, (cout, cin, k, k), device="cuda", generator=gen).float() * 0.05).contiguous()
+    b = torch.randn(cout, device="cuda", generator=gen)
+    table = torch.empty(int(lib.mn_bitconv_table_bytes(C.byref(g))) // 4, dtype=torch.int32, device="cuda")
+    ops._call("mn_bitconv_pack", C.byref(g), ops._p(w), ops._p(b), None, ops._p(table), ops._s())
+    x = torch.randint(-2 ** 31, 2 ** 31 - 1, (bs, (cin + 31) // 32, hw, hw), device="cuda", generator=gen, dtype=torch.int64).to(torch.int32)
+    ya, yb = (torch.empty((bs, (cout + 31) // 32, hw, hw), dtype=torch.int32, device="cuda") for _ in range(2))
+    names, times = {}, {0: [], 0x100: []}
+    run = lambda flag, y: ops._call("mn_bitconv_fwd", C.byref(g), ops._p(table), ops._p(x), ops._p(y), flag, ops._s())
+    for flag, y in ((0, ya), (0x100, yb)):
+        run(flag, y)
+        names[flag] = lib.mn_last_kernel().decode()
+    assert torch.equal(ya, yb), "the two kernels must agree bit for bit"
+    for i in range(warmup + iters):
+        for flag, y in ((0, ya), (0x100, yb)):
+            t = timed(lambda _: run(flag, y), None)
+            if i >= warmup:
+                times[flag].append(t)
+    q = lambda v: dict(median=statistics.median(v), min=min(v), p25=statistics.quantiles(v, n=4)[0], p75=statistics.quantiles(v, n=4)[2])
+    return dict(geometry="%d -> %d, %dx%d on %d x %d, batch %d" % (cin, cout, k, k, hw, hw, bs), plan_kernel=names[0], plan_ms=q(times[0]), alt_kernel=names[0x100],
+                alt_ms=q(times[0x100]), alt_over_plan=statistics.median(times[0x100]) / statistics.median(times[0]))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="nin_gc", choices=["nin_gc", "nin"])
     ap.add_argument("--batches", default="256,1024")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--W", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join("profiles", "bits_inference.json"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join("profiles", "bits_inference.json" if args.model == "nin_gc" else "bits_inference_%s.json" % args.model)
     from micronet.compression.quantization.wbwtab import quantize as Q
     from micronet_amd import _lib, inference
     from micronet_amd.train import build_model, synth_batch
     torch.manual_seed(0)
-    I = Q.prepare(build_model("nin_gc"), inplace=True, A=2, W=args.W, quant_inference=True).cuda()
+    I = Q.prepare(build_model(args.model), inplace=True, A=2, W=args.W, quant_inference=True).cuda()
     inference.prequantize_weights(I)
     F = inference.wbwtab_model_bn_fuse(I, W=args.W).eval()
     B = inference.wbwtab_compile_bits(F)
     lib = _lib.get_lib()
-    res = dict(model="nin_gc", W=args.W, warmup=args.warmup, iters=args.iters, device=torch.cuda.get_device_name(0), report=B.report,
+    res = dict(model=args.model, W=args.W, warmup=args.warmup, iters=args.iters, device=torch.cuda.get_device_name(0), report=B.report,
                designed_bytes_per_image=designed_bytes_per_image(B), batches={})
     with torch.no_grad():
         for bs in [int(v) for v in args.batches.split(",")]:
@@ -90,6 +123,11 @@ def main():
                 F_img_s=bs / med_f * 1e3, B_img_s=bs / med_b * 1e3, B_over_F=med_f / med_b,
                 B_kernels=kb, F_kernels=kf, B_kernel_ms_total=sum(v["ms"] for v in kb.values()), F_kernel_ms_total=sum(v["ms"] for v in kf.values()),
                 B_first_block_kernel_ms=first_ms)
+            if args.model == "nin":
+                res["batches"][str(bs)]["dense_blocks"] = [kernel_ab(lib, _lib, bs, 96, 192, 5, 16, args.iters, args.warmup),
+                                                           kernel_ab(lib, _lib, bs, 192, 192, 3, 8, args.iters, args.warmup)]
+                for d in res["batches"][str(bs)]["dense_blocks"]:
+                    print("  %s: %s %.3f ms, %s %.3f ms" % (d["geometry"], d["plan_kernel"], d["plan_ms"]["median"], d["alt_kernel"], d["alt_ms"]["median"]), flush=True)
             print("batch %d: F %.3f ms (min %.3f)  B %.3f ms (min %.3f)  B/F speed %.2fx" % (bs, med_f, min(tf), med_b, min(tb), med_f / med_b), flush=True)
     os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
     with open(args.out, "w") as f:
