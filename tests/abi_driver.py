@@ -91,6 +91,13 @@ class Backend:
             return b.ctypes.data_as(C.c_void_p)
         return C.c_void_p(b.data_ptr())
 
+    def ptr_at(self, b, elem):
+        """Address of element ``elem`` of a 4-byte-element buffer: with elem % 4 != 0 a view that is not 16-byte aligned, which sends the streaming kernels
+        down their scalar path (both back ends hand out buffers aligned to at least 16 bytes)."""
+        base = self.ptr(b).value
+        assert base % 16 == 0
+        return C.c_void_p(base + 4 * elem)
+
     def call(self, name, *args):
         rc = getattr(self.lib, name)(*args)
         if rc != 0:
