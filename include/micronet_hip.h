@@ -576,6 +576,19 @@ int mn_conv2d_bwd_data_bnh_pool(const mn_conv_geom* g, const mn_wq* wq, const fl
                                 const float* sums, int training, const float* w, float* dx, void* ws, int64_t ws_bytes, mn_stream_t stream);
 int mn_conv2d_bwd_weight_bnh_pool(const mn_conv_geom* g, const float* dpool, const uint8_t* h, const int8_t* own, const float* chan, const float* sums,
                                   int training, const int8_t* x, float* dw, float* dbias, void* ws, int64_t ws_bytes, mn_stream_t stream);
+/* The grouped 3x3 block's backward-data when its input came through a 2x2 / stride-2 max-pool from a POINTWISE BatchNorm+sign block (models/nin_gc.py:88,119: layers
+ * 3 | 4 and 6 | 7): dx [N][C][H][W] is that block's pooled incoming gradient, and the kernel holds every value of it at the moment it is stored.  The launch routes each
+ * value to the first +1 of its window (the upstream codes derived from the stash bytes up_h [N][C][up_H][up_W], up_H = 2 H, up_W = 2 W, by the byte threshold of the
+ * sign pass: bit-equal to the stored codes), applies the clip-STE mask of up_chan [8][C] and leaves sum dz, sum dz zhat per channel as up_part [C][splits][2] doubles
+ * (fixed order, no atomics) -- mn_bnh_bwd_sums(own != NULL)'s pass is replaced by mn_bnh_bwd_sums_finish_pool.  dx is bit-identical to mn_conv2d_bwd_data_bnh.
+ * splits: mn_conv2d_bwd_data_bnh_uppool_splits (0: not covered).  Refused (MN_ENOTSUP): up_H != 2 H or up_W != 2 W, up_chan_rows != 8, up_h not 4-byte aligned. */
+int mn_conv2d_bwd_data_bnh_uppool_splits(const mn_conv_geom* g, const mn_wq* wq);
+int mn_conv2d_bwd_data_bnh_uppool(const mn_conv_geom* g, const mn_wq* wq, const float* da, const uint8_t* h, const float* chan, const float* sums,
+                                  int training, const float* w, float* dx, void* ws, int64_t ws_bytes, const uint8_t* up_h, int64_t up_H, int64_t up_W,
+                                  const float* up_chan, int32_t up_chan_rows, double* up_part, mn_stream_t stream);
+/* the finish of those partials (N, C, H, W: the upstream block's own full size): k_bns_final_bwd, as mn_bnh_bwd_sums_final */
+int mn_bnh_bwd_sums_finish_pool(const double* part, int32_t splits, int64_t N, int64_t C, int64_t H, int64_t W, float* dgamma, float* dbeta, float* sums,
+                                mn_stream_t stream);
 /* BOTH gradients of such a block in ONE launch (round 6): backward-data and backward-weight of the pointwise convolution read (da, h) once and rebuild dy once
  * (wbwtab/quantize.py:11-36, 181-195 + autograd's conv backward; the two calls above read them once each).  own == NULL: da = d loss / d a [N][O][H][W]
  * (16-byte aligned); own != NULL: da is the pooled gradient as in the *_pool calls.  Covers groups of 128 -> 128 channels with H*W a multiple of 32 (every

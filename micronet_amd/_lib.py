@@ -122,6 +122,9 @@ PROTOTYPES = {
     "mn_conv2d_bnh_supported": (_I, [_G, _W]),
     "mn_conv2d_bwd_data_bnh": (_I, [_G, _W, _P, _P, _P, _P, _I, _P, _P, _P, _L, _P]),
     "mn_conv2d_bwd_weight_bnh": (_I, [_G, _P, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P]),
+    "mn_conv2d_bwd_data_bnh_uppool_splits": (_I, [_G, _W]),
+    "mn_conv2d_bwd_data_bnh_uppool": (_I, [_G, _W, _P, _P, _P, _P, _I, _P, _P, _P, _L, _P, _L, _L, _P, _I, _P, _P]),
+    "mn_bnh_bwd_sums_finish_pool": (_I, [_P, _I, _L, _L, _L, _L, _P, _P, _P, _P]),
     "mn_conv2d_bwd_bnh_supported": (_I, [_G, _W, _I]),
     "mn_conv2d_bwd_bnh_ws_bytes": (_L, [_G]),
     "mn_conv2d_bwd_bnh": (_I, [_G, _W, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _L, _P]),

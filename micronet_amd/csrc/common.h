@@ -81,6 +81,16 @@ __device__ __forceinline__ int mn_uniform(int v) { return v; }
 #else
 __device__ __forceinline__ int mn_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 #endif
+// the value that lane I of this lane's quad (lanes 4q .. 4q + 3) holds: a DPP quad_perm broadcast.  Every lane of the wave takes part (no divergent caller).
+template <int I>
+__device__ __forceinline__ float mn_quad_bcast(float v, int lane) {
+#ifdef MN_EMULATION
+    return __shfl(v, (lane & ~3) | I, 64);
+#else
+    (void)lane;
+    return mn_u2f((unsigned)__builtin_amdgcn_update_dpp(0, (int)mn_f2u(v), I * 0x55, 0xf, 0xf, false));
+#endif
+}
 // scheduling fence: no instruction may be moved across it (keeps software-pipelined loads from being hoisted en bloc)
 #ifdef MN_EMULATION
 #define MN_SCHED_FENCE() do { } while (0)

@@ -821,6 +821,24 @@ extern "C" int mn_conv2d_bwd_data_bnh(const mn_conv_geom* g, const mn_wq* wq, co
     if (k3s_bnh_supported(g, wq)) return k3s_bwd_data_bnh(g, wq, da, h, chan, sums, training, w, dx, (hipStream_t)stream);      // grouped 3x3 block: staged-image kernel
     return pwd_bwd_data_bnh(g, wq, da, h, chan, sums, training, w, dx, ws, ws_bytes, (hipStream_t)stream);
 }
+// the grouped 3x3 block behind a 2x2 / stride-2 max-pool behind a pointwise BatchNorm+sign block: dx is that block's pooled incoming gradient, and the launch leaves
+// the sums of its BatchNorm backward (part [C][splits][2] doubles) -- mn_bnh_bwd_sums(own != NULL)'s pass over (pooled gradient, own codes, stash) is not needed
+extern "C" int mn_conv2d_bwd_data_bnh_uppool_splits(const mn_conv_geom* g, const mn_wq* wq) {
+    if (check_geom(g, "mn_conv2d_bwd_data_bnh_uppool_splits") != MN_OK) return 0;
+    return k3s_bnh_supported(g, wq) ? k3s_uppool_splits(g, wq) : 0;
+}
+extern "C" int mn_conv2d_bwd_data_bnh_uppool(const mn_conv_geom* g, const mn_wq* wq, const float* da, const uint8_t* h, const float* chan, const float* sums,
+                                             int training, const float* w, float* dx, void* ws, int64_t ws_bytes, const uint8_t* up_h, int64_t up_H, int64_t up_W,
+                                             const float* up_chan, int32_t up_chan_rows, double* up_part, mn_stream_t stream) {
+    int rc = check_geom(g, "mn_conv2d_bwd_data_bnh_uppool");
+    if (rc) return rc;
+    (void)ws; (void)ws_bytes;
+    if (!da || !h || !chan || !sums || !w || !dx || !up_h || !up_chan || !up_part) MN_FAIL(MN_EINVAL, "mn_conv2d_bwd_data_bnh_uppool: null tensor");
+    if (up_H != 2 * (int64_t)g->H || up_W != 2 * (int64_t)g->W) MN_FAIL(MN_ENOTSUP, "mn_conv2d_bwd_data_bnh_uppool: the upstream plane is not twice the input plane");
+    if (up_chan_rows != 8) MN_FAIL(MN_ENOTSUP, "mn_conv2d_bwd_data_bnh_uppool: the upstream block is not pointwise (8 rows of constants)");
+    if (!mn_conv2d_bwd_data_bnh_uppool_splits(g, wq)) MN_FAIL(MN_ENOTSUP, "mn_conv2d_bwd_data_bnh_uppool: geometry not covered");
+    return k3s_bwd_data_bnh_uppool(g, wq, da, h, chan, sums, training, w, dx, up_h, up_chan, up_part, (hipStream_t)stream);
+}
 extern "C" int mn_conv2d_bwd_weight_bnh(const mn_conv_geom* g, const float* da, const uint8_t* h, const float* chan, const float* sums, int training,
                                         const int8_t* x, float* dw, float* dbias, void* ws, int64_t ws_bytes, mn_stream_t stream) {
     int rc = check_geom(g, "mn_conv2d_bwd_weight_bnh");

@@ -56,6 +56,10 @@ int64_t pwd_ws_bytes(const mn_conv_geom* g);
 int k3s_bnh_supported(const mn_conv_geom* g, const mn_wq* wq);
 int k3s_bwd_data_bnh(const mn_conv_geom* g, const mn_wq* wq, const float* da, const uint8_t* h, const float* chan, const float* sums, int training, const float* w,
                      float* dx, hipStream_t s);
+// ... whose input came through a 2x2 max-pool from a pointwise BatchNorm+sign block: the sums of that block's BatchNorm backward as a by-product (k_k3s_dgrad<1, 1>)
+int k3s_uppool_splits(const mn_conv_geom* g, const mn_wq* wq);
+int k3s_bwd_data_bnh_uppool(const mn_conv_geom* g, const mn_wq* wq, const float* da, const uint8_t* h, const float* chan, const float* sums, int training,
+                            const float* w, float* dx, const uint8_t* uh, const float* uchan, double* part, hipStream_t s);
 int k3s_bwd_weight_bnh(const mn_conv_geom* g, const float* da, const uint8_t* h, const float* chan, const float* sums, int training, const int8_t* x, float* dw,
                        float* dbias, void* ws, int64_t ws_bytes, hipStream_t s);
 int pwd_bwd_data_bnh(const mn_conv_geom* g, const mn_wq* wq, const float* da, const uint8_t* h, const float* chan, const float* sums, int training,

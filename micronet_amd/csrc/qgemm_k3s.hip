@@ -443,15 +443,38 @@ struct K3dParams {
     int NI, SP, HW, IS, TS, nstages, WP;      // images per stage, pixels per stage, slots per image, bytes per term plane, W + 2
     FastDiv fd_hw4, fd_w4, fd_w;
     ChanMap out_map;
+    const unsigned char* uh;  // UP: the byte stash of the pointwise BatchNorm+sign block in front of the 2x2 max-pool, [N][C][2H][2W]
+    const float* uchan;       // UP: its [8][C] channel constants
+    double* part;             // UP: [C][Zb][2] partial sums {sum dz, sum dz zhat} of that block's BatchNorm backward (k_bns_final_bwd's layout, S = Zb)
 };
 
+// UP: the per-channel constants of the upstream block for the 16 input channels of this block's channel tile, K3U_CS floats per channel in LDS:
+//   [0] t  [1] inv  (the block's output code is +1  <=>  (h >= t) != inv: h_sign_stream_pw's byte threshold, qgemm_sign.hip)  [2] nnz  [3] flip  [4] L  [5] U  [6] A  [7] B
+#define K3U_CS 8
+__device__ __forceinline__ void k3u_fill(float* tab, const float* __restrict__ uchan, int C, int cp) {
+    const float T = uchan[cp], fl = uchan[C + cp], nnz = uchan[7 * C + cp];
+    float tf, inv;
+    if (fl > 0.f) { tf = ceilf((T + nnz) * 0.5f); inv = 0.f; }
+    else { tf = floorf((nnz - T) * 0.5f) + 1.f; inv = 1.f; }
+    tab[0] = fminf(fmaxf(tf, 0.f), 256.f); tab[1] = inv; tab[2] = nnz; tab[3] = fl;
+    tab[4] = uchan[2 * C + cp]; tab[5] = uchan[3 * C + cp]; tab[6] = uchan[4 * C + cp]; tab[7] = uchan[5 * C + cp];
+}
+
 // BNH 1: gy is da of the BatchNorm+sign block behind the convolution (ternary / binary weights); dy is formed in commit() (see K3Bnh above).
-template <int BNH>
+// UP 1 (with BNH 1): the convolution's input came through a 2x2 / stride-2 max-pool from a pointwise BatchNorm+sign block, so dx IS that block's pooled incoming
+// gradient: every stored value is routed to its window's first +1 (the codes derived from the stash bytes: one byte threshold per channel), masked by the
+// clip-STE interval and summed per channel -- k_bnh_partial_pool's arithmetic, same operation order per element -- while it sits in the accumulator.  The four
+// stash bytes of a window are fetched as two 2-byte global loads at the top of a tile (in flight during the MFMAs).  The fp32 partials are k_bnh_partial_pool's own -- four neighbouring pooled pixels
+// of a row, left to right, formed across a lane quad -- so that the fp64 sums of the two routes add the same addends (only the fp64 order differs, far below the
+// final fp32 rounding: a step computes the same bits with the hand-over on and off).  The fp64 sums live in registers and are reduced in fixed order at the end:
+// the four quads of a channel row, then the four waves through LDS; one (s1, s2) pair per (channel, z).
+template <int BNH, int UP = 0>
 __global__ __launch_bounds__(256, 2) void k_k3s_dgrad(const K3dParams p) {
     HIP_DYNAMIC_SHARED(float, smem)
     unsigned char* lds = reinterpret_cast<unsigned char*>(smem);
     float* alpha = reinterpret_cast<float*>(lds + 3 * p.TS);          // [32]
     float* btab = alpha + 32;                                         // BNH: [32][K3B_CS]
+    float* utab = btab + 32 * K3B_CS;                                 // UP: [16][K3U_CS]
     const int tid = threadIdx.x, lane = tid & 63, wave = mn_uniform(tid >> 6), j = lane & 15, kg = lane >> 4;
     uint32_t b = blockIdx.x;
     const int z = b % p.Zb; b /= p.Zb;
@@ -494,6 +517,20 @@ __global__ __launch_bounds__(256, 2) void k_k3s_dgrad(const K3dParams p) {
     for (int i = tid; i < (3 * p.TS) / 16; i += 256) *reinterpret_cast<u32x4*>(lds + 16 * i) = u32x4{0u, 0u, 0u, 0u};
     if ((tid & 7) == 0) alpha[tid >> 3] = my_alpha;
     if (BNH && tid < 32) k3b_fill(btab, p.bn, p.O, g * p.Mg, p.Mg, tid);
+    uint32_t u_coff[UP ? 4 : 1];                                       // UP: element offset of this lane's four channels' first upstream plane
+    double u_s1[UP ? 4 : 1], u_s2[UP ? 4 : 1];
+    if (UP) {
+        if (tid >= 64 && tid < 80) {
+            const int c = cb * 16 + (tid - 64);
+            k3u_fill(utab + (tid - 64) * K3U_CS, p.uchan, p.C, chan_phys(p.out_map, g * p.Cg + (c < p.Cg ? c : p.Cg - 1)));
+        }
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const int c = cb * 16 + 4 * kg + rr;
+            u_coff[rr] = (uint32_t)chan_phys(p.out_map, g * p.Cg + (c < p.Cg ? c : p.Cg - 1)) * (uint32_t)(4 * p.HW);
+            u_s1[rr] = 0.0; u_s2[rr] = 0.0;
+        }
+    }
     // staging roles: pair u of this thread = (chunk, sr): rows m = sr + 8 i, pixels 4 chunk .. of the stage
     const int cps = p.SP >> 2;                                         // chunks per stage
     const int npair = (p.SP * 2) >> 8;                                 // pairs per thread (1 or 2)
@@ -583,6 +620,7 @@ __global__ __launch_bounds__(256, 2) void k_k3s_dgrad(const K3dParams p) {
                 for (int t = 0; t < 3; ++t) acc[hh][t] = f32x4{0.f, 0.f, 0.f, 0.f};
             int sb[2];                                                 // byte offset of pixel (hh, j)'s own slot + this lane's k chunk
             int opix[2];
+            uint32_t uw[UP ? 2 : 1][UP ? 4 : 1][2];                    // UP: the two stash bytes of window row 0 / 1 of pixel (hh, j), channel rr
 #pragma unroll
             for (int hh = 0; hh < 2; ++hh) {
                 const int sp = tile * 32 + hh * 16 + j;                // pixel of the stage
@@ -592,6 +630,17 @@ __global__ __launch_bounds__(256, 2) void k_k3s_dgrad(const K3dParams p) {
                 const int col = pp - (int)row * p.W;
                 sb[hh] = ((int)img * p.IS + ((int)row + 1) * p.WP + col + 1) * K3D_RS + 16 * kg;
                 opix[hh] = sp;
+                if (UP) {                                              // issued here, consumed in the store loop behind the MFMAs; images past N are clamped (never summed)
+                    int n = st * p.NI + (int)img;
+                    n = n < p.N ? n : p.N - 1;
+                    const uint32_t base = (uint32_t)n * (uint32_t)p.C * (uint32_t)(4 * p.HW) + (uint32_t)(4 * (int)row * p.W + 2 * col);
+#pragma unroll
+                    for (int rr = 0; rr < 4; ++rr) {
+                        const unsigned char* src = p.uh + (base + u_coff[rr]);
+                        uw[hh][rr][0] = *reinterpret_cast<const unsigned short*>(src);
+                        uw[hh][rr][1] = *reinterpret_cast<const unsigned short*>(src + 2 * p.W);
+                    }
+                }
             }
 #pragma unroll
             for (int r = 0; r < 3; ++r)
@@ -615,16 +664,61 @@ __global__ __launch_bounds__(256, 2) void k_k3s_dgrad(const K3dParams p) {
 #pragma unroll
                 for (int rr = 0; rr < 4; ++rr) {
                     const int c = cb * 16 + 4 * kg + rr;
-                    if (n < p.N && c < p.Cg)
-                        p.dx[((int64_t)n * p.C + chan_phys(p.out_map, g * p.Cg + c)) * p.HW + pp] = (acc[hh][0][rr] + acc[hh][1][rr]) + acc[hh][2][rr];
+                    float dz = 0.f, dzz = 0.f;                          // UP: this pixel's terms of the two sums (0 where nothing is stored)
+                    if (n < p.N && c < p.Cg) {
+                        const float v = (acc[hh][0][rr] + acc[hh][1][rr]) + acc[hh][2][rr];
+                        p.dx[((int64_t)n * p.C + chan_phys(p.out_map, g * p.Cg + c)) * p.HW + pp] = v;
+                        if (UP) {
+                            const float* ut = utab + (4 * kg + rr) * K3U_CS;
+                            const float4 ca = *reinterpret_cast<const float4*>(ut), cc = *reinterpret_cast<const float4*>(ut + 4);
+                            const uint32_t w0 = uw[hh][rr][0], w1 = uw[hh][rr][1];
+                            const float h00 = (float)(w0 & 0xffu), h01 = (float)(w0 >> 8), h10 = (float)(w1 & 0xffu), h11 = (float)(w1 >> 8);
+                            const bool inv = ca.y != 0.f;
+                            const bool p00 = (h00 >= ca.x) != inv, p01 = (h01 >= ca.x) != inv, p10 = (h10 >= ca.x) != inv, p11 = (h11 >= ca.x) != inv;
+                            // first maximum of the window in row-major order (ATen): the first +1, else element 0
+                            const float hv = p00 ? h00 : (p01 ? h01 : (p10 ? h10 : (p11 ? h11 : h00)));
+                            const float ac = 2.f * hv - ca.z;
+                            const float u = ac * ca.w;
+                            dz = (u >= cc.x && u <= cc.y) ? v : 0.f;
+                            dzz = dz * fmaf(ac, cc.z, cc.w);
+                        }
+                    }
+                    if (UP) {
+                        // the fp32 partial of k_bnh_partial_pool: four neighbouring pooled pixels of a row, added left to right -- the four lanes of a quad (W % 4 == 0,
+                        // and n, c are the same across a quad).  Every lane of the quad holds it; the end of the kernel counts each quad once.
+                        const float t1 = ((mn_quad_bcast<0>(dz, lane) + mn_quad_bcast<1>(dz, lane)) + mn_quad_bcast<2>(dz, lane)) + mn_quad_bcast<3>(dz, lane);
+                        const float t2 = ((mn_quad_bcast<0>(dzz, lane) + mn_quad_bcast<1>(dzz, lane)) + mn_quad_bcast<2>(dzz, lane)) + mn_quad_bcast<3>(dzz, lane);
+                        u_s1[rr] += (double)t1; u_s2[rr] += (double)t2;
+                    }
                 }
+            }
+        }
+    }
+    if (UP) {
+        // fixed-order reduction: the four quads of a channel row's 16 pixel lanes (butterfly; the lanes of a quad hold the same sum), then the four waves through LDS
+        // in wave order (the image region is free now)
+        __syncthreads();
+        double* red = reinterpret_cast<double*>(lds);                  // [4 waves][16 channels][2]
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            double a1 = u_s1[rr], a2 = u_s2[rr];
+#pragma unroll
+            for (int o = 4; o < 16; o <<= 1) { a1 += __shfl_xor(a1, o, 64); a2 += __shfl_xor(a2, o, 64); }
+            if (j == 0) { red[(wave * 16 + 4 * kg + rr) * 2] = a1; red[(wave * 16 + 4 * kg + rr) * 2 + 1] = a2; }
+        }
+        __syncthreads();
+        if (tid < 32) {
+            const int ch = tid >> 1, k = tid & 1, c = cb * 16 + ch;
+            if (c < p.Cg) {
+                const double s = ((red[ch * 2 + k] + red[(16 + ch) * 2 + k]) + red[(32 + ch) * 2 + k]) + red[(48 + ch) * 2 + k];
+                p.part[((int64_t)chan_phys(p.out_map, g * p.Cg + c) * p.Zb + z) * 2 + k] = s;
             }
         }
     }
 }
 
 struct K3dPlan { K3dParams p; int grid; size_t lds; };
-static int plan_k3d(const mn_conv_geom* g, const mn_wq* wq, K3dPlan* pl, int bnh = 0) {
+static int plan_k3d(const mn_conv_geom* g, const mn_wq* wq, K3dPlan* pl, int bnh = 0, int up = 0) {
     if (!wq || !(wq->mode == MN_WQ_TERNARY || (wq->mode == MN_WQ_DOREFA && wq->bits >= 2 && wq->bits <= 8))) return 0;
     if (g->KH != 3 || g->KW != 3 || g->stride_h != 1 || g->stride_w != 1 || g->pad_h != 1 || g->pad_w != 1 || g->dil_h != 1 || g->dil_w != 1) return 0;
     if (g->in_shuffle > 1 && g->C % g->in_shuffle) return 0;
@@ -639,7 +733,7 @@ static int plan_k3d(const mn_conv_geom* g, const mn_wq* wq, K3dPlan* pl, int bnh
     p.N = g->N; p.C = g->C; p.H = g->H; p.W = g->W; p.O = g->O; p.Cg = Cg; p.Mg = Mg; p.G = g->groups;
     p.NI = NI; p.SP = SP; p.HW = HW; p.WP = g->W + 2; p.IS = (g->H + 2) * (g->W + 2);
     p.TS = (NI * p.IS * K3D_RS + 255) / 256 * 256;
-    pl->lds = (size_t)3 * p.TS + 128 + (bnh ? (size_t)32 * K3B_CS * 4 : 0);
+    pl->lds = (size_t)3 * p.TS + 128 + (bnh ? (size_t)32 * K3B_CS * 4 : 0) + (up ? (size_t)16 * K3U_CS * 4 : 0);
     if (pl->lds < (size_t)Mg * Cg * 9 * 4) pl->lds = (size_t)Mg * Cg * 9 * 4;          // the prologue's weight image
     if (pl->lds > 80 * 1024) return 0;
     p.nstages = (g->N + NI - 1) / NI;
@@ -664,11 +758,12 @@ int k3s_bwd_data(const mn_conv_geom* g, const mn_wq* wq, const float* gy, const 
     K3dParams& p = pl.p;
     p.gy = gy; p.w = w; p.dx = dx; p.wn = wq->mode == MN_WQ_DOREFA ? (float)((1ll << wq->bits) - 1) : 0.f;
     p.bn.h = nullptr; p.bn.chan = nullptr; p.bn.sums = nullptr; p.bn.training = 0; p.bn.n_f = 1.f;
+    p.uh = nullptr; p.uchan = nullptr; p.part = nullptr;
     mn_set_last_kernel("k_k3s_dgrad");
     { const double nx = (double)g->N * g->C * g->H * g->W, ny = (double)g->N * g->O * g->H * g->W; mn_prof_bytes(4.0 * ny + 4.0 * nx); }
     mn_prof_begin(s);
-    raise_lds_limit((const void*)k_k3s_dgrad<0>, pl.lds);
-    hipLaunchKernelGGL(k_k3s_dgrad<0>, dim3(pl.grid), dim3(256), pl.lds, s, p);
+    raise_lds_limit((const void*)k_k3s_dgrad<0, 0>, pl.lds);
+    hipLaunchKernelGGL((k_k3s_dgrad<0, 0>), dim3(pl.grid), dim3(256), pl.lds, s, p);
     mn_prof_end(s);
     MN_CHECK_LAUNCH("mn_conv2d_bwd_data(3x3 ternary)");
     return MN_OK;
@@ -686,13 +781,41 @@ int k3s_bwd_data_bnh(const mn_conv_geom* g, const mn_wq* wq, const float* da, co
     K3dParams& p = pl.p;
     p.gy = da; p.w = w; p.dx = dx; p.wn = 0.f;
     p.bn.h = h; p.bn.chan = chan; p.bn.sums = sums; p.bn.training = training; p.bn.n_f = (float)g->N * (float)(g->H * g->W);
+    p.uh = nullptr; p.uchan = nullptr; p.part = nullptr;
     mn_set_last_kernel("k_k3s_dgrad<1>");
     { const double nx = (double)g->N * g->C * g->H * g->W, ny = (double)g->N * g->O * g->H * g->W; mn_prof_bytes(5.0 * ny + 4.0 * nx); }
     mn_prof_begin(s);
-    raise_lds_limit((const void*)k_k3s_dgrad<1>, pl.lds);
-    hipLaunchKernelGGL(k_k3s_dgrad<1>, dim3(pl.grid), dim3(256), pl.lds, s, p);
+    raise_lds_limit((const void*)k_k3s_dgrad<1, 0>, pl.lds);
+    hipLaunchKernelGGL((k_k3s_dgrad<1, 0>), dim3(pl.grid), dim3(256), pl.lds, s, p);
     mn_prof_end(s);
     MN_CHECK_LAUNCH("mn_conv2d_bwd_data_bnh(3x3 ternary)");
+    return MN_OK;
+}
+// ... whose input came through a 2x2 / stride-2 max-pool from a pointwise BatchNorm+sign block (uh [N][C][2H][2W], uchan [8][C]): dx is that block's pooled incoming
+// gradient, and the launch leaves the sums of its BatchNorm backward as part [C][splits][2] doubles (k_k3s_dgrad<1, 1>).  splits = 0: not covered.
+int k3s_uppool_splits(const mn_conv_geom* g, const mn_wq* wq) {
+    K3dPlan pl;
+    if (!wq || wq->mode != MN_WQ_TERNARY || g->H < 2 || g->W % 4 || !plan_k3d(g, wq, &pl, 1, 1)) return 0;          // W % 4: a lane quad is four pixels of one row
+    if ((int64_t)g->N * g->C * g->H * g->W * 4 >= ((int64_t)1 << 31)) return 0;          // 32-bit element offsets into the upstream stash
+    return pl.p.Zb;
+}
+int k3s_bwd_data_bnh_uppool(const mn_conv_geom* g, const mn_wq* wq, const float* da, const uint8_t* h, const float* chan, const float* sums, int training,
+                            const float* w, float* dx, const uint8_t* uh, const float* uchan, double* part, hipStream_t s) {
+    K3dPlan pl;
+    if (!k3s_uppool_splits(g, wq) || !plan_k3d(g, wq, &pl, 1, 1) || !aligned16(da) || !h || (((uintptr_t)h) & 3) || !chan || !sums || !w || !dx || !uh ||
+        (((uintptr_t)uh) & 3) || !uchan || !part || (((uintptr_t)part) & 7))
+        MN_FAIL(MN_ENOTSUP, "mn_conv2d_bwd_data_bnh_uppool: geometry / alignment not covered");
+    K3dParams& p = pl.p;
+    p.gy = da; p.w = w; p.dx = dx; p.wn = 0.f;
+    p.bn.h = h; p.bn.chan = chan; p.bn.sums = sums; p.bn.training = training; p.bn.n_f = (float)g->N * (float)(g->H * g->W);
+    p.uh = uh; p.uchan = uchan; p.part = part;
+    mn_set_last_kernel("k_k3s_dgrad<1, 1>");
+    { const double nx = (double)g->N * g->C * g->H * g->W, ny = (double)g->N * g->O * g->H * g->W; mn_prof_bytes(5.0 * ny + 8.0 * nx); }
+    mn_prof_begin(s);
+    raise_lds_limit((const void*)k_k3s_dgrad<1, 1>, pl.lds);
+    hipLaunchKernelGGL((k_k3s_dgrad<1, 1>), dim3(pl.grid), dim3(256), pl.lds, s, p);
+    mn_prof_end(s);
+    MN_CHECK_LAUNCH("mn_conv2d_bwd_data_bnh_uppool");
     return MN_OK;
 }
 

@@ -1923,7 +1923,11 @@ class SignMaxPool2x2(Function):
             with torch.cuda.device_of(codes):
                 _call("mn_maxpool2x2_sign8_fwd", _p(codes), N * Cc, H, W, _p(out), _s())
         ctx.save_for_backward(codes)
-        return SignTensor(out)
+        res = SignTensor(out)
+        rec = getattr(a, "_mn_up_pool", None)
+        if rec is not None and out is getattr(a, "_mn_pooled", None):          # the grouped 3x3 block behind this pool may form the producing block's sums (UpSums kind 4)
+            res._mn_up = rec
+        return res
 
     @staticmethod
     def backward(ctx, g):
@@ -1984,6 +1988,8 @@ class UpSums:
     __slots__ = ("h", "chan", "k", "ready", "kind")
 
     def __init__(self, h, chan, k, kind=1):          # kind 1: byte stash of a wbwtab block (3: behind a 3x3 conv -- nnz per border class); 2: 16-bit stash of a k-bit (DoReFa) block (its `ready[0]` is the raw dq of a QGrad)
+        # kind 4: byte stash of a pointwise wbwtab block whose output goes through a 2x2 max-pool; the consumer is the grouped 3x3 block BEHIND the pool (k_k3s_dgrad<1, 1>),
+        # `ready[0]` is its dx = this block's POOLED incoming gradient
         self.h, self.chan, self.k, self.ready, self.kind = h, chan, int(k), None, kind
 
 
@@ -2130,8 +2136,19 @@ class QConv2d(Function):
                             _call("mn_conv2d_bwd_data_bnh_pool", C.byref(g), _ref(wd), _p(r["da"]), _p(r["h"]), _p(r["own"]), _p(r["chan"]), _p(r["sums"]), r["training"],
                                   _p(wq), _p(dx), _p(ws), nb, _s())
                         else:
-                            _call("mn_conv2d_bwd_data_bnh", C.byref(g), _ref(wd), _p(r["da"]), _p(r["h"]), _p(r["chan"]), _p(r["sums"]), r["training"], _p(wq),
-                                  _p(dx), _p(ws), nb, _s())
+                            up = getattr(ctx, "up_rec", None)
+                            splits = 0
+                            if up is not None and up.kind == 4 and UP_SUMS_FOLD and tuple(up.h.shape) == (x.shape[0], x.shape[1], 2 * x.shape[2], 2 * x.shape[3]) and \
+                                    up.h.is_contiguous() and up.h.data_ptr() % 4 == 0 and r["da"].data_ptr() % 16 == 0 and r["h"].data_ptr() % 4 == 0:
+                                splits = int(_lib_().mn_conv2d_bwd_data_bnh_uppool_splits(C.byref(g), _ref(wd)))
+                            if splits > 0:          # ... and the sums of the BatchNorm backward of the pooled pointwise block in front (this dx is its pooled d a)
+                                part = torch.empty(x.shape[1] * splits * 2, dtype=torch.float64, device=x.device)
+                                _call("mn_conv2d_bwd_data_bnh_uppool", C.byref(g), _ref(wd), _p(r["da"]), _p(r["h"]), _p(r["chan"]), _p(r["sums"]), r["training"], _p(wq),
+                                      _p(dx), _p(ws), nb, _p(up.h), up.h.shape[2], up.h.shape[3], _p(up.chan), up.chan.shape[0], _p(part), _s())
+                                up.ready = (dx, dx._version, part, splits)
+                            else:
+                                _call("mn_conv2d_bwd_data_bnh", C.byref(g), _ref(wd), _p(r["da"]), _p(r["h"]), _p(r["chan"]), _p(r["sums"]), r["training"], _p(wq),
+                                      _p(dx), _p(ws), nb, _s())
                 if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
                     dw = torch.empty_like(wq)
                     db = torch.empty(g.O, dtype=torch.float32, device=x.device) if has_bias else None
@@ -2299,6 +2316,9 @@ class ConvBNSign(Function):
         ctx.up_rec = None
         if chan.shape[0] in (8, 17) and UP_SUMS_FOLD:          # (8: pointwise block, one nnz per channel; 17: 3x3 block, nnz per border class) -- the next block's
             ctx.up_rec = out._mn_up = UpSums(h, chan, wq.shape[1] * wq.shape[2] * wq.shape[3], kind=1 if chan.shape[0] == 8 else 3)          # backward may form this block's sums
+        ctx.up_rec_pool = None
+        if ap is not None and chan.shape[0] == 8 and UP_SUMS_FOLD:          # pooled pointwise block: the record travels with the pooled codes (SignMaxPool2x2.forward)
+            ctx.up_rec_pool = out._mn_up_pool = UpSums(h, chan, wq.shape[1] * wq.shape[2] * wq.shape[3], kind=4)
         return out
 
     @staticmethod
@@ -2318,8 +2338,16 @@ class ConvBNSign(Function):
         ready = None
         if rec is not None:
             ready, rec.ready = rec.ready, None
+        recp = getattr(ctx, "up_rec_pool", None)
+        readyp = None
+        if recp is not None:
+            readyp, recp.ready = recp.ready, None
         with torch.cuda.device_of(h):
-            if ready is not None and not pooled and type(da) is torch.Tensor and da.data_ptr() == ready[0].data_ptr() and tuple(da.shape) == tuple(ready[0].shape) and \
+            if readyp is not None and pooled and recp.kind == 4 and UP_SUMS_FOLD and type(grad) is torch.Tensor and grad.data_ptr() == readyp[0].data_ptr() and \
+                    tuple(grad.shape) == tuple(readyp[0].shape) and grad._version == readyp[1] and grad.is_contiguous():
+                # the producer of the pooled d a (the grouped 3x3 block behind the pool) already routed, masked and summed it per channel: only the finish is left
+                _call("mn_bnh_bwd_sums_finish_pool", _p(readyp[2]), readyp[3], N, Cc, H, W, _p(dgamma), _p(dbeta), _p(sums), _s())
+            elif ready is not None and not pooled and type(da) is torch.Tensor and da.data_ptr() == ready[0].data_ptr() and tuple(da.shape) == tuple(ready[0].shape) and \
                     da._version == ready[1] and da.is_contiguous():
                 # the producer of d a (the next block's one-launch backward) already summed dz and dz zhat per channel: only the fixed-order finish is left
                 _call("mn_bnh_bwd_sums_final", _p(ready[2]), ready[3], N, Cc, H, W, _p(dgamma), _p(dbeta), _p(sums), _s())
