@@ -870,6 +870,15 @@ int mn_adam_step(const mn_adam_tensor* tensors, int count, int step, float beta1
  * param_group['lr'] every epoch: wbwtab/main.py:62-66 adjust_learning_rate) by refreshing that small array between replays. */
 int mn_adam_step_dev(const mn_adam_tensor* tensors, int count, const int32_t* step_dev, const float* hyper_dev, float beta1, float beta2, float eps,
                      mn_stream_t stream);
+/* The sparse-training step of channel pruning (pruning/main.py:65-69 updateBN + optimizer.step()) in the same ONE launch: per element
+ *     g1 = g + l1[i] * sgn(p) ; g2 = g1 + weight_decay * p ; then the update above on g2
+ * -- the order of the reference, which edits .grad before torch's Adam adds the weight decay.  sgn = torch.sign (0 for +0, -0 and NaN).  l1: HOST array, one
+ * value >= 0 per tensor (parallel to `tensors`); a tensor with l1[i] == 0 gets bit-identical results to mn_adam_step.
+ * _dev: l1_dev (nullable) is a device array of one float per tensor, read INSTEAD of l1[i] and indexed like hyper_dev, so that a replayed graph follows edits of
+ * the sparsity coefficient; l1 must still be a valid host array. */
+int mn_adam_step_l1(const mn_adam_tensor* tensors, const float* l1, int count, int step, float beta1, float beta2, float eps, mn_stream_t stream);
+int mn_adam_step_l1_dev(const mn_adam_tensor* tensors, const float* l1, int count, const int32_t* step_dev, const float* hyper_dev, const float* l1_dev,
+                        float beta1, float beta2, float eps, mn_stream_t stream);
 
 /* ------------------------------------------------------------------ bit-packed inference of the BN-folded W-ternary / W-binary, A-binary graph
  * What wbwtab/bn_fuse/bn_fuse.py:36-55 leaves of a hidden block -- sign(conv(a, t * alpha) + b), a in +-1, t in {-1, 0, +1} (F.conv2d of

@@ -217,6 +217,8 @@ PROTOTYPES = {
     "mn_dorefa_w_bwd_multi_cached": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "mn_adam_step": (_I, [C.POINTER(AdamTensor), _I, _I, C.c_float, C.c_float, C.c_float, _P]),
     "mn_adam_step_dev": (_I, [C.POINTER(AdamTensor), _I, _P, _P, C.c_float, C.c_float, C.c_float, _P]),
+    "mn_adam_step_l1": (_I, [C.POINTER(AdamTensor), C.POINTER(C.c_float), _I, _I, C.c_float, C.c_float, C.c_float, _P]),
+    "mn_adam_step_l1_dev": (_I, [C.POINTER(AdamTensor), C.POINTER(C.c_float), _I, _P, _P, _P, C.c_float, C.c_float, C.c_float, _P]),
     "mn_conv2d_ws_bytes": (_L, [_G, _I, _I]),
     "mn_conv2d_mfma_supported": (_I, [_G, _I]),
     "mn_conv2d_first_supported": (_I, [_G, _I]),

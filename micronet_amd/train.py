@@ -43,13 +43,23 @@ def synth_batch(batch, seed=1234, device=None):
     return x, y
 
 
-def make_optimizer(model, lr=0.01, weight_decay=1e-5, fused=None, **kw):
+def make_optimizer(model, lr=0.01, weight_decay=1e-5, fused=None, sparse_s=0.0, **kw):
     """Adam with one parameter group per tensor, as main.py:308-315 builds it.  On the GPU the step runs as ONE launch
     over all tensors (micronet_amd.optim.Adam, same update and state layout as torch.optim.Adam); ``fused=False`` keeps
-    torch's implementation (used by tests to compare)."""
+    torch's implementation (used by tests to compare).
+
+    ``sparse_s > 0``: sparse training for channel pruning -- the group of every ``BatchNorm2d.weight`` gets ``l1 = sparse_s`` (all other groups 0), and the fused
+    step adds ``sparse_s * sign(gamma)`` to its gradient inside the launch: the reference's ``updateBN()`` (pruning/main.py:65-69), which the training loop then no
+    longer calls.  torch's Adam has no such key: ``fused=False`` with ``sparse_s > 0`` raises."""
     groups = [{"params": [p], "lr": lr, "weight_decay": weight_decay} for _, p in model.named_parameters()]
     if fused is None:
         fused = all(p.is_cuda for g in groups for p in g["params"])
+    if sparse_s:
+        if not fused:
+            raise ValueError("make_optimizer: sparse_s needs micronet_amd.optim.Adam (CUDA parameters); with torch.optim.Adam keep calling updateBN()")
+        gammas = {id(m.weight) for m in model.modules() if isinstance(m, nn.BatchNorm2d) and m.weight is not None}
+        for g in groups:
+            g["l1"] = float(sparse_s) if id(g["params"][0]) in gammas else 0.0
     if fused:
         from micronet_amd.optim import Adam
         return Adam(groups, lr=lr, weight_decay=weight_decay, **kw)
