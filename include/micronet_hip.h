@@ -911,6 +911,21 @@ int mn_bitconv_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t*
 /* Max-pool on bits (max over +-1 = OR; padding contributes nothing): k in {2, 3}, stride 2, pad in {0, 1}, floor mode; bits_out is
  * [N][Cw][(H + 2 pad - k) / 2 + 1][(W + 2 pad - k) / 2 + 1]. */
 int mn_bits_maxpool(const uint32_t* bits_in, int64_t N, int64_t Cw, int64_t H, int64_t W, int k, int stride, int pad, uint32_t* bits_out, mn_stream_t stream);
+/* The two ends of the deployed plan on bits (inference.wbwtab_compile_bits(model, bit_ends=True)).
+ *   first : bits = sign(conv(x, w) + bias) of the un-quantised first conv (real fp32 operands, the geometry of mn_conv2d_first_supported(g, 0) whose forward runs on
+ *           k_c1b_fwd) in ONE launch: the accumulation is that forward's, so the value whose sign is taken is its y bit for bit; the rule is mn_bnsign_fwd_i8's with
+ *           the identity statistics -- 0 iff y < 0, so +0, -0 and NaN give 1.  bits: uint32 [N][ceil(O/32)][H][W], 4-byte aligned, every word stored once, unused
+ *           high bits of the last word 0; neither y nor int8 codes are written.  Null / misaligned tensor or an invalid geometry: MN_EINVAL; a valid geometry that
+ *           mn_conv2d_first_sign_bits_supported refuses (groups, stride, dilation, padding other than "same", C KH KW > 76, W % 4, ...): MN_ENOTSUP.  Nothing is
+ *           written in either case.
+ *   last  : y = conv1x1(a, w) + bias of the fp32 classifier (O <= 16) read from activation bits: mn_signconv1x1_small_fwd with the code read replaced by a bit
+ *           extraction (+w where the bit is 1, -w where it is 0), same channel and partial-sum order -- the logits equal that entry point's on the unpacked bits to
+ *           the bit.  bits [N][ceil(C/32)][HW] and y [N][O][HW] 16-byte aligned; HW % 4 == 0.  Null / misaligned / N <= 0: MN_EINVAL; a shape
+ *           mn_bitsconv1x1_small_supported refuses: MN_ENOTSUP. */
+int mn_conv2d_first_sign_bits_supported(const mn_conv_geom* g);
+int mn_conv2d_first_sign_bits(const mn_conv_geom* g, const float* x, const float* w, const float* bias, uint32_t* bits, mn_stream_t stream);
+int mn_bitsconv1x1_small_supported(int64_t C, int64_t HW, int64_t O);
+int mn_bitsconv1x1_small_fwd(const uint32_t* bits, const float* w, const float* bias, float* y, int64_t N, int64_t C, int64_t HW, int64_t O, mn_stream_t stream);
 
 #ifdef __cplusplus
 }

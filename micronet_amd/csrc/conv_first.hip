@@ -60,6 +60,7 @@ struct C1Params {
     void* codes;          // EPI 1: int8 sign codes; EPI 2: uint8 codes of the next conv's a-bit quantizer
     uint8_t* mask4;       // [N][O][H W / 4]: low nibble = pass bits of 4 consecutive pixels (EPI 1: |z| < 1; EPI 2: z > 0), high nibble (EPI 2): ... and the clamp test
     int mask_shift;       // backward: which nibble (4: the gradient is w.r.t. the QUANTISED activation)
+    uint32_t* bits;       // k_c1b_fwd<MT, EPI 3>: sign(conv + bias) as activation bits [N][ceil(O / 32)][H][W] (qgemm_bits.hip), nothing else written
 };
 
 // stage the image strip (with zero halo) of image n, rows [row0 - ph, row0 + R + KH - 1 - ph) into xs[c][prow][pcol]
@@ -204,8 +205,9 @@ __global__ __launch_bounds__(256, 2) void k_c1b_fwd(const C1Params p) {
     c1_stage(p, xs, n, row0);
     for (int k = tid; k < C1B_KP; k += 256) ktab[k] = k < p.K ? c1_koff(p, k) : -1;
     for (int i = tid; i < 64 * MT; i += 256) { const int m = cblk * 64 * MT + i; bs[i] = (p.bias && m < p.O) ? p.bias[m] : 0.f; }
-    float4* bc = reinterpret_cast<float4*>(bs + 64 * MT);          // EPI: [64 MT] mean, invstd, gamma, beta
-    if (EPI)
+    float4* bc = reinterpret_cast<float4*>(bs + 64 * MT);          // EPI 1 / 2: [64 MT] mean, invstd, gamma, beta
+    uint32_t* wvb = reinterpret_cast<uint32_t*>(bs + 64 * MT);     // EPI 3 (same bytes): [4 waves][64 pixels][2] sign bits of a wave's 16 MT channels
+    if (EPI == 1 || EPI == 2)
         for (int i = tid; i < 64 * MT; i += 256) {
             const int m = cblk * 64 * MT + i, mc = m < p.O ? m : p.O - 1;
             bc[i] = make_float4(p.bn_save[mc], p.bn_save[p.O + mc], p.bn_gamma[mc], p.bn_beta[mc]);
@@ -317,6 +319,50 @@ __global__ __launch_bounds__(256, 2) void k_c1b_fwd(const C1Params p) {
         // (opaque per chunk: the 16 MT per-channel constants of the epilogue -- bias, and the BatchNorm's four -- are re-read from LDS; hoisted out of the chunk loop
         //  they cost 80 registers the kernel does not have: 40 scratch reloads per chunk in the first fused build)
         const int ch0 = (int)mn_opaque((uint32_t)(wave * 16 * MT));
+        if (EPI == 3) {
+            // sign(conv + bias) as activation bits (the layout of qgemm_bits.hip), neither y nor byte codes written.  The value is the plain epilogue's acc + bb; the
+            // rule is mn_bnsign_fwd_i8's with the identity statistics, code = (z < 0 ? -1 : +1) with z = ((y - 0) * 1) * 1 + 0: z < 0 iff y < 0 (+-0 and NaN: +1).
+            // A lane holds channels t * 16 + kg * 4 + r of its wave's 16 MT for four pixels: OR them into a 16 MT-bit string per pixel, combine the four kg groups
+            // by two shuffles, and hand the string to LDS; the block's 64 MT channels are 2 MT whole words, each assembled and stored once (64 pixels = 256 bytes).
+            uint32_t lo[4] = {0u, 0u, 0u, 0u}, hi[4] = {0u, 0u, 0u, 0u};
+            const bool pv = pix < npix;
+#pragma unroll
+            for (int t = 0; t < MT; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int cl = t * 16 + kg * 4 + r;
+                    const bool mv = pv && m0 + cl < p.O;          // channels beyond O: zero bits (the unused high bits of the last word)
+                    const float bb = bs[ch0 + cl];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const float yv = acc[q][t][r] + bb;
+                        const uint32_t bit = (mv && !(yv < 0.f)) ? 1u : 0u;
+                        if (t < 2) lo[q] |= bit << cl; else hi[q] |= bit << (cl - 32);
+                    }
+                }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                lo[q] |= __shfl_xor(lo[q], 16, 64); lo[q] |= __shfl_xor(lo[q], 32, 64);
+                if (MT > 2) { hi[q] |= __shfl_xor(hi[q], 16, 64); hi[q] |= __shfl_xor(hi[q], 32, 64); }
+                if (kg == 0) { wvb[(wave * 64 + 4 * j + q) * 2] = lo[q]; wvb[(wave * 64 + 4 * j + q) * 2 + 1] = hi[q]; }
+            }
+            __syncthreads();          // (the strings are rewritten behind the next chunk's expand barrier: every thread has read them by then)
+            const int px = chunk * 64 + lane, OW = (p.O + 31) >> 5;
+            for (int wd = wave; wd < 2 * MT; wd += 4) {          // word wd of the block = bits [32 wd, 32 wd + 32) of the four waves' strings laid end to end
+                uint32_t word = 0u;
+#pragma unroll
+                for (int w4 = 0; w4 < 4; ++w4) {
+                    const int sh = w4 * 16 * MT - 32 * wd;
+                    if (sh > -16 * MT && sh < 32) {
+                        const uint64_t v = (uint64_t)wvb[(w4 * 64 + lane) * 2] | ((uint64_t)wvb[(w4 * 64 + lane) * 2 + 1] << 32);
+                        word |= sh >= 0 ? (uint32_t)(v << sh) : (uint32_t)(v >> -sh);
+                    }
+                }
+                const int gw = cblk * 2 * MT + wd;
+                if (gw < OW && px < npix) p.bits[((int64_t)n * OW + gw) * p.H * p.W + row0 * p.W + px] = word;
+            }
+            continue;
+        }
         if (pix < npix) {
             const uint32_t prow = fd_div(pix, p.fd_w);
             const int pcol = pix - prow * p.W;
@@ -943,6 +989,29 @@ int c1_fwd_bnact(const mn_conv_geom* g, const float* x, const float* w, const fl
 #undef C1B_LAUNCH
     mn_prof_end(s);
     MN_CHECK_LAUNCH("mn_conv2d_first_bnact_fwd");
+    return MN_OK;
+}
+// the deployed first block (inference.wbwtab_compile_bits): sign(conv + bias) straight to activation bits -- the three-term bf16 forward's accumulation, so the value
+// whose sign is taken is bit for bit the y of c1_fwd; a geometry that forward would hand to k_c1_fwd (the strip does not fit the im2col tile's LDS) is refused
+int c1_sign_bits_supported(const mn_conv_geom* g) {
+    C1Plan pl;
+    return plan_c1(g, &pl) && c1b_lds_bytes(pl.p) <= 80 * 1024;
+}
+int c1_fwd_sign_bits(const mn_conv_geom* g, const float* x, const float* w, const float* bias, uint32_t* bits, hipStream_t s) {
+    C1Plan pl;
+    if (!plan_c1(g, &pl) || c1b_lds_bytes(pl.p) > 80 * 1024) MN_FAIL(MN_ENOTSUP, "mn_conv2d_first_sign_bits: geometry not covered by the first-layer forward (k_c1b_fwd)");
+    C1Params& p = pl.p;
+    p.x = x; p.bias = bias; p.y = nullptr; p.gy = nullptr; p.part = nullptr; p.dbpart = nullptr; p.want_db = 0; p.da = nullptr;
+    p.relu = 0; p.mm = nullptr; p.codes = nullptr; p.mask4 = nullptr; p.wp = w; p.bits = bits;
+    const size_t lds_b = c1b_lds_bytes(p);
+    mn_set_last_kernel("k_c1b_fwd<%d, 3>", pl.MT);
+    mn_prof_bytes(4.0 * g->N * ((g->O + 31) / 32) * g->H * g->W + 4.0 * g->N * g->C * g->H * g->W);
+    mn_prof_begin(s);
+#define C1B_LAUNCH(MT_) { raise_lds_limit((const void*)k_c1b_fwd<MT_, 3>, lds_b); hipLaunchKernelGGL((k_c1b_fwd<MT_, 3>), dim3(pl.grid_f), dim3(256), lds_b, s, p); }
+    if (pl.MT == 4) C1B_LAUNCH(4) else if (pl.MT == 3) C1B_LAUNCH(3) else if (pl.MT == 2) C1B_LAUNCH(2) else C1B_LAUNCH(1)
+#undef C1B_LAUNCH
+    mn_prof_end(s);
+    MN_CHECK_LAUNCH("mn_conv2d_first_sign_bits");
     return MN_OK;
 }
 int c1_fwd_act(const mn_conv_geom* g, const float* x, const float* w, const float* bias, float* y, int relu, float* mm, void* ws, int64_t ws_bytes, hipStream_t s) {

@@ -974,6 +974,17 @@ extern "C" int mn_conv2d_first_bnact_fwd(const mn_conv_geom* g, const float* x, 
     if (!c1_supported(g, 0) || !c1_supported(g, 2)) MN_FAIL(MN_ENOTSUP, "mn_conv2d_first_bnact_fwd: geometry not covered by the first-layer kernels");
     return c1_fwd_bnact(g, x, w, bias, save, gamma, beta, act, a_bits, codes, mask4, (hipStream_t)stream);
 }
+extern "C" int mn_conv2d_first_sign_bits_supported(const mn_conv_geom* g) {
+    if (!g || check_geom(g, "mn_conv2d_first_sign_bits_supported") != MN_OK) return 0;
+    return c1_supported(g, 0) && c1_sign_bits_supported(g);
+}
+extern "C" int mn_conv2d_first_sign_bits(const mn_conv_geom* g, const float* x, const float* w, const float* bias, uint32_t* bits, mn_stream_t stream) {
+    int rc = check_geom(g, "mn_conv2d_first_sign_bits");
+    if (rc) return rc;
+    if (!x || !w || !bits || (((uintptr_t)bits) & 3)) MN_FAIL(MN_EINVAL, "mn_conv2d_first_sign_bits: null tensor / bits not 4-byte aligned");
+    if (!mn_conv2d_first_sign_bits_supported(g)) MN_FAIL(MN_ENOTSUP, "mn_conv2d_first_sign_bits: geometry not covered by the first-layer forward (mn_conv2d_first_sign_bits_supported)");
+    return c1_fwd_sign_bits(g, x, w, bias, bits, (hipStream_t)stream);
+}
 extern "C" int mn_conv2d_bwd_first_mask_gram(const mn_conv_geom* g, const float* da, const uint8_t* mask4, int quant, const float* save, const float* gamma,
                                              const float* w, const float* bias, const double* gram, const float* x, float* dw, float* dbias, float* dgamma,
                                              float* dbeta, void* ws, int64_t ws_bytes, mn_stream_t stream) {

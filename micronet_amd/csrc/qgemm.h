@@ -35,6 +35,9 @@ int64_t c1_xgram_ws_bytes(const mn_conv_geom* g);
 int c1_xgram(const mn_conv_geom* g, const float* x, double* gram, void* ws, int64_t ws_bytes, hipStream_t s);
 int c1_fwd_bnact(const mn_conv_geom* g, const float* x, const float* w, const float* bias, const float* save, const float* gamma, const float* beta, int act, int a_bits,
                  void* codes, uint8_t* mask4, hipStream_t s);
+// sign(conv + bias) of the deployed first block as activation bits (qgemm_bits.hip's layout): k_c1b_fwd's accumulation, one launch, neither y nor byte codes written
+int c1_sign_bits_supported(const mn_conv_geom* g);
+int c1_fwd_sign_bits(const mn_conv_geom* g, const float* x, const float* w, const float* bias, uint32_t* bits, hipStream_t s);
 int c1_bwd_first_mask(const mn_conv_geom* g, const float* da, const uint8_t* mask4, int quant, const float* save, const float* gamma, const float* w, const float* bias,
                       const double* gram, const float* x, float* dw, float* dbias, float* dgamma, float* dbeta, void* ws, int64_t ws_bytes, hipStream_t s);
 int c1_gram_bnstats(const mn_conv_geom* g, const float* w, const float* bias, const double* gram, float eps, float momentum, float* running_mean, float* running_var,

@@ -22,7 +22,7 @@
 //   tiled row       : row[0..3] as above, taps x NW pairs (s, m), then S[(KS + 1)][(KS + 1)], S[a][b] = sum of d_t over taps (ty < a, tx < b).
 // The 3x3 / stride 2 / padding 1 max-pool (models/nin.py) is an OR over the in-image cells of the window: folded into a 1x1 block (one lane = one pooled pixel, up to
 // nine decisions) or a word-wise kernel of its own behind any other producer.
-#include "common.h"
+#include "qgemm_dev.h"
 
 namespace mn_bits {
 
@@ -464,7 +464,136 @@ __global__ __launch_bounds__(256) void k_bits_maxpool(const uint32_t* __restrict
     out[i] = v;
 }
 
+// ---------------------------------------------------------------- the classifier on bits: 1x1 conv, few outputs, fp32 weights, activation bits in
+// k_sconv_fwd (norm_kernels.hip: the last conv of a binary net on int8 sign codes) with the code read replaced by a bit extraction: +w where the bit is 1, -w where
+// it is 0 (w * +-1.f: exact).  Everything that decides the fp32 sums is that kernel's: block = 64 consecutive pixels of the [N][HW] pixel axis, 16 waves split the
+// channels into ranges of ceil(C / 16), lane (pq, cs) accumulates 4 pixels x OP outputs over the channels c0 + cs + 4 i of its wave in increasing order, the four
+// cs groups are combined by the same two shuffles and the 16 waves through LDS in the same fixed order -- the logits equal mn_signconv1x1_small_fwd on the unpacked
+// bits to the bit.  What changes is the traffic: a lane's channels of one 32-channel word (every fourth: 8 of them) come out of ONE 16-byte load of the word's four
+// pixels instead of 8 dword loads of codes; two words are in flight per trip.
+enum { BC_MAXO = 16, BC_WAVES = 16 };
+template <int OP>
+__global__ __launch_bounds__(1024) void k_bitsconv1x1_small(const uint32_t* __restrict__ bits, const float* __restrict__ w, const float* __restrict__ bias,
+                                                            float* __restrict__ y, int C, int Cw, int HW, int O, int64_t NP) {
+    HIP_DYNAMIC_SHARED(float, smem)
+    float* wl = smem;                          // [C][OP]
+    float* red = smem + (size_t)C * OP;        // [8][OP][64]
+    const int tid = threadIdx.x, lane = tid & 63, wv = mn_uniform(tid >> 6), pq = lane & 15, cs = lane >> 4;
+    for (int i = tid; i < C * OP; i += 1024) wl[i] = 0.f;
+    __syncthreads();
+    for (int i = tid; i < C * O; i += 1024) {       // coalesced read of w[o][c], transposed LDS write
+        const int o = i / C, c = i - o * C;
+        wl[c * OP + o] = w[i];
+    }
+    const int64_t P = (int64_t)blockIdx.x * 64 + 4 * pq;
+    const int64_t Pc = P < NP ? P : 0;
+    const int64_t n = Pc / HW;
+    const int p = (int)(Pc - n * HW);
+    float acc[4][OP];
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int o = 0; o < OP; ++o) acc[e][o] = 0.f;
+    const int per = (C + BC_WAVES - 1) / BC_WAVES;
+    const int c0 = wv * per, c1 = (c0 + per) < C ? (c0 + per) : C;
+    const uint32_t* src = bits + n * Cw * HW + p;          // word 0 of the lane's four pixels (16-byte aligned: HW % 4 == 0)
+    __syncthreads();
+    auto add = [&](const u32x4& x, int sh, int c) {
+        const float s0 = ((x[0] >> sh) & 1u) ? 1.f : -1.f, s1 = ((x[1] >> sh) & 1u) ? 1.f : -1.f, s2 = ((x[2] >> sh) & 1u) ? 1.f : -1.f, s3 = ((x[3] >> sh) & 1u) ? 1.f : -1.f;
+#pragma unroll
+        for (int o4 = 0; o4 < OP; o4 += 4) {
+            const float4 w4 = *reinterpret_cast<const float4*>(wl + c * OP + o4);
+            const float wv_[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                acc[0][o4 + k] += wv_[k] * s0; acc[1][o4 + k] += wv_[k] * s1; acc[2][o4 + k] += wv_[k] * s2; acc[3][o4 + k] += wv_[k] * s3;
+            }
+        }
+    };
+    const int first = c0 + cs;                               // this lane's channels: first + 4 i < c1, in increasing order
+    if (first < c1) {
+        const int wlast = (c1 - 1) >> 5, r4 = first & 3;     // (wlast <= Cw - 1: every word read lies inside the pixel's Cw words)
+        for (int wi = first >> 5; wi <= wlast; wi += 2) {
+            const int wj = wi + 1 <= wlast ? wi + 1 : wlast;
+            const u32x4 xa = *reinterpret_cast<const u32x4*>(src + (int64_t)wi * HW), xb = *reinterpret_cast<const u32x4*>(src + (int64_t)wj * HW);
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                const int c = wi * 32 + r4 + 4 * b;
+                if (c >= first && c < c1) add(xa, r4 + 4 * b, c);
+            }
+            if (wi + 1 <= wlast) {
+#pragma unroll
+                for (int b = 0; b < 8; ++b) {
+                    const int c = wj * 32 + r4 + 4 * b;
+                    if (c < c1) add(xb, r4 + 4 * b, c);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int o = 0; o < OP; ++o) {
+            float t = acc[e][o];
+            t += __shfl_xor(t, 16, 64); t += __shfl_xor(t, 32, 64);
+            acc[e][o] = t;
+        }
+    if (wv >= 8 && cs == 0) {
+#pragma unroll
+        for (int o = 0; o < OP; ++o)
+            *reinterpret_cast<float4*>(red + ((wv - 8) * OP + o) * 64 + 4 * pq) = make_float4(acc[0][o], acc[1][o], acc[2][o], acc[3][o]);
+    }
+    __syncthreads();
+    if (wv < 8 && cs == 0) {
+#pragma unroll
+        for (int o = 0; o < OP; ++o) {
+            float4* r = reinterpret_cast<float4*>(red + (wv * OP + o) * 64 + 4 * pq);
+            const float4 t = *r;
+            *r = make_float4(acc[0][o] + t.x, acc[1][o] + t.y, acc[2][o] + t.z, acc[3][o] + t.w);
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < O * 16; i += 1024) {
+        const int o = i >> 4, q = i & 15;                       // quad q of the block
+        const int64_t Pq = (int64_t)blockIdx.x * 64 + 4 * q;
+        if (Pq < NP) {
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int k = 0; k < 8; ++k) {                        // fixed order
+                const float4 t = *reinterpret_cast<const float4*>(red + (k * OP + o) * 64 + 4 * q);
+                v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
+            }
+            const float bb = bias ? bias[o] : 0.f;
+            const int64_t nq = Pq / HW;
+            *reinterpret_cast<float4*>(y + (nq * O + o) * HW + (Pq - nq * HW)) = make_float4(v.x + bb, v.y + bb, v.z + bb, v.w + bb);
+        }
+    }
+}
+
 }  // namespace mn_bits
+
+extern "C" int mn_bitsconv1x1_small_supported(int64_t C, int64_t HW, int64_t O) {
+    if (!(O >= 1 && O <= mn_bits::BC_MAXO && C >= 4 && C <= (1 << 20) && HW >= 4 && HW % 4 == 0 && HW <= (1 << 26))) return 0;
+    const int64_t OP = (O + 3) / 4 * 4;
+    return (C * OP + 8 * OP * 64) * 4 <= 128 * 1024;          // the weight image and the partial sums live in LDS (mn_signconv1x1_small_supported's bound)
+}
+extern "C" int mn_bitsconv1x1_small_fwd(const uint32_t* bits, const float* w, const float* bias, float* y, int64_t N, int64_t C, int64_t HW, int64_t O, mn_stream_t stream) {
+    if (!bits || !w || !y || N <= 0 || !aligned16(bits) || !aligned16(y)) MN_FAIL(MN_EINVAL, "mn_bitsconv1x1_small_fwd: null argument / bits and y must be 16-byte aligned");
+    if (!mn_bitsconv1x1_small_supported(C, HW, O)) MN_FAIL(MN_ENOTSUP, "mn_bitsconv1x1_small_fwd: needs O <= 16, C >= 4, HW %% 4 == 0 and the weights in LDS (mn_bitsconv1x1_small_supported)");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t NP = N * HW, nb = (NP + 63) / 64;
+    const int Cw = (int)((C + 31) >> 5);
+    if (nb > 0x7fffffff || N * Cw * HW >= (1ll << 40)) MN_FAIL(MN_ENOTSUP, "mn_bitsconv1x1_small_fwd: tensor too large");
+    const int OP = (int)((O + 3) / 4 * 4);
+    const size_t lds = ((size_t)C * OP + (size_t)8 * OP * 64) * 4;
+    mn_set_last_kernel("k_bitsconv1x1_small"); mn_prof_bytes(4.0 * N * Cw * HW + 4.0 * N * O * HW + 4.0 * O * C); mn_prof_begin(s);
+#define BC_LAUNCH(OPV) { raise_lds_limit((const void*)mn_bits::k_bitsconv1x1_small<OPV>, lds); \
+        hipLaunchKernelGGL((mn_bits::k_bitsconv1x1_small<OPV>), dim3((unsigned)nb), dim3(1024), lds, s, bits, w, bias, y, (int)C, Cw, (int)HW, (int)O, NP); }
+    if (OP == 4) BC_LAUNCH(4) else if (OP == 8) BC_LAUNCH(8) else if (OP == 12) BC_LAUNCH(12) else BC_LAUNCH(16)
+#undef BC_LAUNCH
+    mn_prof_end(s);
+    MN_CHECK_LAUNCH("mn_bitsconv1x1_small_fwd");
+    return MN_OK;
+}
 
 extern "C" int mn_bits_pack_sign8(const int8_t* a, int64_t N, int64_t C, int64_t HW, uint32_t* bits, mn_stream_t stream) {
     if (!a || !bits || N <= 0 || C <= 0 || HW <= 0 || HW % 4 || (((uintptr_t)a) & 3) || (((uintptr_t)bits) & 3) || C > (1 << 20) || HW > (1 << 26))

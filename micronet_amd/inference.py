@@ -14,7 +14,8 @@ The results are ordinary modules of this package: in eval mode they run on the s
 
   * ``wbwtab_compile_bits``: the folded W-ternary / W-binary, A-binary graph compiled into a flat plan that keeps ONE BIT per hidden activation
     (``csrc/qgemm_bits.hip``: XNOR / AND / popcount against bit-plane weight tables, bias and alpha folded into an integer threshold per channel).  It computes
-    exactly what the folded graph computes -- same signs in every hidden stage, same logits to the bit."""
+    exactly what the folded graph computes -- same signs in every hidden stage, same logits to the bit.  ``bit_ends=True``: the two ends stay on bits as well -- the
+    first conv writes activation bits in one launch (``mn_conv2d_first_sign_bits``), the classifier reads them (``mn_bitsconv1x1_small_fwd``)."""
 import copy
 
 import torch
@@ -220,11 +221,13 @@ def _conv_kernel_name(k, cin, groups, fold):
 class BitPlan(nn.Module):
     """What ``wbwtab_compile_bits`` returns: first block (fp32 conv + sign, the folded graph's own module) -> bit pack -> n XNOR-popcount blocks (max-pools folded in,
     or run on the bits behind a block that cannot fold them) -> bit unpack -> last block and tail (the folded graph's own modules).  Eval only; owns the packed weight
-    tables and one set of bit buffers per input shape."""
+    tables and one set of bit buffers per input shape.  ``bit_ends``: the first conv's kernel writes the first stage's bits itself (no fp32 map, no int8 codes, no
+    pack) and the last conv reads the last stage's bits (no unpack, no int8 buffer); what follows the last conv inside its block, and the tail, run unchanged."""
 
-    def __init__(self, first, layers, last, tail, flatten, report):
+    def __init__(self, first, layers, last, tail, flatten, report, bit_ends=False):
         super().__init__()
         self.first, self.last, self.tail = first, last, nn.ModuleList(tail)
+        self.bit_ends = bool(bit_ends)
         self.layers = layers              # dicts: geometry, table, pool, out_order
         self.flatten = flatten
         self.report = report
@@ -244,6 +247,15 @@ class BitPlan(nn.Module):
         key = (tuple(shape), str(device))
         if key not in self._ws:
             N, Cc, H, W = shape
+            g0 = None
+            if self.bit_ends:
+                import ctypes as C
+                conv = self.first.conv
+                g0 = _lib.ConvGeom(N, conv.in_channels, H, W, Cc, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.stride[1], conv.padding[0], conv.padding[1],
+                                   conv.dilation[0], conv.dilation[1], conv.groups, 0)
+                if not _lib.get_lib().mn_conv2d_first_sign_bits_supported(C.byref(g0)):
+                    raise _err("wbwtab_compile_bits(bit_ends=True): %s.conv: a %d x %d x %d x %d input is not covered by mn_conv2d_first_sign_bits (W %% 4 == 0, H * W %% 32 == 0, "
+                               "the image strip in LDS)" % (self.report[0]["name"], N, conv.in_channels, H, W))
             bufs, geoms = [torch.empty((N, (Cc + 31) // 32, H, W), dtype=torch.int32, device=device)], []
             mids = []
             for L in self.layers:
@@ -258,10 +270,16 @@ class BitPlan(nn.Module):
                     H, W = (H + 2 * pool[2] - pool[0]) // pool[1] + 1, (W + 2 * pool[2] - pool[0]) // pool[1] + 1
                 bufs.append(torch.empty((N, (L["cout"] + 31) // 32, H, W), dtype=torch.int32, device=device))
                 Cc = L["cout"]
+            if self.bit_ends:
+                if not _lib.get_lib().mn_bitsconv1x1_small_supported(Cc, H * W, self.last.conv.out_channels):
+                    raise _err("wbwtab_compile_bits(bit_ends=True): %s.conv: a %d-channel %d x %d map is not covered by mn_bitsconv1x1_small_fwd (its lanes own 4 consecutive "
+                               "pixels: H * W %% 4 == 0; the weights in LDS)" % (self.report[-1]["name"], Cc, H, W))
+                self._ws[key] = (bufs, geoms, None, mids, g0)
+                return self._ws[key]
             if (H * W) % 4:
                 raise _err("wbwtab_compile_bits: %s: its %d x %d output cannot be unpacked for the last conv (mn_bits_unpack_sign8 needs H * W %% 4 == 0)"
                            % (self.layers[-1]["name"], H, W))
-            self._ws[key] = (bufs, geoms, torch.empty((N, Cc, H, W), dtype=torch.int8, device=device), mids)
+            self._ws[key] = (bufs, geoms, torch.empty((N, Cc, H, W), dtype=torch.int8, device=device), mids, g0)
         return self._ws[key]
 
     @torch.no_grad()
@@ -269,14 +287,24 @@ class BitPlan(nn.Module):
         import ctypes as C
         from micronet_amd import ops
         from micronet_amd.sign_tensor import SignTensor
-        a = self.first(x)
-        if not isinstance(a, SignTensor):
-            raise _err("wbwtab_compile_bits: the first block did not produce packed signs (input must be a contiguous float32 GPU tensor with H * W % 4 == 0)")
-        codes = a.codes.contiguous()
-        N, Cc, H, W = codes.shape
-        bufs, geoms, a8, mids = self._plan_buffers(codes.shape, codes.device)
-        st = ops._s()
-        ops._call("mn_bits_pack_sign8", ops._p(codes), N, Cc, H * W, ops._p(bufs[0]), st)
+        if self.bit_ends:
+            conv = self.first.conv
+            if not (type(x) is torch.Tensor and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == conv.in_channels):
+                raise _err("wbwtab_compile_bits(bit_ends=True): the input must be a float32 GPU tensor [N, %d, H, W] (no CPU fallback)" % conv.in_channels)
+            x = x.contiguous()
+            bufs, geoms, a8, mids, g0 = self._plan_buffers((x.shape[0], conv.out_channels, x.shape[2], x.shape[3]), x.device)
+            st = ops._s()
+            ops._call("mn_conv2d_first_sign_bits", C.byref(g0), ops._p(x), ops._p(ops._chk(conv.weight.detach(), "weight")), ops._p(ops._chk(conv.bias, "bias")),
+                      ops._p(bufs[0]), st)
+        else:
+            a = self.first(x)
+            if not isinstance(a, SignTensor):
+                raise _err("wbwtab_compile_bits: the first block did not produce packed signs (input must be a contiguous float32 GPU tensor with H * W % 4 == 0)")
+            codes = a.codes.contiguous()
+            N, Cc, H, W = codes.shape
+            bufs, geoms, a8, mids, _ = self._plan_buffers(codes.shape, codes.device)
+            st = ops._s()
+            ops._call("mn_bits_pack_sign8", ops._p(codes), N, Cc, H * W, ops._p(bufs[0]), st)
         for i, L in enumerate(self.layers):
             if mids[i] is None:
                 ops._call("mn_bitconv_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(bufs[i + 1]), int(L["pool"]), st)
@@ -286,15 +314,51 @@ class BitPlan(nn.Module):
                 ops._call("mn_bits_maxpool", ops._p(m), m.shape[0], m.shape[1], m.shape[2], m.shape[3], pk, ps, pp, ops._p(bufs[i + 1]), st)
         if self.keep_stages:
             self.stage_bits = [b.clone() for b in bufs]
-        n_, c_, h_, w_ = a8.shape
-        ops._call("mn_bits_unpack_sign8", ops._p(bufs[-1]), n_, c_, h_ * w_, ops._p(a8), st)
-        y = self.last(SignTensor(a8))
+        if self.bit_ends:
+            conv = self.last.conv
+            n_, _, h_, w_ = bufs[-1].shape
+            y = torch.empty((n_, conv.out_channels, h_, w_), dtype=torch.float32, device=bufs[-1].device)
+            ops._call("mn_bitsconv1x1_small_fwd", ops._p(bufs[-1]), ops._p(ops._chk(conv.weight.detach(), "weight")), ops._p(ops._chk(conv.bias, "bias")), ops._p(y),
+                      n_, conv.in_channels, h_ * w_, conv.out_channels, st)
+            kids = list(self.last.children())
+            for m in kids[kids.index(conv) + 1:]:          # what follows the conv inside the last block (Identity, ReLU)
+                y = m(y)
+        else:
+            n_, c_, h_, w_ = a8.shape
+            ops._call("mn_bits_unpack_sign8", ops._p(bufs[-1]), n_, c_, h_ * w_, ops._p(a8), st)
+            y = self.last(SignTensor(a8))
         for m in self.tail:
             y = m(y)
         return y.view(y.size(0), -1) if self.flatten else y
 
 
-def _walk_bits(model):
+def _check_bit_ends(first, nm_first, last, nm_last):
+    """``bit_ends=True``: both ends must be covered by their bit kernels -- never a silent byte path.  Shape-independent part (the input shape is checked by the plan)."""
+    import ctypes as C
+    from micronet_amd import _lib
+    lib = _lib.get_lib()
+    conv = first.conv
+    if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
+        raise _err("wbwtab_compile_bits(bit_ends=True): %s.conv: padding mode not covered by mn_conv2d_first_sign_bits" % nm_first)
+    g = _lib.ConvGeom(1, conv.in_channels, 8, 8, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.stride[1], conv.padding[0], conv.padding[1],
+                      conv.dilation[0], conv.dilation[1], conv.groups, 0)
+    if not lib.mn_conv2d_first_sign_bits_supported(C.byref(g)):
+        raise _err("wbwtab_compile_bits(bit_ends=True): %s.conv: not covered by mn_conv2d_first_sign_bits (%dx%d, stride %d, padding %d, dilation %d, groups %d, %d taps per "
+                   "output: needs \"same\" padding, stride 1, groups 1, at most 76 taps)"
+                   % (nm_first, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.padding[0], conv.dilation[0], conv.groups,
+                      conv.in_channels // conv.groups * conv.kernel_size[0] * conv.kernel_size[1]))
+    conv = last.conv
+    one = lambda v, k: tuple(v) == (k, k)
+    if not (conv.padding_mode == "zeros" and not isinstance(conv.padding, str) and one(conv.kernel_size, 1) and one(conv.stride, 1) and one(conv.padding, 0) and
+            one(conv.dilation, 1) and conv.groups == 1 and lib.mn_bitsconv1x1_small_supported(conv.in_channels, 4, conv.out_channels)):
+        raise _err("wbwtab_compile_bits(bit_ends=True): %s.conv: the last conv is not the small 1x1 classifier mn_bitsconv1x1_small_fwd covers (%dx%d, stride %d, padding %s, "
+                   "groups %d, %d -> %d channels: needs 1x1, stride 1, no padding, groups 1, at most 16 outputs)"
+                   % (nm_last, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.padding, conv.groups, conv.in_channels, conv.out_channels))
+    if getattr(last, "channel_shuffle_flag", 0) and getattr(last, "shuffle_groups", 1) > 1:
+        raise _err("wbwtab_compile_bits(bit_ends=True): %s: a channel shuffle in front of the last conv is not covered by mn_bitsconv1x1_small_fwd" % nm_last)
+
+
+def _walk_bits(model, bit_ends=False):
     """The graph walk of ``wbwtab_compile_bits`` (no GPU needed): (first, layers, last, tail, flatten, report)."""
     import ctypes as C
     from micronet_amd import _lib
@@ -372,6 +436,9 @@ def _walk_bits(model):
     if first is None or last is None:
         raise _err("wbwtab_compile_bits: module order not recognised (no %s conv block found)" % ("first" if first is None else "last"))
     rep_last = report.pop()
+    if bit_ends:
+        _check_bit_ends(first, report[0]["name"], last, rep_last["name"])
+        report[0]["kernel"], rep_last["kernel"] = "first conv -> bits (k_c1b_fwd)", "last conv on bits (k_bitsconv1x1_small)"
     for L in layers:
         kern = _conv_kernel_name(L["k"], L["cin"], L["groups"], L["pool"])
         pooled = bool(L["pool"])
@@ -385,20 +452,22 @@ def _walk_bits(model):
     return first, layers, last, tail, flatten, report
 
 
-def wbwtab_bits_report(model):
-    """The ``report`` ``wbwtab_compile_bits(model)`` would carry -- one row per stage: kernel, K, words, how a max-pool behind it is done -- from the graph walk alone:
-    no GPU, nothing packed.  Raises like ``wbwtab_compile_bits`` for whatever the bit kernels do not cover."""
-    return _walk_bits(model)[5]
+def wbwtab_bits_report(model, bit_ends=False):
+    """The ``report`` ``wbwtab_compile_bits(model, bit_ends)`` would carry -- one row per stage: kernel, K, words, how a max-pool behind it is done -- from the graph walk
+    alone: no GPU, nothing packed.  Raises like ``wbwtab_compile_bits`` for whatever the bit kernels do not cover."""
+    return _walk_bits(model, bit_ends)[5]
 
 
 @torch.no_grad()
-def wbwtab_compile_bits(model):
+def wbwtab_compile_bits(model, bit_ends=False):
     """``model``: the result of ``wbwtab_model_bn_fuse`` on a pre-quantised W in (2, 3), A = 2 net, on the GPU (the reference's ``nin`` and ``nin_gc``).  Returns a ``BitPlan``
     computing the same function with one bit per hidden activation; ``.report`` lists the stages.  Anything the bit kernels do not cover raises ``MicronetHipError``
-    naming the layer -- never a silent byte path (the caller still has ``model``)."""
+    naming the layer -- never a silent byte path (the caller still has ``model``).  ``bit_ends=True``: the first conv writes the first stage's bits in one launch and the
+    classifier reads the last stage's bits -- no fp32 map, no int8 codes, no pack / unpack launch; same bits in every stage, same logits (off by default until the gain
+    is measured)."""
     import ctypes as C
     from micronet_amd import _lib, ops
-    first, layers, last, tail, flatten, report = _walk_bits(model)
+    first, layers, last, tail, flatten, report = _walk_bits(model, bit_ends)
     for p_ in model.parameters():
         if not p_.is_cuda:
             raise _err("wbwtab_compile_bits: the model is on %s: micronet_amd runs on MI355X only (no CPU fallback)" % p_.device)
@@ -421,4 +490,4 @@ def wbwtab_compile_bits(model):
     for nm, nbad in bad:
         if nbad:
             raise _err("wbwtab_compile_bits: %s.conv: %d output channels whose decision is not monotone in the accumulator" % (nm, nbad))
-    return BitPlan(first, layers, last, tail, flatten, report)
+    return BitPlan(first, layers, last, tail, flatten, report, bit_ends)
