@@ -911,6 +911,32 @@ int mn_bitconv_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t*
 /* Max-pool on bits (max over +-1 = OR; padding contributes nothing): k in {2, 3}, stride 2, pad in {0, 1}, floor mode; bits_out is
  * [N][Cw][(H + 2 pad - k) / 2 + 1][(W + 2 pad - k) / 2 + 1]. */
 int mn_bits_maxpool(const uint32_t* bits_in, int64_t N, int64_t Cw, int64_t H, int64_t W, int k, int stride, int pad, uint32_t* bits_out, mn_stream_t stream);
+/* ------------------------------------------------------------------ code-packed deployment of the k-bit (DoReFa) blocks: 2-bit activations end to end
+ * What a hidden block of a DoReFa W2A2 net computes in eval mode -- conv on activation codes -> BatchNorm -> ReLU -> [2x2 max-pool] -> the next conv's activation
+ * quantizer (wqaq/dorefa/quantize.py:36-46,107-122 around models/nin_gc.py:53-59) -- with the codes bit-plane packed:
+ *   planes : uint32 [N][ceil(C/32)][a_bits][H][W]; bit (c & 31) of plane p in word group (c >> 5) is bit p of channel c's code j in [0, 2^a - 1]; unused high bits of
+ *            the last group are 0 (a zero word = 32 activations of code 0: zero padding needs no mask).
+ * pack / unpack convert from / to the one-byte codes of mn_qa_fwd (any C; H*W % 4 == 0; 4-byte aligned tensors; 1 <= a_bits <= 8).  Bits of an input code above
+ * a_bits are dropped. */
+int mn_codes_pack_planes(const uint8_t* codes, int64_t N, int64_t C, int64_t HW, int a_bits, uint32_t* planes, mn_stream_t stream);
+int mn_codes_unpack_planes(const uint32_t* planes, int64_t N, int64_t C, int64_t HW, int a_bits, uint8_t* codes, mn_stream_t stream);
+/* The block.  Covered (mn_codeconv_supported): a_bits_in = w_bits = a_bits_out = 2; 1x1, or 3x3 with padding 1; stride 1, any groups, any number of channels per
+ * group with K * 9 <= 32767 (K = C / groups * KH * KW: the accumulator range of the 16-bit stash); g->in_shuffle 0 / 1 -- a consumer's channel shuffle is folded
+ * into its PRODUCER through `out_order`.  Everything else is MN_ENOTSUP.
+ *   pack : w = the stored fp32 weights [O][C/groups][KH][KW] on the grid (2k - n) / n, n = 2^w_bits - 1; chan = the [9][O] constants of the block's eval-mode
+ *          BatchNorm as mn_qconv_bnq_fwd_stash(training = 0) writes them -> `table` (private layout, mn_codeconv_table_bytes bytes).  out_order as in
+ *          mn_bitconv_pack.  Per row: the weight code planes, the input word offset and mask of its group, flip and the 2^a_out - 1 integer thresholds T_k found by
+ *          the search mn_qa_fwd runs on the same fp32 chain.  Word 0 of the table counts the rows whose constants are non-finite (or beyond 1e9: mn_qa_fwd's
+ *          element-wise path, which has no threshold form), word 7 the out_order entries out of range plus the rows with a weight off the grid: both 0 for a valid
+ *          table (the caller may read them back once after packing).
+ *   fwd  : acc = 2 sum j k - n sum j from popcounts over the planes, u = flip * acc, code = #{k : u >= T_k}; in_planes [N][ceil(C/32)][2][H][W], out_planes
+ *          [N][ceil(O/32)][2][H][W].  pool == 1: the 2x2 / stride 2 max-pool behind the block folded in (the code of the window's largest u; H and W even),
+ *          out_planes is [N][ceil(O/32)][2][H/2][W/2].  The table carries the bit widths it was packed for (2 / 2 / 2, the only instantiation). */
+int mn_codeconv_supported(const mn_conv_geom* g, int a_bits_in, int w_bits, int a_bits_out);
+int64_t mn_codeconv_table_bytes(const mn_conv_geom* g, int a_bits_in, int w_bits, int a_bits_out);
+int mn_codeconv_pack(const mn_conv_geom* g, const float* w, const float* chan, int a_bits_in, int w_bits, int a_bits_out, const int32_t* out_order, uint32_t* table,
+                     mn_stream_t stream);
+int mn_codeconv_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t* in_planes, uint32_t* out_planes, int pool, mn_stream_t stream);
 /* The two ends of the deployed plan on bits (inference.wbwtab_compile_bits(model, bit_ends=True)).
  *   first : bits = sign(conv(x, w) + bias) of the un-quantised first conv (real fp32 operands, the geometry of mn_conv2d_first_supported(g, 0) whose forward runs on
  *           k_c1b_fwd) in ONE launch: the accumulation is that forward's, so the value whose sign is taken is its y bit for bit; the rule is mn_bnsign_fwd_i8's with

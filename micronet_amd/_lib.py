@@ -265,6 +265,12 @@ PROTOTYPES = {
     "mn_bitconv_pack": (_I, [_G, _P, _P, _P, _P, _P]),
     "mn_bitconv_fwd": (_I, [_G, _P, _P, _P, _I, _P]),
     "mn_bits_maxpool": (_I, [_P, _L, _L, _L, _L, _I, _I, _I, _P, _P]),
+    "mn_codes_pack_planes": (_I, [_P, _L, _L, _L, _I, _P, _P]),
+    "mn_codes_unpack_planes": (_I, [_P, _L, _L, _L, _I, _P, _P]),
+    "mn_codeconv_supported": (_I, [_G, _I, _I, _I]),
+    "mn_codeconv_table_bytes": (_L, [_G, _I, _I, _I]),
+    "mn_codeconv_pack": (_I, [_G, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "mn_codeconv_fwd": (_I, [_G, _P, _P, _P, _I, _P]),
     "mn_conv2d_first_sign_bits_supported": (_I, [_G]),
     "mn_conv2d_first_sign_bits": (_I, [_G, _P, _P, _P, _P, _P]),
     "mn_bitsconv1x1_small_supported": (_I, [_L, _L, _L]),

@@ -17,8 +17,8 @@
 // the batch statistics are (they differ by fp32 round-off of the mean / variance: exact integer sums here).
 // IN = 1: the input is fp32 y (the block behind the un-quantised FIRST conv, whose output is not an integer): same kernels, 4 B/elt in.
 #include "qgemm_dev.h"
+#include "qa_thresholds.h"          // QaCh, qa_eval, qa_code_of, qa_finite, the threshold search (shared with qgemm_bits.hip)
 
-#define QA_NCH 9          // chan rows: alpha, bias, mean, invstd, gamma, beta, A = alpha*invstd, B = (bias - mean)*invstd, gi = gamma*invstd
 struct QaGeom {
     int N, C, H, W, HW, HW8, W8;
     FastDiv fd_hw8, fd_w8;
@@ -34,19 +34,6 @@ struct QaGeom {
     float* fin_dgamma_s; float* fin_dbeta_s; float* fin_sums_s;         // qr with a shortcut BatchNorm (all nullable)
     uint8_t* mask4;         // mn_qa_fwd_f32_mask (fp32 input, no pool, codes out): also the backward's pass nibbles, one byte per 4 elements (as mn_conv2d_first_bnact_fwd act 2)
 };
-struct QaCh { float alpha, bias, mean, invstd, ga, be, A, B, gi; };
-__device__ __forceinline__ QaCh qa_load_ch(const float* __restrict__ chan, int C, int c) {
-    QaCh k;
-    k.alpha = chan[c]; k.bias = chan[C + c]; k.mean = chan[2 * C + c]; k.invstd = chan[3 * C + c]; k.ga = chan[4 * C + c]; k.be = chan[5 * C + c];
-    k.A = chan[6 * C + c]; k.B = chan[7 * C + c]; k.gi = chan[8 * C + c];
-    return k;
-}
-template <int IN>
-__device__ __forceinline__ void qa_eval(float v, const QaCh& k, float& zh, float& z) {
-    const float y = IN == 1 ? v : v * k.alpha + k.bias;
-    zh = (y - k.mean) * k.invstd;
-    z = zh * k.ga + k.be;
-}
 // 8 consecutive elements (one row segment) of channel c at group index i: element offset
 __device__ __forceinline__ int64_t qa_off8(const QaGeom& g, int c, uint32_t i) {
     const uint32_t n = fd_div(i, g.fd_hw8);
@@ -90,35 +77,19 @@ __device__ __forceinline__ int qa_argmax4(const float (&a)[4]) {
 }
 
 // ---------------------------------------------------------------- forward: stash / y  ->  codes (OUT 0) or the fp32 activation (OUT 1)
-// Integer-threshold forward (stash input, codes of <= 3 bits): the code is a monotone step function of the integer accumulator -- every step of the
-// chain acc -> y -> zhat -> z -> relu -> clamp(0.1 a) -> rha(./s) is monotone in fp32 as well -- so per channel there are n = 2^a - 1 integers T_k with
-// code = #{k : u >= T_k}, u = flip * acc (flip = -1 when the chain decreases).  T_k = the smallest u whose EXACT chain value reaches k, found by a
-// binary search over the int16 range with that chain: the codes are bit-identical to the element-wise evaluation, at ~8 instead of ~20 VALU per
-// element (the pass was VALU-bound at 3.5 TB/s of 3 B/elt).  A channel with a non-finite or absurdly large constant keeps the element-wise path.
+// Integer-threshold forward (stash input, codes of <= 3 bits): code = #{k : u >= T_k}, u = flip * acc, with the per-channel integers T_k of qa_thresholds.h -- the
+// codes are bit-identical to the element-wise evaluation, at ~8 instead of ~20 VALU per element (the pass was VALU-bound at 3.5 TB/s of 3 B/elt).  A channel with a
+// non-finite or absurdly large constant keeps the element-wise path.
 #define QA_MAXTHR 7
-template <int IN>
-__device__ __forceinline__ uint32_t qa_code_of(float v, const QaCh& k, float s) { float zh, z; qa_eval<IN>(v, k, zh, z); return qa_code(qa_relu(z), s); }
-// |constant| <= 1e9 for all six: no intermediate of the chain can overflow on an int16 input (|y| <= 3.3e13, |zhat| <= 3.3e22, |z| <= 3.3e31), so no
-// inf * 0 = NaN can break the monotonicity the thresholds rely on; anything wilder (or NaN) takes the element-wise path
-__device__ __forceinline__ bool qa_finite(float v) { return fabsf(v) <= 1.0e9f; }
 template <int IN, int POOL, int OUT>
 __global__ __launch_bounds__(256) void k_qa_fwd(const QaGeom g, const void* __restrict__ in, const float* __restrict__ chan, unsigned char* __restrict__ codes,
                                                 float* __restrict__ af) {
     const int c = blockIdx.x, sp = blockIdx.y, S = gridDim.y;
     const QaCh k = qa_load_ch(chan, g.C, c);
-    if (!IN && !OUT && g.nthr > 0 && qa_finite(k.alpha) && qa_finite(k.bias) && qa_finite(k.mean) && qa_finite(k.invstd) && qa_finite(k.ga) && qa_finite(k.be)) {
+    if (!IN && !OUT && g.nthr > 0 && qa_chan_finite(k)) {
         __shared__ float thr[QA_MAXTHR + 1];
-        const float flip = (qa_code_of<0>(32767.f, k, g.s) < qa_code_of<0>(-32768.f, k, g.s)) ? -1.f : 1.f;
-        if ((int)threadIdx.x < g.nthr) {
-            // smallest u in [-32768, 32768] with code(flip * u) >= level, 32769 if none (u = 32768 only occurs as -(-32768))
-            const uint32_t level = threadIdx.x + 1u;
-            int lo = -32768, hi = 32769;                       // invariant: code(lo - 1) < level (virtually), code(hi) >= level (virtually at 32769)
-            while (lo < hi) {
-                const int mid = lo + ((hi - lo) >> 1);
-                if (qa_code_of<0>(flip * (float)mid, k, g.s) >= level) hi = mid; else lo = mid + 1;
-            }
-            thr[threadIdx.x] = (float)lo;
-        }
+        const float flip = qa_flip_of(k, g.s);
+        if ((int)threadIdx.x < g.nthr) thr[threadIdx.x] = (float)qa_threshold_of(k, g.s, flip, threadIdx.x + 1u);
         __syncthreads();
         float T[QA_MAXTHR];
 #pragma unroll

@@ -22,6 +22,9 @@
 //   tiled row       : row[0..3] as above, taps x NW pairs (s, m), then S[(KS + 1)][(KS + 1)], S[a][b] = sum of d_t over taps (ty < a, tx < b).
 // The 3x3 / stride 2 / padding 1 max-pool (models/nin.py) is an OR over the in-image cells of the window: folded into a 1x1 block (one lane = one pooled pixel, up to
 // nine decisions) or a word-wise kernel of its own behind any other producer.
+//
+// The k-bit (DoReFa W2A2) counterpart -- activation CODES as bit planes, plane-serial popcounts, the block's BatchNorm + ReLU + quantizer as integer thresholds -- is
+// qgemm_codes.h, included at the end of this file.
 #include "qgemm_dev.h"
 
 namespace mn_bits {
@@ -725,3 +728,5 @@ extern "C" int mn_bits_maxpool(const uint32_t* bits_in, int64_t N, int64_t Cw, i
     MN_CHECK_LAUNCH("mn_bits_maxpool");
     return MN_OK;
 }
+
+#include "qgemm_codes.h"          // mn_codes_* / mn_codeconv_*: the code-packed deployment of the k-bit blocks

@@ -1,0 +1,378 @@
+// Code-packed deployment of the k-bit (DoReFa) blocks conv -> bn -> relu -> [2x2 max-pool] -> next quantizer (qact_kernels.hip's block, eval mode): packed
+// activation codes in, packed activation codes out, one kernel per hidden block.  Included by qgemm_bits.hip (whose route into both builds it shares).
+//
+//   activation planes : uint32 [N][ceil(C/32)][a_bits][H][W]; bit (c & 31) of plane p in word group (c >> 5) is bit p of channel c's code j in [0, 2^a - 1]; unused
+//                       high bits of the last group are 0.  A zero word is 32 activations of CODE 0 = the value 0, so zero padding is a zero word: no border
+//                       mask, no correction term.  Planar in (H, W): lanes = pixels read coalesced dwords.
+//   accumulator       : weights (2k - n) / n, k in [0, n], n = 2^w - 1, as w_bits planes k_q.  Per output channel, over the channels c of its group and the taps:
+//                         sum_c j_c k_c = sum_p sum_q 2^(p+q) popc(x_p & k_q)          sum_c j_c = sum_p 2^p popc(x_p & gmask)   (once per lane and group)
+//                         acc = 2 sum j k - n sum j          -- the exact integer the byte path stashes (qgemm_sign.hip: mn_qconv_bnq_fwd_stash)
+//   code              : u = flip * acc, code = #{k : u >= T_k}, T_k the integer thresholds of qa_thresholds.h (the search k_qa_fwd runs, on the same fp32 chain).
+//                       2x2 max-pool: the code of the largest u of the window (the pool sits behind the ReLU and the quantizer is non-decreasing: exact).
+//   weight table      : (private layout) 8 header words -- [0] rows whose channel constants fail qa_finite, [1] NW, [2] taps, [3] row stride, [4] rows, [5] Cw,
+//                       [6] a_in | w_bits << 8 | a_out << 16, [7] bad out_order entries + rows with a weight off the grid -- then one row per output position, the
+//                       32 rows of an output word SORTED BY GROUP (a lane keeps a group's input words and sum j in registers across all rows of the group):
+//                         row[0] = w0 (first input word group the row reads), row[1] = flip (+-1), row[2] = bit position in the output word, row[3] = 1: another
+//                         group than the row before, row[4..6] = T_1..T_3, row[7] = 0, then taps x NW x w_bits weight planes, then NW group-mask words.
+//   consumer order    : the row at bit position j of an output word computes channel out_order[32 * word + j] (mn_bitconv_pack's convention).
+// Covered: a_in = w_bits = a_out = 2; 1x1 and 3x3 / padding 1, stride 1, any groups, the 2x2 / stride 2 pool folded or not.
+#pragma once
+#include "qa_thresholds.h"
+
+namespace mn_codes {
+
+enum { HDR = 8, ROWHDR = 8, A = 2, WB = 2, NTHR = 3 };
+
+struct Geom {
+    int N, C, H, W, O, KS, groups;
+    int Cg, Og, K, taps, Cw, OW, NW, stride;
+    float s;          // the output quantizer's scale, dorefa_scale(a_bits_out): what mn_qa_fwd evaluates the chain with
+};
+
+static inline bool make_geom(const mn_conv_geom* g, int a_in, int w_bits, int a_out, Geom& q) {
+    if (!g || g->N <= 0 || g->C <= 0 || g->H <= 0 || g->W <= 0 || g->O <= 0 || g->groups <= 0) return false;
+    if (a_in != A || w_bits != WB || a_out != 2) return false;          // (3- and 4-bit codes: not instantiated)
+    if (g->KH != g->KW || (g->KH != 1 && g->KH != 3)) return false;
+    const int pad = (g->KH - 1) / 2;
+    if (g->stride_h != 1 || g->stride_w != 1 || g->dil_h != 1 || g->dil_w != 1 || g->pad_h != pad || g->pad_w != pad) return false;
+    if (g->C % g->groups || g->O % g->groups || g->in_shuffle > 1) return false;      // a channel shuffle is folded into the PRODUCER's row order, never gathered here
+    q.N = g->N; q.C = g->C; q.H = g->H; q.W = g->W; q.O = g->O; q.KS = g->KH; q.groups = g->groups;
+    q.Cg = g->C / g->groups; q.Og = g->O / g->groups; q.taps = g->KH * g->KW;
+    if ((int64_t)q.Cg * q.taps * ((1 << a_in) - 1) * ((1 << w_bits) - 1) > 32767) return false;          // the thresholds are searched over the int16 range of the stash
+    q.K = q.Cg * q.taps;
+    q.Cw = (g->C + 31) >> 5; q.OW = (g->O + 31) >> 5;
+    q.NW = mn_bits::span_words(g->C, g->groups);
+    q.stride = ROWHDR + q.taps * q.NW * WB + q.NW;
+    q.s = dorefa_scale(a_out);
+    const int64_t words = (int64_t)g->N * A * (q.Cw > q.OW ? q.Cw : q.OW) * g->H * g->W;
+    if (words >= (1ll << 31) || (int64_t)q.OW * 32 * q.stride >= (1ll << 30)) return false;
+    return true;
+}
+
+// ---------------------------------------------------------------- uint8 codes <-> planes
+// one thread = 4 consecutive pixels of one channel word group: 32 aligned dword reads of 4 codes each per plane, 4 words out per plane.  Only planes p < a_bits are
+// extracted: a code above 2^a - 1 is masked, not propagated.
+__global__ __launch_bounds__(256) void k_codes_pack(const uint8_t* __restrict__ a, uint32_t* __restrict__ planes, int64_t total, int C, int Cw, int HW4, int abits) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int p4 = (int)(i % HW4);
+    const int64_t t = i / HW4;
+    const int cw = (int)(t % Cw);
+    const int64_t n = t / Cw;
+    const int HW = HW4 * 4;
+    const int cend = C - cw * 32 < 32 ? C - cw * 32 : 32;
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(a + (n * C + (int64_t)cw * 32) * HW) + p4;
+    for (int p = 0; p < abits; ++p) {
+        uint32_t o0 = 0, o1 = 0, o2 = 0, o3 = 0;
+        for (int b = 0; b < cend; ++b) {
+            const uint32_t v = src[(int64_t)b * HW4] >> p;
+            o0 |= (v & 1u) << b; o1 |= ((v >> 8) & 1u) << b; o2 |= ((v >> 16) & 1u) << b; o3 |= ((v >> 24) & 1u) << b;
+        }
+        uint32_t* dst = planes + ((n * Cw + cw) * abits + p) * HW + 4 * p4;
+        dst[0] = o0; dst[1] = o1; dst[2] = o2; dst[3] = o3;
+    }
+}
+
+// one thread = 4 consecutive pixels of one channel: 4 words in per plane, one dword of 4 codes out
+__global__ __launch_bounds__(256) void k_codes_unpack(const uint32_t* __restrict__ planes, uint8_t* __restrict__ a, int64_t total, int C, int Cw, int HW4, int abits) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int p4 = (int)(i % HW4);
+    const int64_t t = i / HW4;
+    const int c = (int)(t % C);
+    const int64_t n = t / C;
+    const int HW = HW4 * 4;
+    uint32_t r = 0;
+    for (int p = 0; p < abits; ++p) {
+        const uint32_t* src = planes + ((n * Cw + (c >> 5)) * abits + p) * HW + 4 * p4;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) r |= ((src[e] >> (c & 31)) & 1u) << (8 * e + p);
+    }
+    reinterpret_cast<uint32_t*>(a + (n * C + c) * HW)[p4] = r;
+}
+
+// ---------------------------------------------------------------- weight table: one block per output position
+__global__ __launch_bounds__(256) void k_codes_wpack(Geom q, const float* __restrict__ w, const float* __restrict__ chan, const int32_t* __restrict__ order,
+                                                     uint32_t* __restrict__ tab) {
+    __shared__ int sh[256];
+    const int j = blockIdx.x, tid = threadIdx.x, wd = j >> 5;
+    if (j == 0 && tid == 0) {
+        tab[1] = (uint32_t)q.NW; tab[2] = (uint32_t)q.taps; tab[3] = (uint32_t)q.stride; tab[4] = (uint32_t)(q.OW * 32); tab[5] = (uint32_t)q.Cw;
+        tab[6] = (uint32_t)(A | (WB << 8) | (2 << 16));
+    }
+    // the channel and group of every position of this output word (a bad out_order entry or a position past O: no channel, sorted last, the row never fires)
+    auto chan_of = [&](int jj) { const int o = jj < q.O ? (order ? order[jj] : jj) : -1; return (o >= 0 && o < q.O) ? o : -1; };
+    const int o = chan_of(j);
+    const int grp = o < 0 ? INT_MAX : o / q.Og;
+    int rank = 0, same_before = 0;
+    for (int jj = wd * 32; jj < wd * 32 + 32; ++jj) {
+        const int oo = chan_of(jj);
+        const int gg = oo < 0 ? INT_MAX : oo / q.Og;
+        rank += (gg < grp) || (gg == grp && jj < j);
+        same_before |= (gg == grp && jj < j);
+    }
+    uint32_t* row = tab + HDR + (int64_t)(wd * 32 + rank) * q.stride;
+    if (j < q.O && o < 0 && tid == 0) atomicAdd(tab + 7, 1u);
+    if (o < 0) {
+        for (int i = tid; i < q.stride; i += 256) row[i] = i == 1 ? 1u : i == 2 ? (uint32_t)(j & 31) : i == 3 ? (uint32_t)!same_before : (i >= 4 && i < 4 + NTHR) ? 0x7fffffffu : 0u;
+        return;
+    }
+    const int c0 = grp * q.Cg;
+    int w0 = c0 >> 5;
+    if (w0 > q.Cw - q.NW) w0 = q.Cw - q.NW;          // every row reads NW word groups per tap: keep the window inside the pixel's words
+    const float* wr = w + (int64_t)o * q.K;          // [Cg][taps]
+    const float nf = (float)((1 << WB) - 1);
+    int off = 0;
+    for (int idx = tid; idx < q.taps * q.NW; idx += 256) {
+        const int t = idx / q.NW, k = idx - t * q.NW;
+        uint32_t pl[WB] = {0u, 0u};
+        for (int b = 0; b < 32; ++b) {
+            const int ci = (w0 + k) * 32 + b - c0;
+            if (ci >= 0 && ci < q.Cg) {
+                const float kf = (wr[ci * q.taps + t] * nf + nf) * 0.5f;          // w = (2k - n) / n
+                const float kr = rintf(kf);
+                if (!(fabsf(kf - kr) <= 1e-3f) || kr < 0.f || kr > nf) off = 1;
+                const uint32_t kc = (uint32_t)(kr < 0.f ? 0.f : kr > nf ? nf : kr == kr ? kr : 0.f);
+#pragma unroll
+                for (int qq = 0; qq < WB; ++qq) pl[qq] |= ((kc >> qq) & 1u) << b;
+            }
+        }
+#pragma unroll
+        for (int qq = 0; qq < WB; ++qq) row[ROWHDR + idx * WB + qq] = pl[qq];
+    }
+    for (int k = tid; k < q.NW; k += 256) {
+        uint32_t m = 0;
+        for (int b = 0; b < 32; ++b) {
+            const int ci = (w0 + k) * 32 + b - c0;
+            m |= (uint32_t)(ci >= 0 && ci < q.Cg) << b;
+        }
+        row[ROWHDR + q.taps * q.NW * WB + k] = m;
+    }
+    sh[tid] = off;
+    __syncthreads();
+    if (tid == 0) {
+        int any = 0;
+        for (int i = 0; i < 256; ++i) any |= sh[i];
+        if (any) atomicAdd(tab + 7, 1u);
+    }
+    // thresholds: the search of k_qa_fwd on the block's eval-mode constants
+    const QaCh k = qa_load_ch(chan, q.O, o);
+    const float s = q.s;
+    const bool fin = qa_chan_finite(k);
+    const float flip = fin ? qa_flip_of(k, s) : 1.f;
+    if (tid < NTHR) row[4 + tid] = fin ? (uint32_t)qa_threshold_of(k, s, flip, (uint32_t)tid + 1u) : 0x7fffffffu;
+    if (tid == 0) {
+        if (!fin) atomicAdd(tab + 0, 1u);
+        row[0] = (uint32_t)w0;
+        row[1] = (uint32_t)(flip < 0.f ? -1 : 1);
+        row[2] = (uint32_t)(j & 31);
+        row[3] = (uint32_t)!same_before;
+        row[7] = 0u;
+    }
+}
+
+// ---------------------------------------------------------------- plane-serial popcount convolution + thresholds -> output planes
+struct Fwd {
+    int total, Cw, H, W, Ho, Wo, OW, nw, stride, owpb;
+};
+
+// One lane owns one output pixel (POOL: one pooled pixel = the 2x2 window) and loops over the 32 rows of an output word; the row's words are wave-uniform (scalar
+// loads).  NW > 0: the lane's input patch -- (KS + POOL)^2 cells x NW word groups x 2 planes -- lives in registers and is reloaded only when the row's group changes
+// (rows are sorted by group).  NW == 0: any span, rolled loops, the words re-read per row (they stay in L1 / L2); registers stay flat.
+template <int KS, int NW, bool POOL>
+__global__ __launch_bounds__(256) void k_codeconv(const uint32_t* __restrict__ tab, const uint32_t* __restrict__ x, uint32_t* __restrict__ y, Fwd q) {
+    constexpr int SUB = POOL ? 4 : 1, PD = (POOL ? 2 : 1) + KS - 1, CELLS = PD * PD, P = (KS - 1) / 2, NWR = NW ? NW : 1;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= q.total) return;
+    const int nw = NW ? NW : q.nw;
+    const int HWo = q.Ho * q.Wo, HW = q.H * q.W;
+    const int n = p / HWo, r = p - n * HWo;
+    const int oh = r / q.Wo, ow = r - oh * q.Wo;
+    const int ph0 = (POOL ? 2 * oh : oh) - P, pw0 = (POOL ? 2 * ow : ow) - P;
+    const uint32_t* xn = x + (int64_t)n * q.Cw * A * HW;
+    int off[CELLS];          // pixel offset of every cell of the patch, -1 outside the image (a zero word: code 0)
+#pragma unroll
+    for (int c = 0; c < CELLS; ++c) {
+        const int ih = ph0 + c / PD, iw = pw0 + c % PD;
+        off[c] = (ih >= 0 && ih < q.H && iw >= 0 && iw < q.W) ? ih * q.W + iw : -1;
+    }
+    uint32_t xr[CELLS * NWR * A];
+#pragma unroll
+    for (int i = 0; i < CELLS * NWR * A; ++i) xr[i] = 0u;
+    int S[SUB];          // sum of the group's input codes over the taps of sub-pixel s
+#pragma unroll
+    for (int s = 0; s < SUB; ++s) S[s] = 0;
+    const int ow0 = blockIdx.y * q.owpb;
+    const int ow1 = ow0 + q.owpb < q.OW ? ow0 + q.owpb : q.OW;
+    for (int owi = ow0; owi < ow1; ++owi) {
+        const uint32_t* rowp = tab + HDR + (int64_t)owi * 32 * q.stride;
+        uint32_t word0 = 0, word1 = 0;
+        for (int j = 0; j < 32; ++j) {
+            const uint32_t* row = rowp + j * q.stride;          // wave-uniform: every word of the row is a scalar operand
+            const uint32_t* wp = row + ROWHDR;
+            const uint32_t* xw = xn + (int64_t)row[0] * A * HW;
+            if (row[3]) {          // (wave-uniform) a new group: its input words and the sum of its codes
+                const uint32_t* gm = wp + KS * KS * nw * WB;
+                if (NW) {
+#pragma unroll
+                    for (int c = 0; c < CELLS; ++c)
+#pragma unroll
+                        for (int k = 0; k < NWR; ++k)
+#pragma unroll
+                            for (int a = 0; a < A; ++a) xr[(c * NWR + k) * A + a] = off[c] >= 0 ? xw[(k * A + a) * HW + off[c]] : 0u;
+                }
+#pragma unroll
+                for (int s = 0; s < SUB; ++s) {
+                    int sum = 0;
+#pragma unroll
+                    for (int t = 0; t < KS * KS; ++t) {
+                        const int c = ((s >> 1) + t / KS) * PD + (s & 1) + t % KS;
+                        if (NW) {
+#pragma unroll
+                            for (int k = 0; k < NWR; ++k)
+                                sum += mn_popc(xr[(c * NWR + k) * A] & gm[k]) + 2 * mn_popc(xr[(c * NWR + k) * A + 1] & gm[k]);
+                        } else if (off[c] >= 0) {
+#pragma unroll 1
+                            for (int k = 0; k < nw; ++k)
+                                sum += mn_popc(xw[(k * A) * HW + off[c]] & gm[k]) + 2 * mn_popc(xw[(k * A + 1) * HW + off[c]] & gm[k]);
+                        }
+                    }
+                    S[s] = sum;
+                }
+            }
+            const int flip = (int)row[1];
+            int um = INT_MIN;
+#pragma unroll
+            for (int s = 0; s < SUB; ++s) {
+                int d0 = 0, d1 = 0, d2 = 0;          // weights 1, 2, 4 of sum_p sum_q 2^(p+q) popc(x_p & k_q)
+#pragma unroll
+                for (int t = 0; t < KS * KS; ++t) {
+                    const int c = ((s >> 1) + t / KS) * PD + (s & 1) + t % KS;
+                    if (NW) {
+#pragma unroll
+                        for (int k = 0; k < NWR; ++k) {
+                            const uint32_t x0 = xr[(c * NWR + k) * A], x1 = xr[(c * NWR + k) * A + 1];
+                            const uint32_t k0 = wp[(t * NWR + k) * WB], k1 = wp[(t * NWR + k) * WB + 1];
+                            d0 += mn_popc(x0 & k0); d1 += mn_popc(x0 & k1) + mn_popc(x1 & k0); d2 += mn_popc(x1 & k1);
+                        }
+                    } else if (off[c] >= 0) {
+#pragma unroll 1
+                        for (int k = 0; k < nw; ++k) {
+                            const uint32_t x0 = xw[(k * A) * HW + off[c]], x1 = xw[(k * A + 1) * HW + off[c]];
+                            const uint32_t k0 = wp[(t * nw + k) * WB], k1 = wp[(t * nw + k) * WB + 1];
+                            d0 += mn_popc(x0 & k0); d1 += mn_popc(x0 & k1) + mn_popc(x1 & k0); d2 += mn_popc(x1 & k1);
+                        }
+                    }
+                }
+                const int acc = 2 * (d0 + 2 * d1 + 4 * d2) - 3 * S[s];
+                const int u = flip * acc;
+                um = u > um ? u : um;
+            }
+            const uint32_t code = (uint32_t)(um >= (int)row[4]) + (uint32_t)(um >= (int)row[5]) + (uint32_t)(um >= (int)row[6]);
+            word0 |= (code & 1u) << row[2];
+            word1 |= (code >> 1) << row[2];
+        }
+        uint32_t* yo = y + ((int64_t)n * q.OW + owi) * A * HWo + r;
+        yo[0] = word0;
+        yo[HWo] = word1;
+    }
+}
+
+template <int KS, bool POOL>
+static void launch_nw(int nwsel, dim3 grid, hipStream_t s, const uint32_t* tab, const uint32_t* x, uint32_t* y, const Fwd& f) {
+    switch (nwsel) {
+    case 1: hipLaunchKernelGGL((k_codeconv<KS, 1, POOL>), grid, dim3(256), 0, s, tab, x, y, f); break;
+    case 2: if (KS == 1) { hipLaunchKernelGGL((k_codeconv<1, 2, POOL>), grid, dim3(256), 0, s, tab, x, y, f); break; }
+    case 4: if (KS == 1) { hipLaunchKernelGGL((k_codeconv<1, 4, POOL>), grid, dim3(256), 0, s, tab, x, y, f); break; }
+    default: hipLaunchKernelGGL((k_codeconv<KS, 0, POOL>), grid, dim3(256), 0, s, tab, x, y, f); break;
+    }
+}
+static inline int nw_select(const Geom& q) { return (q.NW == 1 || (q.KS == 1 && (q.NW == 2 || q.NW == 4))) ? q.NW : 0; }
+
+static inline bool planes_args_ok(const void* a, const void* b, int64_t N, int64_t C, int64_t HW, int a_bits) {
+    return a && b && N > 0 && C > 0 && HW > 0 && HW % 4 == 0 && !(((uintptr_t)a) & 3) && !(((uintptr_t)b) & 3) && C <= (1 << 20) && HW <= (1 << 26) && a_bits >= 1 && a_bits <= 8;
+}
+
+}  // namespace mn_codes
+
+extern "C" int mn_codes_pack_planes(const uint8_t* codes, int64_t N, int64_t C, int64_t HW, int a_bits, uint32_t* planes, mn_stream_t stream) {
+    if (!mn_codes::planes_args_ok(codes, planes, N, C, HW, a_bits)) MN_FAIL(MN_EINVAL, "mn_codes_pack_planes: needs H*W %% 4 == 0, 1 <= a_bits <= 8 and 4-byte aligned tensors");
+    const int Cw = (int)((C + 31) >> 5);
+    const int64_t total = N * Cw * (HW / 4);
+    if (total > (int64_t)INT_MAX * 256 || N * Cw * a_bits * HW >= (1ll << 40)) MN_FAIL(MN_ENOTSUP, "mn_codes_pack_planes: tensor too large");
+    mn_set_last_kernel("k_codes_pack"); mn_prof_bytes((double)N * C * HW + 4.0 * N * Cw * a_bits * HW); mn_prof_begin((hipStream_t)stream);
+    hipLaunchKernelGGL(mn_codes::k_codes_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, codes, planes, total, (int)C, Cw, (int)(HW / 4), a_bits);
+    mn_prof_end((hipStream_t)stream);
+    MN_CHECK_LAUNCH("mn_codes_pack_planes");
+    return MN_OK;
+}
+
+extern "C" int mn_codes_unpack_planes(const uint32_t* planes, int64_t N, int64_t C, int64_t HW, int a_bits, uint8_t* codes, mn_stream_t stream) {
+    if (!mn_codes::planes_args_ok(codes, planes, N, C, HW, a_bits)) MN_FAIL(MN_EINVAL, "mn_codes_unpack_planes: needs H*W %% 4 == 0, 1 <= a_bits <= 8 and 4-byte aligned tensors");
+    const int Cw = (int)((C + 31) >> 5);
+    const int64_t total = N * C * (HW / 4);
+    if (total > (int64_t)INT_MAX * 256 || N * Cw * a_bits * HW >= (1ll << 40)) MN_FAIL(MN_ENOTSUP, "mn_codes_unpack_planes: tensor too large");
+    mn_set_last_kernel("k_codes_unpack"); mn_prof_bytes((double)N * C * HW + 4.0 * N * Cw * a_bits * HW); mn_prof_begin((hipStream_t)stream);
+    hipLaunchKernelGGL(mn_codes::k_codes_unpack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, planes, codes, total, (int)C, Cw, (int)(HW / 4), a_bits);
+    mn_prof_end((hipStream_t)stream);
+    MN_CHECK_LAUNCH("mn_codes_unpack_planes");
+    return MN_OK;
+}
+
+extern "C" int mn_codeconv_supported(const mn_conv_geom* g, int a_bits_in, int w_bits, int a_bits_out) {
+    mn_codes::Geom q;
+    return mn_codes::make_geom(g, a_bits_in, w_bits, a_bits_out, q) ? 1 : 0;
+}
+
+extern "C" int64_t mn_codeconv_table_bytes(const mn_conv_geom* g, int a_bits_in, int w_bits, int a_bits_out) {
+    mn_codes::Geom q;
+    if (!mn_codes::make_geom(g, a_bits_in, w_bits, a_bits_out, q)) return 0;
+    return 4 * ((int64_t)mn_codes::HDR + (int64_t)q.OW * 32 * q.stride);
+}
+
+#define MN_CODECONV_COVER "geometry not covered (2-bit codes and weights; 1x1 or 3x3 / padding 1, stride 1, no input shuffle, K * 9 <= 32767)"
+extern "C" int mn_codeconv_pack(const mn_conv_geom* g, const float* w, const float* chan, int a_bits_in, int w_bits, int a_bits_out, const int32_t* out_order,
+                                uint32_t* table, mn_stream_t stream) {
+    mn_codes::Geom q;
+    if (!w || !chan || !table || (((uintptr_t)table) & 3)) MN_FAIL(MN_EINVAL, "mn_codeconv_pack: null / unaligned argument");
+    if (!mn_codes::make_geom(g, a_bits_in, w_bits, a_bits_out, q)) MN_FAIL(MN_ENOTSUP, "mn_codeconv_pack: " MN_CODECONV_COVER);
+    if (hipMemsetAsync(table, 0, 4 * mn_codes::HDR, (hipStream_t)stream) != hipSuccess) MN_FAIL(MN_EHIP, "mn_codeconv_pack: header reset failed");          // the two counters
+    mn_set_last_kernel("k_codes_wpack");
+    hipLaunchKernelGGL(mn_codes::k_codes_wpack, dim3(q.OW * 32), dim3(256), 0, (hipStream_t)stream, q, w, chan, out_order, table);
+    MN_CHECK_LAUNCH("mn_codeconv_pack");
+    return MN_OK;
+}
+
+extern "C" int mn_codeconv_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t* in_planes, uint32_t* out_planes, int pool, mn_stream_t stream) {
+    mn_codes::Geom q;
+    if (!table || !in_planes || !out_planes) MN_FAIL(MN_EINVAL, "mn_codeconv_fwd: null argument");
+    if (!mn_codes::make_geom(g, mn_codes::A, mn_codes::WB, 2, q)) MN_FAIL(MN_ENOTSUP, "mn_codeconv_fwd: " MN_CODECONV_COVER);
+    if (pool < 0 || pool > 1) MN_FAIL(MN_ENOTSUP, "mn_codeconv_fwd: pool must be 0 or 1 (2x2 / stride 2); the 3x3 / stride 2 pool is not folded");
+    if (pool && ((q.H & 1) || (q.W & 1))) MN_FAIL(MN_EINVAL, "mn_codeconv_fwd: the folded 2x2 max-pool needs even H and W");
+    mn_codes::Fwd f;
+    f.Cw = q.Cw; f.H = q.H; f.W = q.W; f.OW = q.OW; f.nw = q.NW; f.stride = q.stride;
+    f.Ho = pool ? q.H / 2 : q.H; f.Wo = pool ? q.W / 2 : q.W;
+    f.total = q.N * f.Ho * f.Wo;
+    const int bx = (f.total + 255) / 256;
+    int gy = (2048 + bx - 1) / bx;          // enough blocks to fill the chip: split the output words over grid.y when the pixels alone do not
+    if (gy > q.OW) gy = q.OW;
+    f.owpb = (q.OW + gy - 1) / gy;
+    gy = (q.OW + f.owpb - 1) / f.owpb;
+    const dim3 grid(bx, gy);
+    const hipStream_t s = (hipStream_t)stream;
+    const int nwsel = mn_codes::nw_select(q);
+    mn_set_last_kernel("k_codeconv<%d,%d,%d>", q.KS, nwsel, pool);
+    mn_prof_bytes(4.0 * mn_codes::A * q.N * q.Cw * q.H * q.W + 4.0 * mn_codes::A * q.N * q.OW * f.Ho * f.Wo + 4.0 * (mn_codes::HDR + (double)q.OW * 32 * q.stride));
+    mn_prof_begin(s);
+    if (q.KS == 1) {
+        if (pool) mn_codes::launch_nw<1, true>(nwsel, grid, s, table, in_planes, out_planes, f);
+        else mn_codes::launch_nw<1, false>(nwsel, grid, s, table, in_planes, out_planes, f);
+    } else {
+        if (pool) mn_codes::launch_nw<3, true>(nwsel, grid, s, table, in_planes, out_planes, f);
+        else mn_codes::launch_nw<3, false>(nwsel, grid, s, table, in_planes, out_planes, f);
+    }
+    mn_prof_end(s);
+    MN_CHECK_LAUNCH("mn_codeconv_fwd");
+    return MN_OK;
+}
+#undef MN_CODECONV_COVER

@@ -15,7 +15,11 @@ The results are ordinary modules of this package: in eval mode they run on the s
   * ``wbwtab_compile_bits``: the folded W-ternary / W-binary, A-binary graph compiled into a flat plan that keeps ONE BIT per hidden activation
     (``csrc/qgemm_bits.hip``: XNOR / AND / popcount against bit-plane weight tables, bias and alpha folded into an integer threshold per channel).  It computes
     exactly what the folded graph computes -- same signs in every hidden stage, same logits to the bit.  ``bit_ends=True``: the two ends stay on bits as well -- the
-    first conv writes activation bits in one launch (``mn_conv2d_first_sign_bits``), the classifier reads them (``mn_bitsconv1x1_small_fwd``)."""
+    first conv writes activation bits in one launch (``mn_conv2d_first_sign_bits``), the classifier reads them (``mn_bitsconv1x1_small_fwd``).
+
+  * ``dorefa_compile_codes``: a pre-quantised DoReFa W2A2 ``quant_inference=True`` net compiled into a flat plan that keeps TWO BITS per hidden activation
+    (``csrc/qgemm_codes.h``: activation codes as bit planes, plane-serial popcounts against weight code planes, the block's BatchNorm + ReLU + quantizer as integer
+    thresholds per channel).  One kernel per hidden block, packed codes in, packed codes out; same codes in every hidden stage as the eval-mode model."""
 import copy
 
 import torch
@@ -491,3 +495,297 @@ def wbwtab_compile_bits(model, bit_ends=False):
         if nbad:
             raise _err("wbwtab_compile_bits: %s.conv: %d output channels whose decision is not monotone in the accumulator" % (nm, nbad))
     return BitPlan(first, layers, last, tail, flatten, report, bit_ends)
+
+
+# ------------------------------------------------------------------------------------------------ code-packed deployment of DoReFa W2A2 nets (csrc/qgemm_codes.h)
+CODE_BITS = 2          # the one instantiation: a_bits = w_bits = 2
+
+
+def pack_codes(t, bits=None):
+    """uint8 activation codes [N, C, H, W] (or a QActTensor) -> int32 tensor [N, ceil(C / 32), bits, H, W] of uint32 words: bit c & 31 of plane p in word group c >> 5 is
+    bit p of channel c's code.  Bits of a code above ``bits`` are dropped."""
+    from micronet_amd import ops
+    from micronet_amd.sign_tensor import QActTensor
+    if isinstance(t, QActTensor):
+        t, bits = t.codes, (t.bits if bits is None else bits)
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 4 and bits is not None and 1 <= int(bits) <= 8):
+        raise _err("pack_codes: needs a QActTensor, or a uint8 code tensor [N, C, H, W] on the GPU and its bit width (no CPU fallback)")
+    c = t.contiguous()
+    N, Cc, H, W = c.shape
+    planes = torch.empty((N, (Cc + 31) // 32, int(bits), H, W), dtype=torch.int32, device=c.device)
+    ops._call("mn_codes_pack_planes", ops._p(c), N, Cc, H * W, int(bits), ops._p(planes), ops._s())
+    return planes
+
+
+def unpack_codes(planes, C):
+    """The inverse of ``pack_codes``: uint8 codes [N, C, H, W]."""
+    from micronet_amd import ops
+    if not (torch.is_tensor(planes) and planes.is_cuda and planes.dtype == torch.int32 and planes.dim() == 5 and planes.shape[1] == (int(C) + 31) // 32
+            and 1 <= planes.shape[2] <= 8):
+        raise _err("unpack_codes: needs an int32 plane tensor [N, ceil(C / 32), bits, H, W] on the GPU")
+    planes = planes.contiguous()
+    N, _, bits, H, W = planes.shape
+    out = torch.empty((N, int(C), H, W), dtype=torch.uint8, device=planes.device)
+    ops._call("mn_codes_unpack_planes", ops._p(planes), N, int(C), H * W, int(bits), ops._p(out), ops._s())
+    return out
+
+
+def _codeconv_kernel_name(k, cin, groups, pool):
+    """The kernel mn_codeconv_fwd launches for a hidden block (csrc/qgemm_codes.h: nw_select)."""
+    cg = cin // groups
+    nw = max(((gi * cg + cg - 1) >> 5) - ((gi * cg) >> 5) + 1 for gi in range(groups))
+    sel = nw if (nw == 1 or (k == 1 and nw in (2, 4))) else 0
+    return "k_codeconv<%d,%d,%d>" % (k, sel, pool)
+
+
+class CodePlan(nn.Module):
+    """What ``dorefa_compile_codes`` returns: first block (fp32 conv + BatchNorm + ReLU + the next conv's quantizer, the model's own module) -> plane pack -> n
+    code blocks (2x2 max-pools folded in) -> plane unpack -> last block and tail (the model's own modules).  Eval only; owns the packed weight tables (and the
+    per-channel constants they were packed from: ``layers[i]["chan"]``) and one set of plane buffers per input shape."""
+
+    def __init__(self, first, layers, last, tail, flatten, report):
+        super().__init__()
+        self.first, self.last, self.tail = first, last, nn.ModuleList(tail)
+        self.layers = layers              # dicts: geometry, table, chan, pool, out_order
+        self.flatten = flatten
+        self.report = report
+        self.keep_stages = False          # True: forward also leaves every stage's planes in ``stage_codes`` (tests)
+        self.stage_codes = []
+        self._ws = {}
+        self.eval()
+
+    def train(self, mode=True):
+        if mode:
+            raise _err("dorefa_compile_codes: the compiled plan is eval-only")
+        return super().train(False)
+
+    def _plan_buffers(self, shape, device):
+        """Plane buffers (and the uint8 buffer in front of the last block) for one first-block output shape; allocated once, reused by every later call."""
+        from micronet_amd import _lib
+        key = (tuple(shape), str(device))
+        if key not in self._ws:
+            N, Cc, H, W = shape
+            if (H * W) % 4:
+                raise _err("dorefa_compile_codes: %s: its %d x %d output cannot be packed (mn_codes_pack_planes needs H * W %% 4 == 0)" % (self.report[0]["name"], H, W))
+            bufs, geoms = [torch.empty((N, (Cc + 31) // 32, CODE_BITS, H, W), dtype=torch.int32, device=device)], []
+            for L in self.layers:
+                k, p = L["k"], L["pad"]
+                geoms.append(_lib.ConvGeom(N, L["cin"], H, W, L["cout"], k, k, 1, 1, p, p, 1, 1, L["groups"], 0))
+                if L["pool"]:
+                    if H % 2 or W % 2:
+                        raise _err("dorefa_compile_codes: %s: the 2x2 max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
+                    H, W = H // 2, W // 2
+                bufs.append(torch.empty((N, (L["cout"] + 31) // 32, CODE_BITS, H, W), dtype=torch.int32, device=device))
+                Cc = L["cout"]
+            if (H * W) % 4:
+                raise _err("dorefa_compile_codes: %s: its %d x %d output cannot be unpacked for the last block (mn_codes_unpack_planes needs H * W %% 4 == 0)"
+                           % (self.layers[-1]["name"], H, W))
+            self._ws[key] = (bufs, geoms, torch.empty((N, Cc, H, W), dtype=torch.uint8, device=device))
+        return self._ws[key]
+
+    @torch.no_grad()
+    def forward(self, x):
+        import ctypes as C
+        from micronet_amd import ops
+        from micronet_amd.sign_tensor import QActTensor
+        a = self.first(x)
+        if not (isinstance(a, QActTensor) and a.bits == CODE_BITS):
+            raise _err("dorefa_compile_codes: %s did not hand over %d-bit activation codes (the input must be a contiguous float32 GPU tensor with H * W %% 8 == 0)"
+                       % (self.report[0]["name"], CODE_BITS))
+        codes = a.codes.contiguous()
+        N, Cc, H, W = codes.shape
+        bufs, geoms, c8 = self._plan_buffers(codes.shape, codes.device)
+        st = ops._s()
+        ops._call("mn_codes_pack_planes", ops._p(codes), N, Cc, H * W, CODE_BITS, ops._p(bufs[0]), st)
+        for i, L in enumerate(self.layers):
+            ops._call("mn_codeconv_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(bufs[i + 1]), int(L["pool"]), st)
+        if self.keep_stages:
+            self.stage_codes = [b.clone() for b in bufs]
+        n_, c_, h_, w_ = c8.shape
+        ops._call("mn_codes_unpack_planes", ops._p(bufs[-1]), n_, c_, h_ * w_, CODE_BITS, ops._p(c8), st)
+        # (materialize: a consumer that does not read codes re-quantises 10 j s to j -- the middle of the code's bin)
+        y = self.last(QActTensor(c8, CODE_BITS, lambda: c8.float() * (10.0 / (2 ** CODE_BITS - 1))))
+        for m in self.tail:
+            y = m(y)
+        return y.view(y.size(0), -1) if self.flatten else y
+
+
+def _walk_codes(model):
+    """The graph walk of ``dorefa_compile_codes`` (no GPU needed): (first, layers, last, tail, flatten, report)."""
+    import ctypes as C
+    from micronet_amd import _lib
+    from micronet_amd.nn import Conv2dFirst
+    from micronet_amd.quantization.wqaq.dorefa import quantize
+    if isinstance(model, nn.Sequential):
+        seq, prefix, flatten = model, "", False
+    else:
+        kids = list(model.named_children())
+        if len(kids) != 1 or not isinstance(kids[0][1], nn.Sequential):
+            raise _err("dorefa_compile_codes: module order not recognised (%s: expected an nn.Sequential of blocks, or the reference's Net holding one)" % type(model).__name__)
+        seq, prefix, flatten = kids[0][1], kids[0][0] + ".", True          # models/nin_gc.py:144-147: forward = model(x).view(N, -1)
+    blocks = [(prefix + n_, m) for n_, m in seq.named_children() if quantize._is_ref_block(m) and isinstance(getattr(m, "conv", None), nn.Conv2d)]
+    if len(blocks) < 3:
+        raise _err("dorefa_compile_codes: module order not recognised (needs a first block, at least one quantised hidden block and a last block)")
+    # ---- what the kernels are instantiated for, checked over the whole net first: the error names the layer
+    for nm, blk in blocks[1:]:
+        conv = blk.conv
+        if not isinstance(conv, quantize.QuantConv2d):
+            raise _err("dorefa_compile_codes: %s.conv is not a DoReFa QuantConv2d" % nm)
+        ab, wb = conv.activation_quantizer.a_bits, conv.weight_quantizer.w_bits
+        if ab != CODE_BITS or wb != CODE_BITS:
+            raise _err("dorefa_compile_codes: %s.conv has a_bits = %d, w_bits = %d; only 2-bit codes and 2-bit weights are code-packed" % (nm, ab, wb))
+        if not conv.quant_inference:
+            raise _err("dorefa_compile_codes: %s.conv is not a quant_inference=True layer (prepare(..., quant_inference=True), then prequantize_weights)" % nm)
+    for nm, blk in blocks[1:-1]:
+        conv = blk.conv
+        if tuple(conv.stride) != (1, 1) or tuple(conv.dilation) != (1, 1) or conv.padding_mode != "zeros" or isinstance(conv.padding, str):
+            raise _err("dorefa_compile_codes: %s.conv: stride / dilation other than 1 (or non-zero padding mode) is not covered by the code kernels" % nm)
+        g = _lib.ConvGeom(1, conv.in_channels, 4, 4, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], 1, 1, conv.padding[0], conv.padding[1], 1, 1, conv.groups, 0)
+        if not _lib.get_lib().mn_codeconv_supported(C.byref(g), CODE_BITS, CODE_BITS, CODE_BITS):
+            raise _err("dorefa_compile_codes: %s.conv: geometry not covered by mn_codeconv_supported (%dx%d, padding %d, groups %d, %d taps per output: needs 1x1 or 3x3 with "
+                       "padding 1, and at most 3640 taps)" % (nm, conv.kernel_size[0], conv.kernel_size[1], conv.padding[0], conv.groups,
+                                                             conv.in_channels // conv.groups * conv.kernel_size[0] * conv.kernel_size[1]))
+    first = last = None
+    layers, tail, report = [], [], []
+    for name, child in seq.named_children():
+        nm = prefix + name
+        if last is not None:
+            tail.append(child)
+            continue
+        if isinstance(child, nn.MaxPool2d):
+            if _pool_kind(child) != (2, 2, 0):
+                raise _err("dorefa_compile_codes: %s: max-pool (kernel %s, stride %s, padding %s, ceil_mode %s) is not covered by the code kernels (2x2 / 2 / 0, floor mode)"
+                           % (nm, child.kernel_size, child.stride, child.padding, child.ceil_mode))
+            if not layers or layers[-1]["pool"] or not getattr(child, "_mn_fused_pool", False):
+                raise _err("dorefa_compile_codes: %s: a 2x2 max-pool is folded only into the code block directly in front of it" % nm)
+            layers[-1]["pool"], layers[-1]["stage"] = 1, name
+            continue
+        if not any(child is b for _, b in blocks):
+            raise _err("dorefa_compile_codes: %s (%s): module order not recognised (expected conv -> bn -> relu blocks and 2x2 max-pools up to the last block)"
+                       % (nm, type(child).__name__))
+        conv, bn = child.conv, getattr(child, "bn", None)
+        if not isinstance(bn, quantize.BatchNorm2dReLU):
+            raise _err("dorefa_compile_codes: %s: conv -> BatchNorm -> ReLU not fused (prepare(..., fuse_bn_act=True, fuse_blocks=True))" % nm)
+        K = conv.in_channels // conv.groups * conv.kernel_size[0] * conv.kernel_size[1]
+        if first is None:
+            if type(conv) is not Conv2dFirst or getattr(child, "channel_shuffle_flag", 0):
+                raise _err("dorefa_compile_codes: %s: the first block must be the fp32 first conv" % nm)
+            if bn.q_out_bits != CODE_BITS:
+                raise _err("dorefa_compile_codes: %s: the first block must hand over %d-bit activation codes (it emits %s)"
+                           % (nm, CODE_BITS, ("%d-bit codes" % bn.q_out_bits) if bn.q_out_bits else "fp32"))
+            if bn.q_pool:
+                raise _err("dorefa_compile_codes: %s: a 2x2 max-pool is folded only into a code block; directly behind the first block it is not covered" % nm)
+            first = child
+            report.append(dict(name=nm, kind="first", K=K, words=0, planes=0, kernel="first conv + k_qa_fwd, k_codes_pack", pooled=False, out_order="identity", stage=name))
+            continue
+        shuffle = int(getattr(conv, "in_shuffle_groups", 0) or 0)
+        if getattr(child, "channel_shuffle_flag", 0) and getattr(child, "shuffle_groups", 1) > 1:
+            if shuffle > 1:
+                raise _err("dorefa_compile_codes: %s: two channel shuffles in front of one conv" % nm)
+            shuffle = int(child.shuffle_groups)
+        if child is blocks[-1][1]:
+            if shuffle > 1:
+                raise _err("dorefa_compile_codes: %s: a channel shuffle in front of the last block is not covered" % nm)
+            last = child
+            report.append(dict(name=nm, kind="last", K=K, words=(conv.in_channels + 31) // 32, planes=CODE_BITS, kernel="k_codes_unpack, last block on byte codes",
+                               pooled=False, out_order="identity", stage=name))
+            continue
+        # ---- a hidden block: conv on codes -> bn -> relu -> [pool] -> the next conv's quantizer
+        if bn.q_out_bits != CODE_BITS:
+            raise _err("dorefa_compile_codes: %s: its output is not handed over as %d-bit codes to the next quantised conv" % (nm, CODE_BITS))
+        if shuffle > 1:
+            if conv.in_channels % shuffle:
+                raise _err("dorefa_compile_codes: %s: %d input channels cannot be shuffled in %d groups" % (nm, conv.in_channels, shuffle))
+            if not layers:
+                raise _err("dorefa_compile_codes: %s: a channel shuffle directly behind the first block is not covered (its producer is not a code block)" % nm)
+            layers[-1]["shuffle"] = shuffle          # folded into the producer's row order
+        layers.append(dict(name=nm, conv=conv, bn=bn, k=conv.kernel_size[0], pad=conv.padding[0], cin=conv.in_channels, cout=conv.out_channels, groups=conv.groups,
+                           pool=0, want_pool=bool(bn.q_pool), shuffle=0, stage=name))
+    if first is None or last is None:
+        raise _err("dorefa_compile_codes: module order not recognised (no %s block found)" % ("first" if first is None else "last"))
+    rep_last = report.pop()
+    for L in layers:
+        if L.pop("want_pool") != bool(L["pool"]):
+            raise _err("dorefa_compile_codes: %s: the block pools its output but no 2x2 max-pool follows it (or the reverse)" % L["name"])
+        report.append(dict(name=L["name"], kind="code", K=L["cin"] // L["groups"] * L["k"] * L["k"], words=(L["cin"] + 31) // 32, planes=CODE_BITS,
+                           kernel=_codeconv_kernel_name(L["k"], L["cin"], L["groups"], L["pool"]), pooled=bool(L["pool"]),
+                           out_order=("shuffle %d" % L["shuffle"]) if L["shuffle"] > 1 else "identity", stage=L["stage"]))
+    report.append(rep_last)
+    return first, layers, last, tail, flatten, report
+
+
+def dorefa_codes_report(model):
+    """The ``report`` ``dorefa_compile_codes(model)`` would carry -- one row per stage: name, kind, K, words, planes, kernel, pooled, out_order -- from the graph walk
+    alone: no GPU, nothing packed.  Raises like ``dorefa_compile_codes`` for whatever the code kernels do not cover."""
+    return _walk_codes(model)[5]
+
+
+@torch.no_grad()
+def dorefa_compile_codes(model):
+    """``model``: a DoReFa W2A2 net prepared with ``quant_inference=True`` after ``prequantize_weights``, on the GPU (the reference's ``nin_gc``, or an ``nn.Sequential``
+    of the same block kinds).  Returns a ``CodePlan`` computing the same function with two bits per hidden activation; ``.report`` lists the stages.  Anything the code
+    kernels do not cover raises ``MicronetHipError`` naming the layer -- never a silent byte path (the caller still has ``model``)."""
+    import ctypes as C
+    from micronet_amd import _lib, ops
+    from micronet_amd.quantization.wqaq.dorefa.quantize import _weight_is_coded
+    first, layers, last, tail, flatten, report = _walk_codes(model)
+    for L in layers:
+        if not _weight_is_coded(L["conv"]):
+            raise _err("dorefa_compile_codes: %s.conv: the stored weights were not found on the 2-bit grid (2k - 3) / 3 (run inference.prequantize_weights on the GPU "
+                       "model first)" % L["name"])
+    for p_ in model.parameters():
+        if not p_.is_cuda:
+            raise _err("dorefa_compile_codes: the model is on %s: micronet_amd runs on MI355X only (no CPU fallback)" % p_.device)
+    lib = _lib.get_lib()
+    for L in layers:
+        conv, bn = L.pop("conv"), L.pop("bn")
+        k, p = L["k"], L["pad"]
+        dev = conv.weight.device
+        w = conv.weight.detach().float().contiguous()
+        b = conv.bias.detach().float().contiguous() if conv.bias is not None else None
+        with torch.cuda.device(dev):
+            # ---- the [9][O] constants of the block's eval-mode BatchNorm, by the calls the block's eval forward makes (ops._bn_front).  They do not depend on the
+            #      input, so one 8 x 8 map of zeros will do.
+            if not (bn.affine and bn.track_running_stats and bn.momentum is not None):
+                raise _err("dorefa_compile_codes: %s.bn: needs affine parameters, running statistics and a momentum" % L["name"])
+            gamma, beta = ops._chk(bn.weight.detach(), "weight"), ops._chk(bn.bias.detach(), "bias")
+            g8 = _lib.ConvGeom(1, L["cin"], 8, 8, L["cout"], k, k, 1, 1, p, p, 1, 1, L["groups"], 0)
+            wd = ops._wq_dorefa(CODE_BITS, None, 0)
+            save = torch.empty((2, L["cout"]), dtype=torch.float32, device=dev)
+            chan = torch.empty((9, L["cout"]), dtype=torch.float32, device=dev)
+            if lib.mn_qconv_bnq_supported(C.byref(g8), C.byref(wd), CODE_BITS) and int(lib.mn_qconv_bnq_stash_bits(C.byref(g8), C.byref(wd), CODE_BITS)) == 16:
+                # the fused block: the conv on codes with training = 0 writes the constants from the running statistics (alpha = weight scale x activation scale)
+                zero = torch.zeros((1, L["cin"], 8, 8), dtype=torch.uint8, device=dev)
+                stash = torch.empty((1, L["cout"], 8, 8), dtype=torch.int16, device=dev)
+                nb = int(lib.mn_qconv_bnq_ws_bytes(C.byref(g8)))
+                ws = torch.empty(nb // 4 + 4, dtype=torch.float32, device=dev)
+                ops._call("mn_qconv_bnq_fwd_stash", C.byref(g8), C.byref(wd), ops._p(zero), CODE_BITS, ops._p(w), ops._p(b), ops._p(gamma), ops._p(beta), float(bn.eps),
+                          float(bn.momentum), 0, ops._p(bn.running_mean), ops._p(bn.running_var), None, ops._p(save), ops._p(stash), ops._p(chan), ops._p(ws), nb, ops._s())
+            else:
+                # a block the stash conv does not cover (narrow groups): its eval forward convolves to fp32 y = acc * alpha + bias (the code kernels' epilogue) and
+                # takes (mean, invstd) from mn_bn_save_stats -- the same two calls here; rows alpha / bias (1 / 0 for an fp32 input) become the epilogue's
+                zero = torch.zeros((1, L["cout"], 8, 8), dtype=torch.float32, device=dev)
+                ws = torch.empty(int(lib.mn_bnsign_ws_floats(L["cout"])), dtype=torch.float32, device=dev)
+                ops._call("mn_bn_save_stats", ops._p(zero), 1, L["cout"], 64, float(bn.eps), float(bn.momentum), 0, ops._p(bn.running_mean), ops._p(bn.running_var),
+                          ops._p(save), ops._p(ws), ops._s())
+                ops._call("mn_qa_chan_from_save", ops._p(save), ops._p(gamma), ops._p(beta), L["cout"], ops._p(chan), ops._s())
+                sc = torch.tensor(1.0 / (2 ** CODE_BITS - 1), dtype=torch.float32, device=dev)
+                chan[0] = sc * sc          # fp32 product of the weight and the activation scale, as k_qa_stats_prep forms it
+                chan[1] = b if b is not None else 0.0
+                chan[6], chan[7] = chan[0] * chan[3], (chan[1] - chan[2]) * chan[3]
+            # ---- the table (one launch per layer, once per model)
+            g = _lib.ConvGeom(1, L["cin"], 4, 4, L["cout"], k, k, 1, 1, p, p, 1, 1, L["groups"], 0)
+            table = torch.empty(int(lib.mn_codeconv_table_bytes(C.byref(g), CODE_BITS, CODE_BITS, CODE_BITS)) // 4, dtype=torch.int32, device=dev)
+            order = None
+            if L["shuffle"] > 1:          # position j of the consumer's shuffled input is this layer's channel (j % s) * (C / s) + j // s (models/nin_gc.py:4-15)
+                j = torch.arange(L["cout"], device=dev)
+                order = ((j % L["shuffle"]) * (L["cout"] // L["shuffle"]) + j // L["shuffle"]).to(torch.int32).contiguous()
+            ops._call("mn_codeconv_pack", C.byref(g), ops._p(w), ops._p(chan), CODE_BITS, CODE_BITS, CODE_BITS, ops._p(order), ops._p(table), ops._s())
+        L["table"], L["chan"], L["out_order"] = table, chan, order
+    for L in layers:          # (compile time: the one place a host read-back is allowed)
+        nonfinite, bad = int(L["table"][0]), int(L["table"][7])
+        if nonfinite:
+            raise _err("dorefa_compile_codes: %s.bn: %d output channels with a non-finite (or beyond 1e9) BatchNorm constant: no integer thresholds" % (L["name"], nonfinite))
+        if bad:
+            raise _err("dorefa_compile_codes: %s.conv: %d table rows with a weight off the 2-bit grid or a bad channel order" % (L["name"], bad))
+    return CodePlan(first, layers, last, tail, flatten, report)

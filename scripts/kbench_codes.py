@@ -1,0 +1,102 @@
+"""Byte path vs code-packed path of a deployed (pre-quantised) DoReFa W2A2 nin_gc: images/s of the eval-mode ``quant_inference=True`` model ``I`` (one byte per hidden
+activation plus a 16-bit stash per block: the training kernels in eval mode -- the yardstick) and of ``P = inference.dorefa_compile_codes(I)`` (two bits per hidden
+activation, one kernel per hidden block), alternated in ONE process, HIP events.
+
+    python scripts/kbench_codes.py [--batches 256,1024] [--warmup 5] [--iters 20] [--out profiles/codes_inference.json]
+
+Per batch: median / min / quartiles of the timed forwards of each, per-kernel times of both from the library's profile hooks, and the designed HBM bytes per image
+per hidden block (arithmetic from the shapes: each operand read or written once)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def timed(fn, x):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn(x)
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def profile(lib, _lib, fn, x):
+    buf = (_lib.ProfEntry * 192)()
+    torch.cuda.synchronize()
+    lib.mn_profile_collect(buf, 192)
+    lib.mn_profile_enable(1)
+    fn(x)
+    torch.cuda.synchronize()
+    n = lib.mn_profile_collect(buf, 192)
+    lib.mn_profile_enable(0)
+    return {buf[i].name.decode(): dict(launches=int(buf[i].launches), ms=float(buf[i].total_ms), designed_bytes=float(buf[i].bytes)) for i in range(n)}
+
+
+def designed_bytes_per_image(P, hw=32):
+    """Hidden blocks.  Byte path: codes in (1 B), 16-bit stash out and in again (2 + 2 B per un-pooled output), codes out (1 B per pooled output).  Code path: 2 bits per
+    input element, 2 bits per (pooled) output element, in whole 32-channel words."""
+    rows, h = [], hw
+    for r, L in zip(P.report[1:-1], P.layers):
+        ho = h // 2 if L["pool"] else h
+        rows.append(dict(name=r["name"], kernel=r["kernel"],
+                         codes_bytes=4 * 2 * ((L["cin"] + 31) // 32) * h * h + 4 * 2 * ((L["cout"] + 31) // 32) * ho * ho,
+                         byte_path_bytes=L["cin"] * h * h + 4 * L["cout"] * h * h + L["cout"] * ho * ho))
+        h = ho
+    return rows
+
+
+def q(v):
+    return dict(median=statistics.median(v), min=min(v), max=max(v), p25=statistics.quantiles(v, n=4)[0], p75=statistics.quantiles(v, n=4)[2])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="256,1024")
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--out", default=os.path.join("profiles", "codes_inference.json"))
+    args = ap.parse_args()
+    from micronet.compression.quantization.wqaq.dorefa import quantize as Q
+    from micronet_amd import _lib, inference
+    from micronet_amd.train import build_model, synth_batch
+    torch.manual_seed(0)
+    I = Q.prepare(build_model("nin_gc"), inplace=True, a_bits=2, w_bits=2, quant_inference=True).cuda()
+    inference.prequantize_weights(I)
+    I.eval()
+    P = inference.dorefa_compile_codes(I)
+    lib = _lib.get_lib()
+    rows = designed_bytes_per_image(P)
+    res = dict(model="nin_gc", a_bits=2, w_bits=2, warmup=args.warmup, iters=args.iters, device=torch.cuda.get_device_name(0), report=P.report,
+               designed_bytes_per_image=rows, designed_hidden_bytes_per_image=dict(codes=sum(r["codes_bytes"] for r in rows), byte_path=sum(r["byte_path_bytes"] for r in rows)),
+               batches={})
+    with torch.no_grad():
+        for bs in [int(v) for v in args.batches.split(",")]:
+            x, _ = synth_batch(bs, device="cuda")
+            ref, got = I(x), P(x)
+            err = float((ref - got).abs().max())
+            for _ in range(args.warmup):
+                I(x), P(x)
+            ti, tp = [], []
+            for _ in range(args.iters):          # alternated: both see the same clocks and the same neighbours
+                ti.append(timed(I, x))
+                tp.append(timed(P, x))
+            kp, ki = profile(lib, _lib, P, x), profile(lib, _lib, I, x)
+            med_i, med_p = statistics.median(ti), statistics.median(tp)
+            res["batches"][str(bs)] = dict(I_ms=q(ti), P_ms=q(tp), I_img_s=bs / med_i * 1e3, P_img_s=bs / med_p * 1e3, P_over_I=med_i / med_p,
+                                           max_abs_logit_diff=err, bit_equal=bool(torch.equal(ref, got)), P_kernels=kp, I_kernels=ki,
+                                           P_kernel_ms_total=sum(v["ms"] for v in kp.values()), I_kernel_ms_total=sum(v["ms"] for v in ki.values()))
+            print("batch %d: I %.3f ms (min %.3f)  P %.3f ms (min %.3f)  P/I speed %.2fx  max |dlogit| %.3g" % (bs, med_i, min(ti), med_p, min(tp), med_i / med_p, err), flush=True)
+    os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
