@@ -6,280 +6,143 @@ failure into a Python exception carrying ``mn_last_error()``.
 """
 import ctypes as C
 import os
+import re
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MN_LIB_PATH") or os.path.join(HERE, "lib", "libmicronet_hip.so")   # MN_LIB_PATH: ablation builds of the same library
-
-MN_ACTQ_NONE, MN_ACTQ_DOREFA, MN_ACTQ_IAO, MN_ACTQ_SIGN8, MN_ACTQ_CODE8 = 0, 1, 2, 3, 4
-MN_ALGO_AUTO, MN_ALGO_DIRECT, MN_ALGO_MFMA, MN_ALGO_QGEMM = 0, 1, 2, 3
-MN_WQ_REAL, MN_WQ_TERNARY, MN_WQ_DOREFA, MN_WQ_IAO = 0, 1, 2, 3
-MN_ACTQ_X_IS_CODE = 1
-MN_ACTQ_CODES_GIVEN = 2
-MN_ENOTSUP = -95
-
-
-class ConvGeom(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("N", "C", "H", "W", "O", "KH", "KW", "stride_h", "stride_w", "pad_h", "pad_w",
-                                         "dil_h", "dil_w", "groups", "in_shuffle")]
-
-
-class ActQ(C.Structure):
-    _fields_ = [("mode", C.c_int32), ("bits", C.c_int32), ("q_type", C.c_int32), ("flags", C.c_int32),
-                ("qp", C.c_void_p), ("codes", C.c_void_p), ("stats", C.c_void_p), ("dx_add", C.c_void_p), ("ste_mask", C.c_void_p), ("acc_mm", C.c_void_p)]
-
-
-class WQ(C.Structure):
-    """mn_wq: how the fake-quantised fp32 weights factor into integer codes x per-channel scale."""
-    _fields_ = [("mode", C.c_int32), ("bits", C.c_int32), ("q_type", C.c_int32), ("per_channel", C.c_int32),
-                ("scale", C.c_void_p), ("packed_fwd", C.c_void_p), ("packed_bwd", C.c_void_p)]
-
-
-class ProfEntry(C.Structure):
-    _fields_ = [("name", C.c_char * 96), ("launches", C.c_int64), ("total_ms", C.c_double), ("bytes", C.c_double), ("flops", C.c_double)]
-
-
-class AdamTensor(C.Structure):
-    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64),
-                ("lr", C.c_float), ("weight_decay", C.c_float)]
-
-
-_P, _I, _L, _D = C.c_void_p, C.c_int, C.c_int64, C.c_double
-_G, _A, _W = C.POINTER(ConvGeom), C.POINTER(ActQ), C.POINTER(WQ)
-
-# name -> (restype, argtypes); must list every symbol declared in include/micronet_hip.h
-PROTOTYPES = {
-    "mn_version": (_I, []),
-    "mn_last_error": (C.c_char_p, []),
-    "mn_last_kernel": (C.c_char_p, []),
-    "mn_profile_next": (None, [_P, _P]),
-    "mn_profile_enable": (None, [_I]),
-    "mn_profile_collect": (_I, [C.POINTER(ProfEntry), _I]),
-    "mn_is_emulation": (_I, []),
-    "mn_dense_grad_terms": (_I, []),
-    "mn_round_half_away": (_I, [_P, _P, _L, _P]),
-    "mn_dorefa_act_fwd": (_I, [_P, _P, _L, _I, _P]),
-    "mn_dorefa_act_bwd": (_I, [_P, _P, _P, _L, _I, _P]),
-    "mn_dorefa_w_ws_floats": (_L, [_L]),
-    "mn_dorefa_w_fwd": (_I, [_P, _P, _L, _I, _P, _P]),
-    "mn_dorefa_w_bwd": (_I, [_P, _P, _P, _L, _I, _P, _P]),
-    "mn_binact_fwd": (_I, [_P, _P, _L, _P]),
-    "mn_binact_bwd": (_I, [_P, _P, _P, _L, _P]),
-    "mn_ternary_w_fwd": (_I, [_P, _P, _P, _L, _L, _P]),
-    "mn_ternary_w_bwd": (_I, [_P, _P, _P, _P, _L, _L, _P]),
-    "mn_ternary_w_fwd_multi": (_I, [_P, _P, _P, _P, _P, C.c_int32, _P]),
-    "mn_ternary_w_bwd_multi": (_I, [_P, _P, _P, _P, _P, _P, C.c_int32, _P]),
-    "mn_binary_w_fwd": (_I, [_P, _P, _P, _L, _L, _L, _P]),
-    "mn_binary_w_bwd": (_I, [_P, _P, _P, _P, _L, _L, _P]),
-    "mn_binary_w_fwd_multi": (_I, [_P, _P, _P, _P, _P, _P, C.c_int32, _P]),
-    "mn_binary_w_bwd_multi": (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_int32, _P]),
-    "mn_iao_observe_ws_floats": (_L, [_L, _L]),
-    "mn_iao_observe": (_I, [_P, _L, _L, _I, _I, _D, _P, _P, _P, _P]),
-    "mn_iao_qparams": (_I, [_P, _P, _L, _I, _I, _I, _I, _P, _P, _P, _P]),
-    "mn_iao_fq_fwd": (_I, [_P, _P, _L, _L, _P, _I, _I, _I, _P]),
-    "mn_iao_fq_bwd": (_I, [_P, _P, _P, _L, _L, _P, _I, _I, _I, _P]),
-    "mn_iao_union_range": (_I, [_P, _P, _P, _P, _P, _P, _P]),
-    "mn_bn_stats_ws_floats": (_L, [_L, _L, _L]),
-    "mn_bn_stats_fwd": (_I, [_P, _L, _L, _L, _P, _P, _P]),
-    "mn_bn_stats_bwd": (_I, [_P, _P, _P, _P, _P, _L, _L, _L, _P]),
-    "mn_bnsign_ws_floats": (_L, [_L]),
-    "mn_bnsign_fwd": (_I, [_P, _L, _L, _L, _P, _P, C.c_float, C.c_float, _I, _P, _P, _P, _P, _P, _P]),
-    "mn_bnsign_fwd_i8": (_I, [_P, _L, _L, _L, _P, _P, C.c_float, C.c_float, _I, _P, _P, _P, _P, _P, _P]),
-    "mn_maxpool2x2_sign8_fwd": (_I, [_P, _L, _L, _L, _P, _P]),
-    "mn_maxpool2x2_sign8_bwd": (_I, [_P, _P, _L, _L, _L, _P, _P]),
-    "mn_bnsign_bwd_sums": (_I, [_P, _P, _P, _P, _P, _L, _L, _L, _P, _P, _P, _P, _P]),
-    "mn_conv2d_bwd_weight_first_bn": (_I, [_G, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P]),
-    "mn_conv2d_bwd_weight_first_qa": (_I, [_G, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P]),
-    "mn_conv2d_first_gram_bnstats": (_I, [_G, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P]),
-    "mn_bnsign_apply": (_I, [_P, _L, _L, _L, _P, _P, _P, _P, _I, _P]),
-    "mn_qa_fwd_f32_mask": (_I, [_P, _P, _L, _L, _L, _L, _I, _P, _P, _P]),
-    "mn_conv2d_first_bnact_fwd": (_I, [_G, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
-    "mn_conv2d_bwd_first_mask_gram": (_I, [_G, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
-    "mn_conv2d_first_xgram_ws_bytes": (_L, [_G]),
-    "mn_conv2d_first_xgram": (_I, [_G, _P, _P, _P, _L, _P]),
-    "mn_conv2d_bwd_first_bn_gram": (_I, [_G, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
-    "mn_conv2d_bwd_first_qa_gram": (_I, [_G, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
-    "mn_bnsign_bwd": (_I, [_P, _P, _P, _P, _P, _L, _L, _L, _I, _P, _P, _P, _P, _P]),
-    "mn_maxpool2x2_f32_supported": (_I, [_L, _L]),
-    "mn_maxpool2x2_f32_fwd": (_I, [_P, _L, _L, _L, _P, _P, _P]),
-    "mn_maxpool2x2_f32_bwd": (_I, [_P, _P, _L, _L, _L, _P, _P]),
-    "mn_bnrelu_fwd": (_I, [_P, _L, _L, _L, _P, _P, C.c_float, C.c_float, _I, _P, _P, _P, _P, _P, _P]),
-    "mn_bnrelu_bwd": (_I, [_P, _P, _P, _P, _P, _L, _L, _L, _I, _P, _P, _P, _P, _P]),
-    "mn_avgpool_global_fwd": (_I, [_P, _L, _L, _P, _P]),
-    "mn_avgpool_global_bwd": (_I, [_P, _L, _L, _P, _P]),
-    "mn_bn2d_fwd": (_I, [_P, _L, _L, _L, _P, _P, C.c_float, C.c_float, _I, _P, _P, _P, _P, _P, _P]),
-    "mn_bn2d_bwd": (_I, [_P, _P, _P, _P, _P, _L, _L, _L, _I, _P, _P, _P, _P, _P]),
-    "mn_qconv_bnsign_supported": (_I, [_G, _W]),
-    "mn_qconv_bnsign_ws_bytes": (_L, [_G]),
-    "mn_qconv_bnsign_stash_supported": (_I, [_G, _W]),
-    "mn_qconv_bnsign_stash_ws_bytes": (_L, [_G]),
-    "mn_qconv_bnsign_stash_chan_rows": (_I, [_G]),
-    "mn_qconv_bnsign_fwd": (_I, [_G, _W, _P, _P, _P, _P, _P, C.c_float, C.c_float, _I, _P, _P, _P, _P, _P, _L, _P]),
-    "mn_qconv_bnsign_fwd_stash": (_I, [_G, _W, _P, _P, _P, _P, _P, C.c_float, C.c_float, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
-    "mn_qconv_bnsign_fwd_stash_pool_supported": (_I, [_G, _W]),
-    "mn_qconv_bnsign_fwd_stash_pool": (_I, [_G, _W, _P, _P, _P, _P, _P, C.c_float, C.c_float, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
-    "mn_bnh_bwd_sums": (_I, [_P, _P, _P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P]),
-    "mn_bnh_bwd_apply": (_I, [_P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P, _P]),
-    "mn_conv2d_bnh_supported": (_I, [_G, _W]),
-    "mn_conv2d_bwd_data_bnh": (_I, [_G, _W, _P, _P, _P, _P, _I, _P, _P, _P, _L, _P]),
-    "mn_conv2d_bwd_weight_bnh": (_I, [_G, _P, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P]),
-    "mn_conv2d_bwd_data_bnh_uppool_splits": (_I, [_G, _W]),
-    "mn_conv2d_bwd_data_bnh_uppool": (_I, [_G, _W, _P, _P, _P, _P, _I, _P, _P, _P, _L, _P, _L, _L, _P, _I, _P, _P]),
-    "mn_bnh_bwd_sums_finish_pool": (_I, [_P, _I, _L, _L, _L, _L, _P, _P, _P, _P]),
-    "mn_conv2d_bwd_bnh_supported": (_I, [_G, _W, _I]),
-    "mn_conv2d_bwd_bnh_ws_bytes": (_L, [_G]),
-    "mn_conv2d_bwd_bnh": (_I, [_G, _W, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _L, _P]),
-    "mn_conv2d_bwd_bnh_up_splits": (_I, [_G, _W, _I, _L]),
-    "mn_conv2d_bwd_bnh_up": (_I, [_G, _W, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P]),
-    "mn_bnh_bwd_sums_final": (_I, [_P, _I, _L, _L, _L, _L, _P, _P, _P, _P]),
-    "mn_conv2d_bwd_bnh_up9_splits": (_I, [_G, _W, _L]),
-    "mn_conv2d_bwd_bnh_up9": (_I, [_G, _W, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P]),
-    "mn_conv2d_bwd_codes": (_I, [_G, _W, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P]),
-    "mn_conv2d_bwd_qa": (_I, [_G, _W, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _L, _P]),
-    "mn_conv2d_bwd_codes_up": (_I, [_G, _W, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P, _P, _I, _P, _P]),
-    "mn_conv2d_bwd_qa_up": (_I, [_G, _W, _P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _L, _P, _P, _I, _P, _P]),
-    "mn_qa_bwd_sums_final": (_I, [_P, _I, _L, _P, _P, _P, _P]),
-    "mn_conv2d_bnh_pool_supported": (_I, [_G, _W]),
-    "mn_conv2d_bwd_data_bnh_pool": (_I, [_G, _W, _P, _P, _P, _P, _P, _I, _P, _P, _P, _L, _P]),
-    "mn_conv2d_bwd_weight_bnh_pool": (_I, [_G, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P]),
-    "mn_qconv_bnsign_bwd": (_I, [_G, _W, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P]),
-    "mn_qconv_bnsign_bwd_pooled": (_I, [_G, _W, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P]),
-    "mn_signconv1x1_small_supported": (_I, [_L, _L, _L]),
-    "mn_signconv1x1_small_fwd": (_I, [_P, _P, _P, _P, _L, _L, _L, _L, _P]),
-    "mn_codeconv1x1_small_fwd": (_I, [_P, _I, _P, _P, _P, _L, _L, _L, _L, _P]),
-    "mn_conv1x1_small_bwd_data": (_I, [_P, _P, _P, _L, _L, _L, _L, _P]),
-    "mn_iao_fq_act_fwd": (_I, [_P, _P, _L, _P, _I, _I, _I, C.c_float, _P]),
-    "mn_iao_fq_act_bwd": (_I, [_P, _P, _P, _L, _P, _I, _I, _I, C.c_float, _P]),
-    "mn_iao_fq_avgpool_supported": (_I, [_L, _L, _L]),
-    "mn_iao_fq_avgpool_fwd": (_I, [_P, _P, _L, _L, _L, _L, _P, _I, _I, _P]),
-    "mn_iao_fq_avgpool_bwd": (_I, [_P, _P, _P, _L, _L, _L, _L, _P, _I, _I, _P]),
-    "mn_kth_abs_ws_bytes": (_L, []),
-    "mn_hist_observe": (_I, [_P, _L, _L, _I, C.c_double, _P, _P, _P, _P]),
-    "mn_qconv_bnq_supported": (_I, [_G, _W, _I]),
-    "mn_qconv_bnq_stash_bits": (_I, [_G, _W, _I]),
-    "mn_qconv_bnq_ws_bytes": (_L, [_G]),
-    "mn_qconv_bnq_fwd_stash": (_I, [_G, _W, _P, _I, _P, _P, _P, _P, C.c_float, C.c_float, _I, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
-    "mn_bn_save_stats": (_I, [_P, _L, _L, _L, C.c_float, C.c_float, _I, _P, _P, _P, _P, _P]),
-    "mn_qa_supported": (_I, [_L, _L, _I]),
-    "mn_qa_ws_floats": (_L, [_L]),
-    "mn_qa_chan_from_save": (_I, [_P, _P, _P, _L, _P, _P]),
-    "mn_qa_fwd": (_I, [_I, _P, _P, _L, _L, _L, _L, _I, _I, _P, _P, _P]),
-    "mn_qa_bwd_sums": (_I, [_I, _P, _P, _P, _L, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P]),
-    "mn_qa_bwd_apply": (_I, [_I, _P, _P, _P, _P, _L, _L, _L, _L, _I, _I, _I, _I, _P, _P]),
-    "mn_qa_bwd": (_I, [_I, _P, _P, _P, _L, _L, _L, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
-    "mn_conv2d_iao_codes_bytes": (_L, [_G, _A, _W]),
-    "mn_conv2d_bwd_data_add_supported": (_I, [_G, _A, _W]),
-    "mn_conv2d_iao_stats_rows": (_L, [_G, _A, _W]),
-    "mn_bn_fwd_acc": (_I, [_P, _L, _L, _L, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P, _I, _P, _L, _P, _P, _L, _P, _P]),
-    "mn_bn_acc_prep": (_I, [_L, _L, _L, _P, _P, C.c_float, C.c_float, _P, _P, _P, _I, _P, _P, _L, _P, _P, _L, _P, _P, _P]),
-    "mn_bnrelu_gap_supported": (_I, [_L, _L, _L]),
-    "mn_bnrelu_gap_fwd": (_I, [_P, _L, _L, _L, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
-    "mn_bnrelu_gap_bwd": (_I, [_P, _P, _P, _P, _P, _L, _L, _L, _P, _P, _P, _P]),
-    "mn_cross_entropy_fwd": (_I, [_P, _P, _L, _L, _L, _P, _P, _P]),
-    "mn_scale_by": (_I, [_P, _P, _P, _L, _P]),
-    "mn_bn_apply_codes": (_I, [_P, _L, _L, _L, _P, _P, _P, _I, _P, _I, _P, _P, _P]),
-    "mn_bn_apply": (_I, [_P, _L, _L, _L, _P, _P, _P, _I, _P, _P]),
-    "mn_iao_qadd_bn_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
-    "mn_iao_qadd_bn_bwd": (_I, [_P, _P, _P, _P, _P, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "mn_iao_w_fwd_multi": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _D, _I, _I, _P]),
-    "mn_iao_w_bwd_multi": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "mn_iao_qadd_ws_floats": (_L, []),
-    "mn_iao_qadd_mm_count": (_L, [_L]),
-    "mn_iao_qadd_fwd_mm": (_I, [_P, _P, _P, _L, _P, _I, _I, _I, _P, _P]),
-    "mn_iao_observe_partials": (_I, [_P, _L, _I, _I, _D, _P, _P, _P]),
-    "mn_iao_observe_partials_qparams": (_I, [_P, _L, _I, _I, _D, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
-    "mn_bnrelu_mm_count": (_L, [_L, _L, _L]),
-    "mn_bnrelu_fwd_mm": (_I, [_P, _L, _L, _L, _P, _P, C.c_float, C.c_float, _I, _P, _P, _P, _P, _P, _P, _P]),
-    "mn_iao_qadd_observe": (_I, [_P, _P, _L, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
-    "mn_iao_qadd_observe_partials": (_I, [_P, _L, _P, _L, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
-    "mn_bn2d_fwd_mm": (_I, [_P, _L, _L, _L, _P, _P, C.c_float, C.c_float, _I, _P, _P, _P, _P, _P, _P, _P]),
-    "mn_iao_qadd_fwd": (_I, [_P, _P, _P, _L, _P, _I, _I, _I, _P]),
-    "mn_iao_qadd_bwd": (_I, [_P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _P]),
-    "mn_qd_packed_bytes": (_L, [_G]),
-    "mn_qd_pack_multi": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
-    "mn_qg_packed_bytes": (_L, [_G, _I]),
-    "mn_qg_pack_multi": (_I, [_I, _P, _P, _P, _P, _P, _P]),
-    "mn_qr_ws_floats": (_L, [_L]),
-    "mn_qr_fwd": (_I, [_I, _P, _P, _I, _P, _P, _L, _L, _L, _L, _I, _P, _P, _P]),
-    "mn_qr_bwd_sums": (_I, [_I, _P, _P, _I, _P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "mn_qr_bwd_apply": (_I, [_I, _P, _P, _P, _I, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P, _P, _P]),
-    "mn_qr_bwd": (_I, [_I, _P, _P, _I, _P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "mn_qlinear_supported": (_I, [_L, _L, _L]),
-    "mn_qlinear_fwd": (_I, [_A, _P, _P, _P, _P, _L, _L, _L, _P]),
-    "mn_qlinear_bwd_data": (_I, [_A, _P, _P, _P, _P, _L, _L, _L, _P]),
-    "mn_qlinear_bwd_weight": (_I, [_A, _P, _P, _P, _P, _L, _L, _L, _P]),
-    "mn_cifar_augment": (_I, [_P, _L, _P, _P, _P, _P, _L, _L, _L, _L, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P]),
-    "mn_iao_bnfold_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_float, _L, _L, _P, _P, _P]),
-    "mn_iao_bnfold_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_float, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "mn_tanh_f32": (_I, [_P, _P, _L, _P]),
-    "mn_dorefa_w_fwd_multi": (_I, [_P, _P, _P, _P, C.c_int32, _I, _P]),
-    "mn_dorefa_w_bwd_multi": (_I, [_P, _P, _P, _P, _P, C.c_int32, _I, _P]),
-    "mn_dorefa_w_fwd_multi_cached": (_I, [_P, _P, _P, _P, _P, _I, _I, _P]),
-    "mn_dorefa_w_bwd_multi_cached": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P]),
-    "mn_adam_step": (_I, [C.POINTER(AdamTensor), _I, _I, C.c_float, C.c_float, C.c_float, _P]),
-    "mn_adam_step_dev": (_I, [C.POINTER(AdamTensor), _I, _P, _P, C.c_float, C.c_float, C.c_float, _P]),
-    "mn_adam_step_l1": (_I, [C.POINTER(AdamTensor), C.POINTER(C.c_float), _I, _I, C.c_float, C.c_float, C.c_float, _P]),
-    "mn_adam_step_l1_dev": (_I, [C.POINTER(AdamTensor), C.POINTER(C.c_float), _I, _P, _P, _P, C.c_float, C.c_float, C.c_float, _P]),
-    "mn_conv2d_ws_bytes": (_L, [_G, _I, _I]),
-    "mn_conv2d_mfma_supported": (_I, [_G, _I]),
-    "mn_conv2d_first_supported": (_I, [_G, _I]),
-    "mn_conv2d_qgemm_supported": (_I, [_G, _A, _W, _I]),
-    "mn_conv2d_fwd": (_I, [_G, _A, _W, _P, _P, _P, _P, _P, _L, _I, _P]),
-    "mn_conv2d_bwd_data": (_I, [_G, _A, _W, _P, _P, _P, _P, _P, _L, _I, _P]),
-    "mn_conv2d_bwd_weight": (_I, [_G, _A, _P, _P, _P, _P, _P, _L, _I, _P]),
-    "mn_conv2d_fwd_act_mm_count": (_L, [_G, _A, _W]),
-    "mn_conv2d_fwd_act": (_I, [_G, _A, _W, _P, _P, _P, _P, _I, _P, _P, _L, _P]),
-    "mn_iao_fq_maxpool2x2_supported": (_I, [_L, _L]),
-    "mn_iao_fq_maxpool2x2_mm_count": (_L, [_L, _L, _L]),
-    "mn_iao_fq_maxpool2x2_fwd": (_I, [_P, _L, _L, _L, _P, _I, _I, _P, _P, _P, _P]),
-    "mn_iao_fq_maxpool2x2_bwd": (_I, [_P, _P, _P, _L, _L, _L, _P, _I, _I, _I, _P, _P]),
-    "mn_add_relu_mask": (_I, [_P, _P, _P, _P, _L, _P]),
-    "mn_relu_mm_count": (_L, [_L]),
-    "mn_relu_mm": (_I, [_P, _P, _L, _P, _P]),
-    "mn_iaobf_gram_supported": (_I, [_G]),
-    "mn_iaobf_gram_ws_bytes": (_L, [_G]),
-    "mn_iaobf_gram": (_I, [_G, _P, _P, _P, _P, _L, _P]),
-    "mn_iaobf_gram_stats": (_I, [_P, _P, _P, _P, _L, _L, _L, _D, _P, _P, _P]),
-    "mn_iaobf_prep_fwd": (_I, [_P, _P, _P, _P, _L, _L, _P, C.c_float, C.c_float, _I, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "mn_iaobf_prep_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _P, _P, _D, C.c_float, _I, _I, _P, _P, _P, _P, _P, _P]),
-    "mn_iaobf_bwd_data_supported": (_I, [_G]),
-    "mn_iaobf_bwd_data_ws_bytes": (_L, [_G]),
-    "mn_iaobf_bwd_data": (_I, [_G, _A, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _L, _P]),
-    "mn_iaobf_g3_supported": (_I, [_G]),
-    "mn_iaobf_g3_ws_bytes": (_L, [_G]),
-    "mn_iaobf_g3_mm_count": (_L, [_G]),
-    "mn_iaobf_g3_stats": (_I, [_G, _P, _P, _I, _P, _P, _P, _P, _L, _P]),
-    "mn_iaobf_g3_fwd": (_I, [_G, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P]),
-    "mn_iaobf_g3_dyraw": (_I, [_G, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
-    "mn_iaobf_g3_bwd_weight": (_I, [_G, _P, _P, _P, _P, _I, _I, _P, _P, _P, _L, _P]),
-    "mn_iaobf_g3_bwd_data": (_I, [_G, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
-    "mn_iaobf_thin_supported": (_I, [_G]),
-    "mn_iaobf_thin_mm_count": (_L, [_G]),
-    "mn_iaobf_thin_pack": (_I, [_P, _L, _L, _P, _P]),
-    "mn_iaobf_thin_fwd": (_I, [_G, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
-    "mn_iaobf_thin_bwd_weight": (_I, [_G, _P, _P, _P, _I, _I, _P, _P, _P]),
-    "mn_iaobf_thin_bwd_data": (_I, [_G, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P]),
-    "mn_bits_pack_sign8": (_I, [_P, _L, _L, _L, _P, _P]),
-    "mn_bits_unpack_sign8": (_I, [_P, _L, _L, _L, _P, _P]),
-    "mn_bitconv_supported": (_I, [_G]),
-    "mn_bitconv_table_bytes": (_L, [_G]),
-    "mn_bitconv_pack": (_I, [_G, _P, _P, _P, _P, _P]),
-    "mn_bitconv_fwd": (_I, [_G, _P, _P, _P, _I, _P]),
-    "mn_bits_maxpool": (_I, [_P, _L, _L, _L, _L, _I, _I, _I, _P, _P]),
-    "mn_codes_pack_planes": (_I, [_P, _L, _L, _L, _I, _P, _P]),
-    "mn_codes_unpack_planes": (_I, [_P, _L, _L, _L, _I, _P, _P]),
-    "mn_codeconv_supported": (_I, [_G, _I, _I, _I]),
-    "mn_codeconv_table_bytes": (_L, [_G, _I, _I, _I]),
-    "mn_codeconv_pack": (_I, [_G, _P, _P, _I, _I, _I, _P, _P, _P]),
-    "mn_codeconv_fwd": (_I, [_G, _P, _P, _P, _I, _P]),
-    "mn_conv2d_first_sign_bits_supported": (_I, [_G]),
-    "mn_conv2d_first_sign_bits": (_I, [_G, _P, _P, _P, _P, _P]),
-    "mn_bitsconv1x1_small_supported": (_I, [_L, _L, _L]),
-    "mn_bitsconv1x1_small_fwd": (_I, [_P, _P, _P, _P, _L, _L, _L, _L, _P]),
-}
+HEADER_PATH = os.path.join(HERE, "..", "include", "micronet_hip.h")
 
 
 class MicronetHipError(RuntimeError):
     pass
+
+
+class ConvGeom(C.Structure):
+    pass
+
+
+class ActQ(C.Structure):
+    pass
+
+
+class WQ(C.Structure):
+    """mn_wq: how the fake-quantised fp32 weights factor into integer codes x per-channel scale."""
+
+
+class ProfEntry(C.Structure):
+    pass
+
+
+class AdamTensor(C.Structure):
+    pass
+
+
+# C struct name -> class: the one thing stated here and not read from the header (the classes get their _fields_ below)
+STRUCTS = {"mn_conv_geom": ConvGeom, "mn_actq": ActQ, "mn_wq": WQ, "mn_prof_entry": ProfEntry, "mn_adam_tensor": AdamTensor}
+
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double}
+_RETURNS = dict(_SCALARS, **{"void": None, "const char*": C.c_char_p})
+_DEFINE = re.compile(r"#\s*define\s+(MN_\w+)\b(.*)")
+_INTEGER = re.compile(r"\(\s*(-?\d+)\s*\)|(0[xX][0-9a-fA-F]+|0|[1-9]\d*)")
+_STRUCT = re.compile(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;")
+_FIELD = re.compile(r"(?:const\s+)?(\w*)(.*)", re.S)
+_DECLARATOR = re.compile(r"(\*[\s*]*)?(\w+)\s*(?:\[\s*(\d+)\s*\])?")
+_FUNCTION = re.compile(r"(.*?)\b(\w+)\s*\(([^()]*)\)")
+_PARAM = re.compile(r"(?:const\s+)?(\w+)\s*((?:\*\s*(?:const\s*)?)*)(\w+)?")
+
+
+def parse_header(text):
+    """``(constants, struct_fields, prototypes)`` of a header written in the vocabulary of ``include/micronet_hip.h``: integer ``#define MN_*``, ``typedef void* T;``,
+    ``typedef struct X { ... } X;`` for the names in ``STRUCTS``, and function declarations over int / int32_t / int64_t / float / double, those structs and pointers.
+    Anything else raises ``MicronetHipError`` naming the item: a construct this reader does not know must fail the import, never be skipped or taken for an int."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants, lines = {}, []
+    for line in text.split("\n"):
+        if not line.lstrip().startswith("#"):
+            lines.append(line)
+            continue
+        m = _DEFINE.match(line.strip())
+        if m:
+            v = _INTEGER.fullmatch(m.group(2).strip())
+            if not v:
+                raise MicronetHipError("header: #define %s is not an integer constant: %r" % (m.group(1), m.group(2).strip()))
+            constants[m.group(1)] = int(v.group(1) or v.group(2), 0)
+    text = "\n".join(lines)
+
+    aliases = set(re.findall(r"typedef\s+void\s*\*\s*(\w+)\s*;", text))             # mn_stream_t
+    text = re.sub(r"typedef\s+void\s*\*\s*\w+\s*;", " ", text)
+
+    struct_fields = {}
+    for tag, body, name in _STRUCT.findall(text):
+        if tag != name or name not in STRUCTS or name in struct_fields:
+            raise MicronetHipError("header: struct %s { ... } %s: not one of _lib.STRUCTS, or declared twice" % (tag, name))
+        fields = struct_fields[name] = []
+        for stmt in filter(None, (s.strip() for s in body.split(";"))):
+            base, rest = _FIELD.fullmatch(stmt).groups()
+            for decl in rest.split(","):
+                d = _DECLARATOR.fullmatch(decl.strip())
+                if not d:
+                    raise MicronetHipError("header: struct %s: cannot read field %r" % (name, stmt))
+                stars, field, dim = d.groups()
+                if stars and not dim:
+                    ctype = C.c_void_p
+                elif base == "char" and dim and not stars:
+                    ctype = C.c_char * int(dim)
+                elif base in _SCALARS and not dim:
+                    ctype = _SCALARS[base]
+                else:
+                    raise MicronetHipError("header: struct %s: field %s has a type outside the vocabulary: %r" % (name, field, stmt))
+                fields.append((field, ctype))
+    text = _STRUCT.sub(" ", text)
+
+    text, opened = re.subn(r'extern\s+"C"\s*\{', " ", text)
+    prototypes, closed = {}, 0
+    for stmt in text.split(";"):
+        stmt = " ".join(stmt.split())
+        while stmt.startswith("}"):
+            closed, stmt = closed + 1, stmt[1:].strip()
+        if not stmt:
+            continue
+        m = _FUNCTION.fullmatch(stmt)
+        if not m:
+            raise MicronetHipError("header: not a declaration this reader knows: %r" % stmt)
+        ret, name, params = m.group(1), m.group(2), m.group(3).strip()
+        ret = re.sub(r"\s*\*\s*", "*", ret.strip())
+        if name in prototypes:
+            raise MicronetHipError("header: %s is declared twice" % name)
+        if ret not in _RETURNS:
+            raise MicronetHipError("header: %s: return type outside the vocabulary: %r" % (name, ret))
+        argtypes = []
+        for param in ([] if params in ("", "void") else params.split(",")):
+            p = _PARAM.fullmatch(param.strip())
+            base, stars = (p.group(1), p.group(2).count("*")) if p else (None, 0)
+            if stars == 1 and base in STRUCTS:
+                argtypes.append(C.POINTER(STRUCTS[base]))
+            elif stars or base in aliases:
+                argtypes.append(C.c_void_p)
+            elif base in _SCALARS:
+                argtypes.append(_SCALARS[base])
+            else:
+                raise MicronetHipError("header: %s: parameter type outside the vocabulary: %r" % (name, param.strip()))
+        prototypes[name] = (_RETURNS[ret], argtypes)
+    if opened != closed:
+        raise MicronetHipError('header: unbalanced extern "C" braces (%d opened, %d closed)' % (opened, closed))
+    return constants, struct_fields, prototypes
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise MicronetHipError("cannot read the C ABI header %s: %s" % (HEADER_PATH, e))
+
+
+# every integer #define MN_* of the header becomes a module attribute; PROTOTYPES: name -> (restype, argtypes) of every function the header declares
+_CONSTANTS, _FIELDS, PROTOTYPES = _read_header()
+globals().update(_CONSTANTS)
+for _name, _cls in STRUCTS.items():
+    _cls._fields_ = _FIELDS[_name]
 
 
 class Lib:

@@ -752,7 +752,7 @@ def dorefa_compile_codes(model):
             g8 = _lib.ConvGeom(1, L["cin"], 8, 8, L["cout"], k, k, 1, 1, p, p, 1, 1, L["groups"], 0)
             wd = ops._wq_dorefa(CODE_BITS, None, 0)
             save = torch.empty((2, L["cout"]), dtype=torch.float32, device=dev)
-            chan = torch.empty((9, L["cout"]), dtype=torch.float32, device=dev)
+            chan = torch.empty((_lib.MN_QA_NCH, L["cout"]), dtype=torch.float32, device=dev)
             if lib.mn_qconv_bnq_supported(C.byref(g8), C.byref(wd), CODE_BITS) and int(lib.mn_qconv_bnq_stash_bits(C.byref(g8), C.byref(wd), CODE_BITS)) == 16:
                 # the fused block: the conv on codes with training = 0 writes the constants from the running statistics (alpha = weight scale x activation scale)
                 zero = torch.zeros((1, L["cin"], 8, 8), dtype=torch.uint8, device=dev)

@@ -2677,7 +2677,7 @@ def _bn_front(y, gamma, beta, running_mean, running_var, eps, momentum, training
         wide = r.get("stash_bits", 16) == 32
         src = torch.empty((N, Cc, H, W), dtype=torch.int32 if wide else torch.int16, device=dev)
         save = torch.empty((2, Cc), dtype=torch.float32, device=dev)
-        chan = torch.empty((9, Cc), dtype=torch.float32, device=dev)
+        chan = torch.empty((_lib.MN_QA_NCH, Cc), dtype=torch.float32, device=dev)
         wd = _wq_dorefa(r["w_bits"], r.get("packed"), 0)
         with torch.cuda.device(dev):
             nb = int(lib.mn_qconv_bnq_ws_bytes(C.byref(g)))
@@ -2689,7 +2689,7 @@ def _bn_front(y, gamma, beta, running_mean, running_var, eps, momentum, training
     src = _chk(y, "input")
     N, Cc, H, W = src.shape
     dev = src.device
-    chan = torch.empty((9, Cc), dtype=torch.float32, device=dev)
+    chan = torch.empty((_lib.MN_QA_NCH, Cc), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         if first is not None:          # y = the first conv's output: statistics from the Gram data of its input, no pass over y (the Gram data stay on the record holder)
             first[1], save = _first_gram(first[0], eps, momentum, running_mean, running_var)
@@ -3138,7 +3138,7 @@ class FirstConvBNReLUQ(Function):
         compute = r["compute"]
 
         def chan_of():
-            chan = torch.empty((9, Cc), dtype=torch.float32, device=dev)
+            chan = torch.empty((_lib.MN_QA_NCH, Cc), dtype=torch.float32, device=dev)
             _call("mn_qa_chan_from_save", _p(save), _p(gamma), _p(beta), Cc, _p(chan), _s())
             return chan
 
