@@ -952,6 +952,26 @@ int mn_conv2d_first_sign_bits_supported(const mn_conv_geom* g);
 int mn_conv2d_first_sign_bits(const mn_conv_geom* g, const float* x, const float* w, const float* bias, uint32_t* bits, mn_stream_t stream);
 int mn_bitsconv1x1_small_supported(int64_t C, int64_t HW, int64_t O);
 int mn_bitsconv1x1_small_fwd(const uint32_t* bits, const float* w, const float* bias, float* y, int64_t N, int64_t C, int64_t HW, int64_t O, mn_stream_t stream);
+/* The two ends of the code-packed plan on planes (inference.dorefa_compile_codes(model, code_ends=True)); a_bits_out / a_bits == 2 is the one instantiation.
+ *   first : planes = the 2-bit code of relu(bn(conv(x, w) + bias)) of the un-quantised first block, in ONE launch.  The accumulation is the first-layer forward's
+ *           (k_c1b_fwd), so the value that is coded is its y bit for bit, and the code is the one mn_qa_fwd(in_f32 = 1) gives for that y: the chain is monotone in y, so
+ *           per channel there are flip and three fp32 thresholds (code = #{k : flip * y >= T_k}, found by bisection over the bit patterns of fp32 on the exact chain);
+ *           |y| > 1e9 and NaN are evaluated by the chain itself.  pack: chan = the [9][O] constants of mn_qa_chan_from_save -> `table`
+ *           (mn_conv2d_first_codes_table_bytes bytes, 16-byte aligned, private layout); word 0 counts the channels with a non-finite (or beyond 1e9) constant, 0 for
+ *           a valid table (the caller may read it back once).  planes: uint32 [N][ceil(O/32)][2][H][W], 4-byte aligned, every word stored once, unused high bits
+ *           of the last word group 0; neither y nor byte codes are written.  Covered: what mn_conv2d_first_sign_bits_supported covers, under the LDS size of this
+ *           epilogue.  Null / misaligned tensor or an invalid geometry (N <= 0, ...): MN_EINVAL; a valid geometry that is not covered: MN_ENOTSUP.  Nothing is
+ *           written in either case.
+ *   last  : y = conv1x1(q, w) + bias of the classifier (O <= 16) read from code planes: mn_codeconv1x1_small_fwd with the byte read replaced by a plane extraction,
+ *           same channel and partial-sum order -- the result equals that entry point's on the unpacked planes to the bit.  planes [N][ceil(C/32)][2][HW] and
+ *           y [N][O][HW] 16-byte aligned; HW % 4 == 0.  Null / misaligned / N <= 0: MN_EINVAL; a shape mn_planesconv1x1_small_supported refuses: MN_ENOTSUP. */
+int mn_conv2d_first_codes_supported(const mn_conv_geom* g, int a_bits_out);
+int64_t mn_conv2d_first_codes_table_bytes(int64_t O, int a_bits_out);
+int mn_conv2d_first_codes_pack(const float* chan, int64_t O, int a_bits_out, uint32_t* table, mn_stream_t stream);
+int mn_conv2d_first_codes(const mn_conv_geom* g, const float* x, const float* w, const float* bias, const uint32_t* table, uint32_t* planes, mn_stream_t stream);
+int mn_planesconv1x1_small_supported(int64_t C, int64_t HW, int64_t O, int a_bits);
+int mn_planesconv1x1_small_fwd(const uint32_t* planes, int a_bits, const float* w, const float* bias, float* y, int64_t N, int64_t C, int64_t HW, int64_t O,
+                               mn_stream_t stream);
 
 #ifdef __cplusplus
 }

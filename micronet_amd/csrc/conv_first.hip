@@ -18,6 +18,7 @@
 // Geometry: groups 1, stride 1, dilation 1, "same" padding (Ho = H, Wo = W), W % 4 == 0, K <= 76 -- anything else stays on
 // the generic kernels.
 #include "qgemm_dev.h"
+#include "qa_thresholds.h"          // EPI 4: the fp32-input thresholds of the DoReFa chain, and the chain itself beyond their range
 
 #include <stdlib.h>
 
@@ -61,6 +62,9 @@ struct C1Params {
     uint8_t* mask4;       // [N][O][H W / 4]: low nibble = pass bits of 4 consecutive pixels (EPI 1: |z| < 1; EPI 2: z > 0), high nibble (EPI 2): ... and the clamp test
     int mask_shift;       // backward: which nibble (4: the gradient is w.r.t. the QUANTISED activation)
     uint32_t* bits;       // k_c1b_fwd<MT, EPI 3>: sign(conv + bias) as activation bits [N][ceil(O / 32)][H][W] (qgemm_bits.hip), nothing else written
+    // k_c1b_fwd<MT, EPI 4>: the 2-bit DoReFa code of conv + bias as code planes [N][ceil(O / 32)][2][H][W] (qgemm_codes.h), nothing else written
+    const float4* ctab;   // [O][2]: (T_1, T_2, T_3, flip), (mean, invstd, gamma, beta) -- k_c1_codes_pack
+    uint32_t* planes;
 };
 
 // stage the image strip (with zero halo) of image n, rows [row0 - ph, row0 + R + KH - 1 - ph) into xs[c][prow][pcol]
@@ -185,6 +189,7 @@ __global__ __launch_bounds__(256, 2) void k_c1_fwd(const C1Params p) {
 // weights are A fragments in registers for the block's lifetime (3 terms x 3 K steps x MT).  Pixel p sits in tile row (p & 3) * 16 + (p >> 2): MFMA column j of
 // n-tile q is pixel 4 j + q, so a lane ends with float4 = 4 consecutive pixels per out-channel (the write side takes the bank conflicts of that permutation: 9
 // writes against 36 fragment reads per chunk).
+constexpr float C1C_S = (float)(1.0 / 3.0);          // dorefa_scale(2): the scale of the 2-bit code EPI 4 writes
 #define C1B_KP 96            // padded K (3 K steps of 32)
 #define C1B_LD 104           // u16 per im2col row: 96 + 8 pad (208-byte rows: the 16 rows of a fragment read cover all banks)
 template <int MT, int EPI = 0>
@@ -207,6 +212,14 @@ __global__ __launch_bounds__(256, 2) void k_c1b_fwd(const C1Params p) {
     for (int i = tid; i < 64 * MT; i += 256) { const int m = cblk * 64 * MT + i; bs[i] = (p.bias && m < p.O) ? p.bias[m] : 0.f; }
     float4* bc = reinterpret_cast<float4*>(bs + 64 * MT);          // EPI 1 / 2: [64 MT] mean, invstd, gamma, beta
     uint32_t* wvb = reinterpret_cast<uint32_t*>(bs + 64 * MT);     // EPI 3 (same bytes): [4 waves][64 pixels][2] sign bits of a wave's 16 MT channels
+    float4* tc = reinterpret_cast<float4*>(bs + 64 * MT);          // EPI 4: [64 MT][2] thresholds + flip, the chain's four constants; behind them [2 planes] x the strings of EPI 3
+    if (EPI == 4) {
+        wvb = reinterpret_cast<uint32_t*>(tc + 2 * 64 * MT);
+        for (int i = tid; i < 2 * 64 * MT; i += 256) {
+            const int m = cblk * 64 * MT + (i >> 1);
+            tc[i] = m < p.O ? p.ctab[2 * m + (i & 1)] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
     if (EPI == 1 || EPI == 2)
         for (int i = tid; i < 64 * MT; i += 256) {
             const int m = cblk * 64 * MT + i, mc = m < p.O ? m : p.O - 1;
@@ -360,6 +373,124 @@ __global__ __launch_bounds__(256, 2) void k_c1b_fwd(const C1Params p) {
                 }
                 const int gw = cblk * 2 * MT + wd;
                 if (gw < OW && px < npix) p.bits[((int64_t)n * OW + gw) * p.H * p.W + row0 * p.W + px] = word;
+            }
+            continue;
+        }
+        if (EPI == 4) {
+            // (lane indices re-derived here: kept live across the MFMA phase they cost registers this epilogue does not have)
+            const int tid4 = (int)mn_opaque((uint32_t)threadIdx.x), lane4 = tid4 & 63, j4 = lane4 & 15, kg4 = lane4 >> 4;
+            // the 2-bit DoReFa code of the plain epilogue's acc + bb as code planes (the layout of qgemm_codes.h), neither y nor byte codes written.  The code is
+            // k_qa_fwd<1, 0, 0>'s: #{k : u >= T_k}, u = flip * yv, with the channel's thresholds of qa_thresholds.h while |u| <= 1e9; beyond that, for NaN, and for a
+            // channel whose constants are not qa_chan_finite (flip = NaN in the table), qa_code_of<1> itself.  The strings are EPI 3's, formed per plane; both
+            // planes' words are assembled behind one barrier.
+            // one plane and one half (two 16-channel tiles: 32 bits per pixel) of the wave's strings at a time: four string registers live, not sixteen
+            // (k_c1b_fwd<4, 3> sits at 246 VGPRs).  Bits are set at the constant positions t2 * 16 + r; the lane's 4 kg is applied to the finished string.
+            auto sweep = [&](int pl, int half, uint32_t (&str)[4]) -> int {
+                int wild = 0;
+#pragma unroll
+                for (int t2 = 0; t2 < 2; ++t2) {
+                    const int t = 2 * half + t2;
+                    if (t >= MT) continue;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        // (opaque: a barrier for the scheduler, which otherwise hoists the constants of all the lane's channels -- 80 registers)
+                        const int ci = (int)mn_opaque((uint32_t)(ch0 + t * 16 + kg4 * 4 + r));
+                        const float bb = bs[ci];
+                        const float4 th = tc[2 * ci];
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const float yv = acc[q][t < MT ? t : 0][r] + bb;
+                            const float u = th.w * yv;
+                            wild |= (int)!(fabsf(u) <= QA_F32_RANGE);
+                            // T_1 <= T_2 <= T_3: bit 1 of the code is u >= T_2, bit 0 is (T_1 <= u < T_2) or u >= T_3
+                            const uint32_t bit = pl ? (uint32_t)(u >= th.y) : (uint32_t)((u >= th.x && !(u >= th.y)) || u >= th.z);
+                            str[q] |= bit << (t2 * 16 + r);
+                        }
+                    }
+                }
+                return wild;
+            };
+            // A lane that meets an element outside the thresholds' range (|u| > 1e9, NaN, or a channel that is not qa_chan_finite: flip = NaN) replaces its bits by
+            // the chain's own.  Unrolled in the sweep, the chain's division costs more registers than the kernel has (128 bytes of scratch per lane at MT = 4), so
+            // every lane parks its accumulators in the im2col tile first -- all waves are past their MFMAs behind this barrier, the next expand is behind the one at
+            // the top of the loop -- and such a lane walks them in a ROLLED loop: one element per trip, both planes from one evaluation of qa_code_of<1>.  The
+            // wave's strings are shared by its four kg groups: a bit is corrected by adding (chain bit - threshold bit) << position, which cannot carry or borrow.
+            __syncthreads();
+            float* stg = reinterpret_cast<float*>(im);          // [8 (t2, q)][256 threads][4 r]: 32 KB of the tile's 39 KB, one half at a time
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                int wild = 0;
+                if (2 * half < MT) {
+#pragma unroll
+                    for (int t2 = 0; t2 < 2; ++t2)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)
+                            if (2 * half + t2 < MT) *reinterpret_cast<f32x4*>(stg + ((t2 * 4 + q) * 256 + tid4) * 4) = acc[q][2 * half + t2 < MT ? 2 * half + t2 : 0];
+                }
+#pragma unroll
+                for (int pl = 0; pl < 2; ++pl) {
+                    uint32_t str[4] = {0u, 0u, 0u, 0u};
+                    if (2 * half < MT) {
+                        wild |= sweep(pl, half, str);
+                        // channels beyond O: code 0 (the unused high bits of the last word group); pixels beyond the strip are never stored
+                        const int nv = p.O - m0 - 32 * half;
+                        const uint32_t vm = nv >= 32 ? 0xffffffffu : (nv > 0 ? (1u << nv) - 1u : 0u);
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            str[q] <<= 4 * kg4;
+                            str[q] |= __shfl_xor(str[q], 16, 64); str[q] |= __shfl_xor(str[q], 32, 64);
+                            str[q] &= vm;
+                        }
+                    }
+                    if (kg4 == 0) {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) wvb[pl * 4 * 64 * 2 + (wave * 64 + 4 * j4 + q) * 2 + half] = str[q];
+                    }
+                }
+                if (2 * half >= MT) continue;
+                int anyw = wild;          // wave-uniform: the wave's strings above are written before any of its lanes corrects them
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) anyw |= __shfl_xor(anyw, d, 64);
+                if (anyw && wild) {
+#pragma unroll 1
+                    for (int e = 0; e < 32; ++e) {          // element (t2, q, r) of the half
+                        const int t2 = e >> 4, q = (e >> 2) & 3, r = e & 3, t = 2 * half + t2;
+                        const int cl = t * 16 + kg4 * 4 + r;
+                        if (t >= MT || m0 + cl >= p.O) continue;
+                        const int ci = ch0 + cl;
+                        const float yv = stg[((t2 * 4 + q) * 256 + tid4) * 4 + r] + bs[ci];
+                        const float4 th = tc[2 * ci], cc = tc[2 * ci + 1];
+                        const float u = th.w * yv;
+                        const uint32_t fast = (uint32_t)(u >= th.x) + (uint32_t)(u >= th.y) + (uint32_t)(u >= th.z);
+                        QaCh k;
+                        k.alpha = 1.f; k.bias = 0.f; k.mean = cc.x; k.invstd = cc.y; k.ga = cc.z; k.be = cc.w; k.A = 0.f; k.B = 0.f; k.gi = 0.f;
+                        const uint32_t code = qa_code_of<1>(yv, k, C1C_S);
+#pragma unroll
+                        for (int pl = 0; pl < 2; ++pl) {
+                            const uint32_t d = ((code >> pl) & 1u) - ((fast >> pl) & 1u);          // 0, 1 or -1 (mod 2^32)
+                            if (d) atomicAdd(wvb + pl * 4 * 64 * 2 + (wave * 64 + 4 * j4 + q) * 2 + half, d << (cl & 31));
+                        }
+                    }
+                }
+            }
+            __syncthreads();          // (the strings are rewritten behind the next chunk's expand barrier: every thread has read them by then)
+            const int px = chunk * 64 + lane4, OW = (p.O + 31) >> 5;
+            for (int wd = wave; wd < 2 * MT; wd += 4) {          // word wd of the block = bits [32 wd, 32 wd + 32) of the four waves' strings laid end to end
+                const int gw = cblk * 2 * MT + wd;
+#pragma unroll
+                for (int pl = 0; pl < 2; ++pl) {
+                    const uint32_t* wv = wvb + pl * 4 * 64 * 2;
+                    uint32_t word = 0u;
+#pragma unroll
+                    for (int w4 = 0; w4 < 4; ++w4) {
+                        const int sh = w4 * 16 * MT - 32 * wd;
+                        if (sh > -16 * MT && sh < 32) {
+                            const uint64_t v = (uint64_t)wv[(w4 * 64 + lane4) * 2] | ((uint64_t)wv[(w4 * 64 + lane4) * 2 + 1] << 32);
+                            word |= sh >= 0 ? (uint32_t)(v << sh) : (uint32_t)(v >> -sh);
+                        }
+                    }
+                    if (gw < OW && px < npix) p.planes[(((int64_t)n * OW + gw) * 2 + pl) * p.H * p.W + row0 * p.W + px] = word;
+                }
             }
             continue;
         }
@@ -1012,6 +1143,75 @@ int c1_fwd_sign_bits(const mn_conv_geom* g, const float* x, const float* w, cons
 #undef C1B_LAUNCH
     mn_prof_end(s);
     MN_CHECK_LAUNCH("mn_conv2d_first_sign_bits");
+    return MN_OK;
+}
+// the deployed first block of a DoReFa W2A2 net (inference.dorefa_compile_codes(code_ends=True)): the 2-bit code of relu(bn(conv + bias)) straight to code planes.
+// Table: 8 header words ([0] channels whose constants fail qa_chan_finite, [1] O, [2] a_bits_out), then per channel (T_1, T_2, T_3, flip), (mean, invstd, gamma, beta).
+#define C1C_HDR 8
+__global__ __launch_bounds__(64) void k_c1_codes_pack(const float* __restrict__ chan, int O, float s, uint32_t* __restrict__ tab) {
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c == 0) { tab[1] = (uint32_t)O; tab[2] = 2u; }
+    if (c >= O) return;
+    const QaCh k = qa_load_ch(chan, O, c);
+    const bool fin = qa_chan_finite(k);
+    float4 th = make_float4(NAN, NAN, NAN, NAN);          // flip = NaN: u is NaN, every element of the channel takes the element-wise chain
+    if (fin) {
+        const float flip = qa_flip_of_f32(k, s);
+        th = make_float4(qa_threshold_of_f32(k, s, flip, 1u), qa_threshold_of_f32(k, s, flip, 2u), qa_threshold_of_f32(k, s, flip, 3u), flip);
+    } else atomicAdd(tab, 1u);
+    float4* row = reinterpret_cast<float4*>(tab + C1C_HDR) + 2 * c;
+    row[0] = th;
+    row[1] = make_float4(k.mean, k.invstd, k.ga, k.be);
+}
+static size_t c1b_codes_lds_bytes(const C1Params& p) {          // c1b_lds_bytes with two float4 per channel in place of one, and the two planes' strings behind them
+    return (size_t)p.xs_bytes + (size_t)3 * 64 * C1B_LD * 2 + C1B_KP * 4 + 64 * 4 * 4 + 64 * 4 * 32 + 2 * 4 * 64 * 2 * 4;
+}
+// k_c1b_fwd<4, 4> does not fit the register file (124 bytes of scratch per lane; <1 .. 3, 4>: none) and is not built: more than 192 output channels run as blocks of
+// 128 on <2, 4> -- the same accumulation per channel, the image strip expanded once more per extra block
+static int plan_c1_codes(const mn_conv_geom* g, C1Plan* pl) {
+    if (!plan_c1(g, pl) || c1b_codes_lds_bytes(pl->p) > 80 * 1024) return 0;
+    if (pl->MT == 4) {
+        pl->MT = 2;
+        pl->cblks = (g->O + 127) / 128;
+        pl->p.Opad = pl->cblks * 128;
+        const int64_t nbf = (int64_t)g->N * pl->p.strips * pl->cblks;
+        if (nbf > 0x7fffffff) return 0;
+        pl->grid_f = (int)nbf;
+    }
+    return 1;
+}
+int c1_codes_supported(const mn_conv_geom* g, int a_bits_out) {
+    C1Plan pl;
+    return a_bits_out == 2 && plan_c1_codes(g, &pl);
+}
+int64_t c1_codes_table_bytes(int64_t O, int a_bits_out) {
+    return (a_bits_out == 2 && O > 0 && O <= (1 << 20)) ? 4 * (int64_t)C1C_HDR + 32 * O : 0;
+}
+int c1_codes_pack(const float* chan, int64_t O, int a_bits_out, uint32_t* table, hipStream_t s) {
+    if (!chan || !table || !aligned16(table) || O <= 0) MN_FAIL(MN_EINVAL, "mn_conv2d_first_codes_pack: null argument / table not 16-byte aligned");
+    if (!c1_codes_table_bytes(O, a_bits_out)) MN_FAIL(MN_ENOTSUP, "mn_conv2d_first_codes_pack: only 2-bit output codes");
+    if (hipMemsetAsync(table, 0, 4 * C1C_HDR, s) != hipSuccess) MN_FAIL(MN_EHIP, "mn_conv2d_first_codes_pack: header reset failed");
+    mn_set_last_kernel("k_c1_codes_pack");
+    hipLaunchKernelGGL(k_c1_codes_pack, dim3((unsigned)((O + 63) / 64)), dim3(64), 0, s, chan, (int)O, dorefa_scale(a_bits_out), table);
+    MN_CHECK_LAUNCH("mn_conv2d_first_codes_pack");
+    return MN_OK;
+}
+int c1_fwd_codes(const mn_conv_geom* g, const float* x, const float* w, const float* bias, const uint32_t* table, uint32_t* planes, hipStream_t s) {
+    C1Plan pl;
+    if (!plan_c1_codes(g, &pl)) MN_FAIL(MN_ENOTSUP, "mn_conv2d_first_codes: geometry not covered by the first-layer forward (k_c1b_fwd)");
+    C1Params& p = pl.p;
+    p.x = x; p.bias = bias; p.y = nullptr; p.gy = nullptr; p.part = nullptr; p.dbpart = nullptr; p.want_db = 0; p.da = nullptr;
+    p.relu = 0; p.mm = nullptr; p.codes = nullptr; p.mask4 = nullptr; p.wp = w; p.bits = nullptr;
+    p.ctab = reinterpret_cast<const float4*>(table + C1C_HDR); p.planes = planes; p.qs = C1C_S;
+    const size_t lds_b = c1b_codes_lds_bytes(p);
+    mn_set_last_kernel("k_c1b_fwd<%d, 4>", pl.MT);
+    mn_prof_bytes(8.0 * g->N * ((g->O + 31) / 32) * g->H * g->W + 4.0 * g->N * g->C * g->H * g->W);
+    mn_prof_begin(s);
+#define C1B_LAUNCH(MT_) { raise_lds_limit((const void*)k_c1b_fwd<MT_, 4>, lds_b); hipLaunchKernelGGL((k_c1b_fwd<MT_, 4>), dim3(pl.grid_f), dim3(256), lds_b, s, p); }
+    if (pl.MT == 3) C1B_LAUNCH(3) else if (pl.MT == 2) C1B_LAUNCH(2) else C1B_LAUNCH(1)
+#undef C1B_LAUNCH
+    mn_prof_end(s);
+    MN_CHECK_LAUNCH("mn_conv2d_first_codes");
     return MN_OK;
 }
 int c1_fwd_act(const mn_conv_geom* g, const float* x, const float* w, const float* bias, float* y, int relu, float* mm, void* ws, int64_t ws_bytes, hipStream_t s) {

@@ -985,6 +985,22 @@ extern "C" int mn_conv2d_first_sign_bits(const mn_conv_geom* g, const float* x, 
     if (!mn_conv2d_first_sign_bits_supported(g)) MN_FAIL(MN_ENOTSUP, "mn_conv2d_first_sign_bits: geometry not covered by the first-layer forward (mn_conv2d_first_sign_bits_supported)");
     return c1_fwd_sign_bits(g, x, w, bias, bits, (hipStream_t)stream);
 }
+extern "C" int mn_conv2d_first_codes_supported(const mn_conv_geom* g, int a_bits_out) {
+    if (!g || check_geom(g, "mn_conv2d_first_codes_supported") != MN_OK) return 0;
+    return c1_supported(g, 0) && c1_codes_supported(g, a_bits_out);
+}
+extern "C" int64_t mn_conv2d_first_codes_table_bytes(int64_t O, int a_bits_out) { return c1_codes_table_bytes(O, a_bits_out); }
+extern "C" int mn_conv2d_first_codes_pack(const float* chan, int64_t O, int a_bits_out, uint32_t* table, mn_stream_t stream) {
+    return c1_codes_pack(chan, O, a_bits_out, table, (hipStream_t)stream);
+}
+extern "C" int mn_conv2d_first_codes(const mn_conv_geom* g, const float* x, const float* w, const float* bias, const uint32_t* table, uint32_t* planes, mn_stream_t stream) {
+    int rc = check_geom(g, "mn_conv2d_first_codes");
+    if (rc) return rc;
+    if (!x || !w || !table || !planes || (((uintptr_t)planes) & 3) || (((uintptr_t)table) & 15))
+        MN_FAIL(MN_EINVAL, "mn_conv2d_first_codes: null tensor / planes not 4-byte aligned / table not 16-byte aligned");
+    if (!mn_conv2d_first_codes_supported(g, 2)) MN_FAIL(MN_ENOTSUP, "mn_conv2d_first_codes: geometry not covered by the first-layer forward (mn_conv2d_first_codes_supported)");
+    return c1_fwd_codes(g, x, w, bias, table, planes, (hipStream_t)stream);
+}
 extern "C" int mn_conv2d_bwd_first_mask_gram(const mn_conv_geom* g, const float* da, const uint8_t* mask4, int quant, const float* save, const float* gamma,
                                              const float* w, const float* bias, const double* gram, const float* x, float* dw, float* dbias, float* dgamma,
                                              float* dbeta, void* ws, int64_t ws_bytes, mn_stream_t stream) {

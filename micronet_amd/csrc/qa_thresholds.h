@@ -40,3 +40,23 @@ __device__ __forceinline__ int qa_threshold_of(const QaCh& k, float s, float fli
     }
     return lo;
 }
+
+// ---- IN = 1: the chain on fp32 y (the block behind the un-quantised first conv; alpha and bias take no part).  It is monotone in y the same way, so per channel
+// there are flip and three fp32 thresholds with code = #{k : u >= T_k}, u = flip * y, for every |y| <= 1e9: with the constants within qa_chan_finite no intermediate
+// overflows (|y - mean| <= 2e9, |zhat| <= 2e18, |z| <= 2e27 + 1e9), so no inf * 0 breaks the monotonicity.  Beyond that range (and for NaN) the caller evaluates
+// qa_code_of<1> itself.  T_k = the smallest u in [-1e9, 1e9] whose exact chain value reaches k: bisection over the ordered bit patterns of fp32.
+// the order-preserving integer key of an fp32 (-0 and +0 are one point, key 0) and its inverse
+__device__ __forceinline__ int64_t qa_f32_key(float v) { const uint32_t b = mn_f2u(v); return (b & 0x80000000u) ? -(int64_t)(b & 0x7fffffffu) : (int64_t)b; }
+__device__ __forceinline__ float qa_f32_of_key(int64_t k) { return k >= 0 ? mn_u2f((uint32_t)k) : mn_u2f(0x80000000u | (uint32_t)(-k)); }
+#define QA_F32_RANGE 1.0e9f
+__device__ __forceinline__ float qa_flip_of_f32(const QaCh& k, float s) { return (qa_code_of<1>(QA_F32_RANGE, k, s) < qa_code_of<1>(-QA_F32_RANGE, k, s)) ? -1.f : 1.f; }
+// smallest u in [-1e9, 1e9] with code(flip * u) >= level, +inf if none (32 steps: the range holds 2.6e9 keys)
+__device__ __forceinline__ float qa_threshold_of_f32(const QaCh& k, float s, float flip, uint32_t level) {
+    int64_t lo = qa_f32_key(-QA_F32_RANGE), hi = qa_f32_key(QA_F32_RANGE) + 1;          // invariant: code(lo - 1) < level (virtually), code(hi) >= level (virtually at the end)
+    const int64_t none = hi;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (qa_code_of<1>(flip * qa_f32_of_key(mid), k, s) >= level) hi = mid; else lo = mid + 1;
+    }
+    return lo == none ? INFINITY : qa_f32_of_key(lo);
+}

@@ -38,6 +38,11 @@ int c1_fwd_bnact(const mn_conv_geom* g, const float* x, const float* w, const fl
 // sign(conv + bias) of the deployed first block as activation bits (qgemm_bits.hip's layout): k_c1b_fwd's accumulation, one launch, neither y nor byte codes written
 int c1_sign_bits_supported(const mn_conv_geom* g);
 int c1_fwd_sign_bits(const mn_conv_geom* g, const float* x, const float* w, const float* bias, uint32_t* bits, hipStream_t s);
+// the 2-bit DoReFa code of relu(bn(conv + bias)) of the deployed first block as code planes (qgemm_codes.h's layout): the same accumulation, per-channel fp32 thresholds
+int c1_codes_supported(const mn_conv_geom* g, int a_bits_out);
+int64_t c1_codes_table_bytes(int64_t O, int a_bits_out);
+int c1_codes_pack(const float* chan, int64_t O, int a_bits_out, uint32_t* table, hipStream_t s);
+int c1_fwd_codes(const mn_conv_geom* g, const float* x, const float* w, const float* bias, const uint32_t* table, uint32_t* planes, hipStream_t s);
 int c1_bwd_first_mask(const mn_conv_geom* g, const float* da, const uint8_t* mask4, int quant, const float* save, const float* gamma, const float* w, const float* bias,
                       const double* gram, const float* x, float* dw, float* dbias, float* dgamma, float* dbeta, void* ws, int64_t ws_bytes, hipStream_t s);
 int c1_gram_bnstats(const mn_conv_geom* g, const float* w, const float* bias, const double* gram, float eps, float momentum, float* running_mean, float* running_var,

@@ -289,6 +289,115 @@ static void launch_nw(int nwsel, dim3 grid, hipStream_t s, const uint32_t* tab, 
 }
 static inline int nw_select(const Geom& q) { return (q.NW == 1 || (q.KS == 1 && (q.NW == 2 || q.NW == 4))) ? q.NW : 0; }
 
+// ---------------------------------------------------------------- the classifier on planes: 1x1 conv, few outputs, fp32 weights, code planes in
+// k_sconv_fwd<OP, 1> (norm_kernels.hip: the last conv of a DoReFa net on one-byte codes) with the byte read replaced by a plane extraction: j = b0 + 2 b1 as a float
+// (exact).  Everything that decides the fp32 sums is that kernel's -- the 1024-thread block of 64 consecutive pixels, 16 waves splitting the channels into ranges of
+// ceil(C / 16), lane (pq, cs) accumulating w * j over the channels c0 + cs + 4 i of its wave in increasing order, the two shuffles, the fixed-order LDS combine, the
+// final * ascale + bias -- so the result equals mn_codeconv1x1_small_fwd on the unpacked planes to the bit (as k_bitsconv1x1_small relates to k_sconv_fwd<OP, 0>).
+// A lane's channels of one 32-channel word group come out of one 16-byte load per plane; two word groups are in flight per trip.
+enum { PC_WAVES = 16 };
+template <int OP>
+__global__ __launch_bounds__(1024) void k_planesconv1x1_small(const uint32_t* __restrict__ planes, const float* __restrict__ w, const float* __restrict__ bias,
+                                                              float* __restrict__ y, int C, int Cw, int HW, int O, int64_t NP, float ascale) {
+    HIP_DYNAMIC_SHARED(float, smem)
+    float* wl = smem;                          // [C][OP]
+    float* red = smem + (size_t)C * OP;        // [8][OP][64]
+    const int tid = threadIdx.x, lane = tid & 63, wv = mn_uniform(tid >> 6), pq = lane & 15, cs = lane >> 4;
+    for (int i = tid; i < C * OP; i += 1024) wl[i] = 0.f;
+    __syncthreads();
+    for (int i = tid; i < C * O; i += 1024) {       // coalesced read of w[o][c], transposed LDS write
+        const int o = i / C, c = i - o * C;
+        wl[c * OP + o] = w[i];
+    }
+    const int64_t P = (int64_t)blockIdx.x * 64 + 4 * pq;
+    const int64_t Pc = P < NP ? P : 0;
+    const int64_t n = Pc / HW;
+    const int p = (int)(Pc - n * HW);
+    float acc[4][OP];
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int o = 0; o < OP; ++o) acc[e][o] = 0.f;
+    const int per = (C + PC_WAVES - 1) / PC_WAVES;
+    const int c0 = wv * per, c1 = (c0 + per) < C ? (c0 + per) : C;
+    const uint32_t* src = planes + n * Cw * A * HW + p;          // plane 0 of word group 0 at the lane's four pixels (16-byte aligned: HW % 4 == 0)
+    __syncthreads();
+    auto add = [&](const u32x4& x0, const u32x4& x1, int sh, int c) {
+        const float s0 = (float)(((x0[0] >> sh) & 1u) + 2u * ((x1[0] >> sh) & 1u)), s1 = (float)(((x0[1] >> sh) & 1u) + 2u * ((x1[1] >> sh) & 1u));
+        const float s2 = (float)(((x0[2] >> sh) & 1u) + 2u * ((x1[2] >> sh) & 1u)), s3 = (float)(((x0[3] >> sh) & 1u) + 2u * ((x1[3] >> sh) & 1u));
+#pragma unroll
+        for (int o4 = 0; o4 < OP; o4 += 4) {
+            const float4 w4 = *reinterpret_cast<const float4*>(wl + c * OP + o4);
+            const float wv_[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                acc[0][o4 + k] += wv_[k] * s0; acc[1][o4 + k] += wv_[k] * s1; acc[2][o4 + k] += wv_[k] * s2; acc[3][o4 + k] += wv_[k] * s3;
+            }
+        }
+    };
+    const int first = c0 + cs;                               // this lane's channels: first + 4 i < c1, in increasing order
+    if (first < c1) {
+        const int wlast = (c1 - 1) >> 5, r4 = first & 3;     // (wlast <= Cw - 1: every word read lies inside the pixel's Cw word groups)
+        for (int wi = first >> 5; wi <= wlast; wi += 2) {
+            const int wj = wi + 1 <= wlast ? wi + 1 : wlast;
+            const uint32_t* pa = src + (int64_t)wi * A * HW;
+            const uint32_t* pb = src + (int64_t)wj * A * HW;
+            const u32x4 xa0 = *reinterpret_cast<const u32x4*>(pa), xa1 = *reinterpret_cast<const u32x4*>(pa + HW);
+            const u32x4 xb0 = *reinterpret_cast<const u32x4*>(pb), xb1 = *reinterpret_cast<const u32x4*>(pb + HW);
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                const int c = wi * 32 + r4 + 4 * b;
+                if (c >= first && c < c1) add(xa0, xa1, r4 + 4 * b, c);
+            }
+            if (wi + 1 <= wlast) {
+#pragma unroll
+                for (int b = 0; b < 8; ++b) {
+                    const int c = wj * 32 + r4 + 4 * b;
+                    if (c < c1) add(xb0, xb1, r4 + 4 * b, c);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int o = 0; o < OP; ++o) {
+            float t = acc[e][o];
+            t += __shfl_xor(t, 16, 64); t += __shfl_xor(t, 32, 64);
+            acc[e][o] = t;
+        }
+    if (wv >= 8 && cs == 0) {
+#pragma unroll
+        for (int o = 0; o < OP; ++o)
+            *reinterpret_cast<float4*>(red + ((wv - 8) * OP + o) * 64 + 4 * pq) = make_float4(acc[0][o], acc[1][o], acc[2][o], acc[3][o]);
+    }
+    __syncthreads();
+    if (wv < 8 && cs == 0) {
+#pragma unroll
+        for (int o = 0; o < OP; ++o) {
+            float4* r = reinterpret_cast<float4*>(red + (wv * OP + o) * 64 + 4 * pq);
+            const float4 t = *r;
+            *r = make_float4(acc[0][o] + t.x, acc[1][o] + t.y, acc[2][o] + t.z, acc[3][o] + t.w);
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < O * 16; i += 1024) {
+        const int o = i >> 4, q = i & 15;                       // quad q of the block
+        const int64_t Pq = (int64_t)blockIdx.x * 64 + 4 * q;
+        if (Pq < NP) {
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int k = 0; k < 8; ++k) {                        // fixed order
+                const float4 t = *reinterpret_cast<const float4*>(red + (k * OP + o) * 64 + 4 * q);
+                v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
+            }
+            const float bb = bias ? bias[o] : 0.f;
+            const int64_t nq = Pq / HW;
+            v.x *= ascale; v.y *= ascale; v.z *= ascale; v.w *= ascale;
+            *reinterpret_cast<float4*>(y + (nq * O + o) * HW + (Pq - nq * HW)) = make_float4(v.x + bb, v.y + bb, v.z + bb, v.w + bb);
+        }
+    }
+}
+
 static inline bool planes_args_ok(const void* a, const void* b, int64_t N, int64_t C, int64_t HW, int a_bits) {
     return a && b && N > 0 && C > 0 && HW > 0 && HW % 4 == 0 && !(((uintptr_t)a) & 3) && !(((uintptr_t)b) & 3) && C <= (1 << 20) && HW <= (1 << 26) && a_bits >= 1 && a_bits <= 8;
 }
@@ -328,6 +437,31 @@ extern "C" int64_t mn_codeconv_table_bytes(const mn_conv_geom* g, int a_bits_in,
     mn_codes::Geom q;
     if (!mn_codes::make_geom(g, a_bits_in, w_bits, a_bits_out, q)) return 0;
     return 4 * ((int64_t)mn_codes::HDR + (int64_t)q.OW * 32 * q.stride);
+}
+
+extern "C" int mn_planesconv1x1_small_supported(int64_t C, int64_t HW, int64_t O, int a_bits) {
+    return a_bits == mn_codes::A && mn_bitsconv1x1_small_supported(C, HW, O);          // (mn_signconv1x1_small_supported's LDS bound)
+}
+extern "C" int mn_planesconv1x1_small_fwd(const uint32_t* planes, int a_bits, const float* w, const float* bias, float* y, int64_t N, int64_t C, int64_t HW, int64_t O,
+                                          mn_stream_t stream) {
+    if (!planes || !w || !y || N <= 0 || !aligned16(planes) || !aligned16(y)) MN_FAIL(MN_EINVAL, "mn_planesconv1x1_small_fwd: null argument / planes and y must be 16-byte aligned");
+    if (!mn_planesconv1x1_small_supported(C, HW, O, a_bits))
+        MN_FAIL(MN_ENOTSUP, "mn_planesconv1x1_small_fwd: needs 2-bit codes, O <= 16, C >= 4, HW %% 4 == 0 and the weights in LDS (mn_planesconv1x1_small_supported)");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t NP = N * HW, nb = (NP + 63) / 64;
+    const int Cw = (int)((C + 31) >> 5);
+    if (nb > 0x7fffffff || N * Cw * a_bits * HW >= (1ll << 40)) MN_FAIL(MN_ENOTSUP, "mn_planesconv1x1_small_fwd: tensor too large");
+    const int OP = (int)((O + 3) / 4 * 4);
+    const size_t lds = ((size_t)C * OP + (size_t)8 * OP * 64) * 4;
+    const float ascale = dorefa_scale(a_bits);
+    mn_set_last_kernel("k_planesconv1x1_small"); mn_prof_bytes(4.0 * N * Cw * a_bits * HW + 4.0 * N * O * HW + 4.0 * O * C); mn_prof_begin(s);
+#define PC_LAUNCH(OPV) { raise_lds_limit((const void*)mn_codes::k_planesconv1x1_small<OPV>, lds); \
+        hipLaunchKernelGGL((mn_codes::k_planesconv1x1_small<OPV>), dim3((unsigned)nb), dim3(1024), lds, s, planes, w, bias, y, (int)C, Cw, (int)HW, (int)O, NP, ascale); }
+    if (OP == 4) PC_LAUNCH(4) else if (OP == 8) PC_LAUNCH(8) else if (OP == 12) PC_LAUNCH(12) else PC_LAUNCH(16)
+#undef PC_LAUNCH
+    mn_prof_end(s);
+    MN_CHECK_LAUNCH("mn_planesconv1x1_small_fwd");
+    return MN_OK;
 }
 
 #define MN_CODECONV_COVER "geometry not covered (2-bit codes and weights; 1x1 or 3x3 / padding 1, stride 1, no input shuffle, K * 9 <= 32767)"

@@ -541,11 +541,15 @@ def _codeconv_kernel_name(k, cin, groups, pool):
 class CodePlan(nn.Module):
     """What ``dorefa_compile_codes`` returns: first block (fp32 conv + BatchNorm + ReLU + the next conv's quantizer, the model's own module) -> plane pack -> n
     code blocks (2x2 max-pools folded in) -> plane unpack -> last block and tail (the model's own modules).  Eval only; owns the packed weight tables (and the
-    per-channel constants they were packed from: ``layers[i]["chan"]``) and one set of plane buffers per input shape."""
+    per-channel constants they were packed from: ``layers[i]["chan"]``) and one set of plane buffers per input shape.  ``code_ends``: the first conv's kernel writes
+    the first stage's planes itself (no fp32 map, no byte codes, no pack; ``first_table`` holds its per-channel thresholds) and the last conv reads the last stage's
+    planes (no unpack, no uint8 buffer); what follows the last conv inside its block, and the tail, run unchanged."""
 
-    def __init__(self, first, layers, last, tail, flatten, report):
+    def __init__(self, first, layers, last, tail, flatten, report, code_ends=False, first_table=None, first_chan=None):
         super().__init__()
         self.first, self.last, self.tail = first, last, nn.ModuleList(tail)
+        self.code_ends = bool(code_ends)
+        self.first_table, self.first_chan = first_table, first_chan
         self.layers = layers              # dicts: geometry, table, chan, pool, out_order
         self.flatten = flatten
         self.report = report
@@ -565,7 +569,16 @@ class CodePlan(nn.Module):
         key = (tuple(shape), str(device))
         if key not in self._ws:
             N, Cc, H, W = shape
-            if (H * W) % 4:
+            g0 = None
+            if self.code_ends:
+                import ctypes as C
+                conv = self.first.conv
+                g0 = _lib.ConvGeom(N, conv.in_channels, H, W, Cc, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.stride[1], conv.padding[0], conv.padding[1],
+                                   conv.dilation[0], conv.dilation[1], conv.groups, 0)
+                if not _lib.get_lib().mn_conv2d_first_codes_supported(C.byref(g0), CODE_BITS):
+                    raise _err("dorefa_compile_codes(code_ends=True): %s.conv: a %d x %d x %d x %d input is not covered by mn_conv2d_first_codes (W %% 4 == 0, H * W %% 32 == 0, "
+                               "the image strip in LDS)" % (self.report[0]["name"], N, conv.in_channels, H, W))
+            elif (H * W) % 4:
                 raise _err("dorefa_compile_codes: %s: its %d x %d output cannot be packed (mn_codes_pack_planes needs H * W %% 4 == 0)" % (self.report[0]["name"], H, W))
             bufs, geoms = [torch.empty((N, (Cc + 31) // 32, CODE_BITS, H, W), dtype=torch.int32, device=device)], []
             for L in self.layers:
@@ -577,10 +590,16 @@ class CodePlan(nn.Module):
                     H, W = H // 2, W // 2
                 bufs.append(torch.empty((N, (L["cout"] + 31) // 32, CODE_BITS, H, W), dtype=torch.int32, device=device))
                 Cc = L["cout"]
+            if self.code_ends:
+                if not _lib.get_lib().mn_planesconv1x1_small_supported(Cc, H * W, self.last.conv.out_channels, CODE_BITS):
+                    raise _err("dorefa_compile_codes(code_ends=True): %s.conv: a %d-channel %d x %d map is not covered by mn_planesconv1x1_small_fwd (its lanes own 4 "
+                               "consecutive pixels: H * W %% 4 == 0; the weights in LDS)" % (self.report[-1]["name"], Cc, H, W))
+                self._ws[key] = (bufs, geoms, None, g0)
+                return self._ws[key]
             if (H * W) % 4:
                 raise _err("dorefa_compile_codes: %s: its %d x %d output cannot be unpacked for the last block (mn_codes_unpack_planes needs H * W %% 4 == 0)"
                            % (self.layers[-1]["name"], H, W))
-            self._ws[key] = (bufs, geoms, torch.empty((N, Cc, H, W), dtype=torch.uint8, device=device))
+            self._ws[key] = (bufs, geoms, torch.empty((N, Cc, H, W), dtype=torch.uint8, device=device), g0)
         return self._ws[key]
 
     @torch.no_grad()
@@ -588,13 +607,38 @@ class CodePlan(nn.Module):
         import ctypes as C
         from micronet_amd import ops
         from micronet_amd.sign_tensor import QActTensor
+        if self.code_ends:
+            conv = self.first.conv
+            if not (type(x) is torch.Tensor and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == conv.in_channels):
+                raise _err("dorefa_compile_codes(code_ends=True): the input must be a float32 GPU tensor [N, %d, H, W] (no CPU fallback)" % conv.in_channels)
+            x = x.contiguous()
+            with torch.cuda.device(x.device):
+                bufs, geoms, c8, g0 = self._plan_buffers((x.shape[0], conv.out_channels, x.shape[2], x.shape[3]), x.device)
+                st = ops._s()
+                ops._call("mn_conv2d_first_codes", C.byref(g0), ops._p(x), ops._p(ops._chk(conv.weight.detach(), "weight")), ops._p(ops._chk(conv.bias, "bias")),
+                          ops._p(self.first_table), ops._p(bufs[0]), st)
+                for i, L in enumerate(self.layers):
+                    ops._call("mn_codeconv_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(bufs[i + 1]), int(L["pool"]), st)
+                if self.keep_stages:
+                    self.stage_codes = [b.clone() for b in bufs]
+                conv = self.last.conv
+                n_, _, _, h_, w_ = bufs[-1].shape
+                y = torch.empty((n_, conv.out_channels, h_, w_), dtype=torch.float32, device=x.device)
+                ops._call("mn_planesconv1x1_small_fwd", ops._p(bufs[-1]), CODE_BITS, ops._p(ops._chk(conv.weight.detach(), "weight")), ops._p(ops._chk(conv.bias, "bias")),
+                          ops._p(y), n_, conv.in_channels, h_ * w_, conv.out_channels, st)
+            kids = list(self.last.children())
+            for m in kids[kids.index(conv) + 1:]:          # what follows the conv inside the last block (BatchNorm + ReLU)
+                y = m(y)
+            for m in self.tail:
+                y = m(y)
+            return y.view(y.size(0), -1) if self.flatten else y
         a = self.first(x)
         if not (isinstance(a, QActTensor) and a.bits == CODE_BITS):
             raise _err("dorefa_compile_codes: %s did not hand over %d-bit activation codes (the input must be a contiguous float32 GPU tensor with H * W %% 8 == 0)"
                        % (self.report[0]["name"], CODE_BITS))
         codes = a.codes.contiguous()
         N, Cc, H, W = codes.shape
-        bufs, geoms, c8 = self._plan_buffers(codes.shape, codes.device)
+        bufs, geoms, c8, _ = self._plan_buffers(codes.shape, codes.device)
         st = ops._s()
         ops._call("mn_codes_pack_planes", ops._p(codes), N, Cc, H * W, CODE_BITS, ops._p(bufs[0]), st)
         for i, L in enumerate(self.layers):
@@ -610,7 +654,34 @@ class CodePlan(nn.Module):
         return y.view(y.size(0), -1) if self.flatten else y
 
 
-def _walk_codes(model):
+def _check_code_ends(first, nm_first, last, nm_last):
+    """``code_ends=True``: both ends must be covered by their plane kernels -- never a silent byte path.  Shape-independent part (the input shape is checked by the plan;
+    the walk has already refused a pool behind the first block, other than 2-bit codes out of it, and a channel shuffle in front of the last block)."""
+    import ctypes as C
+    from micronet_amd import _lib
+    lib = _lib.get_lib()
+    conv = first.conv
+    if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
+        raise _err("dorefa_compile_codes(code_ends=True): %s.conv: padding mode not covered by mn_conv2d_first_codes" % nm_first)
+    g = _lib.ConvGeom(1, conv.in_channels, 8, 8, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.stride[1], conv.padding[0], conv.padding[1],
+                      conv.dilation[0], conv.dilation[1], conv.groups, 0)
+    if not lib.mn_conv2d_first_codes_supported(C.byref(g), CODE_BITS):
+        raise _err("dorefa_compile_codes(code_ends=True): %s.conv: not covered by mn_conv2d_first_codes (%dx%d, stride %d, padding %d, dilation %d, groups %d, %d taps per "
+                   "output: needs \"same\" padding, stride 1, groups 1, at most 76 taps)"
+                   % (nm_first, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.padding[0], conv.dilation[0], conv.groups,
+                      conv.in_channels // conv.groups * conv.kernel_size[0] * conv.kernel_size[1]))
+    conv = last.conv
+    one = lambda v, k: tuple(v) == (k, k)
+    if not (conv.padding_mode == "zeros" and not isinstance(conv.padding, str) and one(conv.kernel_size, 1) and one(conv.stride, 1) and one(conv.padding, 0) and
+            one(conv.dilation, 1) and conv.groups == 1 and lib.mn_planesconv1x1_small_supported(conv.in_channels, 4, conv.out_channels, CODE_BITS)):
+        raise _err("dorefa_compile_codes(code_ends=True): %s.conv: the last conv is not the small 1x1 classifier mn_planesconv1x1_small_fwd covers (%dx%d, stride %d, "
+                   "padding %s, groups %d, %d -> %d channels: needs 1x1, stride 1, no padding, groups 1, at most 16 outputs)"
+                   % (nm_last, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.padding, conv.groups, conv.in_channels, conv.out_channels))
+    if getattr(last, "channel_shuffle_flag", 0) and getattr(last, "shuffle_groups", 1) > 1 or int(getattr(conv, "in_shuffle_groups", 0) or 0) > 1:
+        raise _err("dorefa_compile_codes(code_ends=True): %s: a channel shuffle in front of the last conv is not covered by mn_planesconv1x1_small_fwd" % nm_last)
+
+
+def _walk_codes(model, code_ends=False):
     """The graph walk of ``dorefa_compile_codes`` (no GPU needed): (first, layers, last, tail, flatten, report)."""
     import ctypes as C
     from micronet_amd import _lib
@@ -704,6 +775,9 @@ def _walk_codes(model):
     if first is None or last is None:
         raise _err("dorefa_compile_codes: module order not recognised (no %s block found)" % ("first" if first is None else "last"))
     rep_last = report.pop()
+    if code_ends:
+        _check_code_ends(first, report[0]["name"], last, rep_last["name"])
+        report[0]["kernel"], rep_last["kernel"] = "first conv -> planes (k_c1b_fwd)", "last conv on planes (k_planesconv1x1_small)"
     for L in layers:
         if L.pop("want_pool") != bool(L["pool"]):
             raise _err("dorefa_compile_codes: %s: the block pools its output but no 2x2 max-pool follows it (or the reverse)" % L["name"])
@@ -714,25 +788,30 @@ def _walk_codes(model):
     return first, layers, last, tail, flatten, report
 
 
-def dorefa_codes_report(model):
-    """The ``report`` ``dorefa_compile_codes(model)`` would carry -- one row per stage: name, kind, K, words, planes, kernel, pooled, out_order -- from the graph walk
-    alone: no GPU, nothing packed.  Raises like ``dorefa_compile_codes`` for whatever the code kernels do not cover."""
-    return _walk_codes(model)[5]
+def dorefa_codes_report(model, code_ends=False):
+    """The ``report`` ``dorefa_compile_codes(model, code_ends)`` would carry -- one row per stage: name, kind, K, words, planes, kernel, pooled, out_order -- from the
+    graph walk alone: no GPU, nothing packed.  Raises like ``dorefa_compile_codes`` for whatever the code kernels do not cover."""
+    return _walk_codes(model, code_ends)[5]
 
 
 @torch.no_grad()
-def dorefa_compile_codes(model):
+def dorefa_compile_codes(model, code_ends=False):
     """``model``: a DoReFa W2A2 net prepared with ``quant_inference=True`` after ``prequantize_weights``, on the GPU (the reference's ``nin_gc``, or an ``nn.Sequential``
     of the same block kinds).  Returns a ``CodePlan`` computing the same function with two bits per hidden activation; ``.report`` lists the stages.  Anything the code
-    kernels do not cover raises ``MicronetHipError`` naming the layer -- never a silent byte path (the caller still has ``model``)."""
+    kernels do not cover raises ``MicronetHipError`` naming the layer -- never a silent byte path (the caller still has ``model``).  ``code_ends=True``: the first conv
+    writes the first stage's planes in one launch and the classifier reads the last stage's planes -- no fp32 map, no byte codes, no pack / unpack launch; same codes
+    in every stage, same logits (off by default until the gain is measured)."""
     import ctypes as C
     from micronet_amd import _lib, ops
     from micronet_amd.quantization.wqaq.dorefa.quantize import _weight_is_coded
-    first, layers, last, tail, flatten, report = _walk_codes(model)
+    first, layers, last, tail, flatten, report = _walk_codes(model, code_ends)
     for L in layers:
         if not _weight_is_coded(L["conv"]):
             raise _err("dorefa_compile_codes: %s.conv: the stored weights were not found on the 2-bit grid (2k - 3) / 3 (run inference.prequantize_weights on the GPU "
                        "model first)" % L["name"])
+    if code_ends and not _weight_is_coded(last.conv):
+        raise _err("dorefa_compile_codes(code_ends=True): %s.conv: the stored weights were not found on the 2-bit grid (2k - 3) / 3 (run inference.prequantize_weights "
+                   "on the GPU model first)" % report[-1]["name"])
     for p_ in model.parameters():
         if not p_.is_cuda:
             raise _err("dorefa_compile_codes: the model is on %s: micronet_amd runs on MI355X only (no CPU fallback)" % p_.device)
@@ -788,4 +867,26 @@ def dorefa_compile_codes(model):
             raise _err("dorefa_compile_codes: %s.bn: %d output channels with a non-finite (or beyond 1e9) BatchNorm constant: no integer thresholds" % (L["name"], nonfinite))
         if bad:
             raise _err("dorefa_compile_codes: %s.conv: %d table rows with a weight off the 2-bit grid or a bad channel order" % (L["name"], bad))
-    return CodePlan(first, layers, last, tail, flatten, report)
+    if not code_ends:
+        return CodePlan(first, layers, last, tail, flatten, report)
+    # ---- the first block's per-channel thresholds: its [9][O] constants by the calls its eval forward makes (ops._bn_front on fp32 y: mn_bn_save_stats with
+    #      training = 0, mn_qa_chan_from_save -- invstd is never re-derived here); they do not depend on the input, so one 8 x 8 map of zeros will do
+    bn, nm = first.bn, report[0]["name"]
+    if not (bn.affine and bn.track_running_stats and bn.momentum is not None):
+        raise _err("dorefa_compile_codes(code_ends=True): %s.bn: needs affine parameters, running statistics and a momentum" % nm)
+    dev, Oc = first.conv.weight.device, first.conv.out_channels
+    with torch.cuda.device(dev):
+        gamma, beta = ops._chk(bn.weight.detach(), "weight"), ops._chk(bn.bias.detach(), "bias")
+        zero = torch.zeros((1, Oc, 8, 8), dtype=torch.float32, device=dev)
+        save = torch.empty((2, Oc), dtype=torch.float32, device=dev)
+        chan = torch.empty((_lib.MN_QA_NCH, Oc), dtype=torch.float32, device=dev)
+        ws = torch.empty(int(lib.mn_bnsign_ws_floats(Oc)), dtype=torch.float32, device=dev)
+        ops._call("mn_bn_save_stats", ops._p(zero), 1, Oc, 64, float(bn.eps), float(bn.momentum), 0, ops._p(bn.running_mean), ops._p(bn.running_var), ops._p(save),
+                  ops._p(ws), ops._s())
+        ops._call("mn_qa_chan_from_save", ops._p(save), ops._p(gamma), ops._p(beta), Oc, ops._p(chan), ops._s())
+        table = torch.empty(int(lib.mn_conv2d_first_codes_table_bytes(Oc, CODE_BITS)) // 4, dtype=torch.int32, device=dev)
+        ops._call("mn_conv2d_first_codes_pack", ops._p(chan), Oc, CODE_BITS, ops._p(table), ops._s())
+    nonfinite = int(table[0])          # (compile time: read back once)
+    if nonfinite:
+        raise _err("dorefa_compile_codes(code_ends=True): %s.bn: %d output channels with a non-finite (or beyond 1e9) BatchNorm constant: no thresholds" % (nm, nonfinite))
+    return CodePlan(first, layers, last, tail, flatten, report, code_ends=True, first_table=table, first_chan=chan)

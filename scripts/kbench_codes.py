@@ -5,7 +5,12 @@ activation, one kernel per hidden block), alternated in ONE process, HIP events.
     python scripts/kbench_codes.py [--batches 256,1024] [--warmup 5] [--iters 20] [--out profiles/codes_inference.json]
 
 Per batch: median / min / quartiles of the timed forwards of each, per-kernel times of both from the library's profile hooks, and the designed HBM bytes per image
-per hidden block (arithmetic from the shapes: each operand read or written once)."""
+per hidden block (arithmetic from the shapes: each operand read or written once).
+
+    python scripts/kbench_codes.py --code-ends [--batches 256,1024] [--warmup 5] [--iters 20] [--out profiles/codes_ends.json]
+
+alternates the default plan (``code_ends=False``: the yardstick) and ``dorefa_compile_codes(I, code_ends=True)`` the same way and reports the per-kernel times of
+the launches replaced (first conv, k_qa_fwd, k_codes_pack, k_codes_unpack, the classifier on byte codes) beside the two new ones."""
 import argparse
 import json
 import os
@@ -55,13 +60,60 @@ def q(v):
     return dict(median=statistics.median(v), min=min(v), max=max(v), p25=statistics.quantiles(v, n=4)[0], p75=statistics.quantiles(v, n=4)[2])
 
 
+ENDS_REPLACED = ("k_c1b_fwd<", "k_c1_fwd<", "k_qa_fwd", "k_codes_pack", "k_codes_unpack", "k_sconv_fwd")          # the default plan's two ends
+ENDS_NEW = ("k_c1b_fwd<", "k_planesconv1x1_small")
+
+
+def main_code_ends(args):
+    """The default plan P0 against the plan with both ends on planes P1, alternated in one process."""
+    from micronet.compression.quantization.wqaq.dorefa import quantize as Q
+    from micronet_amd import _lib, inference
+    from micronet_amd.train import build_model, synth_batch
+    torch.manual_seed(0)
+    I = Q.prepare(build_model("nin_gc"), inplace=True, a_bits=2, w_bits=2, quant_inference=True).cuda()
+    inference.prequantize_weights(I)
+    I.eval()
+    P0, P1 = inference.dorefa_compile_codes(I), inference.dorefa_compile_codes(I, code_ends=True)
+    lib = _lib.get_lib()
+    res = dict(model="nin_gc", a_bits=2, w_bits=2, warmup=args.warmup, iters=args.iters, device=torch.cuda.get_device_name(0), report=P1.report, batches={})
+    with torch.no_grad():
+        for bs in [int(v) for v in args.batches.split(",")]:
+            x, _ = synth_batch(bs, device="cuda")
+            ref, got = P0(x), P1(x)
+            for _ in range(args.warmup):
+                P0(x), P1(x)
+            t0, t1 = [], []
+            for _ in range(args.iters):          # alternated: both see the same clocks and the same neighbours
+                t0.append(timed(P0, x))
+                t1.append(timed(P1, x))
+            k0, k1 = profile(lib, _lib, P0, x), profile(lib, _lib, P1, x)
+            us = lambda k, names: {n: round(1e3 * v["ms"] / max(1, v["launches"]), 2) for n, v in k.items() if n.startswith(names)}
+            med0, med1 = statistics.median(t0), statistics.median(t1)
+            res["batches"][str(bs)] = dict(P0_ms=q(t0), P1_ms=q(t1), P0_img_s=bs / med0 * 1e3, P1_img_s=bs / med1 * 1e3, P1_over_P0=med0 / med1,
+                                           bit_equal=bool(torch.equal(ref, got)), replaced_us=us(k0, ENDS_REPLACED), new_us=us(k1, ENDS_NEW),
+                                           P0_kernel_ms_total=sum(v["ms"] for v in k0.values()), P1_kernel_ms_total=sum(v["ms"] for v in k1.values()),
+                                           P0_kernels=k0, P1_kernels=k1)
+            print("batch %d: default plan %.3f ms (min %.3f)  code_ends %.3f ms (min %.3f)  speed %.2fx  bit-equal %s" % (bs, med0, min(t0), med1, min(t1), med0 / med1,
+                                                                                                                  torch.equal(ref, got)), flush=True)
+            print("  replaced (us):", res["batches"][str(bs)]["replaced_us"], " new (us):", res["batches"][str(bs)]["new_us"], flush=True)
+    os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default="256,1024")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join("profiles", "codes_inference.json"))
+    ap.add_argument("--code-ends", action="store_true", help="the default plan against dorefa_compile_codes(I, code_ends=True)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join("profiles", "codes_ends.json" if args.code_ends else "codes_inference.json")
+    if args.code_ends:
+        return main_code_ends(args)
     from micronet.compression.quantization.wqaq.dorefa import quantize as Q
     from micronet_amd import _lib, inference
     from micronet_amd.train import build_model, synth_batch
