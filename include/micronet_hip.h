@@ -937,6 +937,26 @@ int64_t mn_codeconv_table_bytes(const mn_conv_geom* g, int a_bits_in, int w_bits
 int mn_codeconv_pack(const mn_conv_geom* g, const float* w, const float* chan, int a_bits_in, int w_bits, int a_bits_out, const int32_t* out_order, uint32_t* table,
                      mn_stream_t stream);
 int mn_codeconv_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t* in_planes, uint32_t* out_planes, int pool, mn_stream_t stream);
+/* The dense 5x5 block of plain nin (models/nin.py) on code planes: the same quartet, table layout, header words 0 and 7, thresholds and out_order as mn_codeconv_*,
+ * for the one geometry that quartet refuses.  Covered (mn_codeconv_tile_supported): a_bits_in = w_bits = a_bits_out = 2; 5x5 with padding 2, stride 1, dilation 1,
+ * groups 1, g->in_shuffle 0 / 1; any O; C * 25 * 9 <= 32767, i.e. at most 145 input channels (the accumulator range of the 16-bit stash the thresholds are searched
+ * over).  Everything else -- 1x1 and 3x3, which belong to mn_codeconv_*, included -- is MN_ENOTSUP; a null or misaligned tensor or an invalid geometry (N <= 0, ...)
+ * is MN_EINVAL; nothing is written in either case.
+ *   fwd  : a 256-thread block stages the halo tile of its output pixels (x images per block on a small map), all word groups x 2 planes, into LDS once, halo cells
+ *          and cells outside the batch as zero words (= code 0 = the value 0: zero padding needs no mask), then acc = 2 sum j k - 3 sum j, u = flip * acc,
+ *          code = #{k : u >= T_k} per table row; in_planes [N][ceil(C/32)][2][H][W] -> out_planes [N][ceil(O/32)][2][H][W], unused high bits of the last group 0.
+ *          No pool argument: no max-pool is folded into this block (run mn_codes_maxpool behind it). */
+int mn_codeconv_tile_supported(const mn_conv_geom* g, int a_bits_in, int w_bits, int a_bits_out);
+int64_t mn_codeconv_tile_table_bytes(const mn_conv_geom* g, int a_bits_in, int w_bits, int a_bits_out);
+int mn_codeconv_tile_pack(const mn_conv_geom* g, const float* w, const float* chan, int a_bits_in, int w_bits, int a_bits_out, const int32_t* out_order, uint32_t* table,
+                          mn_stream_t stream);
+int mn_codeconv_tile_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t* in_planes, uint32_t* out_planes, mn_stream_t stream);
+/* Max-pool on code planes [N][Cw][a_bits][H][W] -> [N][Cw][a_bits][(H + 2 pad - k) / 2 + 1][(W + 2 pad - k) / 2 + 1] (floor mode): the bit-sliced maximum of the
+ * window's codes, most significant plane first; taps outside the image contribute code 0 (the pool sits behind a ReLU).  (k, stride, pad) in {(2, 2, 0), (3, 2, 1)},
+ * 1 <= a_bits <= 8; anything else, or a tensor of 2^31 words or more: MN_ENOTSUP.  Null / misaligned / empty tensor, or an image smaller than the window: MN_EINVAL.
+ * Nothing is written in either case.  Behind a ReLU and in front of a non-decreasing quantizer, pooling the codes equals quantising the pooled activation. */
+int mn_codes_maxpool(const uint32_t* planes_in, int64_t N, int64_t Cw, int a_bits, int64_t H, int64_t W, int k, int stride, int pad, uint32_t* planes_out,
+                     mn_stream_t stream);
 /* The two ends of the deployed plan on bits (inference.wbwtab_compile_bits(model, bit_ends=True)).
  *   first : bits = sign(conv(x, w) + bias) of the un-quantised first conv (real fp32 operands, the geometry of mn_conv2d_first_supported(g, 0) whose forward runs on
  *           k_c1b_fwd) in ONE launch: the accumulation is that forward's, so the value whose sign is taken is its y bit for bit; the rule is mn_bnsign_fwd_i8's with

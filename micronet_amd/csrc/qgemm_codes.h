@@ -15,7 +15,8 @@
 //                         row[0] = w0 (first input word group the row reads), row[1] = flip (+-1), row[2] = bit position in the output word, row[3] = 1: another
 //                         group than the row before, row[4..6] = T_1..T_3, row[7] = 0, then taps x NW x w_bits weight planes, then NW group-mask words.
 //   consumer order    : the row at bit position j of an output word computes channel out_order[32 * word + j] (mn_bitconv_pack's convention).
-// Covered: a_in = w_bits = a_out = 2; 1x1 and 3x3 / padding 1, stride 1, any groups, the 2x2 / stride 2 pool folded or not.
+// Covered: a_in = w_bits = a_out = 2; 1x1 and 3x3 / padding 1, stride 1, any groups, the 2x2 / stride 2 pool folded or not (mn_codeconv_*); the dense 5x5 / padding 2
+// block of plain nin on an LDS-resident tile (mn_codeconv_tile_*) and the 2x2 / 2 and 3x3 / 2 / 1 max-pools on planes (mn_codes_maxpool).
 #pragma once
 #include "qa_thresholds.h"
 
@@ -29,10 +30,12 @@ struct Geom {
     float s;          // the output quantizer's scale, dorefa_scale(a_bits_out): what mn_qa_fwd evaluates the chain with
 };
 
-static inline bool make_geom(const mn_conv_geom* g, int a_in, int w_bits, int a_out, Geom& q) {
+// tile: the geometry of the LDS-tiled dense block (mn_codeconv_tile_*: 5x5 / padding 2, groups 1) instead of that of mn_codeconv_* (1x1, 3x3 / padding 1); the table
+// layout, the K bound and everything k_codes_wpack reads are the same.
+static inline bool make_geom(const mn_conv_geom* g, int a_in, int w_bits, int a_out, Geom& q, bool tile = false) {
     if (!g || g->N <= 0 || g->C <= 0 || g->H <= 0 || g->W <= 0 || g->O <= 0 || g->groups <= 0) return false;
     if (a_in != A || w_bits != WB || a_out != 2) return false;          // (3- and 4-bit codes: not instantiated)
-    if (g->KH != g->KW || (g->KH != 1 && g->KH != 3)) return false;
+    if (g->KH != g->KW || (tile ? (g->KH != 5 || g->groups != 1) : (g->KH != 1 && g->KH != 3))) return false;
     const int pad = (g->KH - 1) / 2;
     if (g->stride_h != 1 || g->stride_w != 1 || g->dil_h != 1 || g->dil_w != 1 || g->pad_h != pad || g->pad_w != pad) return false;
     if (g->C % g->groups || g->O % g->groups || g->in_shuffle > 1) return false;      // a channel shuffle is folded into the PRODUCER's row order, never gathered here
@@ -402,6 +405,143 @@ static inline bool planes_args_ok(const void* a, const void* b, int64_t N, int64
     return a && b && N > 0 && C > 0 && HW > 0 && HW % 4 == 0 && !(((uintptr_t)a) & 3) && !(((uintptr_t)b) & 3) && C <= (1 << 20) && HW <= (1 << 26) && a_bits >= 1 && a_bits <= 8;
 }
 
+// ---------------------------------------------------------------- dense 5x5 on an LDS-resident tile (k_bitconv_tile's launch shape on code planes)
+// A 256-thread block owns a tile of output pixels (x images per block when the map is small) and stages the (th + 4) x (tw + 4) halo tile of all Cw word groups x 2
+// planes into LDS once; halo cells and cells outside the batch are ZERO words = 32 activations of code 0 = the value 0, which is what zero padding is in this layout:
+// no border mask, no `lost` correction.  The two planes of a cell are adjacent in LDS (one 8-byte read).  groups == 1: sum j is formed once per lane.
+struct Tile {
+    int N, Cw, H, W, OW, stride, owpb, tw, th, ipb, tx, ty;          // tile width / height (8 or 16), images per block (256 / (tw * th)), tiles per image row / column
+};
+enum { TILE_MAXW = 5, TILE_WORDS = 4 * 12 * 12 * TILE_MAXW * A };          // C <= 145: at most 5 word groups; 4 images of 8 x 8 + halo 2 is the largest LDS image
+
+// NW > 0: Cw == NW, the loops over the word groups unrolled; NW == 0: any Cw <= TILE_MAXW, rolled.  Either way the window is read from LDS for every table row, one
+// window row at a time (a 25 x NW x 2 register patch does not fit: fully unrolled, the hoisted window spills).
+template <int KS, int NW>
+__global__ __launch_bounds__(256) void k_codeconv_tile(const uint32_t* __restrict__ tab, const uint32_t* __restrict__ x, uint32_t* __restrict__ y, Tile q) {
+    __shared__ uint32_t sx[TILE_WORDS];
+    constexpr int P = (KS - 1) / 2;
+    const int nw = NW ? NW : q.Cw;
+    const int tid = threadIdx.x;
+    const int pw = q.tw + 2 * P, cells = (q.th + 2 * P) * pw;
+    int b = blockIdx.x;
+    const int bx = b % q.tx; b /= q.tx;
+    const int by = b % q.ty;
+    const int n0 = (b / q.ty) * q.ipb, h0 = by * q.th, w0 = bx * q.tw;
+    const int HW = q.H * q.W;
+    const int tot = q.ipb * nw * A * cells;          // <= TILE_WORDS (checked by the host)
+    for (int i = tid; i < tot; i += 256) {
+        const int c = i % cells, r = i / cells;          // r = (image, word group, plane): consecutive lanes read consecutive pixels of one plane
+        const int pl = r % A, k = (r / A) % nw, im = r / (A * nw);
+        const int n = n0 + im, ih = h0 + c / pw - P, iw = w0 + c % pw - P;
+        uint32_t v = 0u;          // halo and everything outside the batch: zero words
+        if (n < q.N && ih >= 0 && ih < q.H && iw >= 0 && iw < q.W) v = x[(((int64_t)n * q.Cw + k) * A + pl) * HW + ih * q.W + iw];
+        sx[2 * ((im * nw + k) * cells + c) + pl] = v;
+    }
+    __syncthreads();
+    const int per = q.tw * q.th;
+    const int im = tid / per, r = tid - im * per;
+    const int ly = r / q.tw, lx = r - ly * q.tw;
+    const int n = n0 + im, oh = h0 + ly, ow = w0 + lx;
+    if (n >= q.N || oh >= q.H || ow >= q.W) return;
+    const uint32_t* xs = sx + 2 * (im * nw * cells + ly * pw + lx);          // the lane's window: cell (ty, tx) of word group k at xs[2 * (k * cells + ty * pw + tx) + plane]
+    int S = 0;          // sum of the input codes over the window
+#pragma unroll
+    for (int t = 0; t < KS * KS; ++t) {
+        const uint32_t* xp = xs + 2 * ((t / KS) * pw + t % KS);
+        if (NW) {
+#pragma unroll
+            for (int k = 0; k < NW; ++k) S += mn_popc(xp[2 * k * cells]) + 2 * mn_popc(xp[2 * k * cells + 1]);
+        } else {
+#pragma unroll 1
+            for (int k = 0; k < nw; ++k) S += mn_popc(xp[2 * k * cells]) + 2 * mn_popc(xp[2 * k * cells + 1]);
+        }
+    }
+    const int ow0 = blockIdx.y * q.owpb;
+    const int ow1 = ow0 + q.owpb < q.OW ? ow0 + q.owpb : q.OW;
+    for (int owi = ow0; owi < ow1; ++owi) {
+        const uint32_t* rowp = tab + HDR + (int64_t)owi * 32 * q.stride;
+        uint32_t word0 = 0, word1 = 0;
+        for (int j = 0; j < 32; ++j) {
+            const uint32_t* row = rowp + j * q.stride;          // wave-uniform: every word of the row is a scalar operand
+            const uint32_t* wp = row + ROWHDR;
+            int d0 = 0, d1 = 0, d2 = 0;          // weights 1, 2, 4 of sum_p sum_q 2^(p+q) popc(x_p & k_q)
+#pragma unroll 1
+            for (int ty = 0; ty < KS; ++ty) {          // rolled: one window row (KS cells x nw word groups x 2 planes) is in registers at a time, the rest stays in LDS
+                const uint32_t* xp = xs + 2 * ty * pw;
+                const uint32_t* wt = wp + ty * KS * nw * WB;
+                if (NW) {
+#pragma unroll
+                    for (int tx = 0; tx < KS; ++tx)
+#pragma unroll
+                        for (int k = 0; k < NW; ++k) {
+                            const uint32_t x0 = xp[2 * (k * cells + tx)], x1 = xp[2 * (k * cells + tx) + 1];
+                            const uint32_t k0 = wt[(tx * NW + k) * WB], k1 = wt[(tx * NW + k) * WB + 1];
+                            d0 += mn_popc(x0 & k0); d1 += mn_popc(x0 & k1) + mn_popc(x1 & k0); d2 += mn_popc(x1 & k1);
+                        }
+                } else {
+#pragma unroll
+                    for (int tx = 0; tx < KS; ++tx)
+#pragma unroll 1
+                        for (int k = 0; k < nw; ++k) {
+                            const uint32_t x0 = xp[2 * (k * cells + tx)], x1 = xp[2 * (k * cells + tx) + 1];
+                            const uint32_t k0 = wt[(tx * nw + k) * WB], k1 = wt[(tx * nw + k) * WB + 1];
+                            d0 += mn_popc(x0 & k0); d1 += mn_popc(x0 & k1) + mn_popc(x1 & k0); d2 += mn_popc(x1 & k1);
+                        }
+                }
+            }
+            const int acc = 2 * (d0 + 2 * d1 + 4 * d2) - 3 * S;
+            const int u = (int)row[1] * acc;
+            const uint32_t code = (uint32_t)(u >= (int)row[4]) + (uint32_t)(u >= (int)row[5]) + (uint32_t)(u >= (int)row[6]);
+            word0 |= (code & 1u) << row[2];
+            word1 |= (code >> 1) << row[2];
+        }
+        uint32_t* yo = y + ((int64_t)n * q.OW + owi) * A * HW + oh * q.W + ow;
+        yo[0] = word0;
+        yo[HW] = word1;
+    }
+}
+
+// ---------------------------------------------------------------- max-pool on code planes: one lane per output word position, all planes
+// Bit-sliced maximum of 32 codes at once, most significant plane first: gt / lt collect the channels where the running maximum / the tap is already decided to be
+// larger, and the tap's bits are selected where lt.  Taps outside the image contribute code 0 (the pool sits behind a ReLU: no code is below it), i.e. are skipped.
+// Planes at and above abits are zero registers (every index is a compile-time constant: nothing goes to scratch).
+enum { POOL_MAXB = 8 };
+__global__ __launch_bounds__(256) void k_codes_maxpool(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, int64_t total, int abits, int H, int W, int Ho, int Wo,
+                                                       int k, int s, int pad) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int ow = (int)(i % Wo);
+    const int64_t t = i / Wo;
+    const int oh = (int)(t % Ho);
+    const int64_t nc = t / Ho;          // (image, word group)
+    const int HW = H * W, HWo = Ho * Wo;
+    const uint32_t* src = in + nc * abits * HW;
+    uint32_t m[POOL_MAXB];
+#pragma unroll
+    for (int p = 0; p < POOL_MAXB; ++p) m[p] = 0u;
+    for (int dy = 0; dy < k; ++dy)
+        for (int dx = 0; dx < k; ++dx) {
+            const int ih = oh * s - pad + dy, iw = ow * s - pad + dx;
+            if (ih < 0 || ih >= H || iw < 0 || iw >= W) continue;
+            uint32_t v[POOL_MAXB];
+#pragma unroll
+            for (int p = 0; p < POOL_MAXB; ++p) v[p] = p < abits ? src[p * HW + ih * W + iw] : 0u;
+            uint32_t gt = 0u, lt = 0u;
+#pragma unroll
+            for (int p = POOL_MAXB - 1; p >= 0; --p) {
+                const uint32_t open = ~(gt | lt);
+                gt |= open & m[p] & ~v[p];
+                lt |= open & v[p] & ~m[p];
+            }
+#pragma unroll
+            for (int p = 0; p < POOL_MAXB; ++p) m[p] = (m[p] & ~lt) | (v[p] & lt);
+        }
+    uint32_t* dst = out + nc * abits * HWo + oh * Wo + ow;
+#pragma unroll
+    for (int p = 0; p < POOL_MAXB; ++p)
+        if (p < abits) dst[p * HWo] = m[p];
+}
+
 }  // namespace mn_codes
 
 extern "C" int mn_codes_pack_planes(const uint8_t* codes, int64_t N, int64_t C, int64_t HW, int a_bits, uint32_t* planes, mn_stream_t stream) {
@@ -510,3 +650,82 @@ extern "C" int mn_codeconv_fwd(const mn_conv_geom* g, const uint32_t* table, con
     return MN_OK;
 }
 #undef MN_CODECONV_COVER
+
+// ---------------------------------------------------------------- the dense 5x5 block of plain nin, and the max-pool behind a block that cannot fold it
+static inline bool tile_geom_valid(const mn_conv_geom* g) {
+    return g && g->N > 0 && g->C > 0 && g->H > 0 && g->W > 0 && g->O > 0 && g->groups > 0 && g->KH > 0 && g->KW > 0 && g->stride_h > 0 && g->stride_w > 0 && g->dil_h > 0 &&
+           g->dil_w > 0 && g->pad_h >= 0 && g->pad_w >= 0;
+}
+#define MN_CODETILE_COVER "geometry not covered (2-bit codes and weights; dense 5x5 / padding 2, stride 1, groups 1, C * 25 * 9 <= 32767: at most 145 channels)"
+
+extern "C" int mn_codeconv_tile_supported(const mn_conv_geom* g, int a_bits_in, int w_bits, int a_bits_out) {
+    mn_codes::Geom q;
+    return mn_codes::make_geom(g, a_bits_in, w_bits, a_bits_out, q, true) ? 1 : 0;
+}
+
+extern "C" int64_t mn_codeconv_tile_table_bytes(const mn_conv_geom* g, int a_bits_in, int w_bits, int a_bits_out) {
+    mn_codes::Geom q;
+    if (!mn_codes::make_geom(g, a_bits_in, w_bits, a_bits_out, q, true)) return 0;
+    return 4 * ((int64_t)mn_codes::HDR + (int64_t)q.OW * 32 * q.stride);
+}
+
+extern "C" int mn_codeconv_tile_pack(const mn_conv_geom* g, const float* w, const float* chan, int a_bits_in, int w_bits, int a_bits_out, const int32_t* out_order,
+                                     uint32_t* table, mn_stream_t stream) {
+    mn_codes::Geom q;
+    if (!w || !chan || !table || (((uintptr_t)table) & 3) || !tile_geom_valid(g)) MN_FAIL(MN_EINVAL, "mn_codeconv_tile_pack: null / unaligned argument or invalid geometry");
+    if (!mn_codes::make_geom(g, a_bits_in, w_bits, a_bits_out, q, true)) MN_FAIL(MN_ENOTSUP, "mn_codeconv_tile_pack: " MN_CODETILE_COVER);
+    if (hipMemsetAsync(table, 0, 4 * mn_codes::HDR, (hipStream_t)stream) != hipSuccess) MN_FAIL(MN_EHIP, "mn_codeconv_tile_pack: header reset failed");          // the two counters
+    mn_set_last_kernel("k_codes_wpack");
+    hipLaunchKernelGGL(mn_codes::k_codes_wpack, dim3(q.OW * 32), dim3(256), 0, (hipStream_t)stream, q, w, chan, out_order, table);
+    MN_CHECK_LAUNCH("mn_codeconv_tile_pack");
+    return MN_OK;
+}
+
+extern "C" int mn_codeconv_tile_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t* in_planes, uint32_t* out_planes, mn_stream_t stream) {
+    mn_codes::Geom q;
+    if (!table || !in_planes || !out_planes || ((((uintptr_t)table) | ((uintptr_t)in_planes) | ((uintptr_t)out_planes)) & 3) || !tile_geom_valid(g))
+        MN_FAIL(MN_EINVAL, "mn_codeconv_tile_fwd: null / unaligned argument or invalid geometry");
+    if (!mn_codes::make_geom(g, mn_codes::A, mn_codes::WB, 2, q, true)) MN_FAIL(MN_ENOTSUP, "mn_codeconv_tile_fwd: " MN_CODETILE_COVER);
+    mn_codes::Tile t;
+    t.N = q.N; t.Cw = q.Cw; t.H = q.H; t.W = q.W; t.OW = q.OW; t.stride = q.stride;
+    t.tw = q.W <= 8 ? 8 : 16; t.th = q.H <= 8 ? 8 : 16; t.ipb = 256 / (t.tw * t.th);
+    t.tx = (q.W + t.tw - 1) / t.tw; t.ty = (q.H + t.th - 1) / t.th;
+    const int64_t blocks = (int64_t)((q.N + t.ipb - 1) / t.ipb) * t.tx * t.ty;
+    if (blocks > INT_MAX || q.Cw > mn_codes::TILE_MAXW || t.ipb * q.Cw * mn_codes::A * (t.tw + q.KS - 1) * (t.th + q.KS - 1) > mn_codes::TILE_WORDS)
+        MN_FAIL(MN_ENOTSUP, "mn_codeconv_tile_fwd: tile does not fit");
+    const int bx = (int)blocks;
+    int gy = (2048 + bx - 1) / bx;          // enough blocks to fill the chip: split the output words over grid.y when the pixels alone do not
+    if (gy > q.OW) gy = q.OW;
+    t.owpb = (q.OW + gy - 1) / gy;
+    gy = (q.OW + t.owpb - 1) / t.owpb;
+    const dim3 grid(bx, gy);
+    const hipStream_t s = (hipStream_t)stream;
+    const int tsel = q.Cw == 3 ? 3 : 0;
+    mn_set_last_kernel("k_codeconv_tile<%d,%d>", q.KS, tsel);
+    mn_prof_bytes(4.0 * mn_codes::A * q.N * q.Cw * q.H * q.W + 4.0 * mn_codes::A * q.N * q.OW * q.H * q.W + 4.0 * (mn_codes::HDR + (double)q.OW * 32 * q.stride));
+    mn_prof_begin(s);
+    if (tsel) hipLaunchKernelGGL((mn_codes::k_codeconv_tile<5, 3>), grid, dim3(256), 0, s, table, in_planes, out_planes, t);
+    else hipLaunchKernelGGL((mn_codes::k_codeconv_tile<5, 0>), grid, dim3(256), 0, s, table, in_planes, out_planes, t);
+    mn_prof_end(s);
+    MN_CHECK_LAUNCH("mn_codeconv_tile_fwd");
+    return MN_OK;
+}
+#undef MN_CODETILE_COVER
+
+extern "C" int mn_codes_maxpool(const uint32_t* planes_in, int64_t N, int64_t Cw, int a_bits, int64_t H, int64_t W, int k, int stride, int pad, uint32_t* planes_out,
+                                mn_stream_t stream) {
+    if (!planes_in || !planes_out || ((((uintptr_t)planes_in) | ((uintptr_t)planes_out)) & 3) || N <= 0 || Cw <= 0 || H <= 0 || W <= 0)
+        MN_FAIL(MN_EINVAL, "mn_codes_maxpool: null / unaligned / empty argument");
+    if (!((k == 2 && stride == 2 && pad == 0) || (k == 3 && stride == 2 && pad == 1)) || a_bits < 1 || a_bits > mn_codes::POOL_MAXB)
+        MN_FAIL(MN_ENOTSUP, "mn_codes_maxpool: window not covered (2x2 / stride 2 / padding 0 or 3x3 / stride 2 / padding 1, floor mode; 1 <= a_bits <= 8)");
+    if (H > (1 << 15) || W > (1 << 15) || N * Cw * a_bits * H * W >= (1ll << 31)) MN_FAIL(MN_ENOTSUP, "mn_codes_maxpool: tensor too large");
+    if (H + 2 * pad < k || W + 2 * pad < k) MN_FAIL(MN_EINVAL, "mn_codes_maxpool: image smaller than the window");
+    const int Ho = (int)((H + 2 * pad - k) / stride + 1), Wo = (int)((W + 2 * pad - k) / stride + 1);
+    const int64_t total = N * Cw * Ho * Wo;
+    mn_set_last_kernel("k_codes_maxpool"); mn_prof_bytes(4.0 * N * Cw * a_bits * H * W + 4.0 * total * a_bits); mn_prof_begin((hipStream_t)stream);
+    hipLaunchKernelGGL(mn_codes::k_codes_maxpool, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, planes_in, planes_out, total, a_bits, (int)H, (int)W,
+                       Ho, Wo, k, stride, pad);
+    mn_prof_end((hipStream_t)stream);
+    MN_CHECK_LAUNCH("mn_codes_maxpool");
+    return MN_OK;
+}

@@ -19,7 +19,8 @@ The results are ordinary modules of this package: in eval mode they run on the s
 
   * ``dorefa_compile_codes``: a pre-quantised DoReFa W2A2 ``quant_inference=True`` net compiled into a flat plan that keeps TWO BITS per hidden activation
     (``csrc/qgemm_codes.h``: activation codes as bit planes, plane-serial popcounts against weight code planes, the block's BatchNorm + ReLU + quantizer as integer
-    thresholds per channel).  One kernel per hidden block, packed codes in, packed codes out; same codes in every hidden stage as the eval-mode model."""
+    thresholds per channel).  One kernel per hidden block, packed codes in, packed codes out; same codes in every hidden stage as the eval-mode model.
+    ``tile_blocks=True`` adds plain ``nin``: its dense 5x5 block on an LDS tile and its 3x3 / stride 2 max-pools on the planes."""
 import copy
 
 import torch
@@ -538,9 +539,15 @@ def _codeconv_kernel_name(k, cin, groups, pool):
     return "k_codeconv<%d,%d,%d>" % (k, sel, pool)
 
 
+def _codeconv_tile_kernel_name(k, cin):
+    """The kernel mn_codeconv_tile_fwd launches for a dense 5x5 block (csrc/qgemm_codes.h: three word groups unrolled, anything else rolled)."""
+    return "k_codeconv_tile<%d,%d>" % (k, 3 if (cin + 31) // 32 == 3 else 0)
+
+
 class CodePlan(nn.Module):
     """What ``dorefa_compile_codes`` returns: first block (fp32 conv + BatchNorm + ReLU + the next conv's quantizer, the model's own module) -> plane pack -> n
-    code blocks (2x2 max-pools folded in) -> plane unpack -> last block and tail (the model's own modules).  Eval only; owns the packed weight tables (and the
+    code blocks (2x2 max-pools folded in; with ``tile_blocks`` also the dense 5x5 block on an LDS tile, and a max-pool that ``prepare()`` did not fuse run on the planes
+    behind its block) -> plane unpack -> last block and tail (the model's own modules).  Eval only; owns the packed weight tables (and the
     per-channel constants they were packed from: ``layers[i]["chan"]``) and one set of plane buffers per input shape.  ``code_ends``: the first conv's kernel writes
     the first stage's planes itself (no fp32 map, no byte codes, no pack; ``first_table`` holds its per-channel thresholds) and the last conv reads the last stage's
     planes (no unpack, no uint8 buffer); what follows the last conv inside its block, and the tail, run unchanged."""
@@ -580,7 +587,7 @@ class CodePlan(nn.Module):
                                "the image strip in LDS)" % (self.report[0]["name"], N, conv.in_channels, H, W))
             elif (H * W) % 4:
                 raise _err("dorefa_compile_codes: %s: its %d x %d output cannot be packed (mn_codes_pack_planes needs H * W %% 4 == 0)" % (self.report[0]["name"], H, W))
-            bufs, geoms = [torch.empty((N, (Cc + 31) // 32, CODE_BITS, H, W), dtype=torch.int32, device=device)], []
+            bufs, geoms, mids = [torch.empty((N, (Cc + 31) // 32, CODE_BITS, H, W), dtype=torch.int32, device=device)], [], []
             for L in self.layers:
                 k, p = L["k"], L["pad"]
                 geoms.append(_lib.ConvGeom(N, L["cin"], H, W, L["cout"], k, k, 1, 1, p, p, 1, 1, L["groups"], 0))
@@ -588,19 +595,41 @@ class CodePlan(nn.Module):
                     if H % 2 or W % 2:
                         raise _err("dorefa_compile_codes: %s: the 2x2 max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
                     H, W = H // 2, W // 2
+                ksp = L.get("pool_ksp")          # (tile_blocks) a pool the block does not fold: the block at full size into a mid buffer, then mn_codes_maxpool
+                if ksp:
+                    if min(H, W) + 2 * ksp[2] < ksp[0]:
+                        raise _err("dorefa_compile_codes: %s: the max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
+                    mids.append(torch.empty((N, (L["cout"] + 31) // 32, CODE_BITS, H, W), dtype=torch.int32, device=device))
+                    H, W = (H + 2 * ksp[2] - ksp[0]) // ksp[1] + 1, (W + 2 * ksp[2] - ksp[0]) // ksp[1] + 1
+                else:
+                    mids.append(None)
                 bufs.append(torch.empty((N, (L["cout"] + 31) // 32, CODE_BITS, H, W), dtype=torch.int32, device=device))
                 Cc = L["cout"]
             if self.code_ends:
                 if not _lib.get_lib().mn_planesconv1x1_small_supported(Cc, H * W, self.last.conv.out_channels, CODE_BITS):
                     raise _err("dorefa_compile_codes(code_ends=True): %s.conv: a %d-channel %d x %d map is not covered by mn_planesconv1x1_small_fwd (its lanes own 4 "
                                "consecutive pixels: H * W %% 4 == 0; the weights in LDS)" % (self.report[-1]["name"], Cc, H, W))
-                self._ws[key] = (bufs, geoms, None, g0)
+                self._ws[key] = (bufs, geoms, None, g0, mids)
                 return self._ws[key]
             if (H * W) % 4:
                 raise _err("dorefa_compile_codes: %s: its %d x %d output cannot be unpacked for the last block (mn_codes_unpack_planes needs H * W %% 4 == 0)"
                            % (self.layers[-1]["name"], H, W))
-            self._ws[key] = (bufs, geoms, torch.empty((N, Cc, H, W), dtype=torch.uint8, device=device), g0)
+            self._ws[key] = (bufs, geoms, torch.empty((N, Cc, H, W), dtype=torch.uint8, device=device), g0, mids)
         return self._ws[key]
+
+    def _run_layers(self, bufs, geoms, mids, st):
+        """One launch per hidden block (two where a max-pool runs on the planes behind it)."""
+        import ctypes as C
+        from micronet_amd import ops
+        for i, L in enumerate(self.layers):
+            out = bufs[i + 1] if mids[i] is None else mids[i]
+            if L.get("tile"):
+                ops._call("mn_codeconv_tile_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(out), st)
+            else:
+                ops._call("mn_codeconv_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(out), int(L["pool"]), st)
+            if mids[i] is not None:
+                m, (pk, ps, pp) = mids[i], L["pool_ksp"]
+                ops._call("mn_codes_maxpool", ops._p(m), m.shape[0], m.shape[1], CODE_BITS, m.shape[3], m.shape[4], pk, ps, pp, ops._p(bufs[i + 1]), st)
 
     @torch.no_grad()
     def forward(self, x):
@@ -613,12 +642,11 @@ class CodePlan(nn.Module):
                 raise _err("dorefa_compile_codes(code_ends=True): the input must be a float32 GPU tensor [N, %d, H, W] (no CPU fallback)" % conv.in_channels)
             x = x.contiguous()
             with torch.cuda.device(x.device):
-                bufs, geoms, c8, g0 = self._plan_buffers((x.shape[0], conv.out_channels, x.shape[2], x.shape[3]), x.device)
+                bufs, geoms, c8, g0, mids = self._plan_buffers((x.shape[0], conv.out_channels, x.shape[2], x.shape[3]), x.device)
                 st = ops._s()
                 ops._call("mn_conv2d_first_codes", C.byref(g0), ops._p(x), ops._p(ops._chk(conv.weight.detach(), "weight")), ops._p(ops._chk(conv.bias, "bias")),
                           ops._p(self.first_table), ops._p(bufs[0]), st)
-                for i, L in enumerate(self.layers):
-                    ops._call("mn_codeconv_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(bufs[i + 1]), int(L["pool"]), st)
+                self._run_layers(bufs, geoms, mids, st)
                 if self.keep_stages:
                     self.stage_codes = [b.clone() for b in bufs]
                 conv = self.last.conv
@@ -638,11 +666,10 @@ class CodePlan(nn.Module):
                        % (self.report[0]["name"], CODE_BITS))
         codes = a.codes.contiguous()
         N, Cc, H, W = codes.shape
-        bufs, geoms, c8, _ = self._plan_buffers(codes.shape, codes.device)
+        bufs, geoms, c8, _, mids = self._plan_buffers(codes.shape, codes.device)
         st = ops._s()
         ops._call("mn_codes_pack_planes", ops._p(codes), N, Cc, H * W, CODE_BITS, ops._p(bufs[0]), st)
-        for i, L in enumerate(self.layers):
-            ops._call("mn_codeconv_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(bufs[i + 1]), int(L["pool"]), st)
+        self._run_layers(bufs, geoms, mids, st)
         if self.keep_stages:
             self.stage_codes = [b.clone() for b in bufs]
         n_, c_, h_, w_ = c8.shape
@@ -681,8 +708,9 @@ def _check_code_ends(first, nm_first, last, nm_last):
         raise _err("dorefa_compile_codes(code_ends=True): %s: a channel shuffle in front of the last conv is not covered by mn_planesconv1x1_small_fwd" % nm_last)
 
 
-def _walk_codes(model, code_ends=False):
-    """The graph walk of ``dorefa_compile_codes`` (no GPU needed): (first, layers, last, tail, flatten, report)."""
+def _walk_codes(model, code_ends=False, tile_blocks=False):
+    """The graph walk of ``dorefa_compile_codes`` (no GPU needed): (first, layers, last, tail, flatten, report).  ``tile_blocks``: also admit what plain nin needs -- a
+    dense 5x5 block (``layer["tile"]``) and a max-pool ``prepare()`` did not fuse, run on the planes behind its block (``layer["pool_ksp"]``)."""
     import ctypes as C
     from micronet_amd import _lib
     from micronet_amd.nn import Conv2dFirst
@@ -707,21 +735,50 @@ def _walk_codes(model, code_ends=False):
             raise _err("dorefa_compile_codes: %s.conv has a_bits = %d, w_bits = %d; only 2-bit codes and 2-bit weights are code-packed" % (nm, ab, wb))
         if not conv.quant_inference:
             raise _err("dorefa_compile_codes: %s.conv is not a quant_inference=True layer (prepare(..., quant_inference=True), then prequantize_weights)" % nm)
+    tiled = set()          # (tile_blocks) the hidden blocks mn_codeconv_tile_* runs
     for nm, blk in blocks[1:-1]:
         conv = blk.conv
         if tuple(conv.stride) != (1, 1) or tuple(conv.dilation) != (1, 1) or conv.padding_mode != "zeros" or isinstance(conv.padding, str):
             raise _err("dorefa_compile_codes: %s.conv: stride / dilation other than 1 (or non-zero padding mode) is not covered by the code kernels" % nm)
         g = _lib.ConvGeom(1, conv.in_channels, 4, 4, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], 1, 1, conv.padding[0], conv.padding[1], 1, 1, conv.groups, 0)
         if not _lib.get_lib().mn_codeconv_supported(C.byref(g), CODE_BITS, CODE_BITS, CODE_BITS):
+            five = tuple(conv.kernel_size) == (5, 5)
+            if tile_blocks and _lib.get_lib().mn_codeconv_tile_supported(C.byref(g), CODE_BITS, CODE_BITS, CODE_BITS):
+                tiled.add(nm)
+                continue
+            if tile_blocks and five and conv.groups != 1:
+                raise _err("dorefa_compile_codes(tile_blocks=True): %s.conv: a grouped 5x5 block (groups %d) is not covered by mn_codeconv_tile_supported (dense only)"
+                           % (nm, conv.groups))
+            if tile_blocks and five and tuple(conv.padding) == (2, 2):
+                raise _err("dorefa_compile_codes(tile_blocks=True): %s.conv: a 5x5 block of %d input channels is beyond the bound of mn_codeconv_tile_supported (C * 25 * 9 <= "
+                           "32767: at most 145 channels, the int16 range the thresholds are searched over)" % (nm, conv.in_channels))
             raise _err("dorefa_compile_codes: %s.conv: geometry not covered by mn_codeconv_supported (%dx%d, padding %d, groups %d, %d taps per output: needs 1x1 or 3x3 with "
-                       "padding 1, and at most 3640 taps)" % (nm, conv.kernel_size[0], conv.kernel_size[1], conv.padding[0], conv.groups,
-                                                             conv.in_channels // conv.groups * conv.kernel_size[0] * conv.kernel_size[1]))
+                       "padding 1, and at most 3640 taps)%s" % (nm, conv.kernel_size[0], conv.kernel_size[1], conv.padding[0], conv.groups,
+                                                               conv.in_channels // conv.groups * conv.kernel_size[0] * conv.kernel_size[1],
+                                                               "; tile_blocks=True admits the dense 5x5 / padding 2 block of plain nin" if five and not tile_blocks else ""))
     first = last = None
     layers, tail, report = [], [], []
-    for name, child in seq.named_children():
+    kids = list(seq.named_children())
+    pending = None          # (tile_blocks) the standalone pool the walk has just passed: a quantised block must follow
+    for ki, (name, child) in enumerate(kids):
         nm = prefix + name
         if last is not None:
             tail.append(child)
+            continue
+        if tile_blocks and isinstance(child, nn.MaxPool2d) and not getattr(child, "_mn_fused_pool", False):
+            # ---- a max-pool prepare() did not fuse into the block in front of it: run on that block's planes (mn_codes_maxpool)
+            ksp = _pool_kind(child)
+            if ksp is None:
+                raise _err("dorefa_compile_codes(tile_blocks=True): %s: max-pool (kernel %s, stride %s, padding %s, ceil_mode %s) is not covered by the code kernels "
+                           "(2x2 / 2 / 0 and 3x3 / 2 / 1, floor mode)" % (nm, child.kernel_size, child.stride, child.padding, child.ceil_mode))
+            if pending is not None or (layers and (layers[-1]["pool"] or layers[-1].get("pool_ksp"))):
+                raise _err("dorefa_compile_codes(tile_blocks=True): %s: two max-pools in a row are not covered (one pool behind a code block)" % nm)
+            if not layers:
+                raise _err("dorefa_compile_codes(tile_blocks=True): %s: a max-pool directly behind the first block is not covered (its producer is not a code block)" % nm)
+            if not layers[-1]["wants_consumer"]:
+                raise _err("dorefa_compile_codes(tile_blocks=True): %s: the block in front of this max-pool already hands its codes to another consumer" % nm)
+            layers[-1]["wants_consumer"], layers[-1]["pool_ksp"], layers[-1]["stage"] = False, ksp, name
+            pending = nm
             continue
         if isinstance(child, nn.MaxPool2d):
             if _pool_kind(child) != (2, 2, 0):
@@ -737,10 +794,17 @@ def _walk_codes(model, code_ends=False):
         conv, bn = child.conv, getattr(child, "bn", None)
         if not isinstance(bn, quantize.BatchNorm2dReLU):
             raise _err("dorefa_compile_codes: %s: conv -> BatchNorm -> ReLU not fused (prepare(..., fuse_bn_act=True, fuse_blocks=True))" % nm)
+        if pending is not None:          # the consumer of a standalone pool: its activation quantizer is the one the producer's thresholds stand for
+            if not isinstance(conv, quantize.QuantConv2d) or conv.activation_quantizer.a_bits != CODE_BITS:
+                raise _err("dorefa_compile_codes(tile_blocks=True): %s: the block behind the max-pool %s must be a quantised conv reading %d-bit codes" % (nm, pending, CODE_BITS))
+            pending = None
         K = conv.in_channels // conv.groups * conv.kernel_size[0] * conv.kernel_size[1]
         if first is None:
             if type(conv) is not Conv2dFirst or getattr(child, "channel_shuffle_flag", 0):
                 raise _err("dorefa_compile_codes: %s: the first block must be the fp32 first conv" % nm)
+            if tile_blocks and not bn.q_out_bits and ki + 1 < len(kids) and isinstance(kids[ki + 1][1], nn.MaxPool2d):
+                raise _err("dorefa_compile_codes(tile_blocks=True): %s: a max-pool directly behind the first block is not covered (its producer, %s, is not a code block)"
+                           % (prefix + kids[ki + 1][0], nm))
             if bn.q_out_bits != CODE_BITS:
                 raise _err("dorefa_compile_codes: %s: the first block must hand over %d-bit activation codes (it emits %s)"
                            % (nm, CODE_BITS, ("%d-bit codes" % bn.q_out_bits) if bn.q_out_bits else "fp32"))
@@ -762,7 +826,12 @@ def _walk_codes(model, code_ends=False):
                                pooled=False, out_order="identity", stage=name))
             continue
         # ---- a hidden block: conv on codes -> bn -> relu -> [pool] -> the next conv's quantizer
-        if bn.q_out_bits != CODE_BITS:
+        wants = False
+        if tile_blocks and not bn.q_out_bits and ki + 1 < len(kids) and isinstance(kids[ki + 1][1], nn.MaxPool2d) and not getattr(kids[ki + 1][1], "_mn_fused_pool", False):
+            # prepare() left the block emitting fp32 because an un-fused max-pool follows: it emits the codes of the conv behind that pool instead (checked when the
+            # walk gets there) -- exact, the pool sits behind the ReLU and the quantizer is non-decreasing
+            wants = True
+        elif bn.q_out_bits != CODE_BITS:
             raise _err("dorefa_compile_codes: %s: its output is not handed over as %d-bit codes to the next quantised conv" % (nm, CODE_BITS))
         if shuffle > 1:
             if conv.in_channels % shuffle:
@@ -772,6 +841,10 @@ def _walk_codes(model, code_ends=False):
             layers[-1]["shuffle"] = shuffle          # folded into the producer's row order
         layers.append(dict(name=nm, conv=conv, bn=bn, k=conv.kernel_size[0], pad=conv.padding[0], cin=conv.in_channels, cout=conv.out_channels, groups=conv.groups,
                            pool=0, want_pool=bool(bn.q_pool), shuffle=0, stage=name))
+        if tile_blocks:
+            layers[-1].update(tile=nm in tiled, pool_ksp=None, wants_consumer=wants)
+    if pending is not None:
+        raise _err("dorefa_compile_codes(tile_blocks=True): %s: no quantised block behind this max-pool" % pending)
     if first is None or last is None:
         raise _err("dorefa_compile_codes: module order not recognised (no %s block found)" % ("first" if first is None else "last"))
     rep_last = report.pop()
@@ -781,30 +854,42 @@ def _walk_codes(model, code_ends=False):
     for L in layers:
         if L.pop("want_pool") != bool(L["pool"]):
             raise _err("dorefa_compile_codes: %s: the block pools its output but no 2x2 max-pool follows it (or the reverse)" % L["name"])
+        kern, pooled = _codeconv_kernel_name(L["k"], L["cin"], L["groups"], L["pool"]), bool(L["pool"])
+        if tile_blocks:
+            if L.pop("wants_consumer"):
+                raise _err("dorefa_compile_codes(tile_blocks=True): %s: its output is not handed over as %d-bit codes to the next quantised conv" % (L["name"], CODE_BITS))
+            if L["tile"]:
+                kern = _codeconv_tile_kernel_name(L["k"], L["cin"])
+            if L["pool_ksp"]:
+                kern, pooled = kern + ", k_codes_maxpool", "standalone"
         report.append(dict(name=L["name"], kind="code", K=L["cin"] // L["groups"] * L["k"] * L["k"], words=(L["cin"] + 31) // 32, planes=CODE_BITS,
-                           kernel=_codeconv_kernel_name(L["k"], L["cin"], L["groups"], L["pool"]), pooled=bool(L["pool"]),
+                           kernel=kern, pooled=pooled,
                            out_order=("shuffle %d" % L["shuffle"]) if L["shuffle"] > 1 else "identity", stage=L["stage"]))
     report.append(rep_last)
     return first, layers, last, tail, flatten, report
 
 
-def dorefa_codes_report(model, code_ends=False):
+def dorefa_codes_report(model, code_ends=False, tile_blocks=False):
     """The ``report`` ``dorefa_compile_codes(model, code_ends)`` would carry -- one row per stage: name, kind, K, words, planes, kernel, pooled, out_order -- from the
-    graph walk alone: no GPU, nothing packed.  Raises like ``dorefa_compile_codes`` for whatever the code kernels do not cover."""
-    return _walk_codes(model, code_ends)[5]
+    graph walk alone: no GPU, nothing packed.  Raises like ``dorefa_compile_codes`` for whatever the code kernels do not cover.  ``tile_blocks`` as there: a block on
+    ``k_codeconv_tile`` is named so, a max-pool run on the planes behind its block reads ``pooled="standalone"`` and ``"<block kernel>, k_codes_maxpool"``."""
+    return _walk_codes(model, code_ends, tile_blocks)[5]
 
 
 @torch.no_grad()
-def dorefa_compile_codes(model, code_ends=False):
+def dorefa_compile_codes(model, code_ends=False, tile_blocks=False):
     """``model``: a DoReFa W2A2 net prepared with ``quant_inference=True`` after ``prequantize_weights``, on the GPU (the reference's ``nin_gc``, or an ``nn.Sequential``
     of the same block kinds).  Returns a ``CodePlan`` computing the same function with two bits per hidden activation; ``.report`` lists the stages.  Anything the code
     kernels do not cover raises ``MicronetHipError`` naming the layer -- never a silent byte path (the caller still has ``model``).  ``code_ends=True``: the first conv
     writes the first stage's planes in one launch and the classifier reads the last stage's planes -- no fp32 map, no byte codes, no pack / unpack launch; same codes
-    in every stage, same logits (off by default until the gain is measured)."""
+    in every stage, same logits (off by default until the gain is measured).  ``tile_blocks=True``: also admits what plain ``nin`` needs -- a dense 5x5 / padding 2 block
+    of at most 145 input channels on an LDS-resident tile (``mn_codeconv_tile_*``), and a 2x2 / 2 or 3x3 / 2 / 1 max-pool ``prepare()`` did not fuse, directly behind a
+    hidden block and in front of a quantised one, run on the planes (``mn_codes_maxpool``; the block in front emits the codes of the conv behind the pool: exact, the
+    pool sits behind the ReLU and the quantizer is non-decreasing).  Off by default; with it off nothing changes."""
     import ctypes as C
     from micronet_amd import _lib, ops
     from micronet_amd.quantization.wqaq.dorefa.quantize import _weight_is_coded
-    first, layers, last, tail, flatten, report = _walk_codes(model, code_ends)
+    first, layers, last, tail, flatten, report = _walk_codes(model, code_ends, tile_blocks)
     for L in layers:
         if not _weight_is_coded(L["conv"]):
             raise _err("dorefa_compile_codes: %s.conv: the stored weights were not found on the 2-bit grid (2k - 3) / 3 (run inference.prequantize_weights on the GPU "
@@ -832,7 +917,8 @@ def dorefa_compile_codes(model, code_ends=False):
             wd = ops._wq_dorefa(CODE_BITS, None, 0)
             save = torch.empty((2, L["cout"]), dtype=torch.float32, device=dev)
             chan = torch.empty((_lib.MN_QA_NCH, L["cout"]), dtype=torch.float32, device=dev)
-            if lib.mn_qconv_bnq_supported(C.byref(g8), C.byref(wd), CODE_BITS) and int(lib.mn_qconv_bnq_stash_bits(C.byref(g8), C.byref(wd), CODE_BITS)) == 16:
+            tile = bool(L.get("tile"))
+            if not tile and lib.mn_qconv_bnq_supported(C.byref(g8), C.byref(wd), CODE_BITS) and int(lib.mn_qconv_bnq_stash_bits(C.byref(g8), C.byref(wd), CODE_BITS)) == 16:
                 # the fused block: the conv on codes with training = 0 writes the constants from the running statistics (alpha = weight scale x activation scale)
                 zero = torch.zeros((1, L["cin"], 8, 8), dtype=torch.uint8, device=dev)
                 stash = torch.empty((1, L["cout"], 8, 8), dtype=torch.int16, device=dev)
@@ -841,7 +927,8 @@ def dorefa_compile_codes(model, code_ends=False):
                 ops._call("mn_qconv_bnq_fwd_stash", C.byref(g8), C.byref(wd), ops._p(zero), CODE_BITS, ops._p(w), ops._p(b), ops._p(gamma), ops._p(beta), float(bn.eps),
                           float(bn.momentum), 0, ops._p(bn.running_mean), ops._p(bn.running_var), None, ops._p(save), ops._p(stash), ops._p(chan), ops._p(ws), nb, ops._s())
             else:
-                # a block the stash conv does not cover (narrow groups): its eval forward convolves to fp32 y = acc * alpha + bias (the code kernels' epilogue) and
+                # a block the stash conv does not cover (narrow groups) -- and, by the same route, the tiled 5x5 block: its eval forward convolves to fp32
+                # y = acc * alpha + bias (the code kernels' epilogue) and
                 # takes (mean, invstd) from mn_bn_save_stats -- the same two calls here; rows alpha / bias (1 / 0 for an fp32 input) become the epilogue's
                 zero = torch.zeros((1, L["cout"], 8, 8), dtype=torch.float32, device=dev)
                 ws = torch.empty(int(lib.mn_bnsign_ws_floats(L["cout"])), dtype=torch.float32, device=dev)
@@ -854,12 +941,13 @@ def dorefa_compile_codes(model, code_ends=False):
                 chan[6], chan[7] = chan[0] * chan[3], (chan[1] - chan[2]) * chan[3]
             # ---- the table (one launch per layer, once per model)
             g = _lib.ConvGeom(1, L["cin"], 4, 4, L["cout"], k, k, 1, 1, p, p, 1, 1, L["groups"], 0)
-            table = torch.empty(int(lib.mn_codeconv_table_bytes(C.byref(g), CODE_BITS, CODE_BITS, CODE_BITS)) // 4, dtype=torch.int32, device=dev)
+            quartet = "mn_codeconv_tile" if tile else "mn_codeconv"
+            table = torch.empty(int(getattr(lib, quartet + "_table_bytes")(C.byref(g), CODE_BITS, CODE_BITS, CODE_BITS)) // 4, dtype=torch.int32, device=dev)
             order = None
             if L["shuffle"] > 1:          # position j of the consumer's shuffled input is this layer's channel (j % s) * (C / s) + j // s (models/nin_gc.py:4-15)
                 j = torch.arange(L["cout"], device=dev)
                 order = ((j % L["shuffle"]) * (L["cout"] // L["shuffle"]) + j // L["shuffle"]).to(torch.int32).contiguous()
-            ops._call("mn_codeconv_pack", C.byref(g), ops._p(w), ops._p(chan), CODE_BITS, CODE_BITS, CODE_BITS, ops._p(order), ops._p(table), ops._s())
+            ops._call(quartet + "_pack", C.byref(g), ops._p(w), ops._p(chan), CODE_BITS, CODE_BITS, CODE_BITS, ops._p(order), ops._p(table), ops._s())
         L["table"], L["chan"], L["out_order"] = table, chan, order
     for L in layers:          # (compile time: the one place a host read-back is allowed)
         nonfinite, bad = int(L["table"][0]), int(L["table"][7])

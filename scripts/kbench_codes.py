@@ -10,7 +10,11 @@ per hidden block (arithmetic from the shapes: each operand read or written once)
     python scripts/kbench_codes.py --code-ends [--batches 256,1024] [--warmup 5] [--iters 20] [--out profiles/codes_ends.json]
 
 alternates the default plan (``code_ends=False``: the yardstick) and ``dorefa_compile_codes(I, code_ends=True)`` the same way and reports the per-kernel times of
-the launches replaced (first conv, k_qa_fwd, k_codes_pack, k_codes_unpack, the classifier on byte codes) beside the two new ones."""
+the launches replaced (first conv, k_qa_fwd, k_codes_pack, k_codes_unpack, the classifier on byte codes) beside the two new ones.
+
+    python scripts/kbench_codes.py --arch nin [--batches 256,1024] [--warmup 5] [--iters 20] [--out profiles/codes_nin.json]
+
+is the first protocol on PLAIN nin: ``P = dorefa_compile_codes(I, tile_blocks=True)`` (the dense 5x5 block on an LDS tile, the two 3x3 / 2 max-pools on planes)."""
 import argparse
 import json
 import os
@@ -45,13 +49,21 @@ def profile(lib, _lib, fn, x):
 
 def designed_bytes_per_image(P, hw=32):
     """Hidden blocks.  Byte path: codes in (1 B), 16-bit stash out and in again (2 + 2 B per un-pooled output), codes out (1 B per pooled output).  Code path: 2 bits per
-    input element, 2 bits per (pooled) output element, in whole 32-channel words."""
+    input element, 2 bits per (pooled) output element, in whole 32-channel words.  A max-pool that is not folded (plain nin's 3x3 / 2): on the byte path the block
+    writes fp32 (4 B per output), the pool reads it and writes fp32 (4 B per pooled output), the consumer's quantizer reads that and writes codes (4 + 1 B per pooled
+    output); on the code path the block writes planes at full size, the pool reads them and writes the pooled planes."""
     rows, h = [], hw
     for r, L in zip(P.report[1:-1], P.layers):
-        ho = h // 2 if L["pool"] else h
-        rows.append(dict(name=r["name"], kernel=r["kernel"],
-                         codes_bytes=4 * 2 * ((L["cin"] + 31) // 32) * h * h + 4 * 2 * ((L["cout"] + 31) // 32) * ho * ho,
-                         byte_path_bytes=L["cin"] * h * h + 4 * L["cout"] * h * h + L["cout"] * ho * ho))
+        ksp = L.get("pool_ksp")
+        ho = h // 2 if L["pool"] else ((h + 2 * ksp[2] - ksp[0]) // ksp[1] + 1 if ksp else h)
+        wi, wo = (L["cin"] + 31) // 32, (L["cout"] + 31) // 32
+        if ksp:
+            codes = 4 * 2 * wi * h * h + 2 * 4 * 2 * wo * h * h + 4 * 2 * wo * ho * ho
+            byte = L["cin"] * h * h + 4 * L["cout"] * h * h + 2 * 4 * L["cout"] * h * h + (4 + 4 + 1) * L["cout"] * ho * ho
+        else:
+            codes = 4 * 2 * wi * h * h + 4 * 2 * wo * ho * ho
+            byte = L["cin"] * h * h + 4 * L["cout"] * h * h + L["cout"] * ho * ho
+        rows.append(dict(name=r["name"], kernel=r["kernel"], codes_bytes=codes, byte_path_bytes=byte))
         h = ho
     return rows
 
@@ -108,23 +120,26 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--code-ends", action="store_true", help="the default plan against dorefa_compile_codes(I, code_ends=True)")
+    ap.add_argument("--arch", default="nin_gc", choices=("nin_gc", "nin"), help="nin: plain nin, compiled with tile_blocks=True")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.code_ends and args.arch != "nin_gc":
+        ap.error("--code-ends is measured on nin_gc")
     if args.out is None:
-        args.out = os.path.join("profiles", "codes_ends.json" if args.code_ends else "codes_inference.json")
+        args.out = os.path.join("profiles", "codes_ends.json" if args.code_ends else "codes_nin.json" if args.arch == "nin" else "codes_inference.json")
     if args.code_ends:
         return main_code_ends(args)
     from micronet.compression.quantization.wqaq.dorefa import quantize as Q
     from micronet_amd import _lib, inference
     from micronet_amd.train import build_model, synth_batch
     torch.manual_seed(0)
-    I = Q.prepare(build_model("nin_gc"), inplace=True, a_bits=2, w_bits=2, quant_inference=True).cuda()
+    I = Q.prepare(build_model(args.arch), inplace=True, a_bits=2, w_bits=2, quant_inference=True).cuda()
     inference.prequantize_weights(I)
     I.eval()
-    P = inference.dorefa_compile_codes(I)
+    P = inference.dorefa_compile_codes(I, tile_blocks=args.arch == "nin")
     lib = _lib.get_lib()
     rows = designed_bytes_per_image(P)
-    res = dict(model="nin_gc", a_bits=2, w_bits=2, warmup=args.warmup, iters=args.iters, device=torch.cuda.get_device_name(0), report=P.report,
+    res = dict(model=args.arch, a_bits=2, w_bits=2, warmup=args.warmup, iters=args.iters, device=torch.cuda.get_device_name(0), report=P.report,
                designed_bytes_per_image=rows, designed_hidden_bytes_per_image=dict(codes=sum(r["codes_bytes"] for r in rows), byte_path=sum(r["byte_path_bytes"] for r in rows)),
                batches={})
     with torch.no_grad():
