@@ -951,6 +951,24 @@ int64_t mn_codeconv_tile_table_bytes(const mn_conv_geom* g, int a_bits_in, int w
 int mn_codeconv_tile_pack(const mn_conv_geom* g, const float* w, const float* chan, int a_bits_in, int w_bits, int a_bits_out, const int32_t* out_order, uint32_t* table,
                           mn_stream_t stream);
 int mn_codeconv_tile_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t* in_planes, uint32_t* out_planes, mn_stream_t stream);
+/* The int8-MFMA form of the 1x1 hidden block: the same quartet, planes, header words 0 / 6 / 7, thresholds, out_order and `pool` as mn_codeconv_*; only the
+ * contraction differs, so the output planes equal mn_codeconv_fwd's word for word.  Covered (mn_codeconv_mfma_supported): a_bits_in = w_bits = a_bits_out = 2; 1x1,
+ * stride 1, padding 0, dilation 1, g->in_shuffle 0 / 1; groups == 1 with any C, or groups > 1 with C / groups % 32 == 0 (every group starts on an input word); any O
+ * and any O / groups; K * 9 <= 32767.  Everything else -- 3x3 and 5x5, which keep their kernels, and a grouped block of fewer than 32 channels per group, which stays
+ * on mn_codeconv_*, included -- is MN_ENOTSUP, as is pool outside 0 / 1; a null or misaligned tensor (planes 4-byte, `table` 16-byte aligned), an invalid geometry
+ * (N <= 0, ...) or odd H / W with pool is MN_EINVAL; nothing is written in either case.
+ *   pack : the weights as signed bytes 2k - 3 in the A-operand order of v_mfma_i32_16x16x64_i8, K padded with zero bytes to a multiple of 64 -> `table` (private
+ *          layout, mn_codeconv_mfma_table_bytes bytes).  The rows of two consecutive output words are sorted by group and cut into tiles of 16 rows inside a group
+ *          (a tile shares the B operand), padded with dead rows that never set a bit; every row carries flip, T_1 .. T_3 (the search of mn_codeconv_pack) and its
+ *          destination (word, bit).  Positions >= O and bad out_order entries yield 0 bits.
+ *   fwd  : acc = sum j (2k - 3) by MFMA -- a lane expands the codes of 16 channels of its pixel from two dword loads (plane 0, plane 1) by a multiply-and-mask bit
+ *          spread; a wave owns 64 pixels (pool == 1: the four sub-pixels of 16 pooled pixels) -- then u = flip * acc (pool: the window's largest), code =
+ *          #{k : u >= T_k}; the planes of an output word are assembled on chip and stored once, whole, without atomics; unused high bits of the last group are 0. */
+int mn_codeconv_mfma_supported(const mn_conv_geom* g, int a_bits_in, int w_bits, int a_bits_out);
+int64_t mn_codeconv_mfma_table_bytes(const mn_conv_geom* g, int a_bits_in, int w_bits, int a_bits_out);
+int mn_codeconv_mfma_pack(const mn_conv_geom* g, const float* w, const float* chan, int a_bits_in, int w_bits, int a_bits_out, const int32_t* out_order, uint32_t* table,
+                          mn_stream_t stream);
+int mn_codeconv_mfma_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t* in_planes, uint32_t* out_planes, int pool, mn_stream_t stream);
 /* Max-pool on code planes [N][Cw][a_bits][H][W] -> [N][Cw][a_bits][(H + 2 pad - k) / 2 + 1][(W + 2 pad - k) / 2 + 1] (floor mode): the bit-sliced maximum of the
  * window's codes, most significant plane first; taps outside the image contribute code 0 (the pool sits behind a ReLU).  (k, stride, pad) in {(2, 2, 0), (3, 2, 1)},
  * 1 <= a_bits <= 8; anything else, or a tensor of 2^31 words or more: MN_ENOTSUP.  Null / misaligned / empty tensor, or an image smaller than the window: MN_EINVAL.

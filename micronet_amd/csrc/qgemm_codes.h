@@ -16,7 +16,8 @@
 //                         group than the row before, row[4..6] = T_1..T_3, row[7] = 0, then taps x NW x w_bits weight planes, then NW group-mask words.
 //   consumer order    : the row at bit position j of an output word computes channel out_order[32 * word + j] (mn_bitconv_pack's convention).
 // Covered: a_in = w_bits = a_out = 2; 1x1 and 3x3 / padding 1, stride 1, any groups, the 2x2 / stride 2 pool folded or not (mn_codeconv_*); the dense 5x5 / padding 2
-// block of plain nin on an LDS-resident tile (mn_codeconv_tile_*) and the 2x2 / 2 and 3x3 / 2 / 1 max-pools on planes (mn_codes_maxpool).
+// block of plain nin on an LDS-resident tile (mn_codeconv_tile_*) and the 2x2 / 2 and 3x3 / 2 / 1 max-pools on planes (mn_codes_maxpool).  The 1x1 block, dense or with
+// whole input words per group, also has an int8-MFMA form with the same planes, thresholds and bits (mn_codeconv_mfma_*: qgemm_codes_mfma.h).
 #pragma once
 #include "qa_thresholds.h"
 

@@ -14,7 +14,13 @@ the launches replaced (first conv, k_qa_fwd, k_codes_pack, k_codes_unpack, the c
 
     python scripts/kbench_codes.py --arch nin [--batches 256,1024] [--warmup 5] [--iters 20] [--out profiles/codes_nin.json]
 
-is the first protocol on PLAIN nin: ``P = dorefa_compile_codes(I, tile_blocks=True)`` (the dense 5x5 block on an LDS tile, the two 3x3 / 2 max-pools on planes)."""
+is the first protocol on PLAIN nin: ``P = dorefa_compile_codes(I, tile_blocks=True)`` (the dense 5x5 block on an LDS tile, the two 3x3 / 2 max-pools on planes).
+
+    python scripts/kbench_codes.py --mfma-blocks [--batches 256,1024] [--warmup 5] [--iters 20] [--out profiles/codes_mfma.json]
+
+alternates ``I``, the default plan and ``dorefa_compile_codes(I, mfma_blocks=True)`` (the five 1x1 blocks of nin_gc on the int8-MFMA kernel) in one process and puts
+the per-kernel time of ``k_codeconv_mfma`` beside that of the default plan's ``k_codeconv<1,4,*>`` and of the byte path's ``k_pws`` + ``k_qa_fwd`` on the same five
+layers; the three logits must be bit-equal."""
 import argparse
 import json
 import os
@@ -114,21 +120,88 @@ def main_code_ends(args):
     print("wrote", args.out)
 
 
+def main_mfma_blocks(args):
+    """I, the default plan P0 and the plan with the 1x1 blocks on the MFMA kernel P1, alternated in one process."""
+    from micronet.compression.quantization.wqaq.dorefa import quantize as Q
+    from micronet_amd import _lib, inference
+    from micronet_amd.train import build_model, synth_batch
+    torch.manual_seed(0)
+    I = Q.prepare(build_model("nin_gc"), inplace=True, a_bits=2, w_bits=2, quant_inference=True).cuda()
+    inference.prequantize_weights(I)
+    I.eval()
+    P0, P1 = inference.dorefa_compile_codes(I), inference.dorefa_compile_codes(I, mfma_blocks=True)
+    lib = _lib.get_lib()
+    rows = designed_bytes_per_image(P1)
+    # the 1x1 layers' share of the byte path's hidden k_qa_fwd launches (<0, 0> un-pooled, <0, 1> pooled; <1, *> is the first block's): its traffic is per conv output
+    # element, so the share of each kind is taken by those
+    el = {(p_, one): 0 for p_ in (0, 1) for one in (False, True)}
+    for L, h in zip(P1.layers, _map_sizes(P1)):
+        el[(L["pool"], L["k"] == 1)] += L["cout"] * h * h
+    share = {p_: el[(p_, True)] / max(1, el[(p_, True)] + el[(p_, False)]) for p_ in (0, 1)}
+    res = dict(model="nin_gc", a_bits=2, w_bits=2, warmup=args.warmup, iters=args.iters, device=torch.cuda.get_device_name(0), report=P1.report,
+               designed_bytes_per_image=rows, mfma_layers_codes_bytes_per_image=sum(r["codes_bytes"] for r, L in zip(rows, P1.layers) if L.get("mfma")),
+               mfma_layers_macs_per_image=sum(L["cin"] // L["groups"] * L["cout"] * hh * hh for L, hh in zip(P1.layers, _map_sizes(P1)) if L.get("mfma")),
+               qa_fwd_share_of_1x1_layers={"k_qa_fwd<0, 0>": share[0], "k_qa_fwd<0, 1>": share[1]}, batches={})
+    with torch.no_grad():
+        for bs in [int(v) for v in args.batches.split(",")]:
+            x, _ = synth_batch(bs, device="cuda")
+            ref, y0, y1 = I(x), P0(x), P1(x)
+            equal = bool(torch.equal(ref, y0) and torch.equal(ref, y1))
+            assert equal, "I, the default plan and the mfma_blocks plan must give bit-equal logits"
+            for _ in range(args.warmup):
+                I(x), P0(x), P1(x)
+            ti, t0, t1 = [], [], []
+            for _ in range(args.iters):          # alternated: all three see the same clocks and the same neighbours
+                ti.append(timed(I, x))
+                t0.append(timed(P0, x))
+                t1.append(timed(P1, x))
+            ki, k0, k1 = profile(lib, _lib, I, x), profile(lib, _lib, P0, x), profile(lib, _lib, P1, x)
+            ms = lambda k, names: sum(v["ms"] for n, v in k.items() if n.startswith(names))
+            mi, m0, m1 = statistics.median(ti), statistics.median(t0), statistics.median(t1)
+            popc, mfma = ms(k0, ("k_codeconv<1,",)), ms(k1, ("k_codeconv_mfma<",))
+            qa1 = ms(ki, ("k_qa_fwd<0, 0>",)) * share[0] + ms(ki, ("k_qa_fwd<0, 1>",)) * share[1]
+            byte = ms(ki, ("k_pws",)) + qa1
+            res["batches"][str(bs)] = dict(I_ms=q(ti), P0_ms=q(t0), P1_ms=q(t1), P0_over_I=mi / m0, P1_over_I=mi / m1, P1_over_P0=m0 / m1, bit_equal=equal,
+                                           layers_1x1_ms=dict(popcount=popc, mfma=mfma, byte_path=byte, byte_path_k_pws=ms(ki, ("k_pws",)), byte_path_k_qa_fwd_share=qa1),
+                                           I_kernels=ki, P0_kernels=k0, P1_kernels=k1)
+            print("batch %d: I %.3f ms  default plan %.3f ms (%.2fx I)  mfma_blocks %.3f ms (%.2fx I, %.2fx default)  bit-equal %s" % (bs, mi, m0, mi / m0, m1, mi / m1, m0 / m1,
+                                                                                                                              equal), flush=True)
+            print("  five 1x1 layers: k_codeconv<1,*> %.3f ms  k_codeconv_mfma %.3f ms  byte path (k_pws + share of k_qa_fwd) %.3f ms" % (popc, mfma, byte), flush=True)
+    os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", args.out)
+
+
+def _map_sizes(P, hw=32):
+    """The input map size of every hidden block."""
+    out, h = [], hw
+    for L in P.layers:
+        out.append(h)
+        h = h // 2 if L["pool"] else h
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default="256,1024")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--code-ends", action="store_true", help="the default plan against dorefa_compile_codes(I, code_ends=True)")
+    ap.add_argument("--mfma-blocks", action="store_true", help="I, the default plan and dorefa_compile_codes(I, mfma_blocks=True)")
     ap.add_argument("--arch", default="nin_gc", choices=("nin_gc", "nin"), help="nin: plain nin, compiled with tile_blocks=True")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if args.code_ends and args.arch != "nin_gc":
-        ap.error("--code-ends is measured on nin_gc")
+    if (args.code_ends or args.mfma_blocks) and args.arch != "nin_gc":
+        ap.error("--code-ends and --mfma-blocks are measured on nin_gc")
+    if args.code_ends and args.mfma_blocks:
+        ap.error("--code-ends and --mfma-blocks are two protocols: run them one at a time")
     if args.out is None:
-        args.out = os.path.join("profiles", "codes_ends.json" if args.code_ends else "codes_nin.json" if args.arch == "nin" else "codes_inference.json")
+        args.out = os.path.join("profiles", "codes_mfma.json" if args.mfma_blocks else "codes_ends.json" if args.code_ends else "codes_nin.json" if args.arch == "nin" else "codes_inference.json")
     if args.code_ends:
         return main_code_ends(args)
+    if args.mfma_blocks:
+        return main_mfma_blocks(args)
     from micronet.compression.quantization.wqaq.dorefa import quantize as Q
     from micronet_amd import _lib, inference
     from micronet_amd.train import build_model, synth_batch
