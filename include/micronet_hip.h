@@ -969,6 +969,26 @@ int64_t mn_codeconv_mfma_table_bytes(const mn_conv_geom* g, int a_bits_in, int w
 int mn_codeconv_mfma_pack(const mn_conv_geom* g, const float* w, const float* chan, int a_bits_in, int w_bits, int a_bits_out, const int32_t* out_order, uint32_t* table,
                           mn_stream_t stream);
 int mn_codeconv_mfma_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t* in_planes, uint32_t* out_planes, int pool, mn_stream_t stream);
+/* The int8-MFMA form of the 3x3 hidden block: the same quartet, planes, header words 0 / 6 / 7, thresholds and out_order as mn_codeconv_*; only the contraction
+ * differs, so the output planes equal mn_codeconv_fwd's word for word.  Covered (mn_codeconv_mfma3_supported): a_bits_in = w_bits = a_bits_out = 2; 3x3, padding 1,
+ * stride 1, dilation 1, g->in_shuffle 0 / 1; any groups with C / groups % 16 == 0 (every group starts on a half-word); any O and any O / groups; K * 9 <= 32767 (at
+ * most 400 channels per group); pool == 0.  Everything else -- 1x1 and 5x5, which keep their kernels, other paddings and strides, 8 or 24 channels per group, pool
+ * == 1 (the pooled 3x3 block stays on mn_codeconv_*) included -- is MN_ENOTSUP; a null or misaligned tensor (planes 4-byte, `table` 16-byte aligned) or an invalid
+ * geometry (N <= 0, ...) is MN_EINVAL; nothing is written in either case.
+ *   pack : an implicit GEMM over (tap, channel): the K order is tap-major in slots of 16 channels (slot = tap * (C / groups / 16) + chunk), four slots per k-step of
+ *          v_mfma_i32_16x16x64_i8, padded with zero bytes to a multiple of four slots; the weights as signed bytes 2k - 3 in the A-operand order -> `table` (private
+ *          layout, mn_codeconv_mfma3_table_bytes bytes: an upper bound over the spans).  The packer chooses the SPAN of consecutive output words a wave assembles at
+ *          once -- the smallest of 2, 4, 8, 16 with the fewest dead rows (header word 2) -- sorts the rows of a span by group and cuts them into tiles of 16 rows
+ *          inside a group, padded with dead rows that never set a bit (their number: header word 5).  Positions >= O and bad out_order entries yield 0 bits.
+ *   fwd  : acc = sum j (2k - 3) by MFMA -- lane (n, kq) of a k-step loads the two plane words of its slot's 16 channels at pixel n + (dy, dx), zero where the tap is
+ *          outside the image (code 0: no border mask), and spreads the 16 + 16 bits to bytes -- then u = flip * acc, code = #{k : u >= T_k}; a wave owns 64 pixels,
+ *          ORs the bits of a span into an LDS image and stores every output word once, whole, coalesced along pixels: no atomics or read-modify-write on global
+ *          memory, two runs are bit-identical; unused high bits of the last group are 0.  mn_last_kernel(): k_codeconv_mfma3<0>. */
+int mn_codeconv_mfma3_supported(const mn_conv_geom* g, int a_bits_in, int w_bits, int a_bits_out);
+int64_t mn_codeconv_mfma3_table_bytes(const mn_conv_geom* g, int a_bits_in, int w_bits, int a_bits_out);
+int mn_codeconv_mfma3_pack(const mn_conv_geom* g, const float* w, const float* chan, int a_bits_in, int w_bits, int a_bits_out, const int32_t* out_order, uint32_t* table,
+                           mn_stream_t stream);
+int mn_codeconv_mfma3_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t* in_planes, uint32_t* out_planes, int pool, mn_stream_t stream);
 /* Max-pool on code planes [N][Cw][a_bits][H][W] -> [N][Cw][a_bits][(H + 2 pad - k) / 2 + 1][(W + 2 pad - k) / 2 + 1] (floor mode): the bit-sliced maximum of the
  * window's codes, most significant plane first; taps outside the image contribute code 0 (the pool sits behind a ReLU).  (k, stride, pad) in {(2, 2, 0), (3, 2, 1)},
  * 1 <= a_bits <= 8; anything else, or a tensor of 2^31 words or more: MN_ENOTSUP.  Null / misaligned / empty tensor, or an image smaller than the window: MN_EINVAL.

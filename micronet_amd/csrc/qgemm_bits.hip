@@ -731,3 +731,4 @@ extern "C" int mn_bits_maxpool(const uint32_t* bits_in, int64_t N, int64_t Cw, i
 
 #include "qgemm_codes.h"          // mn_codes_* / mn_codeconv_*: the code-packed deployment of the k-bit blocks
 #include "qgemm_codes_mfma.h"     // mn_codeconv_mfma_*: the int8-MFMA form of the 1x1 hidden code blocks
+#include "qgemm_codes_mfma3.h"    // mn_codeconv_mfma3_*: the int8-MFMA form of the 3x3 hidden code blocks

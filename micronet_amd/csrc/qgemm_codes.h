@@ -18,6 +18,7 @@
 // Covered: a_in = w_bits = a_out = 2; 1x1 and 3x3 / padding 1, stride 1, any groups, the 2x2 / stride 2 pool folded or not (mn_codeconv_*); the dense 5x5 / padding 2
 // block of plain nin on an LDS-resident tile (mn_codeconv_tile_*) and the 2x2 / 2 and 3x3 / 2 / 1 max-pools on planes (mn_codes_maxpool).  The 1x1 block, dense or with
 // whole input words per group, also has an int8-MFMA form with the same planes, thresholds and bits (mn_codeconv_mfma_*: qgemm_codes_mfma.h).
+// The un-pooled 3x3 block with C / groups % 16 == 0 has one too, an implicit GEMM over (tap, channel) (mn_codeconv_mfma3_*: qgemm_codes_mfma3.h).
 #pragma once
 #include "qa_thresholds.h"
 

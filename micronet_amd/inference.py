@@ -544,6 +544,11 @@ def _codeconv_mfma_kernel_name(pool):
     return "k_codeconv_mfma<%d>" % pool
 
 
+def _codeconv_mfma3_kernel_name():
+    """The kernel mn_codeconv_mfma3_fwd reports for a 3x3 hidden block (csrc/qgemm_codes_mfma3.h)."""
+    return "k_codeconv_mfma3<0>"
+
+
 def _codeconv_tile_kernel_name(k, cin):
     """The kernel mn_codeconv_tile_fwd launches for a dense 5x5 block (csrc/qgemm_codes.h: three word groups unrolled, anything else rolled)."""
     return "k_codeconv_tile<%d,%d>" % (k, 3 if (cin + 31) // 32 == 3 else 0)
@@ -632,6 +637,8 @@ class CodePlan(nn.Module):
                 ops._call("mn_codeconv_tile_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(out), st)
             elif L.get("mfma"):
                 ops._call("mn_codeconv_mfma_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(out), int(L["pool"]), st)
+            elif L.get("mfma3"):
+                ops._call("mn_codeconv_mfma3_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(out), 0, st)
             else:
                 ops._call("mn_codeconv_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(out), int(L["pool"]), st)
             if mids[i] is not None:
@@ -715,10 +722,11 @@ def _check_code_ends(first, nm_first, last, nm_last):
         raise _err("dorefa_compile_codes(code_ends=True): %s: a channel shuffle in front of the last conv is not covered by mn_planesconv1x1_small_fwd" % nm_last)
 
 
-def _walk_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False):
+def _walk_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False, mfma_k3=False):
     """The graph walk of ``dorefa_compile_codes`` (no GPU needed): (first, layers, last, tail, flatten, report).  ``tile_blocks``: also admit what plain nin needs -- a
     dense 5x5 block (``layer["tile"]``) and a max-pool ``prepare()`` did not fuse, run on the planes behind its block (``layer["pool_ksp"]``).  ``mfma_blocks``: a
-    hidden block ``mn_codeconv_mfma_supported`` covers runs on the MFMA form (``layer["mfma"]``); it refuses nothing."""
+    hidden block ``mn_codeconv_mfma_supported`` covers runs on the MFMA form (``layer["mfma"]``); it refuses nothing.  ``mfma_k3``: a hidden 3x3 block
+    ``mn_codeconv_mfma3_supported`` covers, with no folded pool, runs on the 3x3 MFMA form (``layer["mfma3"]``); it refuses nothing either."""
     import ctypes as C
     from micronet_amd import _lib
     from micronet_amd.nn import Conv2dFirst
@@ -851,9 +859,12 @@ def _walk_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False):
                            pool=0, want_pool=bool(bn.q_pool), shuffle=0, stage=name))
         if tile_blocks:
             layers[-1].update(tile=nm in tiled, pool_ksp=None, wants_consumer=wants)
-        if mfma_blocks:
+        if mfma_blocks or mfma_k3:
             g = _lib.ConvGeom(1, conv.in_channels, 4, 4, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], 1, 1, conv.padding[0], conv.padding[1], 1, 1, conv.groups, 0)
-            layers[-1]["mfma"] = bool(_lib.get_lib().mn_codeconv_mfma_supported(C.byref(g), CODE_BITS, CODE_BITS, CODE_BITS))
+            if mfma_blocks:
+                layers[-1]["mfma"] = bool(_lib.get_lib().mn_codeconv_mfma_supported(C.byref(g), CODE_BITS, CODE_BITS, CODE_BITS))
+            if mfma_k3:
+                layers[-1]["mfma3"] = bool(_lib.get_lib().mn_codeconv_mfma3_supported(C.byref(g), CODE_BITS, CODE_BITS, CODE_BITS))
     if pending is not None:
         raise _err("dorefa_compile_codes(tile_blocks=True): %s: no quantised block behind this max-pool" % pending)
     if first is None or last is None:
@@ -866,6 +877,8 @@ def _walk_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False):
         if L.pop("want_pool") != bool(L["pool"]):
             raise _err("dorefa_compile_codes: %s: the block pools its output but no 2x2 max-pool follows it (or the reverse)" % L["name"])
         kern, pooled = _codeconv_kernel_name(L["k"], L["cin"], L["groups"], L["pool"]), bool(L["pool"])
+        if mfma_k3 and L["pool"]:          # (known only now: the walk folds a 2x2 pool into the layer after it has passed the block)
+            L["mfma3"] = False
         if tile_blocks:
             if L.pop("wants_consumer"):
                 raise _err("dorefa_compile_codes(tile_blocks=True): %s: its output is not handed over as %d-bit codes to the next quantised conv" % (L["name"], CODE_BITS))
@@ -873,6 +886,8 @@ def _walk_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False):
                 kern = _codeconv_tile_kernel_name(L["k"], L["cin"])
         if L.get("mfma"):
             kern = _codeconv_mfma_kernel_name(L["pool"])
+        if L.get("mfma3"):
+            kern = _codeconv_mfma3_kernel_name()
         if tile_blocks:          # (behind the block's own kernel name, whichever it is)
             if L["pool_ksp"]:
                 kern, pooled = kern + ", k_codes_maxpool", "standalone"
@@ -883,16 +898,17 @@ def _walk_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False):
     return first, layers, last, tail, flatten, report
 
 
-def dorefa_codes_report(model, code_ends=False, tile_blocks=False, mfma_blocks=False):
+def dorefa_codes_report(model, code_ends=False, tile_blocks=False, mfma_blocks=False, mfma_k3=False):
     """The ``report`` ``dorefa_compile_codes(model, code_ends)`` would carry -- one row per stage: name, kind, K, words, planes, kernel, pooled, out_order -- from the
     graph walk alone: no GPU, nothing packed.  Raises like ``dorefa_compile_codes`` for whatever the code kernels do not cover.  ``tile_blocks`` as there: a block on
     ``k_codeconv_tile`` is named so, a max-pool run on the planes behind its block reads ``pooled="standalone"`` and ``"<block kernel>, k_codes_maxpool"``.
-    ``mfma_blocks`` as there: the ``kernel`` of a block on the MFMA form reads ``k_codeconv_mfma<0|1>``."""
-    return _walk_codes(model, code_ends, tile_blocks, mfma_blocks)[5]
+    ``mfma_blocks`` as there: the ``kernel`` of a block on the MFMA form reads ``k_codeconv_mfma<0|1>``.  ``mfma_k3`` as there: a 3x3 block on its MFMA form reads
+    ``k_codeconv_mfma3<0>``."""
+    return _walk_codes(model, code_ends, tile_blocks, mfma_blocks, mfma_k3)[5]
 
 
 @torch.no_grad()
-def dorefa_compile_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False):
+def dorefa_compile_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False, mfma_k3=False):
     """``model``: a DoReFa W2A2 net prepared with ``quant_inference=True`` after ``prequantize_weights``, on the GPU (the reference's ``nin_gc``, or an ``nn.Sequential``
     of the same block kinds).  Returns a ``CodePlan`` computing the same function with two bits per hidden activation; ``.report`` lists the stages.  Anything the code
     kernels do not cover raises ``MicronetHipError`` naming the layer -- never a silent byte path (the caller still has ``model``).  ``code_ends=True``: the first conv
@@ -903,11 +919,15 @@ def dorefa_compile_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=
     pool sits behind the ReLU and the quantizer is non-decreasing).  Off by default; with it off nothing changes.  ``mfma_blocks=True``: a 1x1 hidden block
     ``mn_codeconv_mfma_supported`` covers (dense, or at least 32 channels per group on word boundaries; the folded 2x2 pool included) is packed and run in its
     int8-MFMA form (``mn_codeconv_mfma_*``: same planes, thresholds and bits, only the contraction differs); every other block keeps what it has, nothing is refused
-    on its account, and it composes with the other two flags.  The layer dicts gain the key ``"mfma"``.  Off by default; with it off nothing changes."""
+    on its account, and it composes with the other two flags.  The layer dicts gain the key ``"mfma"``.  Off by default; with it off nothing changes.
+    ``mfma_k3=True``: a 3x3 / padding 1 hidden block ``mn_codeconv_mfma3_supported`` covers (C / groups % 16 == 0, at most 400 channels per group) with no folded pool
+    is packed and run in its int8-MFMA form (``mn_codeconv_mfma3_*``: an implicit GEMM over (tap, channel), same planes, thresholds and bits); a pooled 3x3 block
+    and every other block keep what they have, nothing is refused on its account, and it composes with the other three flags.  The layer dicts gain the key
+    ``"mfma3"``.  Off by default; with it off nothing changes."""
     import ctypes as C
     from micronet_amd import _lib, ops
     from micronet_amd.quantization.wqaq.dorefa.quantize import _weight_is_coded
-    first, layers, last, tail, flatten, report = _walk_codes(model, code_ends, tile_blocks, mfma_blocks)
+    first, layers, last, tail, flatten, report = _walk_codes(model, code_ends, tile_blocks, mfma_blocks, mfma_k3)
     for L in layers:
         if not _weight_is_coded(L["conv"]):
             raise _err("dorefa_compile_codes: %s.conv: the stored weights were not found on the 2-bit grid (2k - 3) / 3 (run inference.prequantize_weights on the GPU "
@@ -959,7 +979,7 @@ def dorefa_compile_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=
                 chan[6], chan[7] = chan[0] * chan[3], (chan[1] - chan[2]) * chan[3]
             # ---- the table (one launch per layer, once per model)
             g = _lib.ConvGeom(1, L["cin"], 4, 4, L["cout"], k, k, 1, 1, p, p, 1, 1, L["groups"], 0)
-            quartet = "mn_codeconv_tile" if tile else "mn_codeconv_mfma" if L.get("mfma") else "mn_codeconv"
+            quartet = "mn_codeconv_tile" if tile else "mn_codeconv_mfma" if L.get("mfma") else "mn_codeconv_mfma3" if L.get("mfma3") else "mn_codeconv"
             table = torch.empty(int(getattr(lib, quartet + "_table_bytes")(C.byref(g), CODE_BITS, CODE_BITS, CODE_BITS)) // 4, dtype=torch.int32, device=dev)
             order = None
             if L["shuffle"] > 1:          # position j of the consumer's shuffled input is this layer's channel (j % s) * (C / s) + j // s (models/nin_gc.py:4-15)

@@ -20,7 +20,13 @@ is the first protocol on PLAIN nin: ``P = dorefa_compile_codes(I, tile_blocks=Tr
 
 alternates ``I``, the default plan and ``dorefa_compile_codes(I, mfma_blocks=True)`` (the five 1x1 blocks of nin_gc on the int8-MFMA kernel) in one process and puts
 the per-kernel time of ``k_codeconv_mfma`` beside that of the default plan's ``k_codeconv<1,4,*>`` and of the byte path's ``k_pws`` + ``k_qa_fwd`` on the same five
-layers; the three logits must be bit-equal."""
+layers; the three logits must be bit-equal.
+
+    python scripts/kbench_codes.py --mfma-k3 [--arch nin] [--batches 256,1024] [--warmup 5] [--iters 20] [--out profiles/codes_mfma3.json]
+
+alternates ``I``, ``dorefa_compile_codes(I, mfma_blocks=True)`` and ``dorefa_compile_codes(I, mfma_blocks=True, mfma_k3=True)`` (the un-pooled 3x3 blocks on
+``k_codeconv_mfma3`` as well) the same way and puts the per-kernel time of ``k_codeconv_mfma3`` beside that of ``k_codeconv<3,*>`` in the other plan and of the byte
+path's 3x3 conv kernels; ``--arch nin`` adds ``tile_blocks=True`` to both plans (default output profiles/codes_mfma3_nin.json)."""
 import argparse
 import json
 import os
@@ -173,6 +179,53 @@ def main_mfma_blocks(args):
     print("wrote", args.out)
 
 
+def main_mfma_k3(args):
+    """I, the plan with the 1x1 blocks on MFMA P0 and the plan with the 3x3 blocks on MFMA as well P1, alternated in one process."""
+    from micronet.compression.quantization.wqaq.dorefa import quantize as Q
+    from micronet_amd import _lib, inference
+    from micronet_amd.train import build_model, synth_batch
+    torch.manual_seed(0)
+    I = Q.prepare(build_model(args.arch), inplace=True, a_bits=2, w_bits=2, quant_inference=True).cuda()
+    inference.prequantize_weights(I)
+    I.eval()
+    kw = dict(tile_blocks=True) if args.arch == "nin" else {}
+    P0 = inference.dorefa_compile_codes(I, mfma_blocks=True, **kw)
+    P1 = inference.dorefa_compile_codes(I, mfma_blocks=True, mfma_k3=True, **kw)
+    lib = _lib.get_lib()
+    k3 = [L for L in P1.layers if L.get("mfma3")]
+    res = dict(model=args.arch, a_bits=2, w_bits=2, warmup=args.warmup, iters=args.iters, device=torch.cuda.get_device_name(0), report=P1.report,
+               mfma3_layers=[dict(name=L["name"], cin=L["cin"], cout=L["cout"], groups=L["groups"], span_words=int(L["table"][2]), dead_rows=int(L["table"][5])) for L in k3],
+               batches={})
+    with torch.no_grad():
+        for bs in [int(v) for v in args.batches.split(",")]:
+            x, _ = synth_batch(bs, device="cuda")
+            ref, y0, y1 = I(x), P0(x), P1(x)
+            equal = bool(torch.equal(ref, y0) and torch.equal(ref, y1))
+            assert equal, "I, the mfma_blocks plan and the mfma_k3 plan must give bit-equal logits"
+            for _ in range(args.warmup):
+                I(x), P0(x), P1(x)
+            ti, t0, t1 = [], [], []
+            for _ in range(args.iters):          # alternated: all three see the same clocks and the same neighbours
+                ti.append(timed(I, x))
+                t0.append(timed(P0, x))
+                t1.append(timed(P1, x))
+            ki, k0, k1 = profile(lib, _lib, I, x), profile(lib, _lib, P0, x), profile(lib, _lib, P1, x)
+            ms = lambda k, names: sum(v["ms"] for n, v in k.items() if n.startswith(names))
+            mi, m0, m1 = statistics.median(ti), statistics.median(t0), statistics.median(t1)
+            popc, mfma3 = ms(k0, ("k_codeconv<3,",)), ms(k1, ("k_codeconv_mfma3<",))
+            byte = ms(ki, ("k_k3s_fwd", "k_kk<"))          # the byte path's 3x3 conv launches (its k_qa_fwd share comes on top: I_kernels holds every launch)
+            res["batches"][str(bs)] = dict(I_ms=q(ti), P0_ms=q(t0), P1_ms=q(t1), P0_over_I=mi / m0, P1_over_I=mi / m1, P1_over_P0=m0 / m1, bit_equal=equal,
+                                           layers_3x3_ms=dict(popcount=popc, mfma3=mfma3, popcount_left_in_P1=ms(k1, ("k_codeconv<3,",)), byte_path_conv=byte),
+                                           I_kernels=ki, P0_kernels=k0, P1_kernels=k1)
+            print("batch %d: I %.3f ms  mfma_blocks %.3f ms (%.2fx I)  mfma_blocks + mfma_k3 %.3f ms (%.2fx I, %.2fx mfma_blocks)  bit-equal %s"
+                  % (bs, mi, m0, mi / m0, m1, mi / m1, m0 / m1, equal), flush=True)
+            print("  3x3 layers: k_codeconv<3,*> %.3f ms  k_codeconv_mfma3 %.3f ms  byte path conv kernels %.3f ms" % (popc, mfma3, byte), flush=True)
+    os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", args.out)
+
+
 def _map_sizes(P, hw=32):
     """The input map size of every hidden block."""
     out, h = [], hw
@@ -189,13 +242,18 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--code-ends", action="store_true", help="the default plan against dorefa_compile_codes(I, code_ends=True)")
     ap.add_argument("--mfma-blocks", action="store_true", help="I, the default plan and dorefa_compile_codes(I, mfma_blocks=True)")
+    ap.add_argument("--mfma-k3", action="store_true", help="I, the mfma_blocks plan and dorefa_compile_codes(I, mfma_blocks=True, mfma_k3=True); works with --arch nin")
     ap.add_argument("--arch", default="nin_gc", choices=("nin_gc", "nin"), help="nin: plain nin, compiled with tile_blocks=True")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if (args.code_ends or args.mfma_blocks) and args.arch != "nin_gc":
         ap.error("--code-ends and --mfma-blocks are measured on nin_gc")
-    if args.code_ends and args.mfma_blocks:
-        ap.error("--code-ends and --mfma-blocks are two protocols: run them one at a time")
+    if args.code_ends + args.mfma_blocks + args.mfma_k3 > 1:
+        ap.error("--code-ends, --mfma-blocks and --mfma-k3 are three protocols: run them one at a time")
+    if args.mfma_k3:
+        if args.out is None:
+            args.out = os.path.join("profiles", "codes_mfma3.json" if args.arch == "nin_gc" else "codes_mfma3_nin.json")
+        return main_mfma_k3(args)
     if args.out is None:
         args.out = os.path.join("profiles", "codes_mfma.json" if args.mfma_blocks else "codes_ends.json" if args.code_ends else "codes_nin.json" if args.arch == "nin" else "codes_inference.json")
     if args.code_ends:

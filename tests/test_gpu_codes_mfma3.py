@@ -1,0 +1,36 @@
+"""The int8-MFMA form of the 3x3 hidden code block (csrc/qgemm_codes_mfma3.h: k_codeconv_mfma3) on the MI355X, through the C ABI: the checks of tests/codes_mfma3_cases.py, which
+tests/test_codes_mfma3_emulated.py runs on the CPU emulation build.  All comparisons are exact."""
+import pytest
+
+import abi_driver
+import codes_mfma3_cases as MC
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def be():
+    return abi_driver.Backend("gpu")
+
+
+@pytest.mark.parametrize("case", range(len(MC.BLOCKS)), ids=[c[0] for c in MC.BLOCKS])
+def test_codeconv_mfma3_block(be, case):
+    MC.check_block(be, case)
+
+
+@pytest.mark.parametrize("kcode", [3, 0])
+def test_codeconv_mfma3_k_bound_fill(be, kcode):
+    MC.check_fill(be, kcode)
+
+
+@pytest.mark.parametrize("case", range(len(MC.REFUSED)))
+def test_codeconv_mfma3_refused_is_enotsup(be, case):
+    MC.check_refused(be, case)
+
+
+def test_codeconv_mfma3_invalid_is_einval(be):
+    MC.check_invalid(be)
+
+
+def test_codeconv_mfma3_table_counters(be):
+    MC.check_counters(be)
