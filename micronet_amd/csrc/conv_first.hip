@@ -38,6 +38,7 @@ struct C1Params {
     int N, C, H, W, O, KH, KW, ph, pw, K, KS, Opad;
     int R, strips, PR, PW, CS;      // strip of R output rows; LDS patch rows / row pitch / channel stride
     int Z, want_db, xs_bytes;       // xs_bytes: LDS bytes of the image patch (the backward-weight's row images follow)
+    int xt_bytes;                   // k_c1b_fwd: LDS bytes of the patch as bf16 term planes (c1_stage_terms)
     FastDiv fd_w;
     // BN variant of the backward-weight: gy is not given, it is the BatchNorm+sign backward of (da, yb) formed in registers
     const float* da;      // d loss / d sign output      [N][O][H][W]
@@ -77,6 +78,26 @@ __device__ __forceinline__ void c1_stage(const C1Params& p, float* xs, int n, in
         float v = 0.f;
         if (ir >= 0 && ir < p.H && ic >= 0 && ic < p.W) v = p.x[(((int64_t)n * p.C + c) * p.H + ir) * p.W + ic];
         xs[c * p.CS + pr * p.PW + pc] = v;
+    }
+}
+// the same strip as three exact bf16 terms per value, split ONCE (k_c1b_fwd): x01[i] = term 0 | term 1 << 16, x2[i] = term 2, i = c * CS + prow * PW + pcol as in
+// c1_stage; slot C * CS holds the split of 0, what a padded im2col row reads.  v = t0 + t1 + t2 with t0 = head(v), t1 = head(v - t0), t2 = v - t0 - t1.
+__device__ __forceinline__ void c1_stage_terms(const C1Params& p, uint32_t* x01, uint16_t* x2, int n, int row0) {
+    const int per_c = p.PR * p.PW, total = p.C * per_c;
+    for (int i = threadIdx.x; i <= total; i += 256) {
+        float v = 0.f;
+        if (i < total) {
+            const int c = i / per_c, rem = i - c * per_c;
+            const int pr = rem / p.PW, pc = rem - pr * p.PW;
+            const int ir = row0 - p.ph + pr, ic = pc - p.pw;
+            if (ir >= 0 && ir < p.H && ic >= 0 && ic < p.W) v = p.x[(((int64_t)n * p.C + c) * p.H + ir) * p.W + ic];
+        }
+        const float t0 = mn_bf16_head(v);
+        const float r1 = v - t0;
+        const float t1 = mn_bf16_head(r1);
+        const float t2 = r1 - t1;
+        x01[i] = mn_pack_bf16x2(t0, t1);
+        x2[i] = (uint16_t)(mn_f2u(t2) >> 16);
     }
 }
 // LDS offset of im2col row k = (c, r, s) relative to the top-left tap of a pixel
@@ -185,7 +206,8 @@ __global__ __launch_bounds__(256, 2) void k_c1_fwd(const C1Params p) {
 // against 55 us for writing y).  Both operands are real, so each is written as three exact bf16 terms and a product uses the six largest term products (2^-24
 // relative: the accuracy of an fp32 multiply) on v_mfma_f32_16x16x32_bf16 -- 6 / 16 of the fp32-MFMA time.  The B operand needs 8 consecutive K per lane, which
 // the channel / tap-strided patch cannot give, so every 64-pixel chunk is expanded ONCE per block into an im2col tile [term][pixel][96 k] in LDS (24 consecutive k
-// of one pixel per thread: patch reads conflict-free along the pixels, three 16-byte writes per term) that the four waves -- each 64 out-channels -- share; the
+// of one pixel per thread: patch reads conflict-free along the pixels, three 16-byte writes per term) that the four waves -- each 64 out-channels -- share.  The
+// strip is staged already split (c1_stage_terms: a value's three terms do not depend on the tap that reads it), so the expand is a gather without arithmetic; the
 // weights are A fragments in registers for the block's lifetime (3 terms x 3 K steps x MT).  Pixel p sits in tile row (p & 3) * 16 + (p >> 2): MFMA column j of
 // n-tile q is pixel 4 j + q, so a lane ends with float4 = 4 consecutive pixels per out-channel (the write side takes the bank conflicts of that permutation: 9
 // writes against 36 fragment reads per chunk).
@@ -195,8 +217,10 @@ constexpr float C1C_S = (float)(1.0 / 3.0);          // dorefa_scale(2): the sca
 template <int MT, int EPI = 0>
 __global__ __launch_bounds__(256, 2) void k_c1b_fwd(const C1Params p) {
     HIP_DYNAMIC_SHARED(float, smem)
-    float* xs = smem;
-    uint16_t* im = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(smem) + p.xs_bytes);          // [3 terms][64][C1B_LD]
+    float* xs = smem;          // (the reduction scratch of the min / max partials behind the chunk loop)
+    uint32_t* x01 = reinterpret_cast<uint32_t*>(smem);                                              // [C CS + 1] terms 0 and 1 of the strip, the zero slot last
+    uint16_t* x2 = reinterpret_cast<uint16_t*>(x01 + p.C * p.CS + 1);                               // [C CS + 1] term 2
+    uint16_t* im = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(smem) + p.xt_bytes);          // [3 terms][64][C1B_LD]
     int* ktab = reinterpret_cast<int*>(im + 3 * 64 * C1B_LD);                                      // [96] patch offset of im2col row k (-1: padding)
     const int tid = threadIdx.x, lane = tid & 63, wave = mn_uniform(tid >> 6), j = lane & 15, kg = lane >> 4;
     uint32_t b = blockIdx.x;
@@ -207,7 +231,7 @@ __global__ __launch_bounds__(256, 2) void k_c1b_fwd(const C1Params p) {
     const int m0 = (cblk * 4 + wave) * 16 * MT;
 
     float* bs = reinterpret_cast<float*>(ktab + C1B_KP);                                           // [64 MT] the block's bias
-    c1_stage(p, xs, n, row0);
+    c1_stage_terms(p, x01, x2, n, row0);
     for (int k = tid; k < C1B_KP; k += 256) ktab[k] = k < p.K ? c1_koff(p, k) : -1;
     for (int i = tid; i < 64 * MT; i += 256) { const int m = cblk * 64 * MT + i; bs[i] = (p.bias && m < p.O) ? p.bias[m] : 0.f; }
     float4* bc = reinterpret_cast<float4*>(bs + 64 * MT);          // EPI 1 / 2: [64 MT] mean, invstd, gamma, beta
@@ -226,24 +250,26 @@ __global__ __launch_bounds__(256, 2) void k_c1b_fwd(const C1Params p) {
             bc[i] = make_float4(p.bn_save[mc], p.bn_save[p.O + mc], p.bn_gamma[mc], p.bn_beta[mc]);
         }
     // A fragments: three exact bf16 terms of w[m0 + t * 16 + j][ks * 32 + kg * 8 .. + 7].  The block's weight rows are one contiguous range: they come through LDS
-    // (the tile buffer, not yet in use: 16 MT rows x K <= 64 x 96 floats fit) one wave's rows per round, read from memory coalesced -- a lane fetching its 24 MT
+    // (the tile buffer, not yet in use: 128 rows x K <= 76 floats fit) the rows of WR waves per round, read from memory coalesced -- a lane fetching its 24 MT
     // elements itself touches a different 300-byte row per lane and element (measured on nin_gc's first layer: ~20 us of a 113 us kernel, all 512 blocks at once).
+    // All the waves of a round split their rows at the same time: one round at MT <= 2, two at MT 3 and 4.
     u32x4 wa[3][3][MT];
     float* wl = reinterpret_cast<float*>(im);
-    for (int r = 0; r < 4; ++r) {
+    constexpr int WR = MT <= 2 ? 4 : 2;
+    for (int r = 0; r < 4 / WR; ++r) {
         if (r) __syncthreads();          // the previous round's rows are consumed
-        const int row_r = (cblk * 4 + r) * 16 * MT;
-        const int nrows = p.O - row_r < 16 * MT ? p.O - row_r : 16 * MT;
+        const int row_r = (cblk * 4 + r * WR) * 16 * MT;
+        const int nrows = p.O - row_r < WR * 16 * MT ? p.O - row_r : WR * 16 * MT;
         const int cnt = nrows > 0 ? nrows * p.K : 0;
         const float* src = p.wp + (int64_t)row_r * p.K;
         for (int i = tid; i < cnt; i += 256) wl[i] = src[i];
         __syncthreads();
-        if (wave == r) {
+        if (wave / WR == r) {
 #pragma unroll
             for (int ks = 0; ks < 3; ++ks)
 #pragma unroll
                 for (int t = 0; t < MT; ++t) {
-                    const int lrow = t * 16 + j;
+                    const int lrow = (wave % WR) * 16 * MT + t * 16 + j;
                     const bool mv = row_r + lrow < p.O;
                     float t0[8], t1[8], t2[8];
 #pragma unroll
@@ -275,23 +301,25 @@ __global__ __launch_bounds__(256, 2) void k_c1b_fwd(const C1Params p) {
         const bool pv = pix < npix;
         const uint32_t prow = fd_div(pv ? pix : 0, p.fd_w);
         const int pcol = (pv ? pix : 0) - prow * p.W;
-        const float* src = xs + (int)prow * p.PW + pcol;
+        const int sb = (int)prow * p.PW + pcol, zs = p.C * p.CS;          // top-left tap of the pixel; the zero slot
         uint16_t* dst = im + buf * TB + irow * C1B_LD + wave * 24;
+        // a gather of finished terms: no arithmetic on the values (a pixel outside the strip and a padded row read the zero slot)
 #pragma unroll
         for (int o8 = 0; o8 < 3; ++o8) {
-            float t0[8], t1[8], t2[8];
+            uint32_t a[8], c[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const int kk = ktab[wave * 24 + o8 * 8 + e];
-                const float v = (pv && kk >= 0) ? src[kk < 0 ? 0 : kk] : 0.f;
-                t0[e] = mn_bf16_head(v);
-                const float r1 = v - t0[e];
-                t1[e] = mn_bf16_head(r1);
-                t2[e] = r1 - t1[e];
+                const int idx = (pv && kk >= 0) ? sb + kk : zs;
+                a[e] = x01[idx];
+                c[e] = x2[idx];
             }
-            *reinterpret_cast<u32x4*>(dst + o8 * 8) = u32x4{mn_pack_bf16x2(t0[0], t0[1]), mn_pack_bf16x2(t0[2], t0[3]), mn_pack_bf16x2(t0[4], t0[5]), mn_pack_bf16x2(t0[6], t0[7])};
-            *reinterpret_cast<u32x4*>(dst + 64 * C1B_LD + o8 * 8) = u32x4{mn_pack_bf16x2(t1[0], t1[1]), mn_pack_bf16x2(t1[2], t1[3]), mn_pack_bf16x2(t1[4], t1[5]), mn_pack_bf16x2(t1[6], t1[7])};
-            *reinterpret_cast<u32x4*>(dst + 128 * C1B_LD + o8 * 8) = u32x4{mn_pack_bf16x2(t2[0], t2[1]), mn_pack_bf16x2(t2[2], t2[3]), mn_pack_bf16x2(t2[4], t2[5]), mn_pack_bf16x2(t2[6], t2[7])};
+            auto lo2 = [](uint32_t u, uint32_t v) { return (u & 0xffffu) | (v << 16); };
+            auto hi2 = [](uint32_t u, uint32_t v) { return (u >> 16) | (v & 0xffff0000u); };
+            *reinterpret_cast<u32x4*>(dst + o8 * 8) = u32x4{lo2(a[0], a[1]), lo2(a[2], a[3]), lo2(a[4], a[5]), lo2(a[6], a[7])};
+            *reinterpret_cast<u32x4*>(dst + 64 * C1B_LD + o8 * 8) = u32x4{hi2(a[0], a[1]), hi2(a[2], a[3]), hi2(a[4], a[5]), hi2(a[6], a[7])};
+            *reinterpret_cast<u32x4*>(dst + 128 * C1B_LD + o8 * 8) = u32x4{lo2(c[0], c[1]), lo2(c[2], c[3]), lo2(c[4], c[5]), lo2(c[6], c[7])};
+            MN_SCHED_FENCE();          // (one group's 16 reads in flight, not all 48: the accumulators' registers are the kernel's limit)
         }
     };
     // (one tile buffer, two blocks per CU: the other block's MFMAs fill this block's expand phase.  A double-buffered tile with one block per CU -- the next
@@ -495,8 +523,10 @@ __global__ __launch_bounds__(256, 2) void k_c1b_fwd(const C1Params p) {
             continue;
         }
         if (pix < npix) {
-            const uint32_t prow = fd_div(pix, p.fd_w);
-            const int pcol = pix - prow * p.W;
+            // element offset of the lane's first channel row at its pixel quad, below 2^31 (plan_c1); row (t, r) lies a wave-uniform (16 t + r) H W behind it.
+            // (opaque per chunk: sixteen 64-bit row addresses hoisted out of the chunk loop were spilled, and every reload waited for the previous row's stores)
+            const uint32_t HW = (uint32_t)(p.H * p.W);
+            const uint32_t e0 = mn_opaque(((uint32_t)n * p.O + m0 + kg * 4) * HW + row0 * p.W + pix);
 #pragma unroll
             for (int t = 0; t < MT; ++t)
 #pragma unroll
@@ -504,7 +534,8 @@ __global__ __launch_bounds__(256, 2) void k_c1b_fwd(const C1Params p) {
                     const int m = m0 + t * 16 + kg * 4 + r;
                     if (m < p.O) {
                         const float bb = bs[ch0 + t * 16 + kg * 4 + r];
-                        float* dst = p.y + (((int64_t)n * p.O + m) * p.H + row0 + (int)prow) * p.W + pcol;
+                        const uint32_t e = e0 + (uint32_t)(t * 16 + r) * HW;
+                        float* dst = p.y + e;
                         float4 v = make_float4(acc[0][t][r] + bb, acc[1][t][r] + bb, acc[2][t][r] + bb, acc[3][t][r] + bb);
                         if (EPI) {
                             // BatchNorm + activation on the accumulators, expression for expression k_bns_apply<0, 1> / k_qa_fwd<1, 0, 0>: codes + pass bits leave, y does not
@@ -526,7 +557,6 @@ __global__ __launch_bounds__(256, 2) void k_c1b_fwd(const C1Params p) {
                                     mk |= (pos ? (1u << q) : 0u) | ((pos && tq >= 0.f && tq <= 1.f) ? (16u << q) : 0u);
                                 }
                             }
-                            const int64_t e = (((int64_t)n * p.O + m) * p.H + row0 + (int)prow) * p.W + pcol;
                             *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(p.codes) + e) = code;
                             p.mask4[e >> 2] = (uint8_t)mk;
                             continue;
@@ -1060,6 +1090,7 @@ static int plan_c1(const mn_conv_geom* g, C1Plan* pl, int which = 0) {
     p.PR = R + g->KH - 1; p.PW = g->W + g->KW - 1 + 3;     // + 3: the 4-wide reads of the last pixel quad stay inside the row
     p.CS = p.PR * p.PW;
     p.xs_bytes = (int)(((size_t)g->C * p.CS * 4 + 64 + 15) / 16 * 16);
+    p.xt_bytes = (int)((((size_t)g->C * p.CS + 1) * 6 + 64 + 15) / 16 * 16);
     pl->lds = (size_t)p.xs_bytes + (size_t)4 * 16 * pl->MT * (C1_RSA + 32);   // forward uses the patch only
     if (pl->lds > 80 * 1024) return 0;          // two blocks per CU
     p.fd_w = make_fastdiv((uint32_t)g->W);
@@ -1095,8 +1126,13 @@ int c1_fwd_mm_count(const mn_conv_geom* g) {
 int c1_fwd(const mn_conv_geom* g, const float* x, const float* w, const float* bias, float* y, void* ws, int64_t ws_bytes, hipStream_t s) {
     return c1_fwd_act(g, x, w, bias, y, 0, nullptr, ws, ws_bytes, s);
 }
-static size_t c1b_lds_bytes(const C1Params& p) {          // patch | tile (weight rows before the loop) | k table | bias | BatchNorm constants (fused epilogue)
+// Which geometries run on k_c1b_fwd is decided on the fp32 patch's size (xs_bytes), as before the patch became term planes: a geometry keeps its kernel, and so its
+// bits.  The planes are half as large again (xt_bytes), so the largest covered strips (patch above 24 KB) leave room for one block per CU instead of two.
+static size_t c1b_fit_bytes(const C1Params& p) {
     return (size_t)p.xs_bytes + (size_t)3 * 64 * C1B_LD * 2 + C1B_KP * 4 + 64 * 4 * 4 + 64 * 4 * 16;
+}
+static size_t c1b_lds_bytes(const C1Params& p) {          // term planes | tile (weight rows before the loop) | k table | bias | BatchNorm constants (fused epilogue)
+    return c1b_fit_bytes(p) - p.xs_bytes + p.xt_bytes;
 }
 // the fused first block: act 1 = BatchNorm + sign -> int8 codes, act 2 = BatchNorm + ReLU + the next conv's a-bit DoReFa quantizer -> uint8 codes; mask4 for the backward
 int c1_fwd_bnact(const mn_conv_geom* g, const float* x, const float* w, const float* bias, const float* save, const float* gamma, const float* beta, int act, int a_bits,
@@ -1110,7 +1146,7 @@ int c1_fwd_bnact(const mn_conv_geom* g, const float* x, const float* w, const fl
     p.relu = 0; p.mm = nullptr; p.wp = w;
     p.bn_save = save; p.bn_gamma = gamma; p.bn_beta = beta; p.codes = codes; p.mask4 = mask4; p.qs = act == 2 ? dorefa_scale(a_bits) : 1.f;
     const size_t lds_b = c1b_lds_bytes(p);
-    if (lds_b > 80 * 1024) MN_FAIL(MN_ENOTSUP, "mn_conv2d_first_bnact_fwd: image strip too large for the fused kernel");
+    if (c1b_fit_bytes(p) > 80 * 1024) MN_FAIL(MN_ENOTSUP, "mn_conv2d_first_bnact_fwd: image strip too large for the fused kernel");
     mn_set_last_kernel("k_c1b_fwd<%d, %d>", pl.MT, act);
     { const double ny = (double)g->N * g->O * g->H * g->W; mn_prof_bytes(1.25 * ny + 4.0 * g->N * g->C * g->H * g->W); }
     mn_prof_begin(s);
@@ -1126,11 +1162,11 @@ int c1_fwd_bnact(const mn_conv_geom* g, const float* x, const float* w, const fl
 // whose sign is taken is bit for bit the y of c1_fwd; a geometry that forward would hand to k_c1_fwd (the strip does not fit the im2col tile's LDS) is refused
 int c1_sign_bits_supported(const mn_conv_geom* g) {
     C1Plan pl;
-    return plan_c1(g, &pl) && c1b_lds_bytes(pl.p) <= 80 * 1024;
+    return plan_c1(g, &pl) && c1b_fit_bytes(pl.p) <= 80 * 1024;
 }
 int c1_fwd_sign_bits(const mn_conv_geom* g, const float* x, const float* w, const float* bias, uint32_t* bits, hipStream_t s) {
     C1Plan pl;
-    if (!plan_c1(g, &pl) || c1b_lds_bytes(pl.p) > 80 * 1024) MN_FAIL(MN_ENOTSUP, "mn_conv2d_first_sign_bits: geometry not covered by the first-layer forward (k_c1b_fwd)");
+    if (!plan_c1(g, &pl) || c1b_fit_bytes(pl.p) > 80 * 1024) MN_FAIL(MN_ENOTSUP, "mn_conv2d_first_sign_bits: geometry not covered by the first-layer forward (k_c1b_fwd)");
     C1Params& p = pl.p;
     p.x = x; p.bias = bias; p.y = nullptr; p.gy = nullptr; p.part = nullptr; p.dbpart = nullptr; p.want_db = 0; p.da = nullptr;
     p.relu = 0; p.mm = nullptr; p.codes = nullptr; p.mask4 = nullptr; p.wp = w; p.bits = bits;
@@ -1163,13 +1199,14 @@ __global__ __launch_bounds__(64) void k_c1_codes_pack(const float* __restrict__ 
     row[0] = th;
     row[1] = make_float4(k.mean, k.invstd, k.ga, k.be);
 }
-static size_t c1b_codes_lds_bytes(const C1Params& p) {          // c1b_lds_bytes with two float4 per channel in place of one, and the two planes' strings behind them
+static size_t c1b_codes_fit_bytes(const C1Params& p) {          // c1b_fit_bytes with two float4 per channel in place of one, and the two planes' strings behind them
     return (size_t)p.xs_bytes + (size_t)3 * 64 * C1B_LD * 2 + C1B_KP * 4 + 64 * 4 * 4 + 64 * 4 * 32 + 2 * 4 * 64 * 2 * 4;
 }
+static size_t c1b_codes_lds_bytes(const C1Params& p) { return c1b_codes_fit_bytes(p) - p.xs_bytes + p.xt_bytes; }
 // k_c1b_fwd<4, 4> does not fit the register file (124 bytes of scratch per lane; <1 .. 3, 4>: none) and is not built: more than 192 output channels run as blocks of
 // 128 on <2, 4> -- the same accumulation per channel, the image strip expanded once more per extra block
 static int plan_c1_codes(const mn_conv_geom* g, C1Plan* pl) {
-    if (!plan_c1(g, pl) || c1b_codes_lds_bytes(pl->p) > 80 * 1024) return 0;
+    if (!plan_c1(g, pl) || c1b_codes_fit_bytes(pl->p) > 80 * 1024) return 0;
     if (pl->MT == 4) {
         pl->MT = 2;
         pl->cblks = (g->O + 127) / 128;
@@ -1222,7 +1259,7 @@ int c1_fwd_act(const mn_conv_geom* g, const float* x, const float* w, const floa
     p.x = x; p.bias = bias; p.y = y; p.gy = nullptr; p.part = nullptr; p.dbpart = nullptr; p.want_db = 0; p.da = nullptr;
     p.relu = relu; p.mm = mm; p.codes = nullptr; p.mask4 = nullptr;
     const size_t lds_b = c1b_lds_bytes(p);
-    if (lds_b <= 80 * 1024) {          // three-term bf16 forward (reads the weights as they are: no pack launch)
+    if (c1b_fit_bytes(p) <= 80 * 1024) {          // three-term bf16 forward (reads the weights as they are: no pack launch)
         p.wp = w;
         mn_set_last_kernel("k_c1b_fwd<%d>", pl.MT);
         mn_prof_begin(s);
