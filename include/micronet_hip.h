@@ -908,6 +908,39 @@ int mn_bitconv_supported(const mn_conv_geom* g);
 int64_t mn_bitconv_table_bytes(const mn_conv_geom* g);
 int mn_bitconv_pack(const mn_conv_geom* g, const float* w, const float* bias, const int32_t* out_order, uint32_t* table, mn_stream_t stream);
 int mn_bitconv_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t* x_bits, uint32_t* y_bits, int pool, mn_stream_t stream);
+/* The int8-MFMA form of the 1x1 hidden block: the same quartet, bits, out_order, decision, header word 0 and `pool` as mn_bitconv_*; only the contraction differs, so
+ * the output words equal mn_bitconv_fwd's word for word.  Covered (mn_bitconv_mfma_supported): 1x1, stride 1, padding 0, dilation 1, in_shuffle 0 / 1; groups == 1 with
+ * any C, or C / groups % 32 == 0 (every group starts on an input word); any O; W = 3 and W = 2 weights alike (t = sign(w), 0 where w == 0).  Everything else -- 3x3,
+ * 5x5, fewer than 32 channels per group -- is MN_ENOTSUP, as is pool == 2 (the 3x3 / 2 fold stays on mn_bitconv_fwd); a null or misaligned tensor (bits 4-byte,
+ * `table` 16-byte aligned), an invalid geometry (N <= 0, ...) or odd H / W with pool is MN_EINVAL; nothing is written in either case.
+ *   pack : the weight signs as bytes in {-1, 0, +1} in the A-operand order of v_mfma_i32_16x16x64_i8, K padded with zero bytes to a multiple of 64 -> `table` (private
+ *          layout, mn_bitconv_mfma_table_bytes bytes).  The rows of two consecutive output words are sorted by group and cut into tiles of 16 rows inside a group,
+ *          padded with dead rows (T = INT_MAX, zero weights).  The threshold is mn_bitconv_pack's T (the same search), stored as ceil((T + sum t) / 2) for the sum
+ *          P = sum b t over the activation bits b in {0, 1}: acc = 2 P - sum t.  Word 0 counts what mn_bitconv_pack's word 0 counts.
+ *   fwd  : P by MFMA -- a lane expands the bits of 16 channels of its pixel from one dword load by a multiply-and-mask bit spread; a wave owns 64 pixels (pool == 1:
+ *          the four sub-pixels of 16 pooled pixels, the window's largest P) -- output bit = P >= T'; the two words of a set are assembled on chip and stored once,
+ *          whole, without atomics; unused high bits of the last word are 0.  mn_last_kernel(): k_bitconv_mfma<0> / k_bitconv_mfma<1>. */
+int mn_bitconv_mfma_supported(const mn_conv_geom* g);
+int64_t mn_bitconv_mfma_table_bytes(const mn_conv_geom* g);
+int mn_bitconv_mfma_pack(const mn_conv_geom* g, const float* w, const float* bias, const int32_t* out_order, uint32_t* table, mn_stream_t stream);
+int mn_bitconv_mfma_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t* x_bits, uint32_t* y_bits, int pool, mn_stream_t stream);
+/* The int8-MFMA form of the 3x3 hidden block: the same quartet, bits, out_order, decision and header word 0 as mn_bitconv_*; only the contraction differs, so the
+ * output words equal mn_bitconv_fwd's word for word.  Covered (mn_bitconv_mfma3_supported): 3x3, padding 1, stride 1, in_shuffle 0 / 1; any groups with
+ * C / groups % 16 == 0 (every group starts on a half-word); any O; pool == 0.  Everything else -- 1x1, 5x5, 8 or 24 channels per group, other paddings and strides --
+ * is MN_ENOTSUP, as is pool 1 / 2 (the pooled 3x3 block stays on mn_bitconv_fwd); a null or misaligned tensor (bits 4-byte, `table` 16-byte aligned) or an invalid
+ * geometry is MN_EINVAL; nothing is written in either case.
+ *   pack : an implicit GEMM over (tap, channel): the K order is tap-major in slots of 16 channels (slot = tap * (C / groups / 16) + chunk), four slots per k-step of
+ *          v_mfma_i32_16x16x64_i8, padded with zero bytes to a multiple of four slots; the weight signs as bytes in {-1, 0, +1} -> `table` (private layout,
+ *          mn_bitconv_mfma3_table_bytes bytes: an upper bound over the spans).  The packer chooses the SPAN of consecutive output words a wave assembles at once
+ *          (2, 4, 8 or 16: the smallest with the fewest dead rows) and writes it to header word 2, the dead rows to word 5 ([1] k-steps, [4] rows).  T is
+ *          mn_bitconv_pack's, on acc itself.
+ *   fwd  : acc = sum a t by MFMA, a = +1 / -1 for a set / clear bit of a tap inside the image and 0 for a tap outside it (no border correction); output bit =
+ *          acc >= T; a wave owns 64 pixels, ORs the bits of a span into an LDS image and stores every output word once, whole, coalesced along pixels: no atomics or
+ *          read-modify-write on global memory, two runs are bit-identical.  mn_last_kernel(): k_bitconv_mfma3<0>. */
+int mn_bitconv_mfma3_supported(const mn_conv_geom* g);
+int64_t mn_bitconv_mfma3_table_bytes(const mn_conv_geom* g);
+int mn_bitconv_mfma3_pack(const mn_conv_geom* g, const float* w, const float* bias, const int32_t* out_order, uint32_t* table, mn_stream_t stream);
+int mn_bitconv_mfma3_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t* x_bits, uint32_t* y_bits, int pool, mn_stream_t stream);
 /* Max-pool on bits (max over +-1 = OR; padding contributes nothing): k in {2, 3}, stride 2, pad in {0, 1}, floor mode; bits_out is
  * [N][Cw][(H + 2 pad - k) / 2 + 1][(W + 2 pad - k) / 2 + 1]. */
 int mn_bits_maxpool(const uint32_t* bits_in, int64_t N, int64_t Cw, int64_t H, int64_t W, int k, int stride, int pad, uint32_t* bits_out, mn_stream_t stream);

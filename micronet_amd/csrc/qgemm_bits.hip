@@ -24,7 +24,8 @@
 // nine decisions) or a word-wise kernel of its own behind any other producer.
 //
 // The k-bit (DoReFa W2A2) counterpart -- activation CODES as bit planes, plane-serial popcounts, the block's BatchNorm + ReLU + quantizer as integer thresholds -- is
-// qgemm_codes.h, included at the end of this file.
+// qgemm_codes.h, included at the end of this file.  Behind it: the int8-MFMA forms of the 1x1 and the un-pooled 3x3 bit block (mn_bitconv_mfma_*, mn_bitconv_mfma3_*:
+// qgemm_bits_mfma.h, qgemm_bits_mfma3.h) -- same bits, order, decision and header word 0, only the contraction differs.
 #include "qgemm_dev.h"
 
 namespace mn_bits {
@@ -49,7 +50,9 @@ static inline int span_words(int C, int groups) {
     return nw;
 }
 
-static inline bool make_geom(const mn_conv_geom* g, Geom& q) {
+// popc == false: the geometry alone, for the MFMA forms (qgemm_bits_mfma.h, qgemm_bits_mfma3.h) -- without the bounds that belong to the popcount rows (the words a
+// row spans, the tiled layout, the row stride), which those forms do not have.
+static inline bool make_geom(const mn_conv_geom* g, Geom& q, bool popc = true) {
     if (!g || g->N <= 0 || g->C <= 0 || g->H <= 0 || g->W <= 0 || g->O <= 0 || g->groups <= 0) return false;
     if (g->KH != g->KW || (g->KH != 1 && g->KH != 3 && g->KH != 5)) return false;
     const int pad = (g->KH - 1) / 2;
@@ -61,6 +64,10 @@ static inline bool make_geom(const mn_conv_geom* g, Geom& q) {
     q.K = q.Cg * q.taps;
     q.Cw = (g->C + 31) >> 5; q.OW = (g->O + 31) >> 5;
     q.NW = span_words(g->C, g->groups);
+    if (!popc) {
+        q.tiled = 0; q.stride = 0;
+        return (int64_t)g->N * (q.Cw > q.OW ? q.Cw : q.OW) * g->H * g->W < (1ll << 31);
+    }
     if (q.NW > (g->KH == 1 ? 64 : 8)) return false;
     q.tiled = g->KH > 1 && g->groups == 1 && q.Cw > 1 && q.Cw <= TILE_MAXW;
     if (g->KH == 5 && !(g->groups == 1 && q.Cw <= TILE_MAXW)) return false;          // 5x5: the tiled kernel only (dense, C <= 256)
@@ -123,6 +130,20 @@ __device__ __forceinline__ int block_reduce(int v, int op, int* sh) {      // op
     }
     return sh[0];
 }
+
+// The decision of the byte kernels, !(fl(fl(acc * alpha) + b) < 0), EVALUATED for every accumulator value acc in [-K, K] a row can produce -- the one copy of the
+// search (k_bits_wpack, and the packs of the MFMA forms in qgemm_bits_mfma.h / qgemm_bits_mfma3.h).  Thread `tid` of `nt` takes acc = -K + tid, -K + tid + nt, ...;
+// the caller combines tmin (min) and cnt (sum) over its threads and reads the threshold off the pair.
+__device__ __forceinline__ void decision_scan(int K, float alpha, float b, int tid, int nt, int& tmin, int& cnt) {
+    tmin = INT_MAX; cnt = 0;
+    for (int acc = -K + tid; acc <= K; acc += nt) {
+        const float p = (float)acc * alpha;
+        const float yv = p + b;
+        if (!(yv < 0.f)) { cnt++; if (acc < tmin) tmin = acc; }
+    }
+}
+__device__ __forceinline__ bool decision_monotone(int K, int tmin, int cnt) { return cnt == 0 || cnt == K - tmin + 1; }          // (alpha < 0 cannot come out of max|w|)
+__device__ __forceinline__ int decision_threshold(int K, int tmin, int cnt) { return cnt == 0 ? K + 1 : tmin; }                 // K + 1: never
 
 // one block per table row
 __global__ __launch_bounds__(256) void k_bits_wpack(Geom q, const float* __restrict__ w, const float* __restrict__ bias, const int32_t* __restrict__ order,
@@ -192,17 +213,13 @@ __global__ __launch_bounds__(256) void k_bits_wpack(Geom q, const float* __restr
     }
     // the decision of the byte kernels, evaluated for every accumulator value the row can produce
     const float b = bias ? bias[o] : 0.f;
-    int tmin = INT_MAX, cnt = 0;
-    for (int acc = -q.K + tid; acc <= q.K; acc += 256) {
-        const float p = (float)acc * alpha;
-        const float yv = p + b;
-        if (!(yv < 0.f)) { cnt++; if (acc < tmin) tmin = acc; }
-    }
+    int tmin, cnt;
+    decision_scan(q.K, alpha, b, tid, 256, tmin, cnt);
     tmin = block_reduce(tmin, 1, sh);
     cnt = block_reduce(cnt, 0, sh);
     if (tid == 0) {
-        if (cnt != 0 && cnt != q.K - tmin + 1) atomicAdd(tab + 0, 1u);          // not monotone in acc (alpha < 0 cannot come out of max|w|)
-        row[0] = (uint32_t)(cnt == 0 ? q.K + 1 : tmin);
+        if (!decision_monotone(q.K, tmin, cnt)) atomicAdd(tab + 0, 1u);          // not monotone in acc
+        row[0] = (uint32_t)decision_threshold(q.K, tmin, cnt);
         row[1] = (uint32_t)w0;
         row[2] = (uint32_t)nz;
         row[3] = 0u;
@@ -732,3 +749,5 @@ extern "C" int mn_bits_maxpool(const uint32_t* bits_in, int64_t N, int64_t Cw, i
 #include "qgemm_codes.h"          // mn_codes_* / mn_codeconv_*: the code-packed deployment of the k-bit blocks
 #include "qgemm_codes_mfma.h"     // mn_codeconv_mfma_*: the int8-MFMA form of the 1x1 hidden code blocks
 #include "qgemm_codes_mfma3.h"    // mn_codeconv_mfma3_*: the int8-MFMA form of the 3x3 hidden code blocks
+#include "qgemm_bits_mfma.h"      // mn_bitconv_mfma_*: the int8-MFMA form of the 1x1 hidden bit blocks
+#include "qgemm_bits_mfma3.h"     // mn_bitconv_mfma3_*: the int8-MFMA form of the 3x3 hidden bit blocks

@@ -61,16 +61,20 @@ static inline bool make_m3geom(const mn_conv_geom* g, int a_in, int w_bits, int 
 }
 static inline int64_t table_words(const M3Geom& m) { return (int64_t)m.tiles_off + m.max_tiles * m.tstride; }
 
-// the channel at output position jj: -1 for a position past O or a bad out_order entry
-__device__ __forceinline__ int chan_at(const Geom& q, const int32_t* order, int jj) {
+// the channel at output position jj: -1 for a position past O or a bad out_order entry (G: mn_codes::Geom, or mn_bits::Geom for qgemm_bits_mfma3.h)
+template <class G>
+__device__ __forceinline__ int chan_at(const G& q, const int32_t* order, int jj) {
     const int o = jj < q.O ? (order ? order[jj] : jj) : -1;
     return (o >= 0 && o < q.O) ? o : -1;
 }
 
 // ---------------------------------------------------------------- the span, the header and the slot words: one block
-__global__ __launch_bounds__(256) void k_codes_mfma3_plan(M3Geom m, const int32_t* __restrict__ order, uint32_t* __restrict__ tab) {
+// (MG: M3Geom, or the 1-bit form's geometry of qgemm_bits_mfma3.h, which shares the planner: `word6` is what header word 6 carries, `badword` the header word that counts
+// the bad out_order entries)
+template <class MG>
+__global__ __launch_bounds__(256) void k_codes_mfma3_plan(MG m, const int32_t* __restrict__ order, uint32_t* __restrict__ tab, uint32_t word6, int badword) {
     __shared__ int s_dead[4], s_bad;
-    const Geom& q = m.q;
+    const auto& q = m.q;
     const int tid = threadIdx.x;
     if (tid < 4) s_dead[tid] = 0;
     if (tid == 0) s_bad = 0;
@@ -101,8 +105,8 @@ __global__ __launch_bounds__(256) void k_codes_mfma3_plan(M3Geom m, const int32_
         for (int c = 1; c < 4; ++c)
             if (s_dead[c] < s_dead[best]) best = c;
         tab[1] = (uint32_t)m.nsteps; tab[2] = (uint32_t)(2 << best); tab[3] = (uint32_t)m.tstride; tab[4] = (uint32_t)(q.OW * 32); tab[5] = (uint32_t)s_dead[best];
-        tab[6] = (uint32_t)(mn_codes::A | (mn_codes::WB << 8) | (2 << 16));
-        if (s_bad) atomicAdd(tab + 7, (uint32_t)s_bad);
+        tab[6] = word6;
+        if (s_bad) atomicAdd(tab + badword, (uint32_t)s_bad);
     }
 }
 
@@ -342,7 +346,8 @@ extern "C" int mn_codeconv_mfma3_pack(const mn_conv_geom* g, const float* w, con
         MN_FAIL(MN_EINVAL, "mn_codeconv_mfma3_pack: null / unaligned argument (the table is 16-byte aligned) or invalid geometry");
     if (!mn_codes_mfma3::make_m3geom(g, a_bits_in, w_bits, a_bits_out, m)) MN_FAIL(MN_ENOTSUP, "mn_codeconv_mfma3_pack: " MN_CODEMFMA3_COVER);
     if (hipMemsetAsync(table, 0, 4 * mn_codes_mfma3::HDR, (hipStream_t)stream) != hipSuccess) MN_FAIL(MN_EHIP, "mn_codeconv_mfma3_pack: header reset failed");          // the two counters
-    hipLaunchKernelGGL(mn_codes_mfma3::k_codes_mfma3_plan, dim3(1), dim3(256), 0, (hipStream_t)stream, m, out_order, table);
+    hipLaunchKernelGGL((mn_codes_mfma3::k_codes_mfma3_plan<mn_codes_mfma3::M3Geom>), dim3(1), dim3(256), 0, (hipStream_t)stream, m, out_order, table,
+                       (uint32_t)(mn_codes::A | (mn_codes::WB << 8) | (2 << 16)), 7);
     mn_set_last_kernel("k_codes_mfma3_wpack");
     hipLaunchKernelGGL(mn_codes_mfma3::k_codes_mfma3_wpack, dim3((m.q.OW + 1) >> 1), dim3(256), 0, (hipStream_t)stream, m, w, chan, out_order, table);
     MN_CHECK_LAUNCH("mn_codeconv_mfma3_pack");

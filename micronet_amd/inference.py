@@ -211,6 +211,16 @@ def _pool_kind(m):
     return ksp if ksp in ((2, 2, 0), (3, 2, 1)) else None
 
 
+def _bitconv_mfma_kernel_name(fold):
+    """The kernel mn_bitconv_mfma_fwd reports for a 1x1 hidden block (csrc/qgemm_bits_mfma.h); fold: 0 or 1."""
+    return "k_bitconv_mfma<%d>" % fold
+
+
+def _bitconv_mfma3_kernel_name():
+    """The kernel mn_bitconv_mfma3_fwd reports for a 3x3 hidden block (csrc/qgemm_bits_mfma3.h)."""
+    return "k_bitconv_mfma3<0>"
+
+
 def _conv_kernel_name(k, cin, groups, fold):
     """The kernel mn_bitconv_fwd launches for a hidden block (csrc/qgemm_bits.hip: the dispatch at the end of the file); fold: 0, 1 (2x2 / 2) or 2 (3x3 / 2 / 1)."""
     cw, cg = (cin + 31) // 32, cin // groups
@@ -311,11 +321,12 @@ class BitPlan(nn.Module):
             st = ops._s()
             ops._call("mn_bits_pack_sign8", ops._p(codes), N, Cc, H * W, ops._p(bufs[0]), st)
         for i, L in enumerate(self.layers):
+            fwd = "mn_bitconv_mfma_fwd" if L.get("mfma") else "mn_bitconv_mfma3_fwd" if L.get("mfma3") else "mn_bitconv_fwd"
             if mids[i] is None:
-                ops._call("mn_bitconv_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(bufs[i + 1]), int(L["pool"]), st)
+                ops._call(fwd, C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(bufs[i + 1]), int(L["pool"]), st)
             else:          # a pool the block cannot fold: the block at full size, then the word-wise OR
                 m, (pk, ps, pp) = mids[i], L["pool_ksp"]
-                ops._call("mn_bitconv_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(m), 0, st)
+                ops._call(fwd, C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(m), 0, st)
                 ops._call("mn_bits_maxpool", ops._p(m), m.shape[0], m.shape[1], m.shape[2], m.shape[3], pk, ps, pp, ops._p(bufs[i + 1]), st)
         if self.keep_stages:
             self.stage_bits = [b.clone() for b in bufs]
@@ -363,8 +374,10 @@ def _check_bit_ends(first, nm_first, last, nm_last):
         raise _err("wbwtab_compile_bits(bit_ends=True): %s: a channel shuffle in front of the last conv is not covered by mn_bitsconv1x1_small_fwd" % nm_last)
 
 
-def _walk_bits(model, bit_ends=False):
-    """The graph walk of ``wbwtab_compile_bits`` (no GPU needed): (first, layers, last, tail, flatten, report)."""
+def _walk_bits(model, bit_ends=False, mfma_blocks=False, mfma_k3=False):
+    """The graph walk of ``wbwtab_compile_bits`` (no GPU needed): (first, layers, last, tail, flatten, report).  ``mfma_blocks``: a hidden block
+    ``mn_bitconv_mfma_supported`` covers, whose fold is 0 or 1, runs on the MFMA form (``layer["mfma"]``); ``mfma_k3``: a hidden 3x3 block ``mn_bitconv_mfma3_supported``
+    covers, with no folded pool, runs on the 3x3 MFMA form (``layer["mfma3"]``).  Neither refuses anything: a block they do not cover keeps its kernel."""
     import ctypes as C
     from micronet_amd import _lib
     from micronet_amd.nn import Conv2dFirst
@@ -438,6 +451,10 @@ def _walk_bits(model, bit_ends=False):
                 raise _err("wbwtab_compile_bits: %s: a channel shuffle directly behind the first block is not covered (its producer is not a bit block)" % nm)
             layers[-1]["shuffle"] = shuffle          # folded into the producer's row order
         layers.append(dict(name=nm, conv=conv, k=k, pad=pad, cin=conv.in_channels, cout=conv.out_channels, groups=conv.groups, pool=0, pool_ksp=None, shuffle=0, stage=name))
+        if mfma_blocks:
+            layers[-1]["mfma"] = bool(_lib.get_lib().mn_bitconv_mfma_supported(C.byref(g)))
+        if mfma_k3:
+            layers[-1]["mfma3"] = bool(_lib.get_lib().mn_bitconv_mfma3_supported(C.byref(g)))
     if first is None or last is None:
         raise _err("wbwtab_compile_bits: module order not recognised (no %s conv block found)" % ("first" if first is None else "last"))
     rep_last = report.pop()
@@ -445,7 +462,16 @@ def _walk_bits(model, bit_ends=False):
         _check_bit_ends(first, report[0]["name"], last, rep_last["name"])
         report[0]["kernel"], rep_last["kernel"] = "first conv -> bits (k_c1b_fwd)", "last conv on bits (k_bitsconv1x1_small)"
     for L in layers:
+        # (known only now: the walk folds a pool into the layer after it has passed the block)
+        if mfma_blocks and L["pool"] == 2:          # the 3x3 / 2 fold stays on k_bitconv1_pool3
+            L["mfma"] = False
+        if mfma_k3 and L["pool"]:                   # the pooled 3x3 block stays on k_bitconv<3,*,1>
+            L["mfma3"] = False
         kern = _conv_kernel_name(L["k"], L["cin"], L["groups"], L["pool"])
+        if L.get("mfma"):
+            kern = _bitconv_mfma_kernel_name(L["pool"])
+        if L.get("mfma3"):
+            kern = _bitconv_mfma3_kernel_name()
         pooled = bool(L["pool"])
         if L["pool"] == 2:
             pooled = "folded 3x3/2"
@@ -457,22 +483,28 @@ def _walk_bits(model, bit_ends=False):
     return first, layers, last, tail, flatten, report
 
 
-def wbwtab_bits_report(model, bit_ends=False):
-    """The ``report`` ``wbwtab_compile_bits(model, bit_ends)`` would carry -- one row per stage: kernel, K, words, how a max-pool behind it is done -- from the graph walk
-    alone: no GPU, nothing packed.  Raises like ``wbwtab_compile_bits`` for whatever the bit kernels do not cover."""
-    return _walk_bits(model, bit_ends)[5]
+def wbwtab_bits_report(model, bit_ends=False, mfma_blocks=False, mfma_k3=False):
+    """The ``report`` ``wbwtab_compile_bits(model, bit_ends, mfma_blocks, mfma_k3)`` would carry -- one row per stage: kernel, K, words, how a max-pool behind it is
+    done -- from the graph walk alone: no GPU, nothing packed.  Raises like ``wbwtab_compile_bits`` for whatever the bit kernels do not cover.  Under ``mfma_blocks`` /
+    ``mfma_k3`` the ``kernel`` of a block on an MFMA form reads ``k_bitconv_mfma<0|1>`` / ``k_bitconv_mfma3<0>``; nothing else in its row changes."""
+    return _walk_bits(model, bit_ends, mfma_blocks, mfma_k3)[5]
 
 
 @torch.no_grad()
-def wbwtab_compile_bits(model, bit_ends=False):
+def wbwtab_compile_bits(model, bit_ends=False, mfma_blocks=False, mfma_k3=False):
     """``model``: the result of ``wbwtab_model_bn_fuse`` on a pre-quantised W in (2, 3), A = 2 net, on the GPU (the reference's ``nin`` and ``nin_gc``).  Returns a ``BitPlan``
     computing the same function with one bit per hidden activation; ``.report`` lists the stages.  Anything the bit kernels do not cover raises ``MicronetHipError``
     naming the layer -- never a silent byte path (the caller still has ``model``).  ``bit_ends=True``: the first conv writes the first stage's bits in one launch and the
     classifier reads the last stage's bits -- no fp32 map, no int8 codes, no pack / unpack launch; same bits in every stage, same logits (off by default until the gain
-    is measured)."""
+    is measured).  ``mfma_blocks=True``: a 1x1 hidden block ``mn_bitconv_mfma_supported`` covers (dense, or whole input words per group; the folded 2x2 pool
+    included) is packed and run in its int8-MFMA form (``mn_bitconv_mfma_*``: same bits, thresholds and order, only the contraction differs); a block with the
+    3x3 / 2 fold or fewer than 32 channels per group keeps its kernel.  ``mfma_k3=True``: a 3x3 / padding 1 hidden block ``mn_bitconv_mfma3_supported`` covers
+    (C / groups % 16 == 0) with no folded pool is packed and run in its int8-MFMA form (``mn_bitconv_mfma3_*``); a pooled 3x3 block keeps ``k_bitconv``, one whose pool
+    runs as ``mn_bits_maxpool`` behind it still moves.  Neither flag refuses anything, both compose with ``bit_ends``; the layer dicts gain the keys ``"mfma"`` /
+    ``"mfma3"`` under their flag only.  Off by default; with them off nothing changes."""
     import ctypes as C
     from micronet_amd import _lib, ops
-    first, layers, last, tail, flatten, report = _walk_bits(model, bit_ends)
+    first, layers, last, tail, flatten, report = _walk_bits(model, bit_ends, mfma_blocks, mfma_k3)
     for p_ in model.parameters():
         if not p_.is_cuda:
             raise _err("wbwtab_compile_bits: the model is on %s: micronet_amd runs on MI355X only (no CPU fallback)" % p_.device)
@@ -482,14 +514,15 @@ def wbwtab_compile_bits(model, bit_ends=False):
         conv = L.pop("conv")
         k, p = L["k"], L["pad"]
         g = _lib.ConvGeom(1, L["cin"], 4, 4, L["cout"], k, k, 1, 1, p, p, 1, 1, L["groups"], 0)
-        table = torch.empty(int(lib.mn_bitconv_table_bytes(C.byref(g))) // 4, dtype=torch.int32, device=conv.weight.device)
+        quartet = "mn_bitconv_mfma" if L.get("mfma") else "mn_bitconv_mfma3" if L.get("mfma3") else "mn_bitconv"
+        table = torch.empty(int(getattr(lib, quartet + "_table_bytes")(C.byref(g))) // 4, dtype=torch.int32, device=conv.weight.device)
         order = None
         if L["shuffle"] > 1:          # position j of the consumer's shuffled input is this layer's channel (j % s) * (C / s) + j // s (models/nin_gc.py:4-15)
             j = torch.arange(L["cout"], device=conv.weight.device)
             order = ((j % L["shuffle"]) * (L["cout"] // L["shuffle"]) + j // L["shuffle"]).to(torch.int32).contiguous()
         w = conv.weight.detach().float().contiguous()
         b = conv.bias.detach().float().contiguous() if conv.bias is not None else None
-        ops._call("mn_bitconv_pack", C.byref(g), ops._p(w), ops._p(b), ops._p(order), ops._p(table), ops._s())
+        ops._call(quartet + "_pack", C.byref(g), ops._p(w), ops._p(b), ops._p(order), ops._p(table), ops._s())
         L["table"], L["out_order"] = table, order
     bad = [(L["name"], int(L["table"][0])) for L in layers]          # (compile time: the one place a host read-back is allowed)
     for nm, nbad in bad:

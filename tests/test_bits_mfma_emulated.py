@@ -1,0 +1,29 @@
+"""The int8-MFMA form of the 1x1 hidden bit block (csrc/qgemm_bits_mfma.h: k_bitconv_mfma) compiled for the CPU SIMT emulator, through the real C ABI; the same
+checks run on the MI355X in tests/test_gpu_bits_mfma.py.  All comparisons are exact (tests/bits_mfma_cases.py)."""
+import pytest
+
+import abi_driver
+import bits_mfma_cases as MC
+
+
+@pytest.fixture(scope="module")
+def be():
+    return abi_driver.Backend("emu")
+
+
+@pytest.mark.parametrize("case", range(len(MC.BLOCKS)), ids=[c[0] for c in MC.BLOCKS])
+def test_bitconv_mfma_block(be, case):
+    MC.check_block(be, case)
+
+
+@pytest.mark.parametrize("case", range(len(MC.REFUSED)))
+def test_bitconv_mfma_refused_is_enotsup(be, case):
+    MC.check_refused(be, case)
+
+
+def test_bitconv_mfma_invalid_is_einval(be):
+    MC.check_invalid(be)
+
+
+def test_bitconv_mfma_table_counters(be):
+    MC.check_counters(be)
