@@ -985,7 +985,8 @@ int mn_codeconv_tile_pack(const mn_conv_geom* g, const float* w, const float* ch
                           mn_stream_t stream);
 int mn_codeconv_tile_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t* in_planes, uint32_t* out_planes, mn_stream_t stream);
 /* The int8-MFMA form of the 1x1 hidden block: the same quartet, planes, header words 0 / 6 / 7, thresholds, out_order and `pool` as mn_codeconv_*; only the
- * contraction differs, so the output planes equal mn_codeconv_fwd's word for word.  Covered (mn_codeconv_mfma_supported): a_bits_in = w_bits = a_bits_out = 2; 1x1,
+ * contraction differs, so the output planes equal mn_codeconv_fwd's word for word.  Covered (mn_codeconv_mfma_supported): a_bits_in = w_bits = a_bits_out = 2 (and
+ * 4: see mn_codeconv_mfma_fwd_bits); 1x1,
  * stride 1, padding 0, dilation 1, g->in_shuffle 0 / 1; groups == 1 with any C, or groups > 1 with C / groups % 32 == 0 (every group starts on an input word); any O
  * and any O / groups; K * 9 <= 32767.  Everything else -- 3x3 and 5x5, which keep their kernels, and a grouped block of fewer than 32 channels per group, which stays
  * on mn_codeconv_*, included -- is MN_ENOTSUP, as is pool outside 0 / 1; a null or misaligned tensor (planes 4-byte, `table` 16-byte aligned), an invalid geometry
@@ -1002,8 +1003,18 @@ int64_t mn_codeconv_mfma_table_bytes(const mn_conv_geom* g, int a_bits_in, int w
 int mn_codeconv_mfma_pack(const mn_conv_geom* g, const float* w, const float* chan, int a_bits_in, int w_bits, int a_bits_out, const int32_t* out_order, uint32_t* table,
                           mn_stream_t stream);
 int mn_codeconv_mfma_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t* in_planes, uint32_t* out_planes, int pool, mn_stream_t stream);
+/* The same forward with the width spelled out: the quartet above is also instantiated for 4-bit codes and weights.  Covered (mn_codeconv_mfma_supported, which the
+ * other three entry points follow): (a_bits_in, w_bits, a_bits_out) = (2, 2, 2) as above, or (4, 4, 4) -- codes 0 .. 15 in four planes per word group, weights on the
+ * grid (2k - 15) / 15 as signed bytes 2k - 15, fifteen sorted thresholds per row, header word 6 = 4 | 4 << 8 | 4 << 16 -- with the same geometry and the same K
+ * bound, K * 15 * 15 <= 32767: dense C <= 145, or C / groups in {32, 64, 96, 128}.  Every other or mixed width is MN_ENOTSUP.  At 4 bits the code is found by a
+ * four-step binary search over the row's sorted thresholds, every lane group of the pooled form stores two words per set, and there is no popcount kernel to compare
+ * against: the judge is mn_qa_fwd(a_bits = 4) on the integer accumulator.  mn_codeconv_mfma_fwd is the (2, 2, 2) call of this; mn_last_kernel() reads
+ * k_codeconv_mfma<pool> at either width. */
+int mn_codeconv_mfma_fwd_bits(const mn_conv_geom* g, int a_bits_in, int w_bits, int a_bits_out, const uint32_t* table, const uint32_t* in_planes, uint32_t* out_planes,
+                              int pool, mn_stream_t stream);
 /* The int8-MFMA form of the 3x3 hidden block: the same quartet, planes, header words 0 / 6 / 7, thresholds and out_order as mn_codeconv_*; only the contraction
- * differs, so the output planes equal mn_codeconv_fwd's word for word.  Covered (mn_codeconv_mfma3_supported): a_bits_in = w_bits = a_bits_out = 2; 3x3, padding 1,
+ * differs, so the output planes equal mn_codeconv_fwd's word for word.  Covered (mn_codeconv_mfma3_supported): a_bits_in = w_bits = a_bits_out = 2 (and 4: see
+ * mn_codeconv_mfma3_fwd_bits); 3x3, padding 1,
  * stride 1, dilation 1, g->in_shuffle 0 / 1; any groups with C / groups % 16 == 0 (every group starts on a half-word); any O and any O / groups; K * 9 <= 32767 (at
  * most 400 channels per group); pool == 0.  Everything else -- 1x1 and 5x5, which keep their kernels, other paddings and strides, 8 or 24 channels per group, pool
  * == 1 (the pooled 3x3 block stays on mn_codeconv_*) included -- is MN_ENOTSUP; a null or misaligned tensor (planes 4-byte, `table` 16-byte aligned) or an invalid
@@ -1022,6 +1033,12 @@ int64_t mn_codeconv_mfma3_table_bytes(const mn_conv_geom* g, int a_bits_in, int 
 int mn_codeconv_mfma3_pack(const mn_conv_geom* g, const float* w, const float* chan, int a_bits_in, int w_bits, int a_bits_out, const int32_t* out_order, uint32_t* table,
                            mn_stream_t stream);
 int mn_codeconv_mfma3_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t* in_planes, uint32_t* out_planes, int pool, mn_stream_t stream);
+/* The same forward with the width spelled out.  Covered (mn_codeconv_mfma3_supported): (2, 2, 2) as above, or (4, 4, 4) with C / groups == 16 (K = 144:
+ * 144 * 15 * 15 = 32400 <= 32767; 32 channels per group are beyond the bound); every other or mixed width is MN_ENOTSUP.  At 4 bits the LDS image holds four planes
+ * per word, so the packer chooses the span among 2, 4, 8 only (the image stays 32 KB per block); weights, thresholds, header word 6 and the binary search are those of
+ * mn_codeconv_mfma_fwd_bits.  mn_codeconv_mfma3_fwd is the (2, 2, 2) call of this; mn_last_kernel() reads k_codeconv_mfma3<0> at either width. */
+int mn_codeconv_mfma3_fwd_bits(const mn_conv_geom* g, int a_bits_in, int w_bits, int a_bits_out, const uint32_t* table, const uint32_t* in_planes, uint32_t* out_planes,
+                               int pool, mn_stream_t stream);
 /* Max-pool on code planes [N][Cw][a_bits][H][W] -> [N][Cw][a_bits][(H + 2 pad - k) / 2 + 1][(W + 2 pad - k) / 2 + 1] (floor mode): the bit-sliced maximum of the
  * window's codes, most significant plane first; taps outside the image contribute code 0 (the pool sits behind a ReLU).  (k, stride, pad) in {(2, 2, 0), (3, 2, 1)},
  * 1 <= a_bits <= 8; anything else, or a tensor of 2^31 words or more: MN_ENOTSUP.  Null / misaligned / empty tensor, or an image smaller than the window: MN_EINVAL.

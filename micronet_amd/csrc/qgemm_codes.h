@@ -19,6 +19,7 @@
 // block of plain nin on an LDS-resident tile (mn_codeconv_tile_*) and the 2x2 / 2 and 3x3 / 2 / 1 max-pools on planes (mn_codes_maxpool).  The 1x1 block, dense or with
 // whole input words per group, also has an int8-MFMA form with the same planes, thresholds and bits (mn_codeconv_mfma_*: qgemm_codes_mfma.h).
 // The un-pooled 3x3 block with C / groups % 16 == 0 has one too, an implicit GEMM over (tap, channel) (mn_codeconv_mfma3_*: qgemm_codes_mfma3.h).
+// The two MFMA forms, and only they, are also instantiated for a_in = w_bits = a_out = 4 (make_geom's `wide`); everything in this file is the 2-bit instantiation.
 #pragma once
 #include "qa_thresholds.h"
 
@@ -33,10 +34,12 @@ struct Geom {
 };
 
 // tile: the geometry of the LDS-tiled dense block (mn_codeconv_tile_*: 5x5 / padding 2, groups 1) instead of that of mn_codeconv_* (1x1, 3x3 / padding 1); the table
-// layout, the K bound and everything k_codes_wpack reads are the same.
-static inline bool make_geom(const mn_conv_geom* g, int a_in, int w_bits, int a_out, Geom& q, bool tile = false) {
+// layout, the K bound and everything k_codes_wpack reads are the same.  wide: the caller is one of the two int8-MFMA geometries (qgemm_codes_mfma.h, qgemm_codes_mfma3.h),
+// whose kernels are also instantiated for 4-bit codes and weights: (4, 4, 4) is admitted beside (2, 2, 2); the popcount kernels never pass it.
+static inline bool make_geom(const mn_conv_geom* g, int a_in, int w_bits, int a_out, Geom& q, bool tile = false, bool wide = false) {
     if (!g || g->N <= 0 || g->C <= 0 || g->H <= 0 || g->W <= 0 || g->O <= 0 || g->groups <= 0) return false;
-    if (a_in != A || w_bits != WB || a_out != 2) return false;          // (3- and 4-bit codes: not instantiated)
+    const bool four = wide && !tile && a_in == 4 && w_bits == 4 && a_out == 4;
+    if (!four && (a_in != A || w_bits != WB || a_out != 2)) return false;          // (3-bit and mixed widths: not instantiated)
     if (g->KH != g->KW || (tile ? (g->KH != 5 || g->groups != 1) : (g->KH != 1 && g->KH != 3))) return false;
     const int pad = (g->KH - 1) / 2;
     if (g->stride_h != 1 || g->stride_w != 1 || g->dil_h != 1 || g->dil_w != 1 || g->pad_h != pad || g->pad_w != pad) return false;
@@ -49,7 +52,7 @@ static inline bool make_geom(const mn_conv_geom* g, int a_in, int w_bits, int a_
     q.NW = mn_bits::span_words(g->C, g->groups);
     q.stride = ROWHDR + q.taps * q.NW * WB + q.NW;
     q.s = dorefa_scale(a_out);
-    const int64_t words = (int64_t)g->N * A * (q.Cw > q.OW ? q.Cw : q.OW) * g->H * g->W;
+    const int64_t words = (int64_t)g->N * a_in * (q.Cw > q.OW ? q.Cw : q.OW) * g->H * g->W;
     if (words >= (1ll << 31) || (int64_t)q.OW * 32 * q.stride >= (1ll << 30)) return false;
     return true;
 }

@@ -532,7 +532,8 @@ def wbwtab_compile_bits(model, bit_ends=False, mfma_blocks=False, mfma_k3=False)
 
 
 # ------------------------------------------------------------------------------------------------ code-packed deployment of DoReFa W2A2 nets (csrc/qgemm_codes.h)
-CODE_BITS = 2          # the one instantiation: a_bits = w_bits = 2
+CODE_BITS = 2          # the width every kernel is instantiated for: a_bits = w_bits = 2
+CODE_WIDTHS = (2, 4)   # ... and the widths of a whole net: W2A2, or W4A4 on the two int8-MFMA blocks alone (csrc/qgemm_codes_mfma.h, csrc/qgemm_codes_mfma3.h)
 
 
 def pack_codes(t, bits=None):
@@ -593,12 +594,17 @@ class CodePlan(nn.Module):
     behind its block) -> plane unpack -> last block and tail (the model's own modules).  Eval only; owns the packed weight tables (and the
     per-channel constants they were packed from: ``layers[i]["chan"]``) and one set of plane buffers per input shape.  ``code_ends``: the first conv's kernel writes
     the first stage's planes itself (no fp32 map, no byte codes, no pack; ``first_table`` holds its per-channel thresholds) and the last conv reads the last stage's
-    planes (no unpack, no uint8 buffer); what follows the last conv inside its block, and the tail, run unchanged."""
+    planes (no unpack, no uint8 buffer); what follows the last conv inside its block, and the tail, run unchanged.  ``bits``: the net's code width, 2 or 4 --
+    planes per word group in every buffer, the width of pack / unpack and of the codes handed to the last block; a 4-bit plan holds MFMA blocks only and no
+    ``code_ends``."""
 
-    def __init__(self, first, layers, last, tail, flatten, report, code_ends=False, first_table=None, first_chan=None):
+    def __init__(self, first, layers, last, tail, flatten, report, code_ends=False, first_table=None, first_chan=None, bits=2):
         super().__init__()
         self.first, self.last, self.tail = first, last, nn.ModuleList(tail)
         self.code_ends = bool(code_ends)
+        self.bits = int(bits)
+        if self.bits not in CODE_WIDTHS or (self.bits != CODE_BITS and (self.code_ends or not all(L.get("mfma") or L.get("mfma3") for L in layers))):
+            raise _err("dorefa_compile_codes: a %d-bit plan is not covered (2-bit codes, or 4-bit codes on the int8-MFMA blocks alone and without code_ends)" % self.bits)
         self.first_table, self.first_chan = first_table, first_chan
         self.layers = layers              # dicts: geometry, table, chan, pool, out_order
         self.flatten = flatten
@@ -619,6 +625,7 @@ class CodePlan(nn.Module):
         key = (tuple(shape), str(device))
         if key not in self._ws:
             N, Cc, H, W = shape
+            B = self.bits
             g0 = None
             if self.code_ends:
                 import ctypes as C
@@ -630,7 +637,7 @@ class CodePlan(nn.Module):
                                "the image strip in LDS)" % (self.report[0]["name"], N, conv.in_channels, H, W))
             elif (H * W) % 4:
                 raise _err("dorefa_compile_codes: %s: its %d x %d output cannot be packed (mn_codes_pack_planes needs H * W %% 4 == 0)" % (self.report[0]["name"], H, W))
-            bufs, geoms, mids = [torch.empty((N, (Cc + 31) // 32, CODE_BITS, H, W), dtype=torch.int32, device=device)], [], []
+            bufs, geoms, mids = [torch.empty((N, (Cc + 31) // 32, B, H, W), dtype=torch.int32, device=device)], [], []
             for L in self.layers:
                 k, p = L["k"], L["pad"]
                 geoms.append(_lib.ConvGeom(N, L["cin"], H, W, L["cout"], k, k, 1, 1, p, p, 1, 1, L["groups"], 0))
@@ -642,11 +649,11 @@ class CodePlan(nn.Module):
                 if ksp:
                     if min(H, W) + 2 * ksp[2] < ksp[0]:
                         raise _err("dorefa_compile_codes: %s: the max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
-                    mids.append(torch.empty((N, (L["cout"] + 31) // 32, CODE_BITS, H, W), dtype=torch.int32, device=device))
+                    mids.append(torch.empty((N, (L["cout"] + 31) // 32, B, H, W), dtype=torch.int32, device=device))
                     H, W = (H + 2 * ksp[2] - ksp[0]) // ksp[1] + 1, (W + 2 * ksp[2] - ksp[0]) // ksp[1] + 1
                 else:
                     mids.append(None)
-                bufs.append(torch.empty((N, (L["cout"] + 31) // 32, CODE_BITS, H, W), dtype=torch.int32, device=device))
+                bufs.append(torch.empty((N, (L["cout"] + 31) // 32, B, H, W), dtype=torch.int32, device=device))
                 Cc = L["cout"]
             if self.code_ends:
                 if not _lib.get_lib().mn_planesconv1x1_small_supported(Cc, H * W, self.last.conv.out_channels, CODE_BITS):
@@ -664,19 +671,20 @@ class CodePlan(nn.Module):
         """One launch per hidden block (two where a max-pool runs on the planes behind it)."""
         import ctypes as C
         from micronet_amd import ops
+        B = self.bits
         for i, L in enumerate(self.layers):
             out = bufs[i + 1] if mids[i] is None else mids[i]
             if L.get("tile"):
                 ops._call("mn_codeconv_tile_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(out), st)
             elif L.get("mfma"):
-                ops._call("mn_codeconv_mfma_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(out), int(L["pool"]), st)
+                ops._call("mn_codeconv_mfma_fwd_bits", C.byref(geoms[i]), B, B, B, ops._p(L["table"]), ops._p(bufs[i]), ops._p(out), int(L["pool"]), st)
             elif L.get("mfma3"):
-                ops._call("mn_codeconv_mfma3_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(out), 0, st)
+                ops._call("mn_codeconv_mfma3_fwd_bits", C.byref(geoms[i]), B, B, B, ops._p(L["table"]), ops._p(bufs[i]), ops._p(out), 0, st)
             else:
                 ops._call("mn_codeconv_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(out), int(L["pool"]), st)
             if mids[i] is not None:
                 m, (pk, ps, pp) = mids[i], L["pool_ksp"]
-                ops._call("mn_codes_maxpool", ops._p(m), m.shape[0], m.shape[1], CODE_BITS, m.shape[3], m.shape[4], pk, ps, pp, ops._p(bufs[i + 1]), st)
+                ops._call("mn_codes_maxpool", ops._p(m), m.shape[0], m.shape[1], B, m.shape[3], m.shape[4], pk, ps, pp, ops._p(bufs[i + 1]), st)
 
     @torch.no_grad()
     def forward(self, x):
@@ -707,22 +715,23 @@ class CodePlan(nn.Module):
             for m in self.tail:
                 y = m(y)
             return y.view(y.size(0), -1) if self.flatten else y
+        B = self.bits
         a = self.first(x)
-        if not (isinstance(a, QActTensor) and a.bits == CODE_BITS):
+        if not (isinstance(a, QActTensor) and a.bits == B):
             raise _err("dorefa_compile_codes: %s did not hand over %d-bit activation codes (the input must be a contiguous float32 GPU tensor with H * W %% 8 == 0)"
-                       % (self.report[0]["name"], CODE_BITS))
+                       % (self.report[0]["name"], B))
         codes = a.codes.contiguous()
         N, Cc, H, W = codes.shape
         bufs, geoms, c8, _, mids = self._plan_buffers(codes.shape, codes.device)
         st = ops._s()
-        ops._call("mn_codes_pack_planes", ops._p(codes), N, Cc, H * W, CODE_BITS, ops._p(bufs[0]), st)
+        ops._call("mn_codes_pack_planes", ops._p(codes), N, Cc, H * W, B, ops._p(bufs[0]), st)
         self._run_layers(bufs, geoms, mids, st)
         if self.keep_stages:
             self.stage_codes = [b.clone() for b in bufs]
         n_, c_, h_, w_ = c8.shape
-        ops._call("mn_codes_unpack_planes", ops._p(bufs[-1]), n_, c_, h_ * w_, CODE_BITS, ops._p(c8), st)
+        ops._call("mn_codes_unpack_planes", ops._p(bufs[-1]), n_, c_, h_ * w_, B, ops._p(c8), st)
         # (materialize: a consumer that does not read codes re-quantises 10 j s to j -- the middle of the code's bin)
-        y = self.last(QActTensor(c8, CODE_BITS, lambda: c8.float() * (10.0 / (2 ** CODE_BITS - 1))))
+        y = self.last(QActTensor(c8, B, lambda: c8.float() * (10.0 / (2 ** B - 1))))
         for m in self.tail:
             y = m(y)
         return y.view(y.size(0), -1) if self.flatten else y
@@ -759,7 +768,9 @@ def _walk_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False, mf
     """The graph walk of ``dorefa_compile_codes`` (no GPU needed): (first, layers, last, tail, flatten, report).  ``tile_blocks``: also admit what plain nin needs -- a
     dense 5x5 block (``layer["tile"]``) and a max-pool ``prepare()`` did not fuse, run on the planes behind its block (``layer["pool_ksp"]``).  ``mfma_blocks``: a
     hidden block ``mn_codeconv_mfma_supported`` covers runs on the MFMA form (``layer["mfma"]``); it refuses nothing.  ``mfma_k3``: a hidden 3x3 block
-    ``mn_codeconv_mfma3_supported`` covers, with no folded pool, runs on the 3x3 MFMA form (``layer["mfma3"]``); it refuses nothing either."""
+    ``mn_codeconv_mfma3_supported`` covers, with no folded pool, runs on the 3x3 MFMA form (``layer["mfma3"]``); it refuses nothing either.  The net's code width is that
+    of the first hidden block's conv, W2A2 or W4A4 (``report[i]["planes"]``); every quantised block must have it.  A 4-bit net runs on the two MFMA forms alone, whatever
+    the two flags say: a hidden block neither covers, ``code_ends`` and ``tile_blocks`` raise."""
     import ctypes as C
     from micronet_amd import _lib
     from micronet_amd.nn import Conv2dFirst
@@ -775,21 +786,46 @@ def _walk_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False, mf
     if len(blocks) < 3:
         raise _err("dorefa_compile_codes: module order not recognised (needs a first block, at least one quantised hidden block and a last block)")
     # ---- what the kernels are instantiated for, checked over the whole net first: the error names the layer
+    width = None          # (a_bits, w_bits) of the net: the first hidden block's
     for nm, blk in blocks[1:]:
         conv = blk.conv
         if not isinstance(conv, quantize.QuantConv2d):
             raise _err("dorefa_compile_codes: %s.conv is not a DoReFa QuantConv2d" % nm)
         ab, wb = conv.activation_quantizer.a_bits, conv.weight_quantizer.w_bits
-        if ab != CODE_BITS or wb != CODE_BITS:
-            raise _err("dorefa_compile_codes: %s.conv has a_bits = %d, w_bits = %d; only 2-bit codes and 2-bit weights are code-packed" % (nm, ab, wb))
+        if width is None:
+            width = (ab, wb)
+        if (ab, wb) != width or ab != wb or ab not in CODE_WIDTHS:
+            raise _err("dorefa_compile_codes: %s.conv has a_bits = %d, w_bits = %d; only W2A2 and W4A4 nets are code-packed, every quantised block at the width of the "
+                       "first hidden block (here a_bits = %d, w_bits = %d)" % (nm, ab, wb, width[0], width[1]))
         if not conv.quant_inference:
             raise _err("dorefa_compile_codes: %s.conv is not a quant_inference=True layer (prepare(..., quant_inference=True), then prequantize_weights)" % nm)
+    B = width[0]
+    wide = B != CODE_BITS          # a 4-bit net: the two int8-MFMA forms or nothing
+    if wide and code_ends:
+        raise _err("dorefa_compile_codes(code_ends=True): %s.conv: the net has %d-bit codes; the first conv's plane epilogue and the classifier on planes are built for "
+                   "2 bits only" % (blocks[0][0], B))
+    if wide and tile_blocks:
+        raise _err("dorefa_compile_codes(tile_blocks=True): %s.conv: the net has %d-bit codes; the 5x5 tile block and the max-pools on planes are built for 2 bits only"
+                   % (blocks[1][0], B))
     tiled = set()          # (tile_blocks) the hidden blocks mn_codeconv_tile_* runs
     for nm, blk in blocks[1:-1]:
         conv = blk.conv
         if tuple(conv.stride) != (1, 1) or tuple(conv.dilation) != (1, 1) or conv.padding_mode != "zeros" or isinstance(conv.padding, str):
             raise _err("dorefa_compile_codes: %s.conv: stride / dilation other than 1 (or non-zero padding mode) is not covered by the code kernels" % nm)
         g = _lib.ConvGeom(1, conv.in_channels, 4, 4, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], 1, 1, conv.padding[0], conv.padding[1], 1, 1, conv.groups, 0)
+        if wide:
+            if not (_lib.get_lib().mn_codeconv_mfma_supported(C.byref(g), B, B, B) or _lib.get_lib().mn_codeconv_mfma3_supported(C.byref(g), B, B, B)):
+                ks, cg, n = tuple(conv.kernel_size), conv.in_channels // conv.groups, 2 ** B - 1
+                if ks == (1, 1) and tuple(conv.padding) == (0, 0):
+                    why = ("%d channels per group: a grouped 1x1 block needs whole input words per group (C / groups %% 32 == 0)" % cg if conv.groups > 1 and cg % 32
+                           else "%d taps per output: beyond K * %d * %d <= 32767, the int16 range the thresholds are searched over (at most %d)" % (cg, n, n, 32767 // (n * n)))
+                elif ks == (3, 3) and tuple(conv.padding) == (1, 1):
+                    why = "%d channels per group: the 3x3 MFMA form covers C / groups == 16 at %d bits (K = 144, K * %d * %d <= 32767)" % (cg, B, n, n)
+                else:
+                    why = "%dx%d, padding %d: only the 1x1 and the 3x3 / padding 1 block have a %d-bit form" % (ks[0], ks[1], conv.padding[0], B)
+                raise _err("dorefa_compile_codes: %s.conv: not covered by the %d-bit int8-MFMA blocks (mn_codeconv_mfma_supported, mn_codeconv_mfma3_supported), the "
+                           "only %d-bit code blocks: %s" % (nm, B, B, why))
+            continue
         if not _lib.get_lib().mn_codeconv_supported(C.byref(g), CODE_BITS, CODE_BITS, CODE_BITS):
             five = tuple(conv.kernel_size) == (5, 5)
             if tile_blocks and _lib.get_lib().mn_codeconv_tile_supported(C.byref(g), CODE_BITS, CODE_BITS, CODE_BITS):
@@ -854,9 +890,9 @@ def _walk_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False, mf
             if tile_blocks and not bn.q_out_bits and ki + 1 < len(kids) and isinstance(kids[ki + 1][1], nn.MaxPool2d):
                 raise _err("dorefa_compile_codes(tile_blocks=True): %s: a max-pool directly behind the first block is not covered (its producer, %s, is not a code block)"
                            % (prefix + kids[ki + 1][0], nm))
-            if bn.q_out_bits != CODE_BITS:
+            if bn.q_out_bits != B:
                 raise _err("dorefa_compile_codes: %s: the first block must hand over %d-bit activation codes (it emits %s)"
-                           % (nm, CODE_BITS, ("%d-bit codes" % bn.q_out_bits) if bn.q_out_bits else "fp32"))
+                           % (nm, B, ("%d-bit codes" % bn.q_out_bits) if bn.q_out_bits else "fp32"))
             if bn.q_pool:
                 raise _err("dorefa_compile_codes: %s: a 2x2 max-pool is folded only into a code block; directly behind the first block it is not covered" % nm)
             first = child
@@ -871,7 +907,7 @@ def _walk_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False, mf
             if shuffle > 1:
                 raise _err("dorefa_compile_codes: %s: a channel shuffle in front of the last block is not covered" % nm)
             last = child
-            report.append(dict(name=nm, kind="last", K=K, words=(conv.in_channels + 31) // 32, planes=CODE_BITS, kernel="k_codes_unpack, last block on byte codes",
+            report.append(dict(name=nm, kind="last", K=K, words=(conv.in_channels + 31) // 32, planes=B, kernel="k_codes_unpack, last block on byte codes",
                                pooled=False, out_order="identity", stage=name))
             continue
         # ---- a hidden block: conv on codes -> bn -> relu -> [pool] -> the next conv's quantizer
@@ -880,8 +916,8 @@ def _walk_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False, mf
             # prepare() left the block emitting fp32 because an un-fused max-pool follows: it emits the codes of the conv behind that pool instead (checked when the
             # walk gets there) -- exact, the pool sits behind the ReLU and the quantizer is non-decreasing
             wants = True
-        elif bn.q_out_bits != CODE_BITS:
-            raise _err("dorefa_compile_codes: %s: its output is not handed over as %d-bit codes to the next quantised conv" % (nm, CODE_BITS))
+        elif bn.q_out_bits != B:
+            raise _err("dorefa_compile_codes: %s: its output is not handed over as %d-bit codes to the next quantised conv" % (nm, B))
         if shuffle > 1:
             if conv.in_channels % shuffle:
                 raise _err("dorefa_compile_codes: %s: %d input channels cannot be shuffled in %d groups" % (nm, conv.in_channels, shuffle))
@@ -892,12 +928,12 @@ def _walk_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False, mf
                            pool=0, want_pool=bool(bn.q_pool), shuffle=0, stage=name))
         if tile_blocks:
             layers[-1].update(tile=nm in tiled, pool_ksp=None, wants_consumer=wants)
-        if mfma_blocks or mfma_k3:
+        if mfma_blocks or mfma_k3 or wide:
             g = _lib.ConvGeom(1, conv.in_channels, 4, 4, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], 1, 1, conv.padding[0], conv.padding[1], 1, 1, conv.groups, 0)
-            if mfma_blocks:
-                layers[-1]["mfma"] = bool(_lib.get_lib().mn_codeconv_mfma_supported(C.byref(g), CODE_BITS, CODE_BITS, CODE_BITS))
-            if mfma_k3:
-                layers[-1]["mfma3"] = bool(_lib.get_lib().mn_codeconv_mfma3_supported(C.byref(g), CODE_BITS, CODE_BITS, CODE_BITS))
+            if mfma_blocks or wide:
+                layers[-1]["mfma"] = bool(_lib.get_lib().mn_codeconv_mfma_supported(C.byref(g), B, B, B))
+            if mfma_k3 or wide:
+                layers[-1]["mfma3"] = bool(_lib.get_lib().mn_codeconv_mfma3_supported(C.byref(g), B, B, B))
     if pending is not None:
         raise _err("dorefa_compile_codes(tile_blocks=True): %s: no quantised block behind this max-pool" % pending)
     if first is None or last is None:
@@ -910,6 +946,9 @@ def _walk_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False, mf
         if L.pop("want_pool") != bool(L["pool"]):
             raise _err("dorefa_compile_codes: %s: the block pools its output but no 2x2 max-pool follows it (or the reverse)" % L["name"])
         kern, pooled = _codeconv_kernel_name(L["k"], L["cin"], L["groups"], L["pool"]), bool(L["pool"])
+        if wide and L["mfma3"] and L["pool"]:
+            raise _err("dorefa_compile_codes: %s.conv: a 3x3 block with a folded 2x2 max-pool is not covered at %d bits (no pool is folded into the 3x3 MFMA form, the "
+                       "only %d-bit 3x3 block)" % (L["name"], B, B))
         if mfma_k3 and L["pool"]:          # (known only now: the walk folds a 2x2 pool into the layer after it has passed the block)
             L["mfma3"] = False
         if tile_blocks:
@@ -924,7 +963,7 @@ def _walk_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False, mf
         if tile_blocks:          # (behind the block's own kernel name, whichever it is)
             if L["pool_ksp"]:
                 kern, pooled = kern + ", k_codes_maxpool", "standalone"
-        report.append(dict(name=L["name"], kind="code", K=L["cin"] // L["groups"] * L["k"] * L["k"], words=(L["cin"] + 31) // 32, planes=CODE_BITS,
+        report.append(dict(name=L["name"], kind="code", K=L["cin"] // L["groups"] * L["k"] * L["k"], words=(L["cin"] + 31) // 32, planes=B,
                            kernel=kern, pooled=pooled,
                            out_order=("shuffle %d" % L["shuffle"]) if L["shuffle"] > 1 else "identity", stage=L["stage"]))
     report.append(rep_last)
@@ -936,13 +975,14 @@ def dorefa_codes_report(model, code_ends=False, tile_blocks=False, mfma_blocks=F
     graph walk alone: no GPU, nothing packed.  Raises like ``dorefa_compile_codes`` for whatever the code kernels do not cover.  ``tile_blocks`` as there: a block on
     ``k_codeconv_tile`` is named so, a max-pool run on the planes behind its block reads ``pooled="standalone"`` and ``"<block kernel>, k_codes_maxpool"``.
     ``mfma_blocks`` as there: the ``kernel`` of a block on the MFMA form reads ``k_codeconv_mfma<0|1>``.  ``mfma_k3`` as there: a 3x3 block on its MFMA form reads
-    ``k_codeconv_mfma3<0>``."""
+    ``k_codeconv_mfma3<0>``.  A W4A4 net (the width is the first hidden block's) reads ``planes = 4`` and the two MFMA kernels in every hidden row, with or without the
+    two flags; ``code_ends`` / ``tile_blocks`` and a block neither MFMA form covers raise."""
     return _walk_codes(model, code_ends, tile_blocks, mfma_blocks, mfma_k3)[5]
 
 
 @torch.no_grad()
 def dorefa_compile_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False, mfma_k3=False):
-    """``model``: a DoReFa W2A2 net prepared with ``quant_inference=True`` after ``prequantize_weights``, on the GPU (the reference's ``nin_gc``, or an ``nn.Sequential``
+    """``model``: a DoReFa W2A2 (or W4A4: last paragraph) net prepared with ``quant_inference=True`` after ``prequantize_weights``, on the GPU (the reference's ``nin_gc``, or an ``nn.Sequential``
     of the same block kinds).  Returns a ``CodePlan`` computing the same function with two bits per hidden activation; ``.report`` lists the stages.  Anything the code
     kernels do not cover raises ``MicronetHipError`` naming the layer -- never a silent byte path (the caller still has ``model``).  ``code_ends=True``: the first conv
     writes the first stage's planes in one launch and the classifier reads the last stage's planes -- no fp32 map, no byte codes, no pack / unpack launch; same codes
@@ -956,15 +996,23 @@ def dorefa_compile_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=
     ``mfma_k3=True``: a 3x3 / padding 1 hidden block ``mn_codeconv_mfma3_supported`` covers (C / groups % 16 == 0, at most 400 channels per group) with no folded pool
     is packed and run in its int8-MFMA form (``mn_codeconv_mfma3_*``: an implicit GEMM over (tap, channel), same planes, thresholds and bits); a pooled 3x3 block
     and every other block keep what they have, nothing is refused on its account, and it composes with the other three flags.  The layer dicts gain the key
-    ``"mfma3"``.  Off by default; with it off nothing changes."""
+    ``"mfma3"``.  Off by default; with it off nothing changes.
+
+    A W4A4 net -- every quantised block at ``a_bits = w_bits = 4``, the width read off the first hidden block -- is compiled the same way into a plan with four bits
+    per hidden activation (``plan.bits == 4``, ``report[i]["planes"] == 4``).  At 4 bits only the two int8-MFMA forms exist, so both are selected whatever
+    ``mfma_blocks`` / ``mfma_k3`` say and the layer dicts carry ``"mfma"`` / ``"mfma3"``: a 1x1 block must be dense with at most 145 input channels or have 32, 64, 96
+    or 128 channels per group, a 3x3 / padding 1 block 16 channels per group and no folded pool (K * 15 * 15 <= 32767, the int16 range the thresholds are searched
+    over).  Any other hidden block, ``code_ends=True`` and ``tile_blocks=True`` raise ``MicronetHipError`` naming the layer; so does a net of mixed widths or of any
+    other width.  The stored weights must lie on the 4-bit grid (2k - 15) / 15.  Nothing changes for a W2A2 net."""
     import ctypes as C
     from micronet_amd import _lib, ops
     from micronet_amd.quantization.wqaq.dorefa.quantize import _weight_is_coded
     first, layers, last, tail, flatten, report = _walk_codes(model, code_ends, tile_blocks, mfma_blocks, mfma_k3)
+    B = report[-1]["planes"]          # the net's code width: 2 or 4
     for L in layers:
         if not _weight_is_coded(L["conv"]):
-            raise _err("dorefa_compile_codes: %s.conv: the stored weights were not found on the 2-bit grid (2k - 3) / 3 (run inference.prequantize_weights on the GPU "
-                       "model first)" % L["name"])
+            raise _err("dorefa_compile_codes: %s.conv: the stored weights were not found on the %d-bit grid (2k - %d) / %d (run inference.prequantize_weights on the GPU "
+                       "model first)" % (L["name"], B, 2 ** B - 1, 2 ** B - 1))
     if code_ends and not _weight_is_coded(last.conv):
         raise _err("dorefa_compile_codes(code_ends=True): %s.conv: the stored weights were not found on the 2-bit grid (2k - 3) / 3 (run inference.prequantize_weights "
                    "on the GPU model first)" % report[-1]["name"])
@@ -985,17 +1033,17 @@ def dorefa_compile_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=
                 raise _err("dorefa_compile_codes: %s.bn: needs affine parameters, running statistics and a momentum" % L["name"])
             gamma, beta = ops._chk(bn.weight.detach(), "weight"), ops._chk(bn.bias.detach(), "bias")
             g8 = _lib.ConvGeom(1, L["cin"], 8, 8, L["cout"], k, k, 1, 1, p, p, 1, 1, L["groups"], 0)
-            wd = ops._wq_dorefa(CODE_BITS, None, 0)
+            wd = ops._wq_dorefa(B, None, 0)
             save = torch.empty((2, L["cout"]), dtype=torch.float32, device=dev)
             chan = torch.empty((_lib.MN_QA_NCH, L["cout"]), dtype=torch.float32, device=dev)
             tile = bool(L.get("tile"))
-            if not tile and lib.mn_qconv_bnq_supported(C.byref(g8), C.byref(wd), CODE_BITS) and int(lib.mn_qconv_bnq_stash_bits(C.byref(g8), C.byref(wd), CODE_BITS)) == 16:
+            if not tile and lib.mn_qconv_bnq_supported(C.byref(g8), C.byref(wd), B) and int(lib.mn_qconv_bnq_stash_bits(C.byref(g8), C.byref(wd), B)) == 16:
                 # the fused block: the conv on codes with training = 0 writes the constants from the running statistics (alpha = weight scale x activation scale)
                 zero = torch.zeros((1, L["cin"], 8, 8), dtype=torch.uint8, device=dev)
                 stash = torch.empty((1, L["cout"], 8, 8), dtype=torch.int16, device=dev)
                 nb = int(lib.mn_qconv_bnq_ws_bytes(C.byref(g8)))
                 ws = torch.empty(nb // 4 + 4, dtype=torch.float32, device=dev)
-                ops._call("mn_qconv_bnq_fwd_stash", C.byref(g8), C.byref(wd), ops._p(zero), CODE_BITS, ops._p(w), ops._p(b), ops._p(gamma), ops._p(beta), float(bn.eps),
+                ops._call("mn_qconv_bnq_fwd_stash", C.byref(g8), C.byref(wd), ops._p(zero), B, ops._p(w), ops._p(b), ops._p(gamma), ops._p(beta), float(bn.eps),
                           float(bn.momentum), 0, ops._p(bn.running_mean), ops._p(bn.running_var), None, ops._p(save), ops._p(stash), ops._p(chan), ops._p(ws), nb, ops._s())
             else:
                 # a block the stash conv does not cover (narrow groups) -- and, by the same route, the tiled 5x5 block: its eval forward convolves to fp32
@@ -1006,28 +1054,28 @@ def dorefa_compile_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=
                 ops._call("mn_bn_save_stats", ops._p(zero), 1, L["cout"], 64, float(bn.eps), float(bn.momentum), 0, ops._p(bn.running_mean), ops._p(bn.running_var),
                           ops._p(save), ops._p(ws), ops._s())
                 ops._call("mn_qa_chan_from_save", ops._p(save), ops._p(gamma), ops._p(beta), L["cout"], ops._p(chan), ops._s())
-                sc = torch.tensor(1.0 / (2 ** CODE_BITS - 1), dtype=torch.float32, device=dev)
+                sc = torch.tensor(1.0 / (2 ** B - 1), dtype=torch.float32, device=dev)
                 chan[0] = sc * sc          # fp32 product of the weight and the activation scale, as k_qa_stats_prep forms it
                 chan[1] = b if b is not None else 0.0
                 chan[6], chan[7] = chan[0] * chan[3], (chan[1] - chan[2]) * chan[3]
             # ---- the table (one launch per layer, once per model)
             g = _lib.ConvGeom(1, L["cin"], 4, 4, L["cout"], k, k, 1, 1, p, p, 1, 1, L["groups"], 0)
             quartet = "mn_codeconv_tile" if tile else "mn_codeconv_mfma" if L.get("mfma") else "mn_codeconv_mfma3" if L.get("mfma3") else "mn_codeconv"
-            table = torch.empty(int(getattr(lib, quartet + "_table_bytes")(C.byref(g), CODE_BITS, CODE_BITS, CODE_BITS)) // 4, dtype=torch.int32, device=dev)
+            table = torch.empty(int(getattr(lib, quartet + "_table_bytes")(C.byref(g), B, B, B)) // 4, dtype=torch.int32, device=dev)
             order = None
             if L["shuffle"] > 1:          # position j of the consumer's shuffled input is this layer's channel (j % s) * (C / s) + j // s (models/nin_gc.py:4-15)
                 j = torch.arange(L["cout"], device=dev)
                 order = ((j % L["shuffle"]) * (L["cout"] // L["shuffle"]) + j // L["shuffle"]).to(torch.int32).contiguous()
-            ops._call(quartet + "_pack", C.byref(g), ops._p(w), ops._p(chan), CODE_BITS, CODE_BITS, CODE_BITS, ops._p(order), ops._p(table), ops._s())
+            ops._call(quartet + "_pack", C.byref(g), ops._p(w), ops._p(chan), B, B, B, ops._p(order), ops._p(table), ops._s())
         L["table"], L["chan"], L["out_order"] = table, chan, order
     for L in layers:          # (compile time: the one place a host read-back is allowed)
         nonfinite, bad = int(L["table"][0]), int(L["table"][7])
         if nonfinite:
             raise _err("dorefa_compile_codes: %s.bn: %d output channels with a non-finite (or beyond 1e9) BatchNorm constant: no integer thresholds" % (L["name"], nonfinite))
         if bad:
-            raise _err("dorefa_compile_codes: %s.conv: %d table rows with a weight off the 2-bit grid or a bad channel order" % (L["name"], bad))
+            raise _err("dorefa_compile_codes: %s.conv: %d table rows with a weight off the %d-bit grid or a bad channel order" % (L["name"], bad, B))
     if not code_ends:
-        return CodePlan(first, layers, last, tail, flatten, report)
+        return CodePlan(first, layers, last, tail, flatten, report, bits=B)
     # ---- the first block's per-channel thresholds: its [9][O] constants by the calls its eval forward makes (ops._bn_front on fp32 y: mn_bn_save_stats with
     #      training = 0, mn_qa_chan_from_save -- invstd is never re-derived here); they do not depend on the input, so one 8 x 8 map of zeros will do
     bn, nm = first.bn, report[0]["name"]

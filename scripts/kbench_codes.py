@@ -26,7 +26,14 @@ layers; the three logits must be bit-equal.
 
 alternates ``I``, ``dorefa_compile_codes(I, mfma_blocks=True)`` and ``dorefa_compile_codes(I, mfma_blocks=True, mfma_k3=True)`` (the un-pooled 3x3 blocks on
 ``k_codeconv_mfma3`` as well) the same way and puts the per-kernel time of ``k_codeconv_mfma3`` beside that of ``k_codeconv<3,*>`` in the other plan and of the byte
-path's 3x3 conv kernels; ``--arch nin`` adds ``tile_blocks=True`` to both plans (default output profiles/codes_mfma3_nin.json)."""
+path's 3x3 conv kernels; ``--arch nin`` adds ``tile_blocks=True`` to both plans (default output profiles/codes_mfma3_nin.json).
+
+    python scripts/kbench_codes.py --bits 4 [--batches 256,1024] [--warmup 5] [--iters 20] [--out profiles/codes_w4a4.json] [--two-bit-check PARENT.json THIS.json]
+
+builds nin_gc W4A4, its ``I`` and ``P = dorefa_compile_codes(I)`` (four bits per hidden activation, every hidden block on an int8-MFMA kernel), alternates the two and
+writes medians, per-kernel times, the activation footprint and ``bit_equal``.  ``--two-bit-check``: two results of ``--mfma-k3`` (W2A2), one measured on the parent
+commit and one on this tree in the same session, are compared -- P1's median against the parent's median plus its own p25-p75 width -- and recorded under
+``two_bit_check``."""
 import argparse
 import json
 import os
@@ -226,6 +233,66 @@ def main_mfma_k3(args):
     print("wrote", args.out)
 
 
+def two_bit_check(parent_path, this_path):
+    """P1 (mfma_blocks + mfma_k3, W2A2) of this tree against the parent commit's, both measured by --mfma-k3: per batch the two medians, the parent's p25-p75 width
+    and whether this tree's median stays within the parent's median plus that width."""
+    parent, this = json.load(open(parent_path)), json.load(open(this_path))
+    out = dict(protocol="scripts/kbench_codes.py --mfma-k3 on the parent commit and on this tree, one after the other in one session", batches={})
+    for bs, a in parent["batches"].items():
+        b = this["batches"][bs]
+        width = a["P1_ms"]["p75"] - a["P1_ms"]["p25"]
+        out["batches"][bs] = dict(parent_P1_ms=a["P1_ms"], this_P1_ms=b["P1_ms"], parent_p25_p75_width_ms=width, parent_I_ms=a["I_ms"], this_I_ms=b["I_ms"],
+                                  parent_P1_over_I=a["P1_over_I"], this_P1_over_I=b["P1_over_I"],
+                                  within=bool(b["P1_ms"]["median"] <= a["P1_ms"]["median"] + width))
+    out["within"] = all(v["within"] for v in out["batches"].values())
+    return out
+
+
+def main_w4(args):
+    """nin_gc W4A4: I against its plan, alternated in one process."""
+    from micronet.compression.quantization.wqaq.dorefa import quantize as Q
+    from micronet_amd import _lib, inference
+    from micronet_amd.train import build_model, synth_batch
+    torch.manual_seed(0)
+    I = Q.prepare(build_model("nin_gc"), inplace=True, a_bits=4, w_bits=4, quant_inference=True).cuda()
+    inference.prequantize_weights(I)
+    I.eval()
+    P = inference.dorefa_compile_codes(I)
+    lib = _lib.get_lib()
+    # hidden activations per image, as the plan stores them (whole 32-channel words x 4 planes) and as the byte path does (one byte each)
+    sizes = _map_sizes(P) + [_map_sizes(P)[-1] // 2 if P.layers[-1]["pool"] else _map_sizes(P)[-1]]
+    chans = [P.layers[0]["cin"]] + [L["cout"] for L in P.layers]
+    foot = dict(plan_bytes=sum(4 * P.bits * ((c + 31) // 32) * h * h for c, h in zip(chans, sizes)), byte_path_bytes=sum(c * h * h for c, h in zip(chans, sizes)))
+    res = dict(model="nin_gc", a_bits=4, w_bits=4, warmup=args.warmup, iters=args.iters, device=torch.cuda.get_device_name(0), report=P.report,
+               mfma3_layers=[dict(name=L["name"], cin=L["cin"], cout=L["cout"], groups=L["groups"], span_words=int(L["table"][2]), dead_rows=int(L["table"][5]))
+                             for L in P.layers if L.get("mfma3")],
+               hidden_activation_bytes_per_image=foot, batches={})
+    with torch.no_grad():
+        for bs in [int(v) for v in args.batches.split(",")]:
+            x, _ = synth_batch(bs, device="cuda")
+            ref, got = I(x), P(x)
+            equal = bool(torch.equal(ref, got))
+            for _ in range(args.warmup):
+                I(x), P(x)
+            ti, tp = [], []
+            for _ in range(args.iters):          # alternated: both see the same clocks and the same neighbours
+                ti.append(timed(I, x))
+                tp.append(timed(P, x))
+            kp, ki = profile(lib, _lib, P, x), profile(lib, _lib, I, x)
+            med_i, med_p = statistics.median(ti), statistics.median(tp)
+            res["batches"][str(bs)] = dict(I_ms=q(ti), P_ms=q(tp), I_img_s=bs / med_i * 1e3, P_img_s=bs / med_p * 1e3, P_over_I=med_i / med_p, bit_equal=equal,
+                                           P_kernels=kp, I_kernels=ki, P_kernel_ms_total=sum(v["ms"] for v in kp.values()),
+                                           I_kernel_ms_total=sum(v["ms"] for v in ki.values()))
+            print("batch %d: I %.3f ms (min %.3f)  P %.3f ms (min %.3f)  P/I speed %.2fx  bit-equal %s" % (bs, med_i, min(ti), med_p, min(tp), med_i / med_p, equal), flush=True)
+    if args.two_bit_check:
+        res["two_bit_check"] = two_bit_check(*args.two_bit_check)
+        print("two_bit_check within:", res["two_bit_check"]["within"], flush=True)
+    os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", args.out)
+
+
 def _map_sizes(P, hw=32):
     """The input map size of every hidden block."""
     out, h = [], hw
@@ -244,8 +311,19 @@ def main():
     ap.add_argument("--mfma-blocks", action="store_true", help="I, the default plan and dorefa_compile_codes(I, mfma_blocks=True)")
     ap.add_argument("--mfma-k3", action="store_true", help="I, the mfma_blocks plan and dorefa_compile_codes(I, mfma_blocks=True, mfma_k3=True); works with --arch nin")
     ap.add_argument("--arch", default="nin_gc", choices=("nin_gc", "nin"), help="nin: plain nin, compiled with tile_blocks=True")
+    ap.add_argument("--bits", type=int, default=2, choices=(2, 4), help="4: nin_gc W4A4, I against its plan (every other protocol is measured at 2 bits)")
+    ap.add_argument("--two-bit-check", nargs=2, metavar=("PARENT_JSON", "THIS_JSON"), default=None,
+                    help="with --bits 4: two --mfma-k3 results, of the parent commit and of this tree, recorded under two_bit_check")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.bits == 4:
+        if args.code_ends or args.mfma_blocks or args.mfma_k3 or args.arch != "nin_gc":
+            ap.error("--bits 4 is its own protocol, on nin_gc")
+        if args.out is None:
+            args.out = os.path.join("profiles", "codes_w4a4.json")
+        return main_w4(args)
+    if args.two_bit_check:
+        ap.error("--two-bit-check goes with --bits 4")
     if (args.code_ends or args.mfma_blocks) and args.arch != "nin_gc":
         ap.error("--code-ends and --mfma-blocks are measured on nin_gc")
     if args.code_ends + args.mfma_blocks + args.mfma_k3 > 1:
