@@ -1080,6 +1080,38 @@ int mn_conv2d_first_codes(const mn_conv_geom* g, const float* x, const float* w,
 int mn_planesconv1x1_small_supported(int64_t C, int64_t HW, int64_t O, int a_bits);
 int mn_planesconv1x1_small_fwd(const uint32_t* planes, int a_bits, const float* w, const float* bias, float* y, int64_t N, int64_t C, int64_t HW, int64_t O,
                                mn_stream_t stream);
+/* ------------------------------------------------------------------ int8 deployment of the BN-folded IAO hidden blocks: byte codes on v_mfma_i32_16x16x64_i8
+ * What a hidden stage of a BN-folded, pre-quantised IAO net computes in eval mode -- [channel shuffle] -> QuantConv2d -> ReLU -> [QuantMaxPool2d 2x2 / 2] -> the next
+ * conv's activation quantizer, every quantizer symmetric (zero point 0), code widths 2 .. 8 -- on byte codes:
+ *   codes : int8 [N][ceil(C/16)][H*W][16], 16-byte aligned; byte d of block cb at a pixel is the code of channel 16 cb + d, tail channels 0.
+ * The chain, per element, with acc = sum j k exact in int32 (j input codes, k = rint(w / s_w) weight codes), al = fl(s_a * s_w[o]):
+ *   y = fl(fl(float(acc) * al) + b[o]); r = max(y, 0); c = clamp(rha(fl(r / s_out)), -2^(a-1), 2^(a-1) - 1);
+ *   pool == 1: c1 = clamp(rha(fl(r / s_p))) per sub-pixel, m = the window's largest c1, v = fl(float(m) * s_p), c = clamp(rha(fl(v / s_out))).
+ * `/` is the correctly rounded fp32 quotient, rha the round-half-away of mn_iao_fq_fwd, no contraction anywhere.
+ * Covered (mn_i8conv_supported): 2 <= a_bits, w_bits <= 8; 1x1 / stride 1 / padding 0 with groups == 1 and any C, or C / groups % 16 == 0; 3x3 / stride 1 / padding 1
+ * with C / groups % 16 == 0; dilation 1, g->in_shuffle 0 / 1 (a consumer's shuffle is folded into its PRODUCER through `out_order`); any O.  Everything else is
+ * MN_ENOTSUP, as is pool outside 0 / 1; a null or misaligned tensor (codes and `table` 16-byte aligned), an invalid geometry (N <= 0, ...) or odd H / W with pool is
+ * MN_EINVAL; nothing is written in either case.  No entry allocates.
+ *   pack : w = the stored fp32 weights [O][C/groups][KH][KW] on the grid k * s_w; s_w[o * s_w_stride] the weight scale (s_w_stride 1: per channel, 0: per layer);
+ *          bias [O] or null; s_a the conv's own activation scale, s_p the pool's quantizer scale (pass s_out where there is no pool), s_out the consumer conv's
+ *          activation scale -> `table` (private layout, mn_i8conv_table_bytes bytes): the weight codes as signed bytes in the A-operand order of the MFMA, K over
+ *          (tap, channel) padded with zero bytes to a multiple of 64; the rows of 64 consecutive output positions sorted by group and cut into tiles of 16 rows
+ *          inside a group, filled up with dead rows; per row al, b and its destination.  Row j computes channel out_order[j] (as in mn_bitconv_pack).  Word 0 of
+ *          the table counts the rows with a non-finite al or b or a bad s_w plus each of s_a, s_p, s_out that is non-finite or <= 0; word 7 the out_order entries
+ *          out of range plus the rows with a weight off the grid (|w / s_w - rint| > 1e-3 or |k| > 2^(w-1) - 1): both 0 for a valid table (the caller may read them
+ *          back once after packing).  Word 6 = a_bits | w_bits << 8.
+ *   fwd  : in_codes [N][ceil(C/16)][H*W][16] -> out_codes [N][ceil(O/16)][Ho*Wo][16] (pool == 1: Ho = H / 2, Wo = W / 2).  Every output byte is stored exactly once,
+ *          as part of a whole 16-byte block assembled on chip: no atomics, no read-modify-write.  Positions >= O and bad out_order entries yield 0 bytes.
+ *          mn_last_kernel(): k_i8conv<KS,pool>.
+ * mn_i8_pack_codes: fp32 NCHW x -> codes clamp(rha(fl(x / s)), -2^(a-1), 2^(a-1) - 1) in the layout above, position j holding channel out_order[j] (null: identity;
+ * 0 for a bad entry).  mn_i8_unpack_codes: codes -> fp32 NCHW fl(float(c) * s).  x / y 4-byte aligned; N, C, HW > 0 and s finite and positive, else MN_EINVAL. */
+int mn_i8conv_supported(const mn_conv_geom* g, int a_bits, int w_bits);
+int64_t mn_i8conv_table_bytes(const mn_conv_geom* g, int a_bits, int w_bits);
+int mn_i8conv_pack(const mn_conv_geom* g, const float* w, const float* s_w, int s_w_stride, const float* bias, float s_a, float s_p, float s_out, int a_bits, int w_bits,
+                   const int32_t* out_order, uint32_t* table, mn_stream_t stream);
+int mn_i8conv_fwd(const mn_conv_geom* g, int a_bits, int w_bits, const uint32_t* table, const int8_t* in_codes, int8_t* out_codes, int pool, mn_stream_t stream);
+int mn_i8_pack_codes(const float* x, int64_t N, int64_t C, int64_t HW, float s, int a_bits, const int32_t* out_order, int8_t* codes, mn_stream_t stream);
+int mn_i8_unpack_codes(const int8_t* codes, int64_t N, int64_t C, int64_t HW, float s, float* y, mn_stream_t stream);
 
 #ifdef __cplusplus
 }

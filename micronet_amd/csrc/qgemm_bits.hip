@@ -751,3 +751,4 @@ extern "C" int mn_bits_maxpool(const uint32_t* bits_in, int64_t N, int64_t Cw, i
 #include "qgemm_codes_mfma3.h"    // mn_codeconv_mfma3_*: the int8-MFMA form of the 3x3 hidden code blocks
 #include "qgemm_bits_mfma.h"      // mn_bitconv_mfma_*: the int8-MFMA form of the 1x1 hidden bit blocks
 #include "qgemm_bits_mfma3.h"     // mn_bitconv_mfma3_*: the int8-MFMA form of the 3x3 hidden bit blocks
+#include "qgemm_iao8.h"           // mn_i8conv_* / mn_i8_*: the int8 deployment of the BN-folded IAO hidden blocks (byte codes, i8 MFMA)

@@ -20,7 +20,11 @@ The results are ordinary modules of this package: in eval mode they run on the s
   * ``dorefa_compile_codes``: a pre-quantised DoReFa W2A2 ``quant_inference=True`` net compiled into a flat plan that keeps TWO BITS per hidden activation
     (``csrc/qgemm_codes.h``: activation codes as bit planes, plane-serial popcounts against weight code planes, the block's BatchNorm + ReLU + quantizer as integer
     thresholds per channel).  One kernel per hidden block, packed codes in, packed codes out; same codes in every hidden stage as the eval-mode model.
-    ``tile_blocks=True`` adds plain ``nin``: its dense 5x5 block on an LDS tile and its 3x3 / stride 2 max-pools on the planes."""
+    ``tile_blocks=True`` adds plain ``nin``: its dense 5x5 block on an LDS tile and its 3x3 / stride 2 max-pools on the planes.
+
+  * ``iao_compile_int8``: the BN-folded, pre-quantised symmetric IAO graph compiled into a flat plan that keeps ONE INT8 CODE per hidden activation
+    (``csrc/qgemm_iao8.h``: byte codes against weight-code bytes on v_mfma_i32_16x16x64_i8, bias + ReLU + [2x2 max-pool] + the consumer's quantizer in the epilogue).
+    One kernel per hidden block; the two ends stay on the model's own modules."""
 import copy
 
 import torch
@@ -1097,3 +1101,270 @@ def dorefa_compile_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=
     if nonfinite:
         raise _err("dorefa_compile_codes(code_ends=True): %s.bn: %d output channels with a non-finite (or beyond 1e9) BatchNorm constant: no thresholds" % (nm, nonfinite))
     return CodePlan(first, layers, last, tail, flatten, report, code_ends=True, first_table=table, first_chan=chan)
+
+
+# ------------------------------------------------------------------------------------------------ int8 deployment of the BN-folded IAO graph (csrc/qgemm_iao8.h)
+def _i8conv_kernel_name(k, pool):
+    """The kernel mn_i8conv_fwd reports for a hidden block (csrc/qgemm_iao8.h)."""
+    return "k_i8conv<%d,%d>" % (k, pool)
+
+
+def _iao8_check_quantizer(q, nm, per_tensor):
+    """A quantizer the int8 blocks cover: symmetric (zero point 0), 2 .. 8 bits; ``per_tensor``: exactly one scale."""
+    from micronet_amd.quantization.wqaq.iao import quantize
+    if not isinstance(q, quantize.Quantizer):
+        raise _err("iao_compile_int8: %s is not an IAO quantizer" % nm)
+    if q.bits == 32 or not 2 <= q.bits <= 8:
+        raise _err("iao_compile_int8: %s has %d bits; the int8 blocks cover code widths 2 .. 8" % (nm, q.bits))
+    if q._q_type_static != 0 or q.q_type != 0 or bool((q.zero_point != 0).any()):
+        raise _err("iao_compile_int8: %s is asymmetric; a zero byte must be the value 0 (symmetric quantizers only)" % nm)
+    if per_tensor and q.scale.numel() != 1:
+        raise _err("iao_compile_int8: %s carries %d scales; a per-tensor activation scale must be a single value" % (nm, q.scale.numel()))
+
+
+def _walk_iao8(model, input_hw=(32, 32)):
+    """The graph walk of ``iao_compile_int8`` (no GPU needed): (first, layers, last, tail, flatten, report, pack_shuffle)."""
+    import ctypes as C
+    from micronet_amd import _lib
+    from micronet_amd.quantization.wqaq.dorefa.quantize import _is_ref_block
+    from micronet_amd.quantization.wqaq.iao import quantize
+    if isinstance(model, nn.Sequential):
+        seq, prefix, flatten = model, "", False
+    else:
+        kids = list(model.named_children())
+        if len(kids) != 1 or not isinstance(kids[0][1], nn.Sequential):
+            raise _err("iao_compile_int8: module order not recognised (%s: expected an nn.Sequential of blocks, or the reference's Net holding one)" % type(model).__name__)
+        seq, prefix, flatten = kids[0][1], kids[0][0] + ".", True
+    items = [(prefix + n_, c_) for n_, c_ in seq.named_children()]
+    blocks = [i for i, (_, c_) in enumerate(items) if isinstance(getattr(c_, "conv", None), nn.Conv2d)]
+    if len(blocks) < 3 or blocks[0] != 0:
+        raise _err("iao_compile_int8: module order not recognised (expected a first conv block, at least one hidden block and a last conv block)")
+    last_i = blocks[-1]
+    (nm_first, first), (nm_last, last) = items[0], items[last_i]
+    tail = [c_ for _, c_ in items[last_i + 1:]]
+
+    def block_conv(nm, child):
+        conv, bn, act = getattr(child, "conv", None), getattr(child, "bn", None), getattr(child, "relu", None)
+        if not (_is_ref_block(child) and isinstance(bn, nn.Identity) and type(act) in (nn.ReLU, quantize.ReLUAfterFusedConv)):
+            raise _err("iao_compile_int8: %s (%s): module order not recognised (expected a BN-folded conv -> Identity -> ReLU block)" % (nm, type(child).__name__))
+        if not isinstance(conv, quantize.QuantConv2d) or isinstance(conv, quantize.QuantBNFuseConv2d):
+            raise _err("iao_compile_int8: %s.conv (%s) is not a BN-folded IAO QuantConv2d (run iao_model_bn_fuse first)" % (nm, type(conv).__name__))
+        if not conv.quant_inference:
+            raise _err("iao_compile_int8: %s.conv is not quant_inference: its stored weights are not on the grid (iao_model_bn_fuse + prequantize_weights)" % nm)
+        _iao8_check_quantizer(conv.activation_quantizer, nm + ".conv.activation_quantizer", True)
+        return conv
+
+    def shuffle_of(nm, child, conv):
+        s = int(getattr(conv, "in_shuffle_groups", 0) or 0)
+        if getattr(child, "channel_shuffle_flag", 0) and getattr(child, "shuffle_groups", 1) > 1:
+            if s > 1:
+                raise _err("iao_compile_int8: %s: two channel shuffles in front of one conv" % nm)
+            s = int(child.shuffle_groups)
+        if s > 1 and conv.in_channels % s:
+            raise _err("iao_compile_int8: %s: %d input channels cannot be shuffled in %d groups" % (nm, conv.in_channels, s))
+        return s if s > 1 else 0
+
+    if not isinstance(getattr(first, "conv", None), nn.Conv2d):
+        raise _err("iao_compile_int8: %s: the first block holds no conv" % nm_first)
+    last_conv = block_conv(nm_last, last)
+    c0 = first.conv
+    size = lambda v, k, s, p, d: (v + 2 * p - d * (k - 1) - 1) // s + 1
+    H, W = (size(input_hw[i], c0.kernel_size[i], c0.stride[i], c0.padding[i], c0.dilation[i]) for i in (0, 1))
+    layers, pack_shuffle = [], 0
+    for nm, child in items[1:last_i]:
+        if isinstance(child, nn.MaxPool2d):
+            ok = (type(child) is quantize.QuantMaxPool2d and _pool_kind(child) == (2, 2, 0))
+            if not ok:
+                raise _err("iao_compile_int8: %s (%s, kernel %s, stride %s, padding %s): only a 2x2 / stride 2 QuantMaxPool2d is folded into the int8 block in front of it"
+                           % (nm, type(child).__name__, child.kernel_size, child.stride, child.padding))
+            if not layers:
+                raise _err("iao_compile_int8: %s: a max-pool directly behind the first block is not covered (its producer is not an int8 block)" % nm)
+            if layers[-1]["pool"]:
+                raise _err("iao_compile_int8: %s: a second max-pool behind one block" % nm)
+            _iao8_check_quantizer(child.activation_quantizer, nm + ".activation_quantizer", True)
+            layers[-1]["pool"], layers[-1]["pool_module"], layers[-1]["pool_name"] = 1, child, nm
+            continue
+        conv = block_conv(nm, child)
+        wq = conv.weight_quantizer
+        _iao8_check_quantizer(wq, nm + ".conv.weight_quantizer", False)
+        if wq.scale.numel() not in (1, conv.out_channels):
+            raise _err("iao_compile_int8: %s.conv.weight_quantizer carries %d scales for %d output channels" % (nm, wq.scale.numel(), conv.out_channels))
+        one = lambda v: v[0] if v[0] == v[1] else -1
+        if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
+            raise _err("iao_compile_int8: %s.conv: padding mode not covered by the int8 blocks" % nm)
+        g = _lib.ConvGeom(1, conv.in_channels, 4, 4, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.stride[1], conv.padding[0],
+                          conv.padding[1], conv.dilation[0], conv.dilation[1], conv.groups, 0)
+        if not _lib.get_lib().mn_i8conv_supported(C.byref(g), conv.activation_quantizer.bits, wq.bits):
+            raise _err("iao_compile_int8: %s.conv: geometry not covered by mn_i8conv_supported (%dx%d, stride %d, padding %d, dilation %d, groups %d, %d channels per group: "
+                       "1x1 / padding 0 with groups 1 or C / groups %% 16 == 0, or 3x3 / padding 1 with C / groups %% 16 == 0; stride 1)"
+                       % (nm, conv.kernel_size[0], conv.kernel_size[1], one(conv.stride), one(conv.padding), one(conv.dilation), conv.groups, conv.in_channels // conv.groups))
+        s = shuffle_of(nm, child, conv)
+        if s:
+            if layers:
+                layers[-1]["shuffle"] = s          # folded into the producer's destination positions
+            else:
+                pack_shuffle = s                   # ... or into the pack behind the first block
+        layers.append(dict(name=nm, conv=conv, k=conv.kernel_size[0], pad=conv.padding[0], cin=conv.in_channels, cout=conv.out_channels, groups=conv.groups, pool=0,
+                           pool_module=None, pool_name=None, shuffle=0, w_bits=wq.bits, in_bits=conv.activation_quantizer.bits, per_channel=wq.scale.numel() > 1))
+    if not layers:
+        raise _err("iao_compile_int8: no hidden block between %s and %s" % (nm_first, nm_last))
+    # the consumer of every hidden block: the next hidden conv's activation quantizer, or the last conv's
+    for L, nxt in zip(layers, [M["conv"] for M in layers[1:]] + [last_conv]):
+        L["consumer"] = nxt.activation_quantizer
+        L["a_bits"] = nxt.activation_quantizer.bits
+        if L["pool"] and L["pool_module"].activation_quantizer.bits != L["a_bits"]:
+            raise _err("iao_compile_int8: %s: the pool's quantizer has %d bits, its consumer %d: one code width per block"
+                       % (L["pool_name"], L["pool_module"].activation_quantizer.bits, L["a_bits"]))
+    blocked = lambda c, h, w: (c + 15) // 16 * 16 * h * w
+    report = [dict(name=nm_first, kind="first", kernel="the model's own block (fp32), k_i8_pack", k=c0.kernel_size[0], cin=c0.in_channels, cout=c0.out_channels,
+                   groups=c0.groups, pool=0, out_order=("shuffle %d" % pack_shuffle) if pack_shuffle else "identity", table_bytes=0,
+                   act_bytes_in=4 * c0.in_channels * input_hw[0] * input_hw[1], act_bytes_out=4 * c0.out_channels * H * W + blocked(c0.out_channels, H, W))]
+    for L in layers:
+        g = _lib.ConvGeom(1, L["cin"], 4, 4, L["cout"], L["k"], L["k"], 1, 1, L["pad"], L["pad"], 1, 1, L["groups"], 0)
+        nin = blocked(L["cin"], H, W)
+        if L["pool"]:
+            if H % 2 or W % 2:
+                raise _err("iao_compile_int8: %s: the 2x2 max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
+            H, W = H // 2, W // 2
+        L["table_bytes"] = int(_lib.get_lib().mn_i8conv_table_bytes(C.byref(g), L["a_bits"], L["w_bits"]))
+        report.append(dict(name=L["name"], kind="int8", kernel=_i8conv_kernel_name(L["k"], L["pool"]), k=L["k"], cin=L["cin"], cout=L["cout"], groups=L["groups"],
+                           pool=L["pool"], out_order=("shuffle %d" % L["shuffle"]) if L["shuffle"] else "identity", table_bytes=L["table_bytes"], act_bytes_in=nin,
+                           act_bytes_out=blocked(L["cout"], H, W)))
+    report.append(dict(name=nm_last, kind="last", kernel="k_i8_unpack, the model's own block (fp32)", k=last_conv.kernel_size[0], cin=last_conv.in_channels,
+                       cout=last_conv.out_channels, groups=last_conv.groups, pool=0, out_order="identity", table_bytes=0,
+                       act_bytes_in=blocked(last_conv.in_channels, H, W) + 4 * last_conv.in_channels * H * W, act_bytes_out=4 * last_conv.out_channels * H * W))
+    return first, layers, last, tail, flatten, report, pack_shuffle
+
+
+def iao_int8_report(model, input_hw=(32, 32)):
+    """The ``report`` ``iao_compile_int8(model)`` would carry -- one row per stage: layer, kernel, geometry, folded pool, the consumer's shuffle folded into the stage
+    (``out_order``), table bytes and the activation bytes per image the stage reads and writes at an ``input_hw`` input -- from the graph walk alone: no GPU, nothing
+    packed.  Raises like ``iao_compile_int8`` for whatever the int8 blocks do not cover (weights off the grid excepted: that is read from the packed tables)."""
+    return _walk_iao8(model, input_hw)[5]
+
+
+def _shuffle_order(C_, s, device):
+    """position j of a consumer's shuffled input is its producer's channel (j % s) * (C / s) + j // s (models/nin_gc.py:4-15)"""
+    j = torch.arange(C_, device=device)
+    return ((j % s) * (C_ // s) + j // s).to(torch.int32).contiguous()
+
+
+class Int8Plan(nn.Module):
+    """What ``iao_compile_int8`` returns: the model's own first block (fp32) -> ``mn_i8_pack_codes`` at the second conv's scale -> one ``mn_i8conv_fwd`` per hidden
+    block (2x2 max-pool and the consumer's channel shuffle folded in) -> ``mn_i8_unpack_codes`` at the last conv's scale -> the model's own last block and tail (its
+    quantizer reproduces the same codes: fl(fl(c s) / s) rounds back to c).  Eval only; owns the packed weight tables and one set of byte buffers per input shape.
+    ``layers[i]`` keeps what the table was packed from (w, s_w, bias, s_a, s_p, s_out, a_bits, w_bits, pool, shuffle) for the tests' judge."""
+
+    def __init__(self, first, layers, last, tail, flatten, report, pack):
+        super().__init__()
+        self.first, self.last, self.tail = first, last, nn.ModuleList(tail)
+        self.layers, self.flatten, self.report = layers, flatten, report
+        self.pack = pack                  # dict: s (the second conv's activation scale), a_bits, order
+        self.keep_stages = False          # True: forward also leaves every stage's blocked codes in ``stage_codes`` (tests)
+        self.stage_codes = []
+        self._ws = {}
+        self.eval()
+
+    def train(self, mode=True):
+        if mode:
+            raise _err("iao_compile_int8: the compiled plan is eval-only")
+        return super().train(False)
+
+    def _plan_buffers(self, shape, device):
+        """Byte buffers (and the fp32 buffer in front of the last block) for one first-block output shape; allocated once, reused by every later call."""
+        from micronet_amd import _lib
+        key = (tuple(shape), str(device))
+        if key not in self._ws:
+            N, Cc, H, W = shape
+            if Cc != self.layers[0]["cin"]:
+                raise _err("iao_compile_int8: %s produced %d channels, %s reads %d" % (self.report[0]["name"], Cc, self.layers[0]["name"], self.layers[0]["cin"]))
+            bufs, geoms = [torch.empty((N, (Cc + 15) // 16, H * W, 16), dtype=torch.int8, device=device)], []
+            for L in self.layers:
+                geoms.append(_lib.ConvGeom(N, L["cin"], H, W, L["cout"], L["k"], L["k"], 1, 1, L["pad"], L["pad"], 1, 1, L["groups"], 0))
+                if L["pool"]:
+                    if H % 2 or W % 2:
+                        raise _err("iao_compile_int8: %s: the 2x2 max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
+                    H, W = H // 2, W // 2
+                bufs.append(torch.empty((N, (L["cout"] + 15) // 16, H * W, 16), dtype=torch.int8, device=device))
+            self._ws[key] = (bufs, geoms, torch.empty((N, self.layers[-1]["cout"], H, W), dtype=torch.float32, device=device))
+        return self._ws[key]
+
+    def run_stage(self, i, codes, N, H, W):
+        """Hidden stage ``i`` alone on blocked input codes [N, ceil(cin / 16), H * W, 16] (int8, GPU): its blocked output codes, freshly allocated (tests)."""
+        import ctypes as C
+        from micronet_amd import _lib, ops
+        L = self.layers[i]
+        if not (torch.is_tensor(codes) and codes.is_cuda and codes.dtype == torch.int8 and tuple(codes.shape) == (N, (L["cin"] + 15) // 16, H * W, 16)):
+            raise _err("iao_compile_int8: run_stage needs int8 GPU codes [N, ceil(C / 16), H * W, 16]")
+        codes = codes.contiguous()
+        g = _lib.ConvGeom(N, L["cin"], H, W, L["cout"], L["k"], L["k"], 1, 1, L["pad"], L["pad"], 1, 1, L["groups"], 0)
+        Ho, Wo = (H // 2, W // 2) if L["pool"] else (H, W)
+        out = torch.full((N, (L["cout"] + 15) // 16, Ho * Wo, 16), 77, dtype=torch.int8, device=codes.device)
+        with torch.cuda.device(codes.device):
+            ops._call("mn_i8conv_fwd", C.byref(g), L["a_bits"], L["w_bits"], ops._p(L["table"]), ops._p(codes), ops._p(out), int(L["pool"]), ops._s())
+        return out
+
+    @torch.no_grad()
+    def forward(self, x):
+        import ctypes as C
+        from micronet_amd import ops
+        a = self.first(x)
+        if not (type(a) is torch.Tensor and a.is_cuda and a.dtype == torch.float32 and a.dim() == 4):
+            raise _err("iao_compile_int8: %s did not produce a float32 GPU map (the input must be a float32 GPU tensor; no CPU fallback)" % self.report[0]["name"])
+        a = a.contiguous()
+        N, Cc, H, W = a.shape
+        with torch.cuda.device(a.device):
+            bufs, geoms, y = self._plan_buffers(a.shape, a.device)
+            st = ops._s()
+            ops._call("mn_i8_pack_codes", ops._p(a), N, Cc, H * W, self.pack["s"], self.pack["a_bits"], ops._p(self.pack["order"]), ops._p(bufs[0]), st)
+            for i, L in enumerate(self.layers):
+                ops._call("mn_i8conv_fwd", C.byref(geoms[i]), L["a_bits"], L["w_bits"], ops._p(L["table"]), ops._p(bufs[i]), ops._p(bufs[i + 1]), int(L["pool"]), st)
+            if self.keep_stages:
+                self.stage_codes = [b.clone() for b in bufs]
+            n_, c_, h_, w_ = y.shape
+            ops._call("mn_i8_unpack_codes", ops._p(bufs[-1]), n_, c_, h_ * w_, self.layers[-1]["s_out"], ops._p(y), st)
+        out = self.last(y)
+        for m in self.tail:
+            out = m(out)
+        return out.view(out.size(0), -1) if self.flatten else out
+
+
+@torch.no_grad()
+def iao_compile_int8(model):
+    """``model``: the result of ``iao_model_bn_fuse`` + ``prequantize_weights`` on a symmetric IAO net, on the GPU (the reference's ``nin_gc``, or an ``nn.Sequential``
+    of its block kinds).  Returns an ``Int8Plan`` that keeps every hidden activation as one int8 code and contracts on v_mfma_i32_16x16x64_i8
+    (``csrc/qgemm_iao8.h``); the two ends stay on the model's own modules.  ``.report`` lists the stages.  Scales are read from the quantizer buffers and the table
+    counters read back here, once.  Anything the int8 blocks do not cover -- an asymmetric or 32-bit quantizer, a per-tensor scale that is not a single value, a layer
+    that is not ``quant_inference``, weights off the grid, a geometry ``mn_i8conv_supported`` refuses, a pool other than a 2x2 / 2 ``QuantMaxPool2d``, a pool directly
+    behind the first block -- raises ``MicronetHipError`` naming the layer: never a silent fp32 path (the caller still has ``model``)."""
+    import ctypes as C
+    from micronet_amd import _lib, ops
+    first, layers, last, tail, flatten, report, pack_shuffle = _walk_iao8(model)
+    for p_ in model.parameters():
+        if not p_.is_cuda:
+            raise _err("iao_compile_int8: the model is on %s: micronet_amd runs on MI355X only (no CPU fallback)" % p_.device)
+    lib = _lib.get_lib()
+    scale = lambda q: float(q.scale.detach().float().reshape(-1)[0])          # (compile time: the one place a host read-back is allowed)
+    dev = layers[0]["conv"].weight.device
+    with torch.cuda.device(dev):
+        for L in layers:
+            conv, pool_m = L.pop("conv"), L.pop("pool_module")
+            g = _lib.ConvGeom(1, L["cin"], 4, 4, L["cout"], L["k"], L["k"], 1, 1, L["pad"], L["pad"], 1, 1, L["groups"], 0)
+            table = torch.empty(int(lib.mn_i8conv_table_bytes(C.byref(g), L["a_bits"], L["w_bits"])) // 4, dtype=torch.int32, device=dev)
+            L["w"] = conv.weight.detach().float().contiguous()
+            L["s_w"] = conv.weight_quantizer.scale.detach().float().reshape(-1).contiguous()
+            L["bias"] = conv.bias.detach().float().contiguous() if conv.bias is not None else None
+            L["s_a"], L["s_out"] = scale(conv.activation_quantizer), scale(L.pop("consumer"))
+            L["s_p"] = scale(pool_m.activation_quantizer) if pool_m is not None else L["s_out"]
+            L["out_order"] = _shuffle_order(L["cout"], L["shuffle"], dev) if L["shuffle"] else None
+            ops._call("mn_i8conv_pack", C.byref(g), ops._p(L["w"]), ops._p(L["s_w"]), 1 if L["per_channel"] else 0, ops._p(L["bias"]), L["s_a"], L["s_p"], L["s_out"],
+                      L["a_bits"], L["w_bits"], ops._p(L["out_order"]), ops._p(table), ops._s())
+            L["table"] = table
+        counters = torch.stack([L["table"][[0, 7]] for L in layers]).tolist()
+    for L, (bad, off) in zip(layers, counters):
+        if bad:
+            raise _err("iao_compile_int8: %s.conv: %d rows or scales with a non-finite or non-positive constant (al, bias, s_w, s_a, s_p, s_out)" % (L["name"], bad))
+        if off:
+            raise _err("iao_compile_int8: %s.conv: %d rows whose stored weights are off the grid k * s_w (run prequantize_weights after iao_model_bn_fuse)" % (L["name"], off))
+    pack = dict(s=layers[0]["s_a"], a_bits=layers[0]["in_bits"], order=_shuffle_order(layers[0]["cin"], pack_shuffle, dev) if pack_shuffle else None)
+    return Int8Plan(first, layers, last, tail, flatten, report, pack)

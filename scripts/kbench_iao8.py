@@ -1,0 +1,111 @@
+"""fp32-map path vs int8 path of a deployed (BN-folded, pre-quantised) IAO W8A8 nin_gc: the eval-mode folded model ``F`` (every hidden block re-quantises an fp32
+map, contracts on the fp32-exact kernels and writes an fp32 map: the yardstick) and ``P = inference.iao_compile_int8(F)`` (one int8 code per hidden activation, one
+i8-MFMA kernel per hidden block), alternated in ONE process, HIP events.
+
+    python scripts/kbench_iao8.py [--batches 256,1024] [--warmup 5] [--iters 20] [--out profiles/iao8_inference.json]
+
+Per batch: median / min / quartiles of the timed forwards of each, per-kernel times of both from the library's profile hooks, the largest |P - F| relative to
+max|F| and the argmax agreement; and the designed HBM bytes per image per hidden block on both paths (arithmetic from the shapes)."""
+import argparse
+import importlib
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def timed(fn, x):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn(x)
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def profile(lib, _lib, fn, x):
+    buf = (_lib.ProfEntry * 192)()
+    torch.cuda.synchronize()
+    lib.mn_profile_collect(buf, 192)
+    lib.mn_profile_enable(1)
+    fn(x)
+    torch.cuda.synchronize()
+    n = lib.mn_profile_collect(buf, 192)
+    lib.mn_profile_enable(0)
+    return {buf[i].name.decode(): dict(launches=int(buf[i].launches), ms=float(buf[i].total_ms), us_per_launch=round(1e3 * float(buf[i].total_ms) / max(1, int(buf[i].launches)), 2),
+                                       designed_bytes=float(buf[i].bytes)) for i in range(n)}
+
+
+def designed_bytes_per_image(P):
+    """Hidden blocks, per image.  fp32-map path (F): the conv reads an fp32 map (4 B per input element) and writes one (4 B per output element), the ReLU reads and
+    writes it (8 B), a QuantMaxPool2d reads it and writes the pooled map (4 + 1 B per output element).  int8 path (P): one byte per input element, one per (pooled)
+    output element, in whole 16-channel blocks (``act_bytes_in`` / ``act_bytes_out`` of the report)."""
+    rows = []
+    for r in P.report[1:-1]:
+        n_in, n_out_pooled = r["act_bytes_in"], r["act_bytes_out"]
+        n_out = n_out_pooled * (4 if r["pool"] else 1)
+        fp32 = 4 * n_in + 4 * n_out + 8 * n_out + ((4 * n_out + 4 * n_out_pooled) if r["pool"] else 0)
+        rows.append(dict(name=r["name"], kernel=r["kernel"], int8_bytes=n_in + n_out_pooled, fp32_path_bytes=fp32, table_bytes=r["table_bytes"]))
+    return rows
+
+
+def q(v):
+    return dict(median=statistics.median(v), min=min(v), max=max(v), p25=statistics.quantiles(v, n=4)[0], p75=statistics.quantiles(v, n=4)[2])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="256,1024")
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--out", default=os.path.join("profiles", "iao8_inference.json"))
+    args = ap.parse_args()
+    from micronet_amd import _lib, inference
+    from micronet_amd.train import build_model, make_optimizer, synth_batch, train_step
+    Q = importlib.import_module("micronet.compression.quantization.wqaq.iao.quantize")
+    # two training steps give the observers a range and the scales a meaning; then the fold and the pre-quantisation
+    T = Q.prepare(build_model("nin_gc"), inplace=True, a_bits=8, w_bits=8, q_type=0, q_level=0, weight_observer=0, bn_fuse=True).cuda().train()
+    opt = make_optimizer(T, 0.01, 1e-5)
+    xt, yt = synth_batch(32, device="cuda")
+    for _ in range(2):
+        train_step(T, opt, xt, yt)
+    T.eval()
+    F = inference.iao_model_bn_fuse(T)
+    inference.prequantize_weights(F)
+    F.eval()
+    P = inference.iao_compile_int8(F)
+    lib = _lib.get_lib()
+    res = dict(model="nin_gc", a_bits=8, w_bits=8, warmup=args.warmup, iters=args.iters, device=torch.cuda.get_device_name(0), report=P.report,
+               designed_bytes_per_image=designed_bytes_per_image(P), batches={})
+    with torch.no_grad():
+        for bs in [int(v) for v in args.batches.split(",")]:
+            x, _ = synth_batch(bs, device="cuda")
+            f, p = F(x), P(x)
+            for _ in range(args.warmup):
+                F(x), P(x)
+            tf, tp = [], []
+            for _ in range(args.iters):          # alternated: both see the same clocks and the same neighbours
+                tf.append(timed(F, x))
+                tp.append(timed(P, x))
+            kf, kp = profile(lib, _lib, F, x), profile(lib, _lib, P, x)
+            mf, mp = statistics.median(tf), statistics.median(tp)
+            res["batches"][str(bs)] = dict(F_ms=q(tf), P_ms=q(tp), F_img_s=bs / mf * 1e3, P_img_s=bs / mp * 1e3, P_over_F=mf / mp,
+                                           max_abs_diff_over_max_F=float((p - f).abs().max() / f.abs().max()),
+                                           argmax_agreement=float((p.argmax(1) == f.argmax(1)).float().mean()),
+                                           F_kernel_ms_total=sum(v["ms"] for v in kf.values()), P_kernel_ms_total=sum(v["ms"] for v in kp.values()),
+                                           F_kernels=kf, P_kernels=kp)
+            print("batch %d: F %.3f ms (min %.3f)  P %.3f ms (min %.3f)  speed %.2fx  max|P-F|/max|F| %.2e" % (bs, mf, min(tf), mp, min(tp), mf / mp,
+                                                                                                           res["batches"][str(bs)]["max_abs_diff_over_max_F"]), flush=True)
+            print("  P kernels (us per launch):", {n: v["us_per_launch"] for n, v in kp.items()}, flush=True)
+    os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+    with open(args.out, "w") as f_:
+        json.dump(res, f_, indent=1)
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
