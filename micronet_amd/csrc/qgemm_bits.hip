@@ -27,6 +27,7 @@
 // qgemm_codes.h, included at the end of this file.  Behind it: the int8-MFMA forms of the 1x1 and the un-pooled 3x3 bit block (mn_bitconv_mfma_*, mn_bitconv_mfma3_*:
 // qgemm_bits_mfma.h, qgemm_bits_mfma3.h) -- same bits, order, decision and header word 0, only the contraction differs.
 #include "qgemm_dev.h"
+#include "qgemm_mfma_sets.h"          // (the grid rule)
 
 namespace mn_bits {
 
@@ -690,12 +691,8 @@ extern "C" int mn_bitconv_fwd(const mn_conv_geom* g, const uint32_t* table, cons
         if (blocks > INT_MAX || t.ipb * q.Cw * (t.tw + q.KS - 1) * (t.th + q.KS - 1) > mn_bits::TILE_WORDS) MN_FAIL(MN_ENOTSUP, "mn_bitconv_fwd: tile does not fit");
         bx = (int)blocks;
     }
-    int gy = (2048 + bx - 1) / bx;          // enough blocks to fill the chip: split the output words over grid.y when the pixels alone do not
-    if (gy > q.OW) gy = q.OW;
-    f.owpb = (q.OW + gy - 1) / gy;
-    gy = (q.OW + f.owpb - 1) / f.owpb;
+    const dim3 grid(bx, mn_sets::grid_deal(bx, q.OW, f.owpb));          // the output words over grid.y
     t.owpb = f.owpb;
-    const dim3 grid(bx, gy);
     const hipStream_t s = (hipStream_t)stream;
     const int nwsel = (q.NW == 1 || (q.KS == 1 && (q.NW == 2 || q.NW == 4))) ? q.NW : 0;
     const int tsel = q.KS == 5 ? (q.Cw == 3 ? 3 : 0) : (q.Cw == 6 ? 6 : 0);

@@ -9,13 +9,12 @@
 //                  C / groups % 32 == 0), so byte e of lane (n, kq) at step s is bit 16 (kq & 1) + e of word w0 + 2 s + (kq >> 1): ONE dword load and a
 //                  multiply-and-mask bit spread per step.  Tail bits, channels of a neighbouring group inside the last step and words past the pixel's last (read as
 //                  0) meet zero weight bytes.
-//   weight table : (private layout, 16-byte aligned) 8 header words -- [0] rows whose decision is not monotone in acc + bad out_order entries, [1] k-steps, [2] tile
-//                  slots per set, [3] tile stride, [4] rows, [5] Cw -- then the tile count of every SET (two consecutive output words = 64 positions, the unit a wave
-//                  assembles on chip), then per set `slots` tiles of
+//   weight table : (private layout, 16-byte aligned: the set / tile table of qgemm_mfma_sets.h, a set = two consecutive output words) 8 header words -- [0] rows
+//                  whose decision is not monotone in acc + bad out_order entries, [1] k-steps, [2] tile slots per set, [3] tile stride, [4] rows, [5] Cw -- then the
+//                  tile count of every set, then the tiles:
 //                    [0] w0, [1] 1: first tile of its group in the set, [16 ..) T'[16], dest[16] (32 * word in set + bit),
 //                    [48 ..) per k-step 64 lanes x 16 bytes in the A-operand order of mn_mfma_i8 (lane = 16 kq + row).
-//                  The rows of a set are sorted by group and cut into tiles of 16 inside a group (its rows share the B operand); a tile is padded with dead rows
-//                  (T' = INT_MAX, zero weights: never a bit).  Positions >= O and bad out_order entries have no row at all: their bits stay 0.
+//                  A dead row: T' = INT_MAX, zero weights: never a bit.  The bits of positions without a row stay 0.
 //   kernel       : a wave owns 64 pixels as four N tiles (pool: the four sub-pixels of the 2x2 windows of 16 pooled pixels -- OR of four decisions = the window's
 //                  largest P >= T', a maximum over four accumulators in the lane).  The expanded bits of the wave's pixels stay in registers across all M tiles of a
 //                  group (up to three k-steps; beyond that they are re-expanded per tile from L1 / L2); the weight bytes stream from the L2-resident table.  Every lane
@@ -28,7 +27,9 @@
 namespace mn_bits_mfma {
 
 using mn_bits::Geom;
-enum { HDR = mn_bits::HDR, SETROWS = 64, THDR = 16, TMETA = 32, TA = THDR + TMETA, STEPW = 256, MAXNK = 3 };
+using mn_sets::SETROWS;
+using mn_sets::table_words;
+enum { HDR = mn_bits::HDR, THDR = 16, TMETA = 32, TA = THDR + TMETA, STEPW = 256, MAXNK = 3 };
 
 struct MGeom {
     Geom q;
@@ -40,14 +41,9 @@ static inline bool make_mgeom(const mn_conv_geom* g, MGeom& m) {
     if (m.q.groups > 1 && (m.q.Cg & 31)) return false;          // every group starts on a word
     m.nsteps = (m.q.Cg + 63) >> 6;
     m.nsets = (m.q.OW + 1) >> 1;
-    const int gp = m.q.groups < SETROWS ? m.q.groups : SETROWS;
-    m.slots = (SETROWS + 15 * gp) / 16;          // sum over the groups of a set of ceil(rows / 16), at most
     m.tstride = TA + STEPW * m.nsteps;
-    m.tiles_off = (HDR + m.nsets + 3) & ~3;
-    if ((int64_t)m.tiles_off + (int64_t)m.nsets * m.slots * m.tstride >= (1ll << 30)) return false;
-    return true;
+    return mn_sets::table_layout(m, m.q.groups, HDR);
 }
-static inline int64_t table_words(const MGeom& m) { return (int64_t)m.tiles_off + (int64_t)m.nsets * m.slots * m.tstride; }
 
 // the weight sign k_bits_wpack's planes encode: m = (v != 0), s = (v > 0)
 __device__ __forceinline__ int sign_of(float v) { return v > 0.f ? 1 : v != 0.f ? -1 : 0; }
@@ -73,7 +69,7 @@ __device__ __forceinline__ int row_threshold(const float* wr, int K, float b, in
 // ---------------------------------------------------------------- weight table: one block per set
 __global__ __launch_bounds__(256) void k_bits_mfma_wpack(MGeom m, const float* __restrict__ w, const float* __restrict__ bias, const int32_t* __restrict__ order,
                                                          uint32_t* __restrict__ tab) {
-    __shared__ int s_chan[SETROWS], s_grp[SETROWS], s_cnt[SETROWS], s_first[SETROWS], s_tile[SETROWS], s_row[SETROWS];
+    __shared__ mn_sets::SetPlan sp;
     const Geom& q = m.q;
     const int set = blockIdx.x, tid = threadIdx.x;
     if (set == 0 && tid == 0) { tab[1] = (uint32_t)m.nsteps; tab[2] = (uint32_t)m.slots; tab[3] = (uint32_t)m.tstride; tab[4] = (uint32_t)(q.OW * 32); tab[5] = (uint32_t)q.Cw; }
@@ -83,54 +79,25 @@ __global__ __launch_bounds__(256) void k_bits_mfma_wpack(MGeom m, const float* _
         const int r = i % m.tstride;
         tiles[i] = (r >= THDR && r < THDR + 16) ? 0x7fffffffu : 0u;
     }
-    // the channel and group of every position of the set (a bad out_order entry -- counted -- or a position past O: no row)
-    if (tid < SETROWS) {
-        const int jj = set * SETROWS + tid;
-        int o = jj < q.O ? (order ? order[jj] : jj) : -1;
-        o = (o >= 0 && o < q.O) ? o : -1;
-        s_chan[tid] = o; s_grp[tid] = o < 0 ? INT_MAX : o / q.Og;
-        if (jj < q.O && o < 0) atomicAdd(tab + 0, 1u);
-    }
-    __syncthreads();
-    int before = 0;
-    if (tid < SETROWS) {
-        int cnt = 0;
-        for (int jj = 0; jj < SETROWS; ++jj) {
-            const int same = s_chan[jj] >= 0 && s_grp[jj] == s_grp[tid];
-            cnt += same; before += same && jj < tid;
-        }
-        s_cnt[tid] = cnt; s_first[tid] = s_chan[tid] >= 0 && before == 0;
-    }
-    __syncthreads();
-    if (tid < SETROWS) {
-        int tb = 0;          // tiles of the groups in front of this row's
-        for (int jj = 0; jj < SETROWS; ++jj)
-            if (s_first[jj] && s_grp[jj] < s_grp[tid]) tb += (s_cnt[jj] + 15) >> 4;
-        s_tile[tid] = tb + (before >> 4); s_row[tid] = before & 15;
-        if (tid == 0) {
-            int nt = 0;
-            for (int jj = 0; jj < SETROWS; ++jj)
-                if (s_first[jj]) nt += (s_cnt[jj] + 15) >> 4;
-            tab[HDR + set] = (uint32_t)nt;
-        }
-    }
-    __syncthreads();
+    int nt;
+    const int before = mn_sets::plan_set(order, q.O, q.Og, set, tab + 0, sp, nt);
+    if (tid == 0) tab[HDR + set] = (uint32_t)nt;
     // weight signs: thread = 4 consecutive channels of one row, one dword of the A operand (lane 16 kq + row, byte e = channel & 15 of k-step channel >> 6)
     const int kq4 = m.nsteps * 16;          // dwords per row
     for (int idx = tid; idx < SETROWS * kq4; idx += 256) {
         const int pos = idx / kq4, k4 = (idx - pos * kq4) * 4;
-        const int o = s_chan[pos];
+        const int o = sp.chan[pos];
         if (o < 0 || k4 >= q.Cg) continue;
         const float* wr = w + (int64_t)o * q.Cg + k4;
         uint32_t v = 0u;
         for (int e = 0; e < 4 && k4 + e < q.Cg; ++e) v |= ((uint32_t)sign_of(wr[e]) & 0xffu) << (8 * e);
-        uint32_t* A = tiles + (int64_t)s_tile[pos] * m.tstride + TA;
-        A[(k4 >> 6) * STEPW + ((((k4 >> 4) & 3) * 16 + s_row[pos]) * 4) + ((k4 & 15) >> 2)] = v;
+        uint32_t* A = tiles + (int64_t)sp.tile[pos] * m.tstride + TA;
+        A[(k4 >> 6) * STEPW + ((((k4 >> 4) & 3) * 16 + sp.row[pos]) * 4) + ((k4 & 15) >> 2)] = v;
     }
     // thresholds: T of k_bits_wpack on acc = 2 P - sum t, stored for P
-    if (tid < SETROWS && s_chan[tid] >= 0) {
-        const int o = s_chan[tid], r = s_row[tid];
-        uint32_t* T = tiles + (int64_t)s_tile[tid] * m.tstride;
+    if (tid < SETROWS && sp.chan[tid] >= 0) {
+        const int o = sp.chan[tid], r = sp.row[tid];
+        uint32_t* T = tiles + (int64_t)sp.tile[tid] * m.tstride;
         int st;
         bool mono;
         const int th = row_threshold(w + (int64_t)o * q.Cg, q.Cg, bias ? bias[o] : 0.f, st, mono);
@@ -138,7 +105,7 @@ __global__ __launch_bounds__(256) void k_bits_mfma_wpack(MGeom m, const float* _
         T[THDR + r] = (uint32_t)((th + st + 1) >> 1);          // ceil((T + sum t) / 2); |T + sum t| <= 2 K + 1
         T[THDR + 16 + r] = (uint32_t)tid;                      // 32 * word in set + bit
         if (r == 0) {
-            T[0] = (uint32_t)(s_grp[tid] * q.Cg >> 5);
+            T[0] = (uint32_t)(sp.grp[tid] * q.Cg >> 5);
             T[1] = (uint32_t)((before >> 4) == 0);
         }
     }
@@ -322,11 +289,7 @@ extern "C" int mn_bitconv_mfma_fwd(const mn_conv_geom* g, const uint32_t* table,
     f.total = q.N * f.Ho * f.Wo;
     const int ppb = pool ? 64 : 256;          // (pooled) pixels per block: four waves of four N tiles
     const int bx = (f.total + ppb - 1) / ppb;
-    int gy = (2048 + bx - 1) / bx;          // enough blocks to fill the chip: split the sets over grid.y when the pixels alone do not
-    if (gy > m.nsets) gy = m.nsets;
-    f.spb = (m.nsets + gy - 1) / gy;
-    gy = (m.nsets + f.spb - 1) / f.spb;
-    const dim3 grid(bx, gy);
+    const dim3 grid(bx, mn_sets::grid_deal(bx, m.nsets, f.spb));          // the sets over grid.y
     const hipStream_t s = (hipStream_t)stream;
     const int nk = m.nsteps <= mn_bits_mfma::MAXNK ? m.nsteps : 0;
     mn_set_last_kernel("k_bitconv_mfma<%d>", pool);

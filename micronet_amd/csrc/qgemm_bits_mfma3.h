@@ -274,10 +274,7 @@ extern "C" int mn_bitconv_mfma3_fwd(const mn_conv_geom* g, const uint32_t* table
     f.Cw = q.Cw; f.H = q.H; f.W = q.W; f.OW = q.OW; f.groups = q.groups; f.nsteps = m.nsteps; f.tstride = m.tstride; f.cnt_off = m.cnt_off; f.tiles_off = m.tiles_off;
     f.total = q.N * q.H * q.W;
     const int bx = (f.total + 255) / 256;          // four waves of four N tiles
-    int gy = (2048 + bx - 1) / bx;          // enough blocks to fill the chip: the spans (the table says how wide) are dealt over grid.y when the pixels alone do not
-    const int most = (q.OW + 1) >> 1;
-    if (gy > most) gy = most;
-    const dim3 grid(bx, gy);
+    const dim3 grid(bx, mn_sets::grid_rows(bx, (q.OW + 1) >> 1));          // the spans (the table says how wide; at most one per two output words) round-robin over grid.y
     const hipStream_t s = (hipStream_t)stream;
     mn_set_last_kernel("k_bitconv_mfma3<%d>", pool);
     mn_prof_bytes(4.0 * q.N * q.Cw * q.H * q.W + 4.0 * q.N * q.OW * q.H * q.W + 4.0 * (double)mn_bits_mfma3::table_words(m));

@@ -633,11 +633,7 @@ extern "C" int mn_codeconv_fwd(const mn_conv_geom* g, const uint32_t* table, con
     f.Ho = pool ? q.H / 2 : q.H; f.Wo = pool ? q.W / 2 : q.W;
     f.total = q.N * f.Ho * f.Wo;
     const int bx = (f.total + 255) / 256;
-    int gy = (2048 + bx - 1) / bx;          // enough blocks to fill the chip: split the output words over grid.y when the pixels alone do not
-    if (gy > q.OW) gy = q.OW;
-    f.owpb = (q.OW + gy - 1) / gy;
-    gy = (q.OW + f.owpb - 1) / f.owpb;
-    const dim3 grid(bx, gy);
+    const dim3 grid(bx, mn_sets::grid_deal(bx, q.OW, f.owpb));          // the output words over grid.y
     const hipStream_t s = (hipStream_t)stream;
     const int nwsel = mn_codes::nw_select(q);
     mn_set_last_kernel("k_codeconv<%d,%d,%d>", q.KS, nwsel, pool);
@@ -699,11 +695,7 @@ extern "C" int mn_codeconv_tile_fwd(const mn_conv_geom* g, const uint32_t* table
     if (blocks > INT_MAX || q.Cw > mn_codes::TILE_MAXW || t.ipb * q.Cw * mn_codes::A * (t.tw + q.KS - 1) * (t.th + q.KS - 1) > mn_codes::TILE_WORDS)
         MN_FAIL(MN_ENOTSUP, "mn_codeconv_tile_fwd: tile does not fit");
     const int bx = (int)blocks;
-    int gy = (2048 + bx - 1) / bx;          // enough blocks to fill the chip: split the output words over grid.y when the pixels alone do not
-    if (gy > q.OW) gy = q.OW;
-    t.owpb = (q.OW + gy - 1) / gy;
-    gy = (q.OW + t.owpb - 1) / t.owpb;
-    const dim3 grid(bx, gy);
+    const dim3 grid(bx, mn_sets::grid_deal(bx, q.OW, t.owpb));          // the output words over grid.y
     const hipStream_t s = (hipStream_t)stream;
     const int tsel = q.Cw == 3 ? 3 : 0;
     mn_set_last_kernel("k_codeconv_tile<%d,%d>", q.KS, tsel);

@@ -7,14 +7,13 @@
 //                  C / groups % 32 == 0), so byte e of lane (n, kq) at step s is bit 16 (kq & 1) + e of word group w0 + 2 s + (kq >> 1): two dword loads (plane 0,
 //                  plane 1) and a multiply-and-mask bit spread per step, no per-bit loop.  Tail channels, channels of a neighbouring group inside the last step and
 //                  word groups past the pixel's last (read as 0) meet zero weight bytes: no mask.
-//   weight table : (private layout, 16-byte aligned) 8 header words -- [0] rows whose channel constants fail qa_finite, [1] k-steps, [2] tile slots per set, [3] tile
-//                  stride, [4] rows, [5] Cw, [6] a_in | w_bits << 8 | a_out << 16, [7] bad out_order entries + rows with a weight off the grid -- then the tile count of
-//                  every SET (a set = two consecutive output words = 64 positions, the unit a wave assembles on chip), then per set `slots` tiles of
+//   weight table : (private layout, 16-byte aligned: the set / tile table of qgemm_mfma_sets.h, a set = two consecutive output words) 8 header words -- [0] rows
+//                  whose channel constants fail qa_finite, [1] k-steps, [2] tile slots per set, [3] tile stride, [4] rows, [5] Cw, [6] a_in | w_bits << 8 | a_out << 16,
+//                  [7] bad out_order entries + rows with a weight off the grid -- then the tile count of every set, then the tiles:
 //                    [0] w0, [1] 1: first tile of its group in the set, [16 ..) flip[16], T_1[16] <= T_2[16] <= T_3[16], dest[16] (32 * word in set + bit),
 //                    [96 ..) per k-step 64 lanes x 16 bytes in the A-operand order of mn_mfma_i8 (lane = 16 kq + row).
-//                  The rows of a set are sorted by group and cut into tiles of 16 inside a group (its rows share the B operand); a tile is padded with dead rows
-//                  (T = INT_MAX, zero weights: never a bit).  Under nin_gc's "shuffle 2" a word holds 16 + 16 rows, under "shuffle 4" 8 per group -- 16 per group
-//                  in a set of two words: no dead rows.  Positions >= O and bad out_order entries have no row at all: their bits stay 0.
+//                  A dead row: T = INT_MAX, zero weights: never a bit.  Under nin_gc's "shuffle 2" a word holds 16 + 16 rows, under "shuffle 4" 8 per group -- 16
+//                  per group in a set of two words: no dead rows.  The bits of positions without a row stay 0.
 //   kernel       : a wave owns 64 pixels as four N tiles (pool: the four sub-pixels of the 2x2 windows of 16 pooled pixels, so the window's largest u = flip * acc is a
 //                  maximum over four accumulators in the lane).  The expanded codes of the wave's pixels stay in registers across all M tiles of a group (up to three
 //                  k-steps; beyond that they are re-expanded per tile from L1 / L2); the weight bytes stream from the L2-resident table, 16 bytes per lane.  Every
@@ -27,11 +26,14 @@
 // 2 bits; at 4 bits dense C <= 145 or C / groups in {32, 64, 96, 128}); pool 0 / 1.
 #pragma once
 #include "qgemm_codes.h"
+#include "qgemm_mfma_sets.h"
 
 namespace mn_codes_mfma {
 
 using mn_codes::Geom;
-enum { HDR = mn_codes::HDR, SETROWS = 64, THDR = 16, STEPW = 256, MAXNK = 3 };
+using mn_sets::SETROWS;
+using mn_sets::table_words;
+enum { HDR = mn_codes::HDR, THDR = 16, STEPW = 256, MAXNK = 3 };
 // per code width B: thresholds per row, words of tile metadata (flip[16], T_1 .. T_(2^B - 1)[16], dest[16]) and the offset of the A operand (a multiple of 4 words)
 constexpr int nthr(int B) { return (1 << B) - 1; }
 constexpr int tmeta(int B) { return 16 * ((1 << B) + 1); }
@@ -49,21 +51,16 @@ static inline bool make_mgeom(const mn_conv_geom* g, int a_in, int w_bits, int a
     m.bits = a_in;
     m.nsteps = (m.q.Cg + 63) >> 6;
     m.nsets = (m.q.OW + 1) >> 1;
-    const int gp = m.q.groups < SETROWS ? m.q.groups : SETROWS;
-    m.slots = (SETROWS + 15 * gp) / 16;          // sum over the groups of a set of ceil(rows / 16), at most
     m.tstride = ta(m.bits) + STEPW * m.nsteps;
-    m.tiles_off = (HDR + m.nsets + 3) & ~3;
-    if ((int64_t)m.tiles_off + (int64_t)m.nsets * m.slots * m.tstride >= (1ll << 30)) return false;
-    return true;
+    return mn_sets::table_layout(m, m.q.groups, HDR);
 }
-static inline int64_t table_words(const MGeom& m) { return (int64_t)m.tiles_off + (int64_t)m.nsets * m.slots * m.tstride; }
 
 // ---------------------------------------------------------------- weight table: one block per set
 template <int B>
 __global__ __launch_bounds__(256) void k_codes_mfma_wpack(MGeom m, const float* __restrict__ w, const float* __restrict__ chan, const int32_t* __restrict__ order,
                                                           uint32_t* __restrict__ tab) {
     constexpr int NTHR = nthr(B), TA = ta(B);
-    __shared__ int s_chan[SETROWS], s_grp[SETROWS], s_cnt[SETROWS], s_first[SETROWS], s_tile[SETROWS], s_row[SETROWS], s_off[SETROWS];
+    __shared__ mn_sets::SetPlan sp;
     const Geom& q = m.q;
     const int set = blockIdx.x, tid = threadIdx.x;
     if (set == 0 && tid == 0) {
@@ -76,44 +73,15 @@ __global__ __launch_bounds__(256) void k_codes_mfma_wpack(MGeom m, const float* 
         const int r = i % m.tstride;
         tiles[i] = (r >= THDR + 16 && r < THDR + 16 * (NTHR + 1)) ? 0x7fffffffu : (r >= THDR && r < THDR + 16) ? 1u : 0u;
     }
-    // the channel and group of every position of the set (a bad out_order entry or a position past O: no row)
-    if (tid < SETROWS) {
-        const int jj = set * SETROWS + tid;
-        int o = jj < q.O ? (order ? order[jj] : jj) : -1;
-        o = (o >= 0 && o < q.O) ? o : -1;
-        s_chan[tid] = o; s_grp[tid] = o < 0 ? INT_MAX : o / q.Og; s_off[tid] = 0;
-        if (jj < q.O && o < 0) atomicAdd(tab + 7, 1u);
-    }
-    __syncthreads();
-    int before = 0;
-    if (tid < SETROWS) {
-        int cnt = 0;
-        for (int jj = 0; jj < SETROWS; ++jj) {
-            const int same = s_chan[jj] >= 0 && s_grp[jj] == s_grp[tid];
-            cnt += same; before += same && jj < tid;
-        }
-        s_cnt[tid] = cnt; s_first[tid] = s_chan[tid] >= 0 && before == 0;
-    }
-    __syncthreads();
-    if (tid < SETROWS) {
-        int tb = 0;          // tiles of the groups in front of this row's
-        for (int jj = 0; jj < SETROWS; ++jj)
-            if (s_first[jj] && s_grp[jj] < s_grp[tid]) tb += (s_cnt[jj] + 15) >> 4;
-        s_tile[tid] = tb + (before >> 4); s_row[tid] = before & 15;
-        if (tid == 0) {
-            int nt = 0;
-            for (int jj = 0; jj < SETROWS; ++jj)
-                if (s_first[jj]) nt += (s_cnt[jj] + 15) >> 4;
-            tab[HDR + set] = (uint32_t)nt;
-        }
-    }
-    __syncthreads();
+    int nt;
+    const int before = mn_sets::plan_set(order, q.O, q.Og, set, tab + 7, sp, nt);
+    if (tid == 0) tab[HDR + set] = (uint32_t)nt;
     // weight bytes 2k - (2^B - 1): thread = 4 consecutive channels of one row, one dword of the A operand (lane 16 kq + row, byte e = channel & 15 of k-step channel >> 6)
     const int kq4 = m.nsteps * 16;          // dwords per row
     const float nf = (float)NTHR;
     for (int idx = tid; idx < SETROWS * kq4; idx += 256) {
         const int pos = idx / kq4, k4 = (idx - pos * kq4) * 4;
-        const int o = s_chan[pos];
+        const int o = sp.chan[pos];
         if (o < 0 || k4 >= q.Cg) continue;
         const float* wr = w + (int64_t)o * q.Cg + k4;
         uint32_t v = 0u;
@@ -125,14 +93,14 @@ __global__ __launch_bounds__(256) void k_codes_mfma_wpack(MGeom m, const float* 
             const int kc = (int)(kr < 0.f ? 0.f : kr > nf ? nf : kr == kr ? kr : 0.f);
             v |= ((uint32_t)(2 * kc - NTHR) & 0xffu) << (8 * e);
         }
-        if (off) s_off[pos] = 1;
-        uint32_t* A = tiles + (int64_t)s_tile[pos] * m.tstride + TA;
-        A[(k4 >> 6) * STEPW + ((((k4 >> 4) & 3) * 16 + s_row[pos]) * 4) + ((k4 & 15) >> 2)] = v;
+        if (off) sp.off[pos] = 1;
+        uint32_t* A = tiles + (int64_t)sp.tile[pos] * m.tstride + TA;
+        A[(k4 >> 6) * STEPW + ((((k4 >> 4) & 3) * 16 + sp.row[pos]) * 4) + ((k4 & 15) >> 2)] = v;
     }
     // thresholds: the search of k_qa_fwd on the block's eval-mode constants (qa_thresholds.h, as k_codes_wpack)
-    if (tid < SETROWS && s_chan[tid] >= 0) {
-        const int o = s_chan[tid], r = s_row[tid];
-        uint32_t* T = tiles + (int64_t)s_tile[tid] * m.tstride;
+    if (tid < SETROWS && sp.chan[tid] >= 0) {
+        const int o = sp.chan[tid], r = sp.row[tid];
+        uint32_t* T = tiles + (int64_t)sp.tile[tid] * m.tstride;
         const QaCh k = qa_load_ch(chan, q.O, o);
         const float s = q.s;
         const bool fin = qa_chan_finite(k);
@@ -148,17 +116,12 @@ __global__ __launch_bounds__(256) void k_codes_mfma_wpack(MGeom m, const float* 
         T[THDR + 16 * (NTHR + 1) + r] = (uint32_t)tid;          // 32 * word in set + bit
         if (!fin) atomicAdd(tab + 0, 1u);
         if (r == 0) {
-            const int c0 = s_grp[tid] * q.Cg;
+            const int c0 = sp.grp[tid] * q.Cg;
             T[0] = (uint32_t)(c0 >> 5);
             T[1] = (uint32_t)((before >> 4) == 0);
         }
     }
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t nbad = 0;
-        for (int i = 0; i < SETROWS; ++i) nbad += (uint32_t)(s_off[i] != 0);
-        if (nbad) atomicAdd(tab + 7, nbad);
-    }
+    mn_sets::tally_off(sp, tab + 7);
 }
 
 // ---------------------------------------------------------------- MFMA contraction + thresholds -> output planes
@@ -470,11 +433,7 @@ static int codeconv_mfma_fwd_impl(const char* who, const char* cover, const mn_c
     f.total = q.N * f.Ho * f.Wo;
     const int ppb = pool ? 64 : 256;          // (pooled) pixels per block: four waves of four N tiles
     const int bx = (f.total + ppb - 1) / ppb;
-    int gy = (2048 + bx - 1) / bx;          // enough blocks to fill the chip: split the sets over grid.y when the pixels alone do not
-    if (gy > m.nsets) gy = m.nsets;
-    f.spb = (m.nsets + gy - 1) / gy;
-    gy = (m.nsets + f.spb - 1) / f.spb;
-    const dim3 grid(bx, gy);
+    const dim3 grid(bx, mn_sets::grid_deal(bx, m.nsets, f.spb));          // the sets over grid.y
     const hipStream_t s = (hipStream_t)stream;
     const int nk = m.nsteps <= mn_codes_mfma::MAXNK ? m.nsteps : 0;
     mn_set_last_kernel("k_codeconv_mfma<%d>", pool);

@@ -12,16 +12,14 @@
 //   chain        : y = fl(fl(float(acc) * al) + b), r = max(y, 0), c = clamp(rha(fl(r / s_out)), qmin, qmax); with the pool c1 = clamp(rha(fl(r / s_p))) per sub-pixel,
 //                  m = the window's largest c1, v = fl(float(m) * s_p), c = clamp(rha(fl(v / s_out))) -- codes first, then the maximum, as the modules do it.  `/`
 //                  is the IEEE quotient; al = fl(s_a * s_w) is formed once by the packer.
-//   weight table : (private layout, 16-byte aligned) 16 header words -- [0] rows with a non-finite al or b or a bad s_w, plus each of s_a, s_p, s_out that is
-//                  non-finite or <= 0, [1] k-steps, [2] tile slots per set, [3] tile stride, [4] sets, [5] chunks, [6] a_bits | w_bits << 8, [7] bad out_order
-//                  entries + rows with a weight off the grid, [8] s_p, [9] s_out, [10] qmin, [11] qmax, [12] s_a (fp32 bit patterns) -- then one word per slot
-//                  (dy + 1 | (dx + 1) << 2 | chunk << 4), then the tile count of every SET (64 consecutive output positions = four 16-byte blocks, the unit a wave
-//                  assembles on chip), then per set `slots` tiles of
+//   weight table : (private layout, 16-byte aligned: the set / tile table of qgemm_mfma_sets.h, a set = four 16-byte output blocks) 16 header words -- [0] rows
+//                  with a non-finite al or b or a bad s_w, plus each of s_a, s_p, s_out that is non-finite or <= 0, [1] k-steps, [2] tile slots per set, [3] tile
+//                  stride, [4] sets, [5] chunks, [6] a_bits | w_bits << 8, [7] bad out_order entries + rows with a weight off the grid, [8] s_p, [9] s_out,
+//                  [10] qmin, [11] qmax, [12] s_a (fp32 bit patterns) -- then one word per slot (dy + 1 | (dx + 1) << 2 | chunk << 4), then the tile count of every
+//                  set, then the tiles:
 //                    [0] first 16-channel block of the tile's group, [16 ..) al[16], [32 ..) b[16], [48 ..) dest[16] (position in the set, -1: a dead row),
 //                    [64 ..) per k-step 64 lanes x 16 bytes in the A-operand order of mn_mfma_i8 (lane = 16 kq + row).
-//                  The rows of a set are sorted by group and cut into tiles of 16 inside a group (its rows share the B operand); a tile is filled up with dead rows
-//                  (zero weights, no destination).  Row j of the table computes channel out_order[j]: the consumer's channel shuffle folded into its producer.
-//                  Positions >= O and bad out_order entries have no row: their bytes are 0.
+//                  A dead row: zero weights, no destination.  The bytes of positions without a row are 0.
 //   kernel       : a wave owns 64 pixels as four N tiles (pool: the four sub-pixels of the 2x2 windows of 16 pooled pixels, so the window's maximum is taken
 //                  inside a lane).  Every lane writes the code bytes of its four rows into the wave's LDS image [4 blocks][pixels][16 bytes] (zero where no row
 //                  writes); behind a barrier every 16-byte block is read back and stored once, whole, coalesced along pixels: no atomics and no read-modify-write
@@ -30,10 +28,13 @@
 // any O; pool 0 / 1 (even H and W).
 #pragma once
 #include "qgemm_codes.h"
+#include "qgemm_mfma_sets.h"
 
 namespace mn_iao8 {
 
-enum { HDR = 16, SETROWS = 64, THDR = 64, T_AL = 16, T_B = 32, T_DEST = 48, STEPW = 256 };
+using mn_sets::SETROWS;
+using mn_sets::table_words;
+enum { HDR = 16, THDR = 64, T_AL = 16, T_B = 32, T_DEST = 48, STEPW = 256 };
 
 struct IGeom {
     int N, C, H, W, O, KS, groups, Cg, Og, taps;
@@ -59,18 +60,14 @@ static inline bool make_igeom(const mn_conv_geom* g, int a_bits, int w_bits, IGe
     m.nslots = m.taps * m.chunks;
     m.nsteps = (m.nslots + 3) >> 2;
     m.nsets = (m.OB + 3) >> 2;
-    const int gp = m.groups < SETROWS ? m.groups : SETROWS;
-    m.slots = (SETROWS + 15 * gp) / 16;          // sum over the groups of a set of ceil(rows / 16), at most
     m.tstride = THDR + STEPW * m.nsteps;
     m.slot_off = HDR;
     m.cnt_off = HDR + 4 * m.nsteps;
-    m.tiles_off = (m.cnt_off + m.nsets + 3) & ~3;
-    if ((int64_t)m.tiles_off + (int64_t)m.nsets * m.slots * m.tstride >= (1ll << 30)) return false;
+    if (!mn_sets::table_layout(m, m.groups, m.cnt_off)) return false;
     const int64_t blocks = (int64_t)g->N * (m.CB > m.OB ? m.CB : m.OB) * g->H * g->W;          // 16-byte blocks: indexed in int
     if (blocks >= (1ll << 27)) return false;
     return true;
 }
-static inline int64_t table_words(const IGeom& m) { return (int64_t)m.tiles_off + (int64_t)m.nsets * m.slots * m.tstride; }
 
 __host__ __device__ static inline bool fin(float v) { return fabsf(v) <= 3.402823466e38f; }          // false for NaN
 __host__ __device__ static inline bool scale_ok(float s) { return fin(s) && s > 0.f; }
@@ -78,7 +75,7 @@ __host__ __device__ static inline bool scale_ok(float s) { return fin(s) && s > 
 // ---------------------------------------------------------------- weight table: one block per set
 __global__ __launch_bounds__(256) void k_i8conv_wpack(IGeom m, const float* __restrict__ w, const float* __restrict__ sw, int sw_stride, const float* __restrict__ bias,
                                                       float s_a, float s_p, float s_out, const int32_t* __restrict__ order, uint32_t* __restrict__ tab) {
-    __shared__ int s_chan[SETROWS], s_grp[SETROWS], s_cnt[SETROWS], s_first[SETROWS], s_tile[SETROWS], s_row[SETROWS], s_off[SETROWS];
+    __shared__ mn_sets::SetPlan sp;
     const int set = blockIdx.x, tid = threadIdx.x;
     if (set == 0) {
         for (int i = tid; i < 4 * m.nsteps; i += 256) {
@@ -102,44 +99,15 @@ __global__ __launch_bounds__(256) void k_i8conv_wpack(IGeom m, const float* __re
         const int r = i % m.tstride;
         tiles[i] = (r >= T_DEST && r < T_DEST + 16) ? 0xffffffffu : 0u;
     }
-    // the channel and group of every position of the set (a bad out_order entry or a position past O: no row)
-    if (tid < SETROWS) {
-        const int jj = set * SETROWS + tid;
-        int o = jj < m.O ? (order ? order[jj] : jj) : -1;
-        o = (o >= 0 && o < m.O) ? o : -1;
-        s_chan[tid] = o; s_grp[tid] = o < 0 ? INT_MAX : o / m.Og; s_off[tid] = 0;
-        if (jj < m.O && o < 0) atomicAdd(tab + 7, 1u);
-    }
-    __syncthreads();
-    int before = 0;
-    if (tid < SETROWS) {
-        int cnt = 0;
-        for (int jj = 0; jj < SETROWS; ++jj) {
-            const int same = s_chan[jj] >= 0 && s_grp[jj] == s_grp[tid];
-            cnt += same; before += same && jj < tid;
-        }
-        s_cnt[tid] = cnt; s_first[tid] = s_chan[tid] >= 0 && before == 0;
-    }
-    __syncthreads();
-    if (tid < SETROWS) {
-        int tb = 0;          // tiles of the groups in front of this row's
-        for (int jj = 0; jj < SETROWS; ++jj)
-            if (s_first[jj] && s_grp[jj] < s_grp[tid]) tb += (s_cnt[jj] + 15) >> 4;
-        s_tile[tid] = tb + (before >> 4); s_row[tid] = before & 15;
-        if (tid == 0) {
-            int nt = 0;
-            for (int jj = 0; jj < SETROWS; ++jj)
-                if (s_first[jj]) nt += (s_cnt[jj] + 15) >> 4;
-            tab[m.cnt_off + set] = (uint32_t)nt;
-        }
-    }
-    __syncthreads();
+    int nt;
+    mn_sets::plan_set(order, m.O, m.Og, set, tab + 7, sp, nt);
+    if (tid == 0) tab[m.cnt_off + set] = (uint32_t)nt;
     // weight codes k = rint(w / s_w): thread = 4 consecutive channels of one row at one tap, one dword of the A operand (lane 16 (slot & 3) + row of k-step slot >> 2)
     const int dpr = m.nslots * 4;          // dwords per row
     const float kmax = (float)((1 << (m.w_bits - 1)) - 1);
     for (int idx = tid; idx < SETROWS * dpr; idx += 256) {
         const int pos = idx / dpr, d = idx - pos * dpr, slot = d >> 2, e4 = d & 3;
-        const int o = s_chan[pos];
+        const int o = sp.chan[pos];
         if (o < 0) continue;
         const int tap = slot / m.chunks, c0 = (slot - tap * m.chunks) * 16 + e4 * 4;
         if (c0 >= m.Cg) continue;
@@ -154,26 +122,21 @@ __global__ __launch_bounds__(256) void k_i8conv_wpack(IGeom m, const float* __re
             const int kc = (int)(kr < -kmax ? -kmax : kr > kmax ? kmax : kr == kr ? kr : 0.f);
             v |= ((uint32_t)kc & 0xffu) << (8 * e);
         }
-        if (off) s_off[pos] = 1;
-        uint32_t* A = tiles + (int64_t)s_tile[pos] * m.tstride + THDR;
-        A[(slot >> 2) * STEPW + ((slot & 3) * 16 + s_row[pos]) * 4 + e4] = v;
+        if (off) sp.off[pos] = 1;
+        uint32_t* A = tiles + (int64_t)sp.tile[pos] * m.tstride + THDR;
+        A[(slot >> 2) * STEPW + ((slot & 3) * 16 + sp.row[pos]) * 4 + e4] = v;
     }
     // the row constants
-    if (tid < SETROWS && s_chan[tid] >= 0) {
-        const int o = s_chan[tid], r = s_row[tid];
-        uint32_t* T = tiles + (int64_t)s_tile[tid] * m.tstride;
+    if (tid < SETROWS && sp.chan[tid] >= 0) {
+        const int o = sp.chan[tid], r = sp.row[tid];
+        uint32_t* T = tiles + (int64_t)sp.tile[tid] * m.tstride;
         const float s = sw[(int64_t)o * sw_stride];
         const float al = s_a * s, b = bias ? bias[o] : 0.f;
         T[T_AL + r] = mn_f2u(al); T[T_B + r] = mn_f2u(b); T[T_DEST + r] = (uint32_t)tid;
         if (!fin(al) || !fin(b) || !scale_ok(s)) atomicAdd(tab + 0, 1u);
-        if (r == 0) T[0] = (uint32_t)(s_grp[tid] * m.Cg >> 4);          // (groups == 1 with any C: group 0 starts at block 0)
+        if (r == 0) T[0] = (uint32_t)(sp.grp[tid] * m.Cg >> 4);          // (groups == 1 with any C: group 0 starts at block 0)
     }
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t nbad = 0;
-        for (int i = 0; i < SETROWS; ++i) nbad += (uint32_t)(s_off[i] != 0);
-        if (nbad) atomicAdd(tab + 7, nbad);
-    }
+    mn_sets::tally_off(sp, tab + 7);
 }
 
 // ---------------------------------------------------------------- MFMA contraction + the requantisation chain -> output bytes
@@ -363,11 +326,7 @@ extern "C" int mn_i8conv_fwd(const mn_conv_geom* g, int a_bits, int w_bits, cons
     f.total = m.N * f.Ho * f.Wo;
     const int ppb = pool ? 64 : 256;          // (pooled) pixels per block: four waves of four N tiles
     const int bx = (f.total + ppb - 1) / ppb;
-    int gy = (2048 + bx - 1) / bx;          // enough blocks to fill the chip: split the sets over grid.y when the pixels alone do not
-    if (gy > m.nsets) gy = m.nsets;
-    f.spb = (m.nsets + gy - 1) / gy;
-    gy = (m.nsets + f.spb - 1) / f.spb;
-    const dim3 grid(bx, gy);
+    const dim3 grid(bx, mn_sets::grid_deal(bx, m.nsets, f.spb));          // the sets over grid.y
     const hipStream_t s = (hipStream_t)stream;
     const u32x4* xin = reinterpret_cast<const u32x4*>(in_codes);
     u32x4* yout = reinterpret_cast<u32x4*>(out_codes);

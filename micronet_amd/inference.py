@@ -176,6 +176,86 @@ def _err(msg):
     return MicronetHipError(msg)
 
 
+def _net_sequence(model, who):
+    """(seq, prefix, flatten) of a model that is an nn.Sequential of blocks, or the reference's Net holding one (models/nin_gc.py:144-147: forward = model(x).view(N, -1))."""
+    if isinstance(model, nn.Sequential):
+        return model, "", False
+    kids = list(model.named_children())
+    if len(kids) != 1 or not isinstance(kids[0][1], nn.Sequential):
+        raise _err("%s: module order not recognised (%s: expected an nn.Sequential of blocks, or the reference's Net holding one)" % (who, type(model).__name__))
+    return kids[0][1], kids[0][0] + ".", True
+
+
+def _shuffle_in_front(who, nm, child, conv):
+    """The groups of the channel shuffle in front of ``conv`` -- its own ``in_shuffle_groups`` or its block's -- or 0."""
+    s = int(getattr(conv, "in_shuffle_groups", 0) or 0)
+    if getattr(child, "channel_shuffle_flag", 0) and getattr(child, "shuffle_groups", 1) > 1:
+        if s > 1:
+            raise _err("%s: %s: two channel shuffles in front of one conv" % (who, nm))
+        s = int(child.shuffle_groups)
+    return s if s > 1 else 0
+
+
+def _check_shuffle_divides(who, nm, conv, s):
+    if conv.in_channels % s:
+        raise _err("%s: %s: %d input channels cannot be shuffled in %d groups" % (who, nm, conv.in_channels, s))
+
+
+def _shuffle_order(C_, s, device):
+    """position j of a consumer's shuffled input is its producer's channel (j % s) * (C / s) + j // s (models/nin_gc.py:4-15)"""
+    j = torch.arange(C_, device=device)
+    return ((j % s) * (C_ // s) + j // s).to(torch.int32).contiguous()
+
+
+def _require_gpu(model, who):
+    for p_ in model.parameters():
+        if not p_.is_cuda:
+            raise _err("%s: the model is on %s: micronet_amd runs on MI355X only (no CPU fallback)" % (who, p_.device))
+
+
+def _block_geom(L, N=1, H=4, W=4):
+    """The ConvGeom of a hidden layer's dict (square kernel, stride 1) on an N x H x W input; the shape-independent calls take the default."""
+    from micronet_amd import _lib
+    return _lib.ConvGeom(N, L["cin"], H, W, L["cout"], L["k"], L["k"], 1, 1, L["pad"], L["pad"], 1, 1, L["groups"], 0)
+
+
+class _Plan(nn.Module):
+    """What the three compiled plans share: the model's own two ends and tail, the layer dicts, eval only, one set of buffers per first-block output shape."""
+    who = None          # the entry point's name in the plan's messages
+
+    def __init__(self, first, layers, last, tail, flatten, report):
+        super().__init__()
+        self.first, self.last, self.tail = first, last, nn.ModuleList(tail)
+        self.layers, self.flatten, self.report = layers, flatten, report
+        self.keep_stages = False          # True: forward also leaves every stage's buffer in ``stage_bits`` / ``stage_codes`` (tests)
+        self._ws = {}
+        self.eval()
+
+    def train(self, mode=True):
+        if mode:
+            raise _err("%s: the compiled plan is eval-only" % self.who)
+        return super().train(False)
+
+    def _shape_buffers(self, shape, device):
+        """What ``_plan_buffers`` makes for one first-block output shape: allocated once, reused by every later call."""
+        key = (tuple(shape), str(device))
+        if key not in self._ws:
+            self._ws[key] = self._plan_buffers(shape, device)
+        return self._ws[key]
+
+    @staticmethod
+    def _after_conv(block, conv, y):
+        kids = list(block.children())
+        for m in kids[kids.index(conv) + 1:]:          # what follows the conv inside the block
+            y = m(y)
+        return y
+
+    def _finish(self, y):
+        for m in self.tail:
+            y = m(y)
+        return y.view(y.size(0), -1) if self.flatten else y
+
+
 def _codes_of(t):
     from micronet_amd.sign_tensor import SignTensor
     c = t.codes if isinstance(t, SignTensor) else t
@@ -237,69 +317,55 @@ def _conv_kernel_name(k, cin, groups, fold):
     return "k_bitconv<%d,%d,%d>" % (k, sel, fold)
 
 
-class BitPlan(nn.Module):
+class BitPlan(_Plan):
     """What ``wbwtab_compile_bits`` returns: first block (fp32 conv + sign, the folded graph's own module) -> bit pack -> n XNOR-popcount blocks (max-pools folded in,
     or run on the bits behind a block that cannot fold them) -> bit unpack -> last block and tail (the folded graph's own modules).  Eval only; owns the packed weight
     tables and one set of bit buffers per input shape.  ``bit_ends``: the first conv's kernel writes the first stage's bits itself (no fp32 map, no int8 codes, no
     pack) and the last conv reads the last stage's bits (no unpack, no int8 buffer); what follows the last conv inside its block, and the tail, run unchanged."""
 
-    def __init__(self, first, layers, last, tail, flatten, report, bit_ends=False):
-        super().__init__()
-        self.first, self.last, self.tail = first, last, nn.ModuleList(tail)
-        self.bit_ends = bool(bit_ends)
-        self.layers = layers              # dicts: geometry, table, pool, out_order
-        self.flatten = flatten
-        self.report = report
-        self.keep_stages = False          # True: forward also leaves every stage's bits in ``stage_bits`` (tests)
-        self.stage_bits = []
-        self._ws = {}
-        self.eval()
+    who = "wbwtab_compile_bits"
 
-    def train(self, mode=True):
-        if mode:
-            raise _err("wbwtab_compile_bits: the compiled plan is eval-only")
-        return super().train(False)
+    def __init__(self, first, layers, last, tail, flatten, report, bit_ends=False):
+        super().__init__(first, layers, last, tail, flatten, report)          # layers: dicts of geometry, table, pool, out_order
+        self.bit_ends = bool(bit_ends)
+        self.stage_bits = []
 
     def _plan_buffers(self, shape, device):
-        """Bit buffers (and the int8 buffer in front of the last conv) for one first-block output shape; allocated once, reused by every later call."""
+        """Bit buffers (and the int8 buffer in front of the last conv) for one first-block output shape."""
         from micronet_amd import _lib
-        key = (tuple(shape), str(device))
-        if key not in self._ws:
-            N, Cc, H, W = shape
-            g0 = None
-            if self.bit_ends:
-                import ctypes as C
-                conv = self.first.conv
-                g0 = _lib.ConvGeom(N, conv.in_channels, H, W, Cc, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.stride[1], conv.padding[0], conv.padding[1],
-                                   conv.dilation[0], conv.dilation[1], conv.groups, 0)
-                if not _lib.get_lib().mn_conv2d_first_sign_bits_supported(C.byref(g0)):
-                    raise _err("wbwtab_compile_bits(bit_ends=True): %s.conv: a %d x %d x %d x %d input is not covered by mn_conv2d_first_sign_bits (W %% 4 == 0, H * W %% 32 == 0, "
-                               "the image strip in LDS)" % (self.report[0]["name"], N, conv.in_channels, H, W))
-            bufs, geoms = [torch.empty((N, (Cc + 31) // 32, H, W), dtype=torch.int32, device=device)], []
-            mids = []
-            for L in self.layers:
-                k, p = L["k"], L["pad"]
-                geoms.append(_lib.ConvGeom(N, L["cin"], H, W, L["cout"], k, k, 1, 1, p, p, 1, 1, L["groups"], 0))
-                H, W = H + 2 * p - k + 1, W + 2 * p - k + 1
-                pool = L["pool_ksp"]
-                if pool and (min(H, W) + 2 * pool[2] < pool[0] or (L["pool"] == 1 and (H % 2 or W % 2))):
-                    raise _err("wbwtab_compile_bits: %s: the max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
-                mids.append(torch.empty((N, (L["cout"] + 31) // 32, H, W), dtype=torch.int32, device=device) if pool and not L["pool"] else None)
-                if pool:
-                    H, W = (H + 2 * pool[2] - pool[0]) // pool[1] + 1, (W + 2 * pool[2] - pool[0]) // pool[1] + 1
-                bufs.append(torch.empty((N, (L["cout"] + 31) // 32, H, W), dtype=torch.int32, device=device))
-                Cc = L["cout"]
-            if self.bit_ends:
-                if not _lib.get_lib().mn_bitsconv1x1_small_supported(Cc, H * W, self.last.conv.out_channels):
-                    raise _err("wbwtab_compile_bits(bit_ends=True): %s.conv: a %d-channel %d x %d map is not covered by mn_bitsconv1x1_small_fwd (its lanes own 4 consecutive "
-                               "pixels: H * W %% 4 == 0; the weights in LDS)" % (self.report[-1]["name"], Cc, H, W))
-                self._ws[key] = (bufs, geoms, None, mids, g0)
-                return self._ws[key]
-            if (H * W) % 4:
-                raise _err("wbwtab_compile_bits: %s: its %d x %d output cannot be unpacked for the last conv (mn_bits_unpack_sign8 needs H * W %% 4 == 0)"
-                           % (self.layers[-1]["name"], H, W))
-            self._ws[key] = (bufs, geoms, torch.empty((N, Cc, H, W), dtype=torch.int8, device=device), mids, g0)
-        return self._ws[key]
+        N, Cc, H, W = shape
+        g0 = None
+        if self.bit_ends:
+            import ctypes as C
+            conv = self.first.conv
+            g0 = _lib.ConvGeom(N, conv.in_channels, H, W, Cc, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.stride[1], conv.padding[0], conv.padding[1],
+                               conv.dilation[0], conv.dilation[1], conv.groups, 0)
+            if not _lib.get_lib().mn_conv2d_first_sign_bits_supported(C.byref(g0)):
+                raise _err("wbwtab_compile_bits(bit_ends=True): %s.conv: a %d x %d x %d x %d input is not covered by mn_conv2d_first_sign_bits (W %% 4 == 0, H * W %% 32 == 0, "
+                           "the image strip in LDS)" % (self.report[0]["name"], N, conv.in_channels, H, W))
+        bufs, geoms = [torch.empty((N, (Cc + 31) // 32, H, W), dtype=torch.int32, device=device)], []
+        mids = []
+        for L in self.layers:
+            k, p = L["k"], L["pad"]
+            geoms.append(_block_geom(L, N, H, W))
+            H, W = H + 2 * p - k + 1, W + 2 * p - k + 1
+            pool = L["pool_ksp"]
+            if pool and (min(H, W) + 2 * pool[2] < pool[0] or (L["pool"] == 1 and (H % 2 or W % 2))):
+                raise _err("wbwtab_compile_bits: %s: the max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
+            mids.append(torch.empty((N, (L["cout"] + 31) // 32, H, W), dtype=torch.int32, device=device) if pool and not L["pool"] else None)
+            if pool:
+                H, W = (H + 2 * pool[2] - pool[0]) // pool[1] + 1, (W + 2 * pool[2] - pool[0]) // pool[1] + 1
+            bufs.append(torch.empty((N, (L["cout"] + 31) // 32, H, W), dtype=torch.int32, device=device))
+            Cc = L["cout"]
+        if self.bit_ends:
+            if not _lib.get_lib().mn_bitsconv1x1_small_supported(Cc, H * W, self.last.conv.out_channels):
+                raise _err("wbwtab_compile_bits(bit_ends=True): %s.conv: a %d-channel %d x %d map is not covered by mn_bitsconv1x1_small_fwd (its lanes own 4 consecutive "
+                           "pixels: H * W %% 4 == 0; the weights in LDS)" % (self.report[-1]["name"], Cc, H, W))
+            return (bufs, geoms, None, mids, g0)
+        if (H * W) % 4:
+            raise _err("wbwtab_compile_bits: %s: its %d x %d output cannot be unpacked for the last conv (mn_bits_unpack_sign8 needs H * W %% 4 == 0)"
+                       % (self.layers[-1]["name"], H, W))
+        return (bufs, geoms, torch.empty((N, Cc, H, W), dtype=torch.int8, device=device), mids, g0)
 
     @torch.no_grad()
     def forward(self, x):
@@ -311,7 +377,7 @@ class BitPlan(nn.Module):
             if not (type(x) is torch.Tensor and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == conv.in_channels):
                 raise _err("wbwtab_compile_bits(bit_ends=True): the input must be a float32 GPU tensor [N, %d, H, W] (no CPU fallback)" % conv.in_channels)
             x = x.contiguous()
-            bufs, geoms, a8, mids, g0 = self._plan_buffers((x.shape[0], conv.out_channels, x.shape[2], x.shape[3]), x.device)
+            bufs, geoms, a8, mids, g0 = self._shape_buffers((x.shape[0], conv.out_channels, x.shape[2], x.shape[3]), x.device)
             st = ops._s()
             ops._call("mn_conv2d_first_sign_bits", C.byref(g0), ops._p(x), ops._p(ops._chk(conv.weight.detach(), "weight")), ops._p(ops._chk(conv.bias, "bias")),
                       ops._p(bufs[0]), st)
@@ -321,7 +387,7 @@ class BitPlan(nn.Module):
                 raise _err("wbwtab_compile_bits: the first block did not produce packed signs (input must be a contiguous float32 GPU tensor with H * W % 4 == 0)")
             codes = a.codes.contiguous()
             N, Cc, H, W = codes.shape
-            bufs, geoms, a8, mids, _ = self._plan_buffers(codes.shape, codes.device)
+            bufs, geoms, a8, mids, _ = self._shape_buffers(codes.shape, codes.device)
             st = ops._s()
             ops._call("mn_bits_pack_sign8", ops._p(codes), N, Cc, H * W, ops._p(bufs[0]), st)
         for i, L in enumerate(self.layers):
@@ -340,40 +406,43 @@ class BitPlan(nn.Module):
             y = torch.empty((n_, conv.out_channels, h_, w_), dtype=torch.float32, device=bufs[-1].device)
             ops._call("mn_bitsconv1x1_small_fwd", ops._p(bufs[-1]), ops._p(ops._chk(conv.weight.detach(), "weight")), ops._p(ops._chk(conv.bias, "bias")), ops._p(y),
                       n_, conv.in_channels, h_ * w_, conv.out_channels, st)
-            kids = list(self.last.children())
-            for m in kids[kids.index(conv) + 1:]:          # what follows the conv inside the last block (Identity, ReLU)
-                y = m(y)
+            y = self._after_conv(self.last, conv, y)          # (Identity, ReLU)
         else:
             n_, c_, h_, w_ = a8.shape
             ops._call("mn_bits_unpack_sign8", ops._p(bufs[-1]), n_, c_, h_ * w_, ops._p(a8), st)
             y = self.last(SignTensor(a8))
-        for m in self.tail:
-            y = m(y)
-        return y.view(y.size(0), -1) if self.flatten else y
+        return self._finish(y)
 
 
-def _check_bit_ends(first, nm_first, last, nm_last):
-    """``bit_ends=True``: both ends must be covered by their bit kernels -- never a silent byte path.  Shape-independent part (the input shape is checked by the plan)."""
-    import ctypes as C
+def _check_ends(who, first, nm_first, last, nm_last, first_kernel, first_supported, last_kernel, last_supported):
+    """Both ends must be covered by their kernels -- never a silent byte path.  Shape-independent part (the input shape is checked by the plan).  ``first_supported(g)``
+    / ``last_supported(cin, hw, cout)``: the library's verdicts; ``*_kernel``: the names in the messages."""
     from micronet_amd import _lib
-    lib = _lib.get_lib()
     conv = first.conv
     if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
-        raise _err("wbwtab_compile_bits(bit_ends=True): %s.conv: padding mode not covered by mn_conv2d_first_sign_bits" % nm_first)
+        raise _err("%s: %s.conv: padding mode not covered by %s" % (who, nm_first, first_kernel))
     g = _lib.ConvGeom(1, conv.in_channels, 8, 8, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.stride[1], conv.padding[0], conv.padding[1],
                       conv.dilation[0], conv.dilation[1], conv.groups, 0)
-    if not lib.mn_conv2d_first_sign_bits_supported(C.byref(g)):
-        raise _err("wbwtab_compile_bits(bit_ends=True): %s.conv: not covered by mn_conv2d_first_sign_bits (%dx%d, stride %d, padding %d, dilation %d, groups %d, %d taps per "
-                   "output: needs \"same\" padding, stride 1, groups 1, at most 76 taps)"
-                   % (nm_first, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.padding[0], conv.dilation[0], conv.groups,
-                      conv.in_channels // conv.groups * conv.kernel_size[0] * conv.kernel_size[1]))
+    if not first_supported(g):
+        raise _err("%s: %s.conv: not covered by %s (%dx%d, stride %d, padding %d, dilation %d, groups %d, %d taps per output: needs \"same\" padding, stride 1, groups 1, "
+                   "at most 76 taps)" % (who, nm_first, first_kernel, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.padding[0], conv.dilation[0], conv.groups,
+                                         conv.in_channels // conv.groups * conv.kernel_size[0] * conv.kernel_size[1]))
     conv = last.conv
     one = lambda v, k: tuple(v) == (k, k)
     if not (conv.padding_mode == "zeros" and not isinstance(conv.padding, str) and one(conv.kernel_size, 1) and one(conv.stride, 1) and one(conv.padding, 0) and
-            one(conv.dilation, 1) and conv.groups == 1 and lib.mn_bitsconv1x1_small_supported(conv.in_channels, 4, conv.out_channels)):
-        raise _err("wbwtab_compile_bits(bit_ends=True): %s.conv: the last conv is not the small 1x1 classifier mn_bitsconv1x1_small_fwd covers (%dx%d, stride %d, padding %s, "
-                   "groups %d, %d -> %d channels: needs 1x1, stride 1, no padding, groups 1, at most 16 outputs)"
-                   % (nm_last, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.padding, conv.groups, conv.in_channels, conv.out_channels))
+            one(conv.dilation, 1) and conv.groups == 1 and last_supported(conv.in_channels, 4, conv.out_channels)):
+        raise _err("%s: %s.conv: the last conv is not the small 1x1 classifier %s covers (%dx%d, stride %d, padding %s, groups %d, %d -> %d channels: needs 1x1, stride 1, "
+                   "no padding, groups 1, at most 16 outputs)"
+                   % (who, nm_last, last_kernel, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.padding, conv.groups, conv.in_channels, conv.out_channels))
+
+
+def _check_bit_ends(first, nm_first, last, nm_last):
+    """``bit_ends=True``: ``_check_ends`` for the two bit kernels, and no channel shuffle in front of the last conv."""
+    import ctypes as C
+    from micronet_amd import _lib
+    lib = _lib.get_lib()
+    _check_ends("wbwtab_compile_bits(bit_ends=True)", first, nm_first, last, nm_last, "mn_conv2d_first_sign_bits", lambda g: lib.mn_conv2d_first_sign_bits_supported(C.byref(g)),
+                "mn_bitsconv1x1_small_fwd", lib.mn_bitsconv1x1_small_supported)
     if getattr(last, "channel_shuffle_flag", 0) and getattr(last, "shuffle_groups", 1) > 1:
         raise _err("wbwtab_compile_bits(bit_ends=True): %s: a channel shuffle in front of the last conv is not covered by mn_bitsconv1x1_small_fwd" % nm_last)
 
@@ -386,13 +455,7 @@ def _walk_bits(model, bit_ends=False, mfma_blocks=False, mfma_k3=False):
     from micronet_amd import _lib
     from micronet_amd.nn import Conv2dFirst
     from micronet_amd.quantization.wbwtab import quantize
-    if isinstance(model, nn.Sequential):
-        seq, prefix, flatten = model, "", False
-    else:
-        kids = list(model.named_children())
-        if len(kids) != 1 or not isinstance(kids[0][1], nn.Sequential):
-            raise _err("wbwtab_compile_bits: module order not recognised (%s: expected an nn.Sequential of blocks, or the reference's Net holding one)" % type(model).__name__)
-        seq, prefix, flatten = kids[0][1], kids[0][0] + ".", True          # models/nin_gc.py:144-147: forward = model(x).view(N, -1)
+    seq, prefix, flatten = _net_sequence(model, "wbwtab_compile_bits")
     for n_, m in model.named_modules():
         if isinstance(m, quantize.ActivationQuantizer) and m.A != 2:
             raise _err("wbwtab_compile_bits: %s has A = %d; only binary activations (A = 2) are bit-packed" % (n_, m.A))
@@ -440,17 +503,12 @@ def _walk_bits(model, bit_ends=False, mfma_blocks=False, mfma_k3=False):
         if tuple(conv.stride) != (1, 1) or tuple(conv.dilation) != (1, 1) or conv.padding_mode != "zeros" or isinstance(conv.padding, str):
             raise _err("wbwtab_compile_bits: %s.conv: stride / dilation other than 1 (or non-zero padding mode) is not covered by the bit kernels" % nm)
         k, pad = conv.kernel_size[0], conv.padding[0]
-        shuffle = int(getattr(conv, "in_shuffle_groups", 0) or 0)
-        if getattr(child, "channel_shuffle_flag", 0) and getattr(child, "shuffle_groups", 1) > 1:
-            if shuffle > 1:
-                raise _err("wbwtab_compile_bits: %s: two channel shuffles in front of one conv" % nm)
-            shuffle = int(child.shuffle_groups)
+        shuffle = _shuffle_in_front("wbwtab_compile_bits", nm, child, conv)
         g = _lib.ConvGeom(1, conv.in_channels, 4, 4, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], 1, 1, conv.padding[0], conv.padding[1], 1, 1, conv.groups, 0)
         if not _lib.get_lib().mn_bitconv_supported(C.byref(g)):
             raise _err("wbwtab_compile_bits: %s.conv: geometry not covered by mn_bitconv_supported (%dx%d, padding %d, groups %d)" % (nm, k, conv.kernel_size[1], pad, conv.groups))
-        if shuffle > 1:
-            if conv.in_channels % shuffle:
-                raise _err("wbwtab_compile_bits: %s: %d input channels cannot be shuffled in %d groups" % (nm, conv.in_channels, shuffle))
+        if shuffle:
+            _check_shuffle_divides("wbwtab_compile_bits", nm, conv, shuffle)
             if not layers:
                 raise _err("wbwtab_compile_bits: %s: a channel shuffle directly behind the first block is not covered (its producer is not a bit block)" % nm)
             layers[-1]["shuffle"] = shuffle          # folded into the producer's row order
@@ -509,21 +567,15 @@ def wbwtab_compile_bits(model, bit_ends=False, mfma_blocks=False, mfma_k3=False)
     import ctypes as C
     from micronet_amd import _lib, ops
     first, layers, last, tail, flatten, report = _walk_bits(model, bit_ends, mfma_blocks, mfma_k3)
-    for p_ in model.parameters():
-        if not p_.is_cuda:
-            raise _err("wbwtab_compile_bits: the model is on %s: micronet_amd runs on MI355X only (no CPU fallback)" % p_.device)
+    _require_gpu(model, "wbwtab_compile_bits")
     # ---- pack the weight tables (one launch per layer, once per model)
     lib = _lib.get_lib()
     for L in layers:
         conv = L.pop("conv")
-        k, p = L["k"], L["pad"]
-        g = _lib.ConvGeom(1, L["cin"], 4, 4, L["cout"], k, k, 1, 1, p, p, 1, 1, L["groups"], 0)
+        g = _block_geom(L)
         quartet = "mn_bitconv_mfma" if L.get("mfma") else "mn_bitconv_mfma3" if L.get("mfma3") else "mn_bitconv"
         table = torch.empty(int(getattr(lib, quartet + "_table_bytes")(C.byref(g))) // 4, dtype=torch.int32, device=conv.weight.device)
-        order = None
-        if L["shuffle"] > 1:          # position j of the consumer's shuffled input is this layer's channel (j % s) * (C / s) + j // s (models/nin_gc.py:4-15)
-            j = torch.arange(L["cout"], device=conv.weight.device)
-            order = ((j % L["shuffle"]) * (L["cout"] // L["shuffle"]) + j // L["shuffle"]).to(torch.int32).contiguous()
+        order = _shuffle_order(L["cout"], L["shuffle"], conv.weight.device) if L["shuffle"] > 1 else None
         w = conv.weight.detach().float().contiguous()
         b = conv.bias.detach().float().contiguous() if conv.bias is not None else None
         ops._call(quartet + "_pack", C.byref(g), ops._p(w), ops._p(b), ops._p(order), ops._p(table), ops._s())
@@ -592,7 +644,7 @@ def _codeconv_tile_kernel_name(k, cin):
     return "k_codeconv_tile<%d,%d>" % (k, 3 if (cin + 31) // 32 == 3 else 0)
 
 
-class CodePlan(nn.Module):
+class CodePlan(_Plan):
     """What ``dorefa_compile_codes`` returns: first block (fp32 conv + BatchNorm + ReLU + the next conv's quantizer, the model's own module) -> plane pack -> n
     code blocks (2x2 max-pools folded in; with ``tile_blocks`` also the dense 5x5 block on an LDS tile, and a max-pool that ``prepare()`` did not fuse run on the planes
     behind its block) -> plane unpack -> last block and tail (the model's own modules).  Eval only; owns the packed weight tables (and the
@@ -602,74 +654,59 @@ class CodePlan(nn.Module):
     planes per word group in every buffer, the width of pack / unpack and of the codes handed to the last block; a 4-bit plan holds MFMA blocks only and no
     ``code_ends``."""
 
+    who = "dorefa_compile_codes"
+
     def __init__(self, first, layers, last, tail, flatten, report, code_ends=False, first_table=None, first_chan=None, bits=2):
-        super().__init__()
-        self.first, self.last, self.tail = first, last, nn.ModuleList(tail)
+        super().__init__(first, layers, last, tail, flatten, report)          # layers: dicts of geometry, table, chan, pool, out_order
         self.code_ends = bool(code_ends)
         self.bits = int(bits)
         if self.bits not in CODE_WIDTHS or (self.bits != CODE_BITS and (self.code_ends or not all(L.get("mfma") or L.get("mfma3") for L in layers))):
             raise _err("dorefa_compile_codes: a %d-bit plan is not covered (2-bit codes, or 4-bit codes on the int8-MFMA blocks alone and without code_ends)" % self.bits)
         self.first_table, self.first_chan = first_table, first_chan
-        self.layers = layers              # dicts: geometry, table, chan, pool, out_order
-        self.flatten = flatten
-        self.report = report
-        self.keep_stages = False          # True: forward also leaves every stage's planes in ``stage_codes`` (tests)
         self.stage_codes = []
-        self._ws = {}
-        self.eval()
-
-    def train(self, mode=True):
-        if mode:
-            raise _err("dorefa_compile_codes: the compiled plan is eval-only")
-        return super().train(False)
 
     def _plan_buffers(self, shape, device):
-        """Plane buffers (and the uint8 buffer in front of the last block) for one first-block output shape; allocated once, reused by every later call."""
+        """Plane buffers (and the uint8 buffer in front of the last block) for one first-block output shape."""
         from micronet_amd import _lib
-        key = (tuple(shape), str(device))
-        if key not in self._ws:
-            N, Cc, H, W = shape
-            B = self.bits
-            g0 = None
-            if self.code_ends:
-                import ctypes as C
-                conv = self.first.conv
-                g0 = _lib.ConvGeom(N, conv.in_channels, H, W, Cc, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.stride[1], conv.padding[0], conv.padding[1],
-                                   conv.dilation[0], conv.dilation[1], conv.groups, 0)
-                if not _lib.get_lib().mn_conv2d_first_codes_supported(C.byref(g0), CODE_BITS):
-                    raise _err("dorefa_compile_codes(code_ends=True): %s.conv: a %d x %d x %d x %d input is not covered by mn_conv2d_first_codes (W %% 4 == 0, H * W %% 32 == 0, "
-                               "the image strip in LDS)" % (self.report[0]["name"], N, conv.in_channels, H, W))
-            elif (H * W) % 4:
-                raise _err("dorefa_compile_codes: %s: its %d x %d output cannot be packed (mn_codes_pack_planes needs H * W %% 4 == 0)" % (self.report[0]["name"], H, W))
-            bufs, geoms, mids = [torch.empty((N, (Cc + 31) // 32, B, H, W), dtype=torch.int32, device=device)], [], []
-            for L in self.layers:
-                k, p = L["k"], L["pad"]
-                geoms.append(_lib.ConvGeom(N, L["cin"], H, W, L["cout"], k, k, 1, 1, p, p, 1, 1, L["groups"], 0))
-                if L["pool"]:
-                    if H % 2 or W % 2:
-                        raise _err("dorefa_compile_codes: %s: the 2x2 max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
-                    H, W = H // 2, W // 2
-                ksp = L.get("pool_ksp")          # (tile_blocks) a pool the block does not fold: the block at full size into a mid buffer, then mn_codes_maxpool
-                if ksp:
-                    if min(H, W) + 2 * ksp[2] < ksp[0]:
-                        raise _err("dorefa_compile_codes: %s: the max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
-                    mids.append(torch.empty((N, (L["cout"] + 31) // 32, B, H, W), dtype=torch.int32, device=device))
-                    H, W = (H + 2 * ksp[2] - ksp[0]) // ksp[1] + 1, (W + 2 * ksp[2] - ksp[0]) // ksp[1] + 1
-                else:
-                    mids.append(None)
-                bufs.append(torch.empty((N, (L["cout"] + 31) // 32, B, H, W), dtype=torch.int32, device=device))
-                Cc = L["cout"]
-            if self.code_ends:
-                if not _lib.get_lib().mn_planesconv1x1_small_supported(Cc, H * W, self.last.conv.out_channels, CODE_BITS):
-                    raise _err("dorefa_compile_codes(code_ends=True): %s.conv: a %d-channel %d x %d map is not covered by mn_planesconv1x1_small_fwd (its lanes own 4 "
-                               "consecutive pixels: H * W %% 4 == 0; the weights in LDS)" % (self.report[-1]["name"], Cc, H, W))
-                self._ws[key] = (bufs, geoms, None, g0, mids)
-                return self._ws[key]
-            if (H * W) % 4:
-                raise _err("dorefa_compile_codes: %s: its %d x %d output cannot be unpacked for the last block (mn_codes_unpack_planes needs H * W %% 4 == 0)"
-                           % (self.layers[-1]["name"], H, W))
-            self._ws[key] = (bufs, geoms, torch.empty((N, Cc, H, W), dtype=torch.uint8, device=device), g0, mids)
-        return self._ws[key]
+        N, Cc, H, W = shape
+        B = self.bits
+        g0 = None
+        if self.code_ends:
+            import ctypes as C
+            conv = self.first.conv
+            g0 = _lib.ConvGeom(N, conv.in_channels, H, W, Cc, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.stride[1], conv.padding[0], conv.padding[1],
+                               conv.dilation[0], conv.dilation[1], conv.groups, 0)
+            if not _lib.get_lib().mn_conv2d_first_codes_supported(C.byref(g0), CODE_BITS):
+                raise _err("dorefa_compile_codes(code_ends=True): %s.conv: a %d x %d x %d x %d input is not covered by mn_conv2d_first_codes (W %% 4 == 0, H * W %% 32 == 0, "
+                           "the image strip in LDS)" % (self.report[0]["name"], N, conv.in_channels, H, W))
+        elif (H * W) % 4:
+            raise _err("dorefa_compile_codes: %s: its %d x %d output cannot be packed (mn_codes_pack_planes needs H * W %% 4 == 0)" % (self.report[0]["name"], H, W))
+        bufs, geoms, mids = [torch.empty((N, (Cc + 31) // 32, B, H, W), dtype=torch.int32, device=device)], [], []
+        for L in self.layers:
+            geoms.append(_block_geom(L, N, H, W))
+            if L["pool"]:
+                if H % 2 or W % 2:
+                    raise _err("dorefa_compile_codes: %s: the 2x2 max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
+                H, W = H // 2, W // 2
+            ksp = L.get("pool_ksp")          # (tile_blocks) a pool the block does not fold: the block at full size into a mid buffer, then mn_codes_maxpool
+            if ksp:
+                if min(H, W) + 2 * ksp[2] < ksp[0]:
+                    raise _err("dorefa_compile_codes: %s: the max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
+                mids.append(torch.empty((N, (L["cout"] + 31) // 32, B, H, W), dtype=torch.int32, device=device))
+                H, W = (H + 2 * ksp[2] - ksp[0]) // ksp[1] + 1, (W + 2 * ksp[2] - ksp[0]) // ksp[1] + 1
+            else:
+                mids.append(None)
+            bufs.append(torch.empty((N, (L["cout"] + 31) // 32, B, H, W), dtype=torch.int32, device=device))
+            Cc = L["cout"]
+        if self.code_ends:
+            if not _lib.get_lib().mn_planesconv1x1_small_supported(Cc, H * W, self.last.conv.out_channels, CODE_BITS):
+                raise _err("dorefa_compile_codes(code_ends=True): %s.conv: a %d-channel %d x %d map is not covered by mn_planesconv1x1_small_fwd (its lanes own 4 "
+                           "consecutive pixels: H * W %% 4 == 0; the weights in LDS)" % (self.report[-1]["name"], Cc, H, W))
+            return (bufs, geoms, None, g0, mids)
+        if (H * W) % 4:
+            raise _err("dorefa_compile_codes: %s: its %d x %d output cannot be unpacked for the last block (mn_codes_unpack_planes needs H * W %% 4 == 0)"
+                       % (self.layers[-1]["name"], H, W))
+        return (bufs, geoms, torch.empty((N, Cc, H, W), dtype=torch.uint8, device=device), g0, mids)
 
     def _run_layers(self, bufs, geoms, mids, st):
         """One launch per hidden block (two where a max-pool runs on the planes behind it)."""
@@ -701,7 +738,7 @@ class CodePlan(nn.Module):
                 raise _err("dorefa_compile_codes(code_ends=True): the input must be a float32 GPU tensor [N, %d, H, W] (no CPU fallback)" % conv.in_channels)
             x = x.contiguous()
             with torch.cuda.device(x.device):
-                bufs, geoms, c8, g0, mids = self._plan_buffers((x.shape[0], conv.out_channels, x.shape[2], x.shape[3]), x.device)
+                bufs, geoms, c8, g0, mids = self._shape_buffers((x.shape[0], conv.out_channels, x.shape[2], x.shape[3]), x.device)
                 st = ops._s()
                 ops._call("mn_conv2d_first_codes", C.byref(g0), ops._p(x), ops._p(ops._chk(conv.weight.detach(), "weight")), ops._p(ops._chk(conv.bias, "bias")),
                           ops._p(self.first_table), ops._p(bufs[0]), st)
@@ -713,12 +750,7 @@ class CodePlan(nn.Module):
                 y = torch.empty((n_, conv.out_channels, h_, w_), dtype=torch.float32, device=x.device)
                 ops._call("mn_planesconv1x1_small_fwd", ops._p(bufs[-1]), CODE_BITS, ops._p(ops._chk(conv.weight.detach(), "weight")), ops._p(ops._chk(conv.bias, "bias")),
                           ops._p(y), n_, conv.in_channels, h_ * w_, conv.out_channels, st)
-            kids = list(self.last.children())
-            for m in kids[kids.index(conv) + 1:]:          # what follows the conv inside the last block (BatchNorm + ReLU)
-                y = m(y)
-            for m in self.tail:
-                y = m(y)
-            return y.view(y.size(0), -1) if self.flatten else y
+            return self._finish(self._after_conv(self.last, conv, y))          # (BatchNorm + ReLU)
         B = self.bits
         a = self.first(x)
         if not (isinstance(a, QActTensor) and a.bits == B):
@@ -726,7 +758,7 @@ class CodePlan(nn.Module):
                        % (self.report[0]["name"], B))
         codes = a.codes.contiguous()
         N, Cc, H, W = codes.shape
-        bufs, geoms, c8, _, mids = self._plan_buffers(codes.shape, codes.device)
+        bufs, geoms, c8, _, mids = self._shape_buffers(codes.shape, codes.device)
         st = ops._s()
         ops._call("mn_codes_pack_planes", ops._p(codes), N, Cc, H * W, B, ops._p(bufs[0]), st)
         self._run_layers(bufs, geoms, mids, st)
@@ -735,36 +767,19 @@ class CodePlan(nn.Module):
         n_, c_, h_, w_ = c8.shape
         ops._call("mn_codes_unpack_planes", ops._p(bufs[-1]), n_, c_, h_ * w_, B, ops._p(c8), st)
         # (materialize: a consumer that does not read codes re-quantises 10 j s to j -- the middle of the code's bin)
-        y = self.last(QActTensor(c8, B, lambda: c8.float() * (10.0 / (2 ** B - 1))))
-        for m in self.tail:
-            y = m(y)
-        return y.view(y.size(0), -1) if self.flatten else y
+        return self._finish(self.last(QActTensor(c8, B, lambda: c8.float() * (10.0 / (2 ** B - 1)))))
 
 
 def _check_code_ends(first, nm_first, last, nm_last):
-    """``code_ends=True``: both ends must be covered by their plane kernels -- never a silent byte path.  Shape-independent part (the input shape is checked by the plan;
-    the walk has already refused a pool behind the first block, other than 2-bit codes out of it, and a channel shuffle in front of the last block)."""
+    """``code_ends=True``: ``_check_ends`` for the two plane kernels, and no channel shuffle in front of the last conv (the walk has already refused a pool behind the
+    first block, other than 2-bit codes out of it, and a block's shuffle in front of the last block)."""
     import ctypes as C
     from micronet_amd import _lib
     lib = _lib.get_lib()
-    conv = first.conv
-    if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
-        raise _err("dorefa_compile_codes(code_ends=True): %s.conv: padding mode not covered by mn_conv2d_first_codes" % nm_first)
-    g = _lib.ConvGeom(1, conv.in_channels, 8, 8, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.stride[1], conv.padding[0], conv.padding[1],
-                      conv.dilation[0], conv.dilation[1], conv.groups, 0)
-    if not lib.mn_conv2d_first_codes_supported(C.byref(g), CODE_BITS):
-        raise _err("dorefa_compile_codes(code_ends=True): %s.conv: not covered by mn_conv2d_first_codes (%dx%d, stride %d, padding %d, dilation %d, groups %d, %d taps per "
-                   "output: needs \"same\" padding, stride 1, groups 1, at most 76 taps)"
-                   % (nm_first, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.padding[0], conv.dilation[0], conv.groups,
-                      conv.in_channels // conv.groups * conv.kernel_size[0] * conv.kernel_size[1]))
-    conv = last.conv
-    one = lambda v, k: tuple(v) == (k, k)
-    if not (conv.padding_mode == "zeros" and not isinstance(conv.padding, str) and one(conv.kernel_size, 1) and one(conv.stride, 1) and one(conv.padding, 0) and
-            one(conv.dilation, 1) and conv.groups == 1 and lib.mn_planesconv1x1_small_supported(conv.in_channels, 4, conv.out_channels, CODE_BITS)):
-        raise _err("dorefa_compile_codes(code_ends=True): %s.conv: the last conv is not the small 1x1 classifier mn_planesconv1x1_small_fwd covers (%dx%d, stride %d, "
-                   "padding %s, groups %d, %d -> %d channels: needs 1x1, stride 1, no padding, groups 1, at most 16 outputs)"
-                   % (nm_last, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.padding, conv.groups, conv.in_channels, conv.out_channels))
-    if getattr(last, "channel_shuffle_flag", 0) and getattr(last, "shuffle_groups", 1) > 1 or int(getattr(conv, "in_shuffle_groups", 0) or 0) > 1:
+    _check_ends("dorefa_compile_codes(code_ends=True)", first, nm_first, last, nm_last, "mn_conv2d_first_codes",
+                lambda g: lib.mn_conv2d_first_codes_supported(C.byref(g), CODE_BITS), "mn_planesconv1x1_small_fwd",
+                lambda cin, hw, cout: lib.mn_planesconv1x1_small_supported(cin, hw, cout, CODE_BITS))
+    if getattr(last, "channel_shuffle_flag", 0) and getattr(last, "shuffle_groups", 1) > 1 or int(getattr(last.conv, "in_shuffle_groups", 0) or 0) > 1:
         raise _err("dorefa_compile_codes(code_ends=True): %s: a channel shuffle in front of the last conv is not covered by mn_planesconv1x1_small_fwd" % nm_last)
 
 
@@ -779,13 +794,7 @@ def _walk_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False, mf
     from micronet_amd import _lib
     from micronet_amd.nn import Conv2dFirst
     from micronet_amd.quantization.wqaq.dorefa import quantize
-    if isinstance(model, nn.Sequential):
-        seq, prefix, flatten = model, "", False
-    else:
-        kids = list(model.named_children())
-        if len(kids) != 1 or not isinstance(kids[0][1], nn.Sequential):
-            raise _err("dorefa_compile_codes: module order not recognised (%s: expected an nn.Sequential of blocks, or the reference's Net holding one)" % type(model).__name__)
-        seq, prefix, flatten = kids[0][1], kids[0][0] + ".", True          # models/nin_gc.py:144-147: forward = model(x).view(N, -1)
+    seq, prefix, flatten = _net_sequence(model, "dorefa_compile_codes")
     blocks = [(prefix + n_, m) for n_, m in seq.named_children() if quantize._is_ref_block(m) and isinstance(getattr(m, "conv", None), nn.Conv2d)]
     if len(blocks) < 3:
         raise _err("dorefa_compile_codes: module order not recognised (needs a first block, at least one quantised hidden block and a last block)")
@@ -902,13 +911,9 @@ def _walk_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False, mf
             first = child
             report.append(dict(name=nm, kind="first", K=K, words=0, planes=0, kernel="first conv + k_qa_fwd, k_codes_pack", pooled=False, out_order="identity", stage=name))
             continue
-        shuffle = int(getattr(conv, "in_shuffle_groups", 0) or 0)
-        if getattr(child, "channel_shuffle_flag", 0) and getattr(child, "shuffle_groups", 1) > 1:
-            if shuffle > 1:
-                raise _err("dorefa_compile_codes: %s: two channel shuffles in front of one conv" % nm)
-            shuffle = int(child.shuffle_groups)
+        shuffle = _shuffle_in_front("dorefa_compile_codes", nm, child, conv)
         if child is blocks[-1][1]:
-            if shuffle > 1:
+            if shuffle:
                 raise _err("dorefa_compile_codes: %s: a channel shuffle in front of the last block is not covered" % nm)
             last = child
             report.append(dict(name=nm, kind="last", K=K, words=(conv.in_channels + 31) // 32, planes=B, kernel="k_codes_unpack, last block on byte codes",
@@ -922,9 +927,8 @@ def _walk_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False, mf
             wants = True
         elif bn.q_out_bits != B:
             raise _err("dorefa_compile_codes: %s: its output is not handed over as %d-bit codes to the next quantised conv" % (nm, B))
-        if shuffle > 1:
-            if conv.in_channels % shuffle:
-                raise _err("dorefa_compile_codes: %s: %d input channels cannot be shuffled in %d groups" % (nm, conv.in_channels, shuffle))
+        if shuffle:
+            _check_shuffle_divides("dorefa_compile_codes", nm, conv, shuffle)
             if not layers:
                 raise _err("dorefa_compile_codes: %s: a channel shuffle directly behind the first block is not covered (its producer is not a code block)" % nm)
             layers[-1]["shuffle"] = shuffle          # folded into the producer's row order
@@ -984,6 +988,20 @@ def dorefa_codes_report(model, code_ends=False, tile_blocks=False, mfma_blocks=F
     return _walk_codes(model, code_ends, tile_blocks, mfma_blocks, mfma_k3)[5]
 
 
+def _bn_chan_constants(bn, O, gamma, beta):
+    """The [9][O] constants of an eval-mode BatchNorm + quantizer on an fp32 map, by the calls its eval forward makes (ops._bn_front: mn_bn_save_stats with training = 0,
+    mn_qa_chan_from_save -- invstd is never re-derived here).  They do not depend on the input, so one 8 x 8 map of zeros will do."""
+    from micronet_amd import _lib, ops
+    dev = gamma.device
+    zero = torch.zeros((1, O, 8, 8), dtype=torch.float32, device=dev)
+    save = torch.empty((2, O), dtype=torch.float32, device=dev)
+    chan = torch.empty((_lib.MN_QA_NCH, O), dtype=torch.float32, device=dev)
+    ws = torch.empty(int(_lib.get_lib().mn_bnsign_ws_floats(O)), dtype=torch.float32, device=dev)
+    ops._call("mn_bn_save_stats", ops._p(zero), 1, O, 64, float(bn.eps), float(bn.momentum), 0, ops._p(bn.running_mean), ops._p(bn.running_var), ops._p(save), ops._p(ws), ops._s())
+    ops._call("mn_qa_chan_from_save", ops._p(save), ops._p(gamma), ops._p(beta), O, ops._p(chan), ops._s())
+    return chan
+
+
 @torch.no_grad()
 def dorefa_compile_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False, mfma_k3=False):
     """``model``: a DoReFa W2A2 (or W4A4: last paragraph) net prepared with ``quant_inference=True`` after ``prequantize_weights``, on the GPU (the reference's ``nin_gc``, or an ``nn.Sequential``
@@ -1020,13 +1038,10 @@ def dorefa_compile_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=
     if code_ends and not _weight_is_coded(last.conv):
         raise _err("dorefa_compile_codes(code_ends=True): %s.conv: the stored weights were not found on the 2-bit grid (2k - 3) / 3 (run inference.prequantize_weights "
                    "on the GPU model first)" % report[-1]["name"])
-    for p_ in model.parameters():
-        if not p_.is_cuda:
-            raise _err("dorefa_compile_codes: the model is on %s: micronet_amd runs on MI355X only (no CPU fallback)" % p_.device)
+    _require_gpu(model, "dorefa_compile_codes")
     lib = _lib.get_lib()
     for L in layers:
         conv, bn = L.pop("conv"), L.pop("bn")
-        k, p = L["k"], L["pad"]
         dev = conv.weight.device
         w = conv.weight.detach().float().contiguous()
         b = conv.bias.detach().float().contiguous() if conv.bias is not None else None
@@ -1036,14 +1051,14 @@ def dorefa_compile_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=
             if not (bn.affine and bn.track_running_stats and bn.momentum is not None):
                 raise _err("dorefa_compile_codes: %s.bn: needs affine parameters, running statistics and a momentum" % L["name"])
             gamma, beta = ops._chk(bn.weight.detach(), "weight"), ops._chk(bn.bias.detach(), "bias")
-            g8 = _lib.ConvGeom(1, L["cin"], 8, 8, L["cout"], k, k, 1, 1, p, p, 1, 1, L["groups"], 0)
+            g8 = _block_geom(L, 1, 8, 8)
             wd = ops._wq_dorefa(B, None, 0)
-            save = torch.empty((2, L["cout"]), dtype=torch.float32, device=dev)
-            chan = torch.empty((_lib.MN_QA_NCH, L["cout"]), dtype=torch.float32, device=dev)
             tile = bool(L.get("tile"))
             if not tile and lib.mn_qconv_bnq_supported(C.byref(g8), C.byref(wd), B) and int(lib.mn_qconv_bnq_stash_bits(C.byref(g8), C.byref(wd), B)) == 16:
                 # the fused block: the conv on codes with training = 0 writes the constants from the running statistics (alpha = weight scale x activation scale)
                 zero = torch.zeros((1, L["cin"], 8, 8), dtype=torch.uint8, device=dev)
+                save = torch.empty((2, L["cout"]), dtype=torch.float32, device=dev)
+                chan = torch.empty((_lib.MN_QA_NCH, L["cout"]), dtype=torch.float32, device=dev)
                 stash = torch.empty((1, L["cout"], 8, 8), dtype=torch.int16, device=dev)
                 nb = int(lib.mn_qconv_bnq_ws_bytes(C.byref(g8)))
                 ws = torch.empty(nb // 4 + 4, dtype=torch.float32, device=dev)
@@ -1053,23 +1068,16 @@ def dorefa_compile_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=
                 # a block the stash conv does not cover (narrow groups) -- and, by the same route, the tiled 5x5 block: its eval forward convolves to fp32
                 # y = acc * alpha + bias (the code kernels' epilogue) and
                 # takes (mean, invstd) from mn_bn_save_stats -- the same two calls here; rows alpha / bias (1 / 0 for an fp32 input) become the epilogue's
-                zero = torch.zeros((1, L["cout"], 8, 8), dtype=torch.float32, device=dev)
-                ws = torch.empty(int(lib.mn_bnsign_ws_floats(L["cout"])), dtype=torch.float32, device=dev)
-                ops._call("mn_bn_save_stats", ops._p(zero), 1, L["cout"], 64, float(bn.eps), float(bn.momentum), 0, ops._p(bn.running_mean), ops._p(bn.running_var),
-                          ops._p(save), ops._p(ws), ops._s())
-                ops._call("mn_qa_chan_from_save", ops._p(save), ops._p(gamma), ops._p(beta), L["cout"], ops._p(chan), ops._s())
+                chan = _bn_chan_constants(bn, L["cout"], gamma, beta)
                 sc = torch.tensor(1.0 / (2 ** B - 1), dtype=torch.float32, device=dev)
                 chan[0] = sc * sc          # fp32 product of the weight and the activation scale, as k_qa_stats_prep forms it
                 chan[1] = b if b is not None else 0.0
                 chan[6], chan[7] = chan[0] * chan[3], (chan[1] - chan[2]) * chan[3]
             # ---- the table (one launch per layer, once per model)
-            g = _lib.ConvGeom(1, L["cin"], 4, 4, L["cout"], k, k, 1, 1, p, p, 1, 1, L["groups"], 0)
+            g = _block_geom(L)
             quartet = "mn_codeconv_tile" if tile else "mn_codeconv_mfma" if L.get("mfma") else "mn_codeconv_mfma3" if L.get("mfma3") else "mn_codeconv"
             table = torch.empty(int(getattr(lib, quartet + "_table_bytes")(C.byref(g), B, B, B)) // 4, dtype=torch.int32, device=dev)
-            order = None
-            if L["shuffle"] > 1:          # position j of the consumer's shuffled input is this layer's channel (j % s) * (C / s) + j // s (models/nin_gc.py:4-15)
-                j = torch.arange(L["cout"], device=dev)
-                order = ((j % L["shuffle"]) * (L["cout"] // L["shuffle"]) + j // L["shuffle"]).to(torch.int32).contiguous()
+            order = _shuffle_order(L["cout"], L["shuffle"], dev) if L["shuffle"] > 1 else None
             ops._call(quartet + "_pack", C.byref(g), ops._p(w), ops._p(chan), B, B, B, ops._p(order), ops._p(table), ops._s())
         L["table"], L["chan"], L["out_order"] = table, chan, order
     for L in layers:          # (compile time: the one place a host read-back is allowed)
@@ -1080,21 +1088,13 @@ def dorefa_compile_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=
             raise _err("dorefa_compile_codes: %s.conv: %d table rows with a weight off the %d-bit grid or a bad channel order" % (L["name"], bad, B))
     if not code_ends:
         return CodePlan(first, layers, last, tail, flatten, report, bits=B)
-    # ---- the first block's per-channel thresholds: its [9][O] constants by the calls its eval forward makes (ops._bn_front on fp32 y: mn_bn_save_stats with
-    #      training = 0, mn_qa_chan_from_save -- invstd is never re-derived here); they do not depend on the input, so one 8 x 8 map of zeros will do
+    # ---- the first block's per-channel thresholds, from its [9][O] constants
     bn, nm = first.bn, report[0]["name"]
     if not (bn.affine and bn.track_running_stats and bn.momentum is not None):
         raise _err("dorefa_compile_codes(code_ends=True): %s.bn: needs affine parameters, running statistics and a momentum" % nm)
     dev, Oc = first.conv.weight.device, first.conv.out_channels
     with torch.cuda.device(dev):
-        gamma, beta = ops._chk(bn.weight.detach(), "weight"), ops._chk(bn.bias.detach(), "bias")
-        zero = torch.zeros((1, Oc, 8, 8), dtype=torch.float32, device=dev)
-        save = torch.empty((2, Oc), dtype=torch.float32, device=dev)
-        chan = torch.empty((_lib.MN_QA_NCH, Oc), dtype=torch.float32, device=dev)
-        ws = torch.empty(int(lib.mn_bnsign_ws_floats(Oc)), dtype=torch.float32, device=dev)
-        ops._call("mn_bn_save_stats", ops._p(zero), 1, Oc, 64, float(bn.eps), float(bn.momentum), 0, ops._p(bn.running_mean), ops._p(bn.running_var), ops._p(save),
-                  ops._p(ws), ops._s())
-        ops._call("mn_qa_chan_from_save", ops._p(save), ops._p(gamma), ops._p(beta), Oc, ops._p(chan), ops._s())
+        chan = _bn_chan_constants(bn, Oc, ops._chk(bn.weight.detach(), "weight"), ops._chk(bn.bias.detach(), "bias"))
         table = torch.empty(int(lib.mn_conv2d_first_codes_table_bytes(Oc, CODE_BITS)) // 4, dtype=torch.int32, device=dev)
         ops._call("mn_conv2d_first_codes_pack", ops._p(chan), Oc, CODE_BITS, ops._p(table), ops._s())
     nonfinite = int(table[0])          # (compile time: read back once)
@@ -1128,13 +1128,7 @@ def _walk_iao8(model, input_hw=(32, 32)):
     from micronet_amd import _lib
     from micronet_amd.quantization.wqaq.dorefa.quantize import _is_ref_block
     from micronet_amd.quantization.wqaq.iao import quantize
-    if isinstance(model, nn.Sequential):
-        seq, prefix, flatten = model, "", False
-    else:
-        kids = list(model.named_children())
-        if len(kids) != 1 or not isinstance(kids[0][1], nn.Sequential):
-            raise _err("iao_compile_int8: module order not recognised (%s: expected an nn.Sequential of blocks, or the reference's Net holding one)" % type(model).__name__)
-        seq, prefix, flatten = kids[0][1], kids[0][0] + ".", True
+    seq, prefix, flatten = _net_sequence(model, "iao_compile_int8")
     items = [(prefix + n_, c_) for n_, c_ in seq.named_children()]
     blocks = [i for i, (_, c_) in enumerate(items) if isinstance(getattr(c_, "conv", None), nn.Conv2d)]
     if len(blocks) < 3 or blocks[0] != 0:
@@ -1153,16 +1147,6 @@ def _walk_iao8(model, input_hw=(32, 32)):
             raise _err("iao_compile_int8: %s.conv is not quant_inference: its stored weights are not on the grid (iao_model_bn_fuse + prequantize_weights)" % nm)
         _iao8_check_quantizer(conv.activation_quantizer, nm + ".conv.activation_quantizer", True)
         return conv
-
-    def shuffle_of(nm, child, conv):
-        s = int(getattr(conv, "in_shuffle_groups", 0) or 0)
-        if getattr(child, "channel_shuffle_flag", 0) and getattr(child, "shuffle_groups", 1) > 1:
-            if s > 1:
-                raise _err("iao_compile_int8: %s: two channel shuffles in front of one conv" % nm)
-            s = int(child.shuffle_groups)
-        if s > 1 and conv.in_channels % s:
-            raise _err("iao_compile_int8: %s: %d input channels cannot be shuffled in %d groups" % (nm, conv.in_channels, s))
-        return s if s > 1 else 0
 
     if not isinstance(getattr(first, "conv", None), nn.Conv2d):
         raise _err("iao_compile_int8: %s: the first block holds no conv" % nm_first)
@@ -1198,8 +1182,9 @@ def _walk_iao8(model, input_hw=(32, 32)):
             raise _err("iao_compile_int8: %s.conv: geometry not covered by mn_i8conv_supported (%dx%d, stride %d, padding %d, dilation %d, groups %d, %d channels per group: "
                        "1x1 / padding 0 with groups 1 or C / groups %% 16 == 0, or 3x3 / padding 1 with C / groups %% 16 == 0; stride 1)"
                        % (nm, conv.kernel_size[0], conv.kernel_size[1], one(conv.stride), one(conv.padding), one(conv.dilation), conv.groups, conv.in_channels // conv.groups))
-        s = shuffle_of(nm, child, conv)
+        s = _shuffle_in_front("iao_compile_int8", nm, child, conv)
         if s:
+            _check_shuffle_divides("iao_compile_int8", nm, conv, s)
             if layers:
                 layers[-1]["shuffle"] = s          # folded into the producer's destination positions
             else:
@@ -1220,7 +1205,7 @@ def _walk_iao8(model, input_hw=(32, 32)):
                    groups=c0.groups, pool=0, out_order=("shuffle %d" % pack_shuffle) if pack_shuffle else "identity", table_bytes=0,
                    act_bytes_in=4 * c0.in_channels * input_hw[0] * input_hw[1], act_bytes_out=4 * c0.out_channels * H * W + blocked(c0.out_channels, H, W))]
     for L in layers:
-        g = _lib.ConvGeom(1, L["cin"], 4, 4, L["cout"], L["k"], L["k"], 1, 1, L["pad"], L["pad"], 1, 1, L["groups"], 0)
+        g = _block_geom(L)
         nin = blocked(L["cin"], H, W)
         if L["pool"]:
             if H % 2 or W % 2:
@@ -1243,61 +1228,43 @@ def iao_int8_report(model, input_hw=(32, 32)):
     return _walk_iao8(model, input_hw)[5]
 
 
-def _shuffle_order(C_, s, device):
-    """position j of a consumer's shuffled input is its producer's channel (j % s) * (C / s) + j // s (models/nin_gc.py:4-15)"""
-    j = torch.arange(C_, device=device)
-    return ((j % s) * (C_ // s) + j // s).to(torch.int32).contiguous()
-
-
-class Int8Plan(nn.Module):
+class Int8Plan(_Plan):
     """What ``iao_compile_int8`` returns: the model's own first block (fp32) -> ``mn_i8_pack_codes`` at the second conv's scale -> one ``mn_i8conv_fwd`` per hidden
     block (2x2 max-pool and the consumer's channel shuffle folded in) -> ``mn_i8_unpack_codes`` at the last conv's scale -> the model's own last block and tail (its
     quantizer reproduces the same codes: fl(fl(c s) / s) rounds back to c).  Eval only; owns the packed weight tables and one set of byte buffers per input shape.
     ``layers[i]`` keeps what the table was packed from (w, s_w, bias, s_a, s_p, s_out, a_bits, w_bits, pool, shuffle) for the tests' judge."""
 
-    def __init__(self, first, layers, last, tail, flatten, report, pack):
-        super().__init__()
-        self.first, self.last, self.tail = first, last, nn.ModuleList(tail)
-        self.layers, self.flatten, self.report = layers, flatten, report
-        self.pack = pack                  # dict: s (the second conv's activation scale), a_bits, order
-        self.keep_stages = False          # True: forward also leaves every stage's blocked codes in ``stage_codes`` (tests)
-        self.stage_codes = []
-        self._ws = {}
-        self.eval()
+    who = "iao_compile_int8"
 
-    def train(self, mode=True):
-        if mode:
-            raise _err("iao_compile_int8: the compiled plan is eval-only")
-        return super().train(False)
+    def __init__(self, first, layers, last, tail, flatten, report, pack):
+        super().__init__(first, layers, last, tail, flatten, report)
+        self.pack = pack                  # dict: s (the second conv's activation scale), a_bits, order
+        self.stage_codes = []
 
     def _plan_buffers(self, shape, device):
-        """Byte buffers (and the fp32 buffer in front of the last block) for one first-block output shape; allocated once, reused by every later call."""
-        from micronet_amd import _lib
-        key = (tuple(shape), str(device))
-        if key not in self._ws:
-            N, Cc, H, W = shape
-            if Cc != self.layers[0]["cin"]:
-                raise _err("iao_compile_int8: %s produced %d channels, %s reads %d" % (self.report[0]["name"], Cc, self.layers[0]["name"], self.layers[0]["cin"]))
-            bufs, geoms = [torch.empty((N, (Cc + 15) // 16, H * W, 16), dtype=torch.int8, device=device)], []
-            for L in self.layers:
-                geoms.append(_lib.ConvGeom(N, L["cin"], H, W, L["cout"], L["k"], L["k"], 1, 1, L["pad"], L["pad"], 1, 1, L["groups"], 0))
-                if L["pool"]:
-                    if H % 2 or W % 2:
-                        raise _err("iao_compile_int8: %s: the 2x2 max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
-                    H, W = H // 2, W // 2
-                bufs.append(torch.empty((N, (L["cout"] + 15) // 16, H * W, 16), dtype=torch.int8, device=device))
-            self._ws[key] = (bufs, geoms, torch.empty((N, self.layers[-1]["cout"], H, W), dtype=torch.float32, device=device))
-        return self._ws[key]
+        """Byte buffers (and the fp32 buffer in front of the last block) for one first-block output shape."""
+        N, Cc, H, W = shape
+        if Cc != self.layers[0]["cin"]:
+            raise _err("iao_compile_int8: %s produced %d channels, %s reads %d" % (self.report[0]["name"], Cc, self.layers[0]["name"], self.layers[0]["cin"]))
+        bufs, geoms = [torch.empty((N, (Cc + 15) // 16, H * W, 16), dtype=torch.int8, device=device)], []
+        for L in self.layers:
+            geoms.append(_block_geom(L, N, H, W))
+            if L["pool"]:
+                if H % 2 or W % 2:
+                    raise _err("iao_compile_int8: %s: the 2x2 max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
+                H, W = H // 2, W // 2
+            bufs.append(torch.empty((N, (L["cout"] + 15) // 16, H * W, 16), dtype=torch.int8, device=device))
+        return (bufs, geoms, torch.empty((N, self.layers[-1]["cout"], H, W), dtype=torch.float32, device=device))
 
     def run_stage(self, i, codes, N, H, W):
         """Hidden stage ``i`` alone on blocked input codes [N, ceil(cin / 16), H * W, 16] (int8, GPU): its blocked output codes, freshly allocated (tests)."""
         import ctypes as C
-        from micronet_amd import _lib, ops
+        from micronet_amd import ops
         L = self.layers[i]
         if not (torch.is_tensor(codes) and codes.is_cuda and codes.dtype == torch.int8 and tuple(codes.shape) == (N, (L["cin"] + 15) // 16, H * W, 16)):
             raise _err("iao_compile_int8: run_stage needs int8 GPU codes [N, ceil(C / 16), H * W, 16]")
         codes = codes.contiguous()
-        g = _lib.ConvGeom(N, L["cin"], H, W, L["cout"], L["k"], L["k"], 1, 1, L["pad"], L["pad"], 1, 1, L["groups"], 0)
+        g = _block_geom(L, N, H, W)
         Ho, Wo = (H // 2, W // 2) if L["pool"] else (H, W)
         out = torch.full((N, (L["cout"] + 15) // 16, Ho * Wo, 16), 77, dtype=torch.int8, device=codes.device)
         with torch.cuda.device(codes.device):
@@ -1314,7 +1281,7 @@ class Int8Plan(nn.Module):
         a = a.contiguous()
         N, Cc, H, W = a.shape
         with torch.cuda.device(a.device):
-            bufs, geoms, y = self._plan_buffers(a.shape, a.device)
+            bufs, geoms, y = self._shape_buffers(a.shape, a.device)
             st = ops._s()
             ops._call("mn_i8_pack_codes", ops._p(a), N, Cc, H * W, self.pack["s"], self.pack["a_bits"], ops._p(self.pack["order"]), ops._p(bufs[0]), st)
             for i, L in enumerate(self.layers):
@@ -1323,10 +1290,7 @@ class Int8Plan(nn.Module):
                 self.stage_codes = [b.clone() for b in bufs]
             n_, c_, h_, w_ = y.shape
             ops._call("mn_i8_unpack_codes", ops._p(bufs[-1]), n_, c_, h_ * w_, self.layers[-1]["s_out"], ops._p(y), st)
-        out = self.last(y)
-        for m in self.tail:
-            out = m(out)
-        return out.view(out.size(0), -1) if self.flatten else out
+        return self._finish(self.last(y))
 
 
 @torch.no_grad()
@@ -1340,16 +1304,14 @@ def iao_compile_int8(model):
     import ctypes as C
     from micronet_amd import _lib, ops
     first, layers, last, tail, flatten, report, pack_shuffle = _walk_iao8(model)
-    for p_ in model.parameters():
-        if not p_.is_cuda:
-            raise _err("iao_compile_int8: the model is on %s: micronet_amd runs on MI355X only (no CPU fallback)" % p_.device)
+    _require_gpu(model, "iao_compile_int8")
     lib = _lib.get_lib()
     scale = lambda q: float(q.scale.detach().float().reshape(-1)[0])          # (compile time: the one place a host read-back is allowed)
     dev = layers[0]["conv"].weight.device
     with torch.cuda.device(dev):
         for L in layers:
             conv, pool_m = L.pop("conv"), L.pop("pool_module")
-            g = _lib.ConvGeom(1, L["cin"], 4, 4, L["cout"], L["k"], L["k"], 1, 1, L["pad"], L["pad"], 1, 1, L["groups"], 0)
+            g = _block_geom(L)
             table = torch.empty(int(lib.mn_i8conv_table_bytes(C.byref(g), L["a_bits"], L["w_bits"])) // 4, dtype=torch.int32, device=dev)
             L["w"] = conv.weight.detach().float().contiguous()
             L["s_w"] = conv.weight_quantizer.scale.detach().float().reshape(-1).contiguous()
