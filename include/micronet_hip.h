@@ -1113,6 +1113,32 @@ int mn_i8conv_fwd(const mn_conv_geom* g, int a_bits, int w_bits, const uint32_t*
 int mn_i8_pack_codes(const float* x, int64_t N, int64_t C, int64_t HW, float s, int a_bits, const int32_t* out_order, int8_t* codes, mn_stream_t stream);
 int mn_i8_unpack_codes(const int8_t* codes, int64_t N, int64_t C, int64_t HW, float s, float* y, mn_stream_t stream);
 
+/* The two ends of the int8 deployment (csrc/qgemm_iao8_ends.h): the first conv block reads the fp32 image and writes byte codes, the last one reads byte codes and
+ * writes the fp32 map the model's tail runs on, so that no fp32 activation map stands between the image and the classifier's output.
+ * First block (mn_i8first_*): x fp32 NCHW; j = clamp(rha(fl(x / s_a)), -2^(in-1), 2^(in-1) - 1) (mn_i8_pack_codes' arithmetic), k = rint(w / s_w[o]), acc = sum j k
+ * exact in int32 over (c, dy, dx) with zero padding the code 0, then the un-pooled chain of mn_i8conv_fwd at the consumer's scale s_out and width a_bits:
+ *   y = fl(fl(float(acc) * al) + b[o]), al = fl(s_a * s_w[o]); r = max(y, 0); c = clamp(rha(fl(r / s_out)), -2^(a-1), 2^(a-1) - 1).
+ * Covered (mn_i8first_supported): groups == 1, g->in_shuffle == 0, KH == KW in {3, 5}, stride 1, dilation 1, padding (KH - 1) / 2, C * KH * KW <= 128 (at most two
+ * k-steps of v_mfma_i32_16x16x64_i8), any O, H, W >= 1 whose staged rows C * (min(H, 255 / W + 2) + KH - 1) * (W + KH - 1) fit 32 KB of LDS (every W <= 512 does),
+ * 2 <= in_bits, a_bits, w_bits <= 8.  Everything else is MN_ENOTSUP; a null or misaligned tensor (x 4-byte, codes and `table` 16-byte aligned) or an invalid geometry
+ * (N <= 0, ...) is MN_EINVAL; nothing is written in either case.  No entry allocates.
+ *   pack : as mn_i8conv_pack (w [O][C][KH][KW] on the grid k * s_w, s_w_stride 1 / 0, bias or null, out_order or null: row j computes channel out_order[j]) ->
+ *          `table` (private layout, mn_i8first_table_bytes bytes): the set / tile table of mn_i8conv_pack with K over (c, dy, dx) padded with zero bytes to 64 or
+ *          128.  Word 0 counts the rows with a non-finite al or b or a bad s_w plus each of s_a, s_out that is non-finite or <= 0, word 7 the bad out_order entries
+ *          plus the rows with a weight off the grid or beyond 2^(w-1) - 1: a table with either non-zero must not be used.  Word 6 = a_bits | w_bits << 8 | in_bits << 16.
+ *   fwd  : x [N][C][H][W] -> out_codes [N][ceil(O/16)][H*W][16].  Every output byte is stored exactly once, as part of a whole 16-byte block assembled on chip: no
+ *          atomics, no read-modify-write.  Positions >= O and bad out_order entries yield 0 bytes.  mn_last_kernel(): k_i8first<KS>.
+ * Last block (mn_i8conv_fwd_f32): in_codes and `table` as for mn_i8conv_fwd, the table packed by mn_i8conv_pack with s_p = s_out = 1 (neither is read); acc and y as
+ * there, r = relu ? max(y, 0) : y written as fp32 y [N][O][H*W], position j holding channel out_order[j].  Covers what mn_i8conv_supported covers (1x1 and 3x3), else
+ * MN_ENOTSUP; relu outside 0 / 1, a null or misaligned tensor (y 4-byte, codes and `table` 16-byte aligned) or an invalid geometry is MN_EINVAL; nothing is written in
+ * either case.  mn_last_kernel(): k_i8conv_f32<KS>. */
+int mn_i8first_supported(const mn_conv_geom* g, int in_bits, int a_bits, int w_bits);
+int64_t mn_i8first_table_bytes(const mn_conv_geom* g, int in_bits, int a_bits, int w_bits);
+int mn_i8first_pack(const mn_conv_geom* g, const float* w, const float* s_w, int s_w_stride, const float* bias, float s_a, float s_out, int in_bits, int a_bits, int w_bits,
+                    const int32_t* out_order, uint32_t* table, mn_stream_t stream);
+int mn_i8first_fwd(const mn_conv_geom* g, int in_bits, int a_bits, int w_bits, const uint32_t* table, const float* x, int8_t* out_codes, mn_stream_t stream);
+int mn_i8conv_fwd_f32(const mn_conv_geom* g, int a_bits, int w_bits, const uint32_t* table, const int8_t* in_codes, float* y, int relu, mn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

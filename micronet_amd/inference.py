@@ -1109,21 +1109,33 @@ def _i8conv_kernel_name(k, pool):
     return "k_i8conv<%d,%d>" % (k, pool)
 
 
-def _iao8_check_quantizer(q, nm, per_tensor):
+def _iao8_check_quantizer(q, nm, per_tensor, who="iao_compile_int8"):
     """A quantizer the int8 blocks cover: symmetric (zero point 0), 2 .. 8 bits; ``per_tensor``: exactly one scale."""
     from micronet_amd.quantization.wqaq.iao import quantize
     if not isinstance(q, quantize.Quantizer):
-        raise _err("iao_compile_int8: %s is not an IAO quantizer" % nm)
+        raise _err("%s: %s is not an IAO quantizer" % (who, nm))
     if q.bits == 32 or not 2 <= q.bits <= 8:
-        raise _err("iao_compile_int8: %s has %d bits; the int8 blocks cover code widths 2 .. 8" % (nm, q.bits))
+        raise _err("%s: %s has %d bits; the int8 blocks cover code widths 2 .. 8" % (who, nm, q.bits))
     if q._q_type_static != 0 or q.q_type != 0 or bool((q.zero_point != 0).any()):
-        raise _err("iao_compile_int8: %s is asymmetric; a zero byte must be the value 0 (symmetric quantizers only)" % nm)
+        raise _err("%s: %s is asymmetric; a zero byte must be the value 0 (symmetric quantizers only)" % (who, nm))
     if per_tensor and q.scale.numel() != 1:
-        raise _err("iao_compile_int8: %s carries %d scales; a per-tensor activation scale must be a single value" % (nm, q.scale.numel()))
+        raise _err("%s: %s carries %d scales; a per-tensor activation scale must be a single value" % (who, nm, q.scale.numel()))
 
 
-def _walk_iao8(model, input_hw=(32, 32)):
-    """The graph walk of ``iao_compile_int8`` (no GPU needed): (first, layers, last, tail, flatten, report, pack_shuffle)."""
+def _iao8_check_weights(conv, nm, who="iao_compile_int8"):
+    """The weight quantizer and padding mode of a conv the int8 blocks contract: symmetric, 2 .. 8 bits, one scale per layer or per output channel, zero padding."""
+    wq = conv.weight_quantizer
+    _iao8_check_quantizer(wq, nm + ".conv.weight_quantizer", False, who)
+    if wq.scale.numel() not in (1, conv.out_channels):
+        raise _err("%s: %s.conv.weight_quantizer carries %d scales for %d output channels" % (who, nm, wq.scale.numel(), conv.out_channels))
+    if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
+        raise _err("%s: %s.conv: padding mode not covered by the int8 blocks" % (who, nm))
+    return wq
+
+
+def _walk_iao8(model, input_hw=(32, 32), byte_ends=False):
+    """The graph walk of ``iao_compile_int8`` (no GPU needed): (first, layers, last, tail, flatten, report, pack_shuffle, ends); ``ends``: None, or with ``byte_ends``
+    the layer dicts (first, last) of the two end blocks."""
     import ctypes as C
     from micronet_amd import _lib
     from micronet_amd.quantization.wqaq.dorefa.quantize import _is_ref_block
@@ -1137,21 +1149,27 @@ def _walk_iao8(model, input_hw=(32, 32)):
     (nm_first, first), (nm_last, last) = items[0], items[last_i]
     tail = [c_ for _, c_ in items[last_i + 1:]]
 
-    def block_conv(nm, child):
+    ends_who = "iao_compile_int8(byte_ends=True)"
+
+    def block_conv(nm, child, who="iao_compile_int8"):
         conv, bn, act = getattr(child, "conv", None), getattr(child, "bn", None), getattr(child, "relu", None)
         if not (_is_ref_block(child) and isinstance(bn, nn.Identity) and type(act) in (nn.ReLU, quantize.ReLUAfterFusedConv)):
-            raise _err("iao_compile_int8: %s (%s): module order not recognised (expected a BN-folded conv -> Identity -> ReLU block)" % (nm, type(child).__name__))
+            raise _err("%s: %s (%s): module order not recognised (expected a BN-folded conv -> Identity -> ReLU block)" % (who, nm, type(child).__name__))
         if not isinstance(conv, quantize.QuantConv2d) or isinstance(conv, quantize.QuantBNFuseConv2d):
-            raise _err("iao_compile_int8: %s.conv (%s) is not a BN-folded IAO QuantConv2d (run iao_model_bn_fuse first)" % (nm, type(conv).__name__))
+            raise _err("%s: %s.conv (%s) is not a BN-folded IAO QuantConv2d (run iao_model_bn_fuse first)" % (who, nm, type(conv).__name__))
         if not conv.quant_inference:
-            raise _err("iao_compile_int8: %s.conv is not quant_inference: its stored weights are not on the grid (iao_model_bn_fuse + prequantize_weights)" % nm)
-        _iao8_check_quantizer(conv.activation_quantizer, nm + ".conv.activation_quantizer", True)
+            raise _err("%s: %s.conv is not quant_inference: its stored weights are not on the grid (iao_model_bn_fuse + prequantize_weights)" % (who, nm))
+        _iao8_check_quantizer(conv.activation_quantizer, nm + ".conv.activation_quantizer", True, who)
         return conv
 
     if not isinstance(getattr(first, "conv", None), nn.Conv2d):
         raise _err("iao_compile_int8: %s: the first block holds no conv" % nm_first)
     last_conv = block_conv(nm_last, last)
     c0 = first.conv
+    if byte_ends:
+        block_conv(nm_first, first, ends_who)          # the first block is an int8 block too: the image goes through its own activation quantizer
+        _iao8_check_weights(c0, nm_first, ends_who)
+        _iao8_check_weights(last_conv, nm_last, ends_who)
     size = lambda v, k, s, p, d: (v + 2 * p - d * (k - 1) - 1) // s + 1
     H, W = (size(input_hw[i], c0.kernel_size[i], c0.stride[i], c0.padding[i], c0.dilation[i]) for i in (0, 1))
     layers, pack_shuffle = [], 0
@@ -1161,6 +1179,8 @@ def _walk_iao8(model, input_hw=(32, 32)):
             if not ok:
                 raise _err("iao_compile_int8: %s (%s, kernel %s, stride %s, padding %s): only a 2x2 / stride 2 QuantMaxPool2d is folded into the int8 block in front of it"
                            % (nm, type(child).__name__, child.kernel_size, child.stride, child.padding))
+            if not layers and byte_ends:
+                raise _err("%s: %s: a max-pool directly behind the first block is not covered (the pooled form of k_i8first is not built)" % (ends_who, nm))
             if not layers:
                 raise _err("iao_compile_int8: %s: a max-pool directly behind the first block is not covered (its producer is not an int8 block)" % nm)
             if layers[-1]["pool"]:
@@ -1169,13 +1189,8 @@ def _walk_iao8(model, input_hw=(32, 32)):
             layers[-1]["pool"], layers[-1]["pool_module"], layers[-1]["pool_name"] = 1, child, nm
             continue
         conv = block_conv(nm, child)
-        wq = conv.weight_quantizer
-        _iao8_check_quantizer(wq, nm + ".conv.weight_quantizer", False)
-        if wq.scale.numel() not in (1, conv.out_channels):
-            raise _err("iao_compile_int8: %s.conv.weight_quantizer carries %d scales for %d output channels" % (nm, wq.scale.numel(), conv.out_channels))
+        wq = _iao8_check_weights(conv, nm)
         one = lambda v: v[0] if v[0] == v[1] else -1
-        if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
-            raise _err("iao_compile_int8: %s.conv: padding mode not covered by the int8 blocks" % nm)
         g = _lib.ConvGeom(1, conv.in_channels, 4, 4, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.stride[1], conv.padding[0],
                           conv.padding[1], conv.dilation[0], conv.dilation[1], conv.groups, 0)
         if not _lib.get_lib().mn_i8conv_supported(C.byref(g), conv.activation_quantizer.bits, wq.bits):
@@ -1201,9 +1216,26 @@ def _walk_iao8(model, input_hw=(32, 32)):
             raise _err("iao_compile_int8: %s: the pool's quantizer has %d bits, its consumer %d: one code width per block"
                        % (L["pool_name"], L["pool_module"].activation_quantizer.bits, L["a_bits"]))
     blocked = lambda c, h, w: (c + 15) // 16 * 16 * h * w
+    geom = lambda conv, h, w, shuffle=0: _lib.ConvGeom(1, conv.in_channels, h, w, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0],
+                                                       conv.stride[1], conv.padding[0], conv.padding[1], conv.dilation[0], conv.dilation[1], conv.groups, shuffle)
     report = [dict(name=nm_first, kind="first", kernel="the model's own block (fp32), k_i8_pack", k=c0.kernel_size[0], cin=c0.in_channels, cout=c0.out_channels,
                    groups=c0.groups, pool=0, out_order=("shuffle %d" % pack_shuffle) if pack_shuffle else "identity", table_bytes=0,
                    act_bytes_in=4 * c0.in_channels * input_hw[0] * input_hw[1], act_bytes_out=4 * c0.out_channels * H * W + blocked(c0.out_channels, H, W))]
+    ends = None
+    if byte_ends:
+        # the first block: an int8 block whose input is the fp32 image (mn_i8first_*), its consumer the first hidden conv's activation quantizer
+        bits = (c0.activation_quantizer.bits, layers[0]["in_bits"], c0.weight_quantizer.bits)
+        g = geom(c0, input_hw[0], input_hw[1], _shuffle_in_front(ends_who, nm_first, first, c0))
+        if not _lib.get_lib().mn_i8first_supported(C.byref(g), *bits):
+            raise _err("%s: %s.conv: geometry not covered by mn_i8first_supported (%dx%d, stride %s, padding %s, dilation %s, groups %d, %d input channels, in_shuffle %d, "
+                       "a %d x %d image: groups 1, no channel shuffle, 3x3 or 5x5 / stride 1 / dilation 1 / padding (KS - 1) / 2, C * KS * KS <= 128 and an LDS tile "
+                       "C * (min(H, 255 / W + 2) + KS - 1) * (W + KS - 1) <= 32768: every W <= 512)"
+                       % (ends_who, nm_first, c0.kernel_size[0], c0.kernel_size[1], c0.stride, c0.padding, c0.dilation, c0.groups, c0.in_channels, g.in_shuffle,
+                          input_hw[0], input_hw[1]))
+        Lf = dict(name=nm_first, conv=c0, k=c0.kernel_size[0], pad=c0.padding[0], cin=c0.in_channels, cout=c0.out_channels, groups=1, pool=0, shuffle=pack_shuffle,
+                  in_bits=bits[0], a_bits=bits[1], w_bits=bits[2], per_channel=c0.weight_quantizer.scale.numel() > 1, consumer=layers[0]["conv"].activation_quantizer,
+                  table_bytes=int(_lib.get_lib().mn_i8first_table_bytes(C.byref(g), *bits)))
+        report[0] = dict(report[0], kind="int8_first", kernel="k_i8first<%d>" % Lf["k"], table_bytes=Lf["table_bytes"], act_bytes_out=blocked(Lf["cout"], H, W))
     for L in layers:
         g = _block_geom(L)
         nin = blocked(L["cin"], H, W)
@@ -1218,35 +1250,60 @@ def _walk_iao8(model, input_hw=(32, 32)):
     report.append(dict(name=nm_last, kind="last", kernel="k_i8_unpack, the model's own block (fp32)", k=last_conv.kernel_size[0], cin=last_conv.in_channels,
                        cout=last_conv.out_channels, groups=last_conv.groups, pool=0, out_order="identity", table_bytes=0,
                        act_bytes_in=blocked(last_conv.in_channels, H, W) + 4 * last_conv.in_channels * H * W, act_bytes_out=4 * last_conv.out_channels * H * W))
-    return first, layers, last, tail, flatten, report, pack_shuffle
+    if byte_ends:
+        # the last block: the hidden kernel's contraction, stopped at r and written as the fp32 map of the tail (mn_i8conv_fwd_f32)
+        bits = (last_conv.activation_quantizer.bits, last_conv.weight_quantizer.bits)
+        if _shuffle_in_front(ends_who, nm_last, last, last_conv):
+            raise _err("%s: %s: a channel shuffle in front of the last block is not covered (folding it into the last hidden block is not built)" % (ends_who, nm_last))
+        g = geom(last_conv, 4, 4)
+        if not _lib.get_lib().mn_i8conv_supported(C.byref(g), *bits):
+            raise _err("%s: %s.conv: geometry not covered by mn_i8conv_supported, the rule of mn_i8conv_fwd_f32 (%dx%d, stride %s, padding %s, dilation %s, groups %d, "
+                       "%d channels per group: 1x1 / padding 0 with groups 1 or C / groups %% 16 == 0, or 3x3 / padding 1 with C / groups %% 16 == 0; stride 1)"
+                       % (ends_who, nm_last, last_conv.kernel_size[0], last_conv.kernel_size[1], last_conv.stride, last_conv.padding, last_conv.dilation,
+                          last_conv.groups, last_conv.in_channels // last_conv.groups))
+        Ll = dict(name=nm_last, conv=last_conv, k=last_conv.kernel_size[0], pad=last_conv.padding[0], cin=last_conv.in_channels, cout=last_conv.out_channels,
+                  groups=last_conv.groups, pool=0, shuffle=0, a_bits=bits[0], w_bits=bits[1], per_channel=last_conv.weight_quantizer.scale.numel() > 1, relu=1,
+                  table_bytes=int(_lib.get_lib().mn_i8conv_table_bytes(C.byref(g), *bits)))
+        report[-1] = dict(report[-1], kind="int8_last", kernel="k_i8conv_f32<%d>" % Ll["k"], table_bytes=Ll["table_bytes"], act_bytes_in=blocked(Ll["cin"], H, W))
+        ends = (Lf, Ll)
+    return first, layers, last, tail, flatten, report, pack_shuffle, ends
 
 
-def iao_int8_report(model, input_hw=(32, 32)):
-    """The ``report`` ``iao_compile_int8(model)`` would carry -- one row per stage: layer, kernel, geometry, folded pool, the consumer's shuffle folded into the stage
-    (``out_order``), table bytes and the activation bytes per image the stage reads and writes at an ``input_hw`` input -- from the graph walk alone: no GPU, nothing
-    packed.  Raises like ``iao_compile_int8`` for whatever the int8 blocks do not cover (weights off the grid excepted: that is read from the packed tables)."""
-    return _walk_iao8(model, input_hw)[5]
+def iao_int8_report(model, input_hw=(32, 32), byte_ends=False):
+    """The ``report`` ``iao_compile_int8(model, byte_ends)`` would carry -- one row per stage: layer, kernel, geometry, folded pool, the consumer's shuffle folded into
+    the stage (``out_order``), table bytes and the activation bytes per image the stage reads and writes at an ``input_hw`` input -- from the graph walk alone: no GPU,
+    nothing packed.  With ``byte_ends`` the two end rows are the kinds ``int8_first`` / ``int8_last`` and no fp32 map stands between the rows.  Raises like
+    ``iao_compile_int8`` for whatever the int8 blocks do not cover (weights off the grid excepted: that is read from the packed tables)."""
+    return _walk_iao8(model, input_hw, byte_ends)[5]
 
 
 class Int8Plan(_Plan):
     """What ``iao_compile_int8`` returns: the model's own first block (fp32) -> ``mn_i8_pack_codes`` at the second conv's scale -> one ``mn_i8conv_fwd`` per hidden
     block (2x2 max-pool and the consumer's channel shuffle folded in) -> ``mn_i8_unpack_codes`` at the last conv's scale -> the model's own last block and tail (its
     quantizer reproduces the same codes: fl(fl(c s) / s) rounds back to c).  Eval only; owns the packed weight tables and one set of byte buffers per input shape.
-    ``layers[i]`` keeps what the table was packed from (w, s_w, bias, s_a, s_p, s_out, a_bits, w_bits, pool, shuffle) for the tests' judge."""
+    ``layers[i]`` keeps what the table was packed from (w, s_w, bias, s_a, s_p, s_out, a_bits, w_bits, pool, shuffle) for the tests' judge.
+
+    With ``byte_ends`` (``ends`` is set) neither end runs the model's own modules: ``mn_i8first_fwd`` takes the fp32 image to the first hidden block's codes, the hidden
+    stages run unchanged, ``mn_i8conv_fwd_f32`` takes the last hidden codes to the fp32 map [N][O][H * W] of the model's tail: no ``k_i8_pack``, no ``k_i8_unpack``
+    and no fp32 activation map in between.  ``ends`` = (first, last) keeps what the two tables were packed from, as ``layers[i]`` does (the first also ``in_bits``)."""
 
     who = "iao_compile_int8"
 
-    def __init__(self, first, layers, last, tail, flatten, report, pack):
+    def __init__(self, first, layers, last, tail, flatten, report, pack, ends=None):
         super().__init__(first, layers, last, tail, flatten, report)
         self.pack = pack                  # dict: s (the second conv's activation scale), a_bits, order
+        self.ends = ends                  # None, or the layer dicts (first, last) of a byte_ends plan
         self.stage_codes = []
 
     def _plan_buffers(self, shape, device):
-        """Byte buffers (and the fp32 buffer in front of the last block) for one first-block output shape."""
+        """Byte buffers and the fp32 buffer in front of the last block (byte_ends: behind it) for one first-block output shape; byte_ends: the geometries of the two
+        ends stand around the hidden ones."""
         N, Cc, H, W = shape
         if Cc != self.layers[0]["cin"]:
             raise _err("iao_compile_int8: %s produced %d channels, %s reads %d" % (self.report[0]["name"], Cc, self.layers[0]["name"], self.layers[0]["cin"]))
         bufs, geoms = [torch.empty((N, (Cc + 15) // 16, H * W, 16), dtype=torch.int8, device=device)], []
+        if self.ends:
+            geoms.append(_block_geom(self.ends[0], N, H, W))          # (stride 1, padding (k - 1) / 2: the image has the first block's H x W)
         for L in self.layers:
             geoms.append(_block_geom(L, N, H, W))
             if L["pool"]:
@@ -1254,7 +1311,58 @@ class Int8Plan(_Plan):
                     raise _err("iao_compile_int8: %s: the 2x2 max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
                 H, W = H // 2, W // 2
             bufs.append(torch.empty((N, (L["cout"] + 15) // 16, H * W, 16), dtype=torch.int8, device=device))
-        return (bufs, geoms, torch.empty((N, self.layers[-1]["cout"], H, W), dtype=torch.float32, device=device))
+        if self.ends:
+            geoms.append(_block_geom(self.ends[1], N, H, W))
+        return (bufs, geoms, torch.empty((N, (self.ends[1] if self.ends else self.layers[-1])["cout"], H, W), dtype=torch.float32, device=device))
+
+    def _image(self, x):
+        Lf = self.ends[0] if self.ends else None
+        if not (Lf and type(x) is torch.Tensor and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == Lf["cin"]):
+            raise _err("iao_compile_int8(byte_ends=True): the input must be a float32 GPU image [N, %s, H, W] of a byte_ends plan (no CPU fallback)"
+                       % (Lf["cin"] if Lf else "C"))
+        return x.contiguous()
+
+    def run_first(self, x):
+        """The first block alone on the fp32 image (byte_ends): the blocked codes [N, ceil(cout / 16), H * W, 16] the first hidden stage reads, freshly allocated
+        (tests)."""
+        import ctypes as C
+        from micronet_amd import ops
+        x = self._image(x)
+        Lf, (N, _, H, W) = self.ends[0], x.shape
+        out = torch.full((N, (Lf["cout"] + 15) // 16, H * W, 16), 77, dtype=torch.int8, device=x.device)
+        with torch.cuda.device(x.device):
+            ops._call("mn_i8first_fwd", C.byref(_block_geom(Lf, N, H, W)), Lf["in_bits"], Lf["a_bits"], Lf["w_bits"], ops._p(Lf["table"]), ops._p(x), ops._p(out), ops._s())
+        return out
+
+    def run_last(self, codes, N, H, W):
+        """The last block alone on blocked input codes [N, ceil(cin / 16), H * W, 16] (byte_ends): the fp32 map [N, cout, H, W] of the tail, freshly allocated (tests)."""
+        import ctypes as C
+        from micronet_amd import ops
+        Ll = self.ends[1] if self.ends else None
+        if not (Ll and torch.is_tensor(codes) and codes.is_cuda and codes.dtype == torch.int8 and tuple(codes.shape) == (N, (Ll["cin"] + 15) // 16, H * W, 16)):
+            raise _err("iao_compile_int8(byte_ends=True): run_last needs a byte_ends plan and int8 GPU codes [N, ceil(C / 16), H * W, 16]")
+        codes = codes.contiguous()
+        out = torch.full((N, Ll["cout"], H, W), float("nan"), dtype=torch.float32, device=codes.device)
+        with torch.cuda.device(codes.device):
+            ops._call("mn_i8conv_fwd_f32", C.byref(_block_geom(Ll, N, H, W)), Ll["a_bits"], Ll["w_bits"], ops._p(Ll["table"]), ops._p(codes), ops._p(out), Ll["relu"],
+                      ops._s())
+        return out
+
+    def _forward_ends(self, x):
+        import ctypes as C
+        from micronet_amd import ops
+        x = self._image(x)
+        (Lf, Ll), (N, _, H, W) = self.ends, x.shape
+        with torch.cuda.device(x.device):
+            bufs, geoms, y = self._shape_buffers((N, Lf["cout"], H, W), x.device)
+            st = ops._s()
+            ops._call("mn_i8first_fwd", C.byref(geoms[0]), Lf["in_bits"], Lf["a_bits"], Lf["w_bits"], ops._p(Lf["table"]), ops._p(x), ops._p(bufs[0]), st)
+            for i, L in enumerate(self.layers):
+                ops._call("mn_i8conv_fwd", C.byref(geoms[i + 1]), L["a_bits"], L["w_bits"], ops._p(L["table"]), ops._p(bufs[i]), ops._p(bufs[i + 1]), int(L["pool"]), st)
+            if self.keep_stages:
+                self.stage_codes = [b.clone() for b in bufs]
+            ops._call("mn_i8conv_fwd_f32", C.byref(geoms[-1]), Ll["a_bits"], Ll["w_bits"], ops._p(Ll["table"]), ops._p(bufs[-1]), ops._p(y), Ll["relu"], st)
+        return self._finish(y if len(self.tail) else y.clone())          # (the buffer belongs to the plan: never handed out)
 
     def run_stage(self, i, codes, N, H, W):
         """Hidden stage ``i`` alone on blocked input codes [N, ceil(cin / 16), H * W, 16] (int8, GPU): its blocked output codes, freshly allocated (tests)."""
@@ -1275,6 +1383,8 @@ class Int8Plan(_Plan):
     def forward(self, x):
         import ctypes as C
         from micronet_amd import ops
+        if self.ends:
+            return self._forward_ends(x)
         a = self.first(x)
         if not (type(a) is torch.Tensor and a.is_cuda and a.dtype == torch.float32 and a.dim() == 4):
             raise _err("iao_compile_int8: %s did not produce a float32 GPU map (the input must be a float32 GPU tensor; no CPU fallback)" % self.report[0]["name"])
@@ -1294,39 +1404,58 @@ class Int8Plan(_Plan):
 
 
 @torch.no_grad()
-def iao_compile_int8(model):
+def iao_compile_int8(model, byte_ends=False):
     """``model``: the result of ``iao_model_bn_fuse`` + ``prequantize_weights`` on a symmetric IAO net, on the GPU (the reference's ``nin_gc``, or an ``nn.Sequential``
     of its block kinds).  Returns an ``Int8Plan`` that keeps every hidden activation as one int8 code and contracts on v_mfma_i32_16x16x64_i8
     (``csrc/qgemm_iao8.h``); the two ends stay on the model's own modules.  ``.report`` lists the stages.  Scales are read from the quantizer buffers and the table
     counters read back here, once.  Anything the int8 blocks do not cover -- an asymmetric or 32-bit quantizer, a per-tensor scale that is not a single value, a layer
     that is not ``quant_inference``, weights off the grid, a geometry ``mn_i8conv_supported`` refuses, a pool other than a 2x2 / 2 ``QuantMaxPool2d``, a pool directly
-    behind the first block -- raises ``MicronetHipError`` naming the layer: never a silent fp32 path (the caller still has ``model``)."""
+    behind the first block -- raises ``MicronetHipError`` naming the layer: never a silent fp32 path (the caller still has ``model``).
+
+    ``byte_ends=True``: the two ends run on the int8 kernels as well (``csrc/qgemm_iao8_ends.h``): the first conv quantises the fp32 image with its own activation
+    quantizer on the way in and writes the first hidden block's codes, the last conv writes the fp32 map of the model's tail (``QuantAvgPool2d``, ...) straight from
+    the last hidden codes.  The first block must be a BN-folded ``quant_inference`` block like the hidden ones with a geometry ``mn_i8first_supported`` covers (3x3 or
+    5x5, C * KS * KS <= 128, no pool behind it), the last one a geometry ``mn_i8conv_supported`` covers; anything else raises naming the layer."""
     import ctypes as C
-    from micronet_amd import _lib, ops
-    first, layers, last, tail, flatten, report, pack_shuffle = _walk_iao8(model)
+    from micronet_amd import ops
+    who = "iao_compile_int8(byte_ends=True)" if byte_ends else "iao_compile_int8"
+    first, layers, last, tail, flatten, report, pack_shuffle, ends = _walk_iao8(model, byte_ends=byte_ends)
     _require_gpu(model, "iao_compile_int8")
-    lib = _lib.get_lib()
     scale = lambda q: float(q.scale.detach().float().reshape(-1)[0])          # (compile time: the one place a host read-back is allowed)
     dev = layers[0]["conv"].weight.device
+
+    def packed_from(L, conv):
+        L["w"] = conv.weight.detach().float().contiguous()
+        L["s_w"] = conv.weight_quantizer.scale.detach().float().reshape(-1).contiguous()
+        L["bias"] = conv.bias.detach().float().contiguous() if conv.bias is not None else None
+        L["s_a"] = scale(conv.activation_quantizer)
+        L["out_order"] = _shuffle_order(L["cout"], L["shuffle"], dev) if L["shuffle"] else None
+        L["table"] = torch.empty(L["table_bytes"] // 4, dtype=torch.int32, device=dev)
+
     with torch.cuda.device(dev):
+        if ends:
+            Lf, Ll = ends
+            packed_from(Lf, Lf.pop("conv"))
+            Lf["s_out"] = scale(Lf.pop("consumer"))
+            ops._call("mn_i8first_pack", C.byref(_block_geom(Lf)), ops._p(Lf["w"]), ops._p(Lf["s_w"]), 1 if Lf["per_channel"] else 0, ops._p(Lf["bias"]), Lf["s_a"],
+                      Lf["s_out"], Lf["in_bits"], Lf["a_bits"], Lf["w_bits"], ops._p(Lf["out_order"]), ops._p(Lf["table"]), ops._s())
+            packed_from(Ll, Ll.pop("conv"))
+            Ll["s_p"] = Ll["s_out"] = 1.0          # (mn_i8conv_fwd_f32 stops at r: neither is read)
+            ops._call("mn_i8conv_pack", C.byref(_block_geom(Ll)), ops._p(Ll["w"]), ops._p(Ll["s_w"]), 1 if Ll["per_channel"] else 0, ops._p(Ll["bias"]), Ll["s_a"], 1.0, 1.0,
+                      Ll["a_bits"], Ll["w_bits"], None, ops._p(Ll["table"]), ops._s())
         for L in layers:
             conv, pool_m = L.pop("conv"), L.pop("pool_module")
-            g = _block_geom(L)
-            table = torch.empty(int(lib.mn_i8conv_table_bytes(C.byref(g), L["a_bits"], L["w_bits"])) // 4, dtype=torch.int32, device=dev)
-            L["w"] = conv.weight.detach().float().contiguous()
-            L["s_w"] = conv.weight_quantizer.scale.detach().float().reshape(-1).contiguous()
-            L["bias"] = conv.bias.detach().float().contiguous() if conv.bias is not None else None
-            L["s_a"], L["s_out"] = scale(conv.activation_quantizer), scale(L.pop("consumer"))
+            packed_from(L, conv)
+            L["s_out"] = scale(L.pop("consumer"))
             L["s_p"] = scale(pool_m.activation_quantizer) if pool_m is not None else L["s_out"]
-            L["out_order"] = _shuffle_order(L["cout"], L["shuffle"], dev) if L["shuffle"] else None
-            ops._call("mn_i8conv_pack", C.byref(g), ops._p(L["w"]), ops._p(L["s_w"]), 1 if L["per_channel"] else 0, ops._p(L["bias"]), L["s_a"], L["s_p"], L["s_out"],
-                      L["a_bits"], L["w_bits"], ops._p(L["out_order"]), ops._p(table), ops._s())
-            L["table"] = table
-        counters = torch.stack([L["table"][[0, 7]] for L in layers]).tolist()
-    for L, (bad, off) in zip(layers, counters):
+            ops._call("mn_i8conv_pack", C.byref(_block_geom(L)), ops._p(L["w"]), ops._p(L["s_w"]), 1 if L["per_channel"] else 0, ops._p(L["bias"]), L["s_a"], L["s_p"],
+                      L["s_out"], L["a_bits"], L["w_bits"], ops._p(L["out_order"]), ops._p(L["table"]), ops._s())
+        packed = ([ends[0]] if ends else []) + layers + ([ends[1]] if ends else [])
+        counters = torch.stack([L["table"][[0, 7]] for L in packed]).tolist()
+    for L, (bad, off) in zip(packed, counters):
         if bad:
-            raise _err("iao_compile_int8: %s.conv: %d rows or scales with a non-finite or non-positive constant (al, bias, s_w, s_a, s_p, s_out)" % (L["name"], bad))
+            raise _err("%s: %s.conv: %d rows or scales with a non-finite or non-positive constant (al, bias, s_w, s_a, s_p, s_out)" % (who, L["name"], bad))
         if off:
-            raise _err("iao_compile_int8: %s.conv: %d rows whose stored weights are off the grid k * s_w (run prequantize_weights after iao_model_bn_fuse)" % (L["name"], off))
+            raise _err("%s: %s.conv: %d rows whose stored weights are off the grid k * s_w (run prequantize_weights after iao_model_bn_fuse)" % (who, L["name"], off))
     pack = dict(s=layers[0]["s_a"], a_bits=layers[0]["in_bits"], order=_shuffle_order(layers[0]["cin"], pack_shuffle, dev) if pack_shuffle else None)
-    return Int8Plan(first, layers, last, tail, flatten, report, pack)
+    return Int8Plan(first, layers, last, tail, flatten, report, pack, ends)

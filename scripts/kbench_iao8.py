@@ -5,7 +5,12 @@ i8-MFMA kernel per hidden block), alternated in ONE process, HIP events.
     python scripts/kbench_iao8.py [--batches 256,1024] [--warmup 5] [--iters 20] [--out profiles/iao8_inference.json]
 
 Per batch: median / min / quartiles of the timed forwards of each, per-kernel times of both from the library's profile hooks, the largest |P - F| relative to
-max|F| and the argmax agreement; and the designed HBM bytes per image per hidden block on both paths (arithmetic from the shapes)."""
+max|F| and the argmax agreement; and the designed HBM bytes per image per hidden block on both paths (arithmetic from the shapes).
+
+    python scripts/kbench_iao8.py --byte-ends [...] [--out profiles/iao8_ends_inference.json]
+
+adds ``E = inference.iao_compile_int8(F, byte_ends=True)`` (the first conv writes bytes, the classifier reads them) as a third path alternated with the two: its
+yardstick is ``P`` in the same run (``E_over_P``), and its per-kernel times stand beside P's."""
 import argparse
 import importlib
 import json
@@ -62,8 +67,10 @@ def main():
     ap.add_argument("--batches", default="256,1024")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join("profiles", "iao8_inference.json"))
+    ap.add_argument("--byte-ends", action="store_true", help="also time the byte_ends plan, against the default plan of the same run")
+    ap.add_argument("--out", default=None, help="default: profiles/iao8_inference.json, with --byte-ends profiles/iao8_ends_inference.json")
     args = ap.parse_args()
+    args.out = args.out or os.path.join("profiles", "iao8_ends_inference.json" if args.byte_ends else "iao8_inference.json")
     from micronet_amd import _lib, inference
     from micronet_amd.train import build_model, make_optimizer, synth_batch, train_step
     Q = importlib.import_module("micronet.compression.quantization.wqaq.iao.quantize")
@@ -78,19 +85,27 @@ def main():
     inference.prequantize_weights(F)
     F.eval()
     P = inference.iao_compile_int8(F)
+    E = inference.iao_compile_int8(F, byte_ends=True) if args.byte_ends else None
     lib = _lib.get_lib()
     res = dict(model="nin_gc", a_bits=8, w_bits=8, warmup=args.warmup, iters=args.iters, device=torch.cuda.get_device_name(0), report=P.report,
                designed_bytes_per_image=designed_bytes_per_image(P), batches={})
+    if E is not None:
+        res["ends_report"] = E.report
     with torch.no_grad():
         for bs in [int(v) for v in args.batches.split(",")]:
             x, _ = synth_batch(bs, device="cuda")
             f, p = F(x), P(x)
+            e = E(x) if E is not None else None
             for _ in range(args.warmup):
                 F(x), P(x)
-            tf, tp = [], []
+                if E is not None:
+                    E(x)
+            tf, tp, te = [], [], []
             for _ in range(args.iters):          # alternated: both see the same clocks and the same neighbours
                 tf.append(timed(F, x))
                 tp.append(timed(P, x))
+                if E is not None:
+                    te.append(timed(E, x))
             kf, kp = profile(lib, _lib, F, x), profile(lib, _lib, P, x)
             mf, mp = statistics.median(tf), statistics.median(tp)
             res["batches"][str(bs)] = dict(F_ms=q(tf), P_ms=q(tp), F_img_s=bs / mf * 1e3, P_img_s=bs / mp * 1e3, P_over_F=mf / mp,
@@ -101,6 +116,16 @@ def main():
             print("batch %d: F %.3f ms (min %.3f)  P %.3f ms (min %.3f)  speed %.2fx  max|P-F|/max|F| %.2e" % (bs, mf, min(tf), mp, min(tp), mf / mp,
                                                                                                            res["batches"][str(bs)]["max_abs_diff_over_max_F"]), flush=True)
             print("  P kernels (us per launch):", {n: v["us_per_launch"] for n, v in kp.items()}, flush=True)
+            if E is not None:
+                ke, me = profile(lib, _lib, E, x), statistics.median(te)
+                res["batches"][str(bs)].update(E_ms=q(te), E_img_s=bs / me * 1e3, E_over_P=mp / me, E_over_F=mf / me,
+                                               E_max_abs_diff_over_max_F=float((e - f).abs().max() / f.abs().max()),
+                                               E_max_abs_diff_over_max_P=float((e - p).abs().max() / p.abs().max()),
+                                               E_argmax_agreement=float((e.argmax(1) == f.argmax(1)).float().mean()),
+                                               E_kernel_ms_total=sum(v["ms"] for v in ke.values()), E_kernels=ke)
+                print("  byte_ends: E %.3f ms (min %.3f, p25 %.3f, p75 %.3f)  against P %.2fx  max|E-F|/max|F| %.2e" % (me, min(te), q(te)["p25"], q(te)["p75"], mp / me,
+                                                                                                                    res["batches"][str(bs)]["E_max_abs_diff_over_max_F"]), flush=True)
+                print("  E kernels (us per launch):", {n: v["us_per_launch"] for n, v in ke.items()}, flush=True)
     os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
     with open(args.out, "w") as f_:
         json.dump(res, f_, indent=1)
