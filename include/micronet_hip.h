@@ -908,6 +908,13 @@ int mn_bitconv_supported(const mn_conv_geom* g);
 int64_t mn_bitconv_table_bytes(const mn_conv_geom* g);
 int mn_bitconv_pack(const mn_conv_geom* g, const float* w, const float* bias, const int32_t* out_order, uint32_t* table, mn_stream_t stream);
 int mn_bitconv_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t* x_bits, uint32_t* y_bits, int pool, mn_stream_t stream);
+/* The launch rule every bit / code / byte forward of this header sizes grid.y with (host only, nothing is launched): `bx` pixel blocks (grid.x) and `units` -- output
+ * words, sets of 64 rows or spans -- to deal over grid.y.
+ *   rows : grid.y where the units go round-robin (unit u, u + grid.y, ...: the 3x3 MFMA forms);
+ *   deal : grid.y where block b takes the consecutive units b * per .. min((b + 1) * per, units) - 1 (every other forward); *per receives `per`.
+ * bx < 1, units < 1 or a null `per` is MN_EINVAL. */
+int mn_deploy_grid_rows(int bx, int units);
+int mn_deploy_grid_deal(int bx, int units, int* per);
 /* The int8-MFMA form of the 1x1 hidden block: the same quartet, bits, out_order, decision, header word 0 and `pool` as mn_bitconv_*; only the contraction differs, so
  * the output words equal mn_bitconv_fwd's word for word.  Covered (mn_bitconv_mfma_supported): 1x1, stride 1, padding 0, dilation 1, in_shuffle 0 / 1; groups == 1 with
  * any C, or C / groups % 32 == 0 (every group starts on an input word); any O; W = 3 and W = 2 weights alike (t = sign(w), 0 where w == 0).  Everything else -- 3x3,

@@ -728,6 +728,17 @@ extern "C" int mn_bitconv_fwd(const mn_conv_geom* g, const uint32_t* table, cons
     return MN_OK;
 }
 
+// the launch rule of every bit / code / byte forward (qgemm_mfma_sets.h), for a caller that wants to know how a geometry is dealt: host only, nothing is launched
+extern "C" int mn_deploy_grid_rows(int bx, int units) {
+    if (bx < 1 || units < 1) MN_FAIL(MN_EINVAL, "mn_deploy_grid_rows: bx and units must be at least 1");
+    return mn_sets::grid_rows(bx, units);
+}
+
+extern "C" int mn_deploy_grid_deal(int bx, int units, int* per) {
+    if (bx < 1 || units < 1 || !per) MN_FAIL(MN_EINVAL, "mn_deploy_grid_deal: bx and units must be at least 1, per not null");
+    return mn_sets::grid_deal(bx, units, *per);
+}
+
 extern "C" int mn_bits_maxpool(const uint32_t* bits_in, int64_t N, int64_t Cw, int64_t H, int64_t W, int k, int stride, int pad, uint32_t* bits_out, mn_stream_t stream) {
     if (!bits_in || !bits_out || N <= 0 || Cw <= 0 || H <= 0 || W <= 0 || H > (1 << 15) || W > (1 << 15)) MN_FAIL(MN_EINVAL, "mn_bits_maxpool: null / empty argument");
     if ((k != 2 && k != 3) || stride != 2 || pad < 0 || pad > 1) MN_FAIL(MN_ENOTSUP, "mn_bits_maxpool: window not covered (k in {2, 3}, stride 2, padding in {0, 1}, floor mode)");

@@ -27,6 +27,12 @@ BLOCKS = [
     ("binary_weights", (1, 64, 4, 4), (64, 32, 3, 3), 2, 0, 2, 0, 4308),         # W = 2: no zero weight
     ("span_of_four", (1, 256, 4, 4), (512, 16, 3, 3), 16, 8, 3, 0, 4309),        # span of 4 words (shuffle 8 over 16 groups: 8 groups x 16 rows in 128 positions)
 ]
+# Several spans per block (tests/deploy_grid.py): the smallest shapes at which a block of k_bitconv_mfma3 takes a second span (sp += gridDim.y).  Seven words in spans
+# of two: four spans over grid.y = 3 at bx = 688 -- block 0 takes spans 0 and 3.  GPU only (tests/test_gpu_bits_mfma3.py): about 120 s each on the CPU emulation build (8 cores).
+LARGE_GRID = [
+    ("four_spans", (43, 16, 64, 64), (224, 16, 3, 3), 1, 0, 3, 0, 4310),
+    ("four_spans_shuffled_partial", (43, 16, 64, 64), (200, 16, 3, 3), 1, 4, 3, None, 4311),          # O % 32 = 8
+]
 SPANS = {"nin_gc_l4": 8, "nin_gc_l7": 16, "nin_dense": 2, "span_of_four": 4}          # header word 2 where the span is known
 FILL_X, FILL_W = (1, 400, 3, 3), (32, 400, 3, 3)          # all nine taps inside at the centre pixel only: acc = +-3600 there, +-1600 / +-2400 elsewhere
 
@@ -43,8 +49,8 @@ REFUSED = [
 ]
 
 
-def check_block(be, case):
-    cid, x_shape, w_shape, groups, s, Wb, dead, seed = BLOCKS[case]
+def check_block(be, case, table=None):
+    cid, x_shape, w_shape, groups, s, Wb, dead, seed = (BLOCKS if table is None else table)[case]
     _, x_log, w, b, a_ref = make_inputs(x_shape, w_shape, groups, 0, 1, seed, Wb)
     assert (a_ref == 1).any() and (a_ref == -1).any()
     order = shuffle_order(w_shape[0], s) if s else None
@@ -54,6 +60,18 @@ def check_block(be, case):
     assert int(hdr[1]) == (9 * (x_shape[1] // groups // 16) + 3) // 4 and int(hdr[4]) == 32 * ((w_shape[0] + 31) // 32)
     if cid in SPANS:
         assert int(hdr[2]) == SPANS[cid], ("span", int(hdr[2]))
+    return hdr
+
+
+def check_large(be, case):
+    """One LARGE_GRID case: check_block -- both judges --, and through the library's own launch rule and the span the packer wrote into the table (header word 2) that
+    some block of grid.y took a second span and some block did not."""
+    import deploy_grid as DG
+    _, (N, _, H, Wd), w_shape, _, _, _, _, _ = LARGE_GRID[case]
+    hdr = check_block(be, case, LARGE_GRID)
+    OW = (w_shape[0] + 31) // 32
+    span = int(hdr[2])
+    DG.assert_uneven_rows(be, DG.pixel_blocks(N * H * Wd, 256), (OW + 1) >> 1, (OW + span - 1) // span)
 
 
 def check_fill(be, sign):

@@ -24,6 +24,13 @@ BLOCKS = [
     ("binary_weights", (1, 128, 4, 8), (64, 64, 1, 1), 2, 2, 0, 2, 4106),           # W = 2: no zero weight
 ]
 
+# Several sets per block (tests/deploy_grid.py): the smallest shapes at which a block of k_bitconv_mfma walks set0 .. set1 over more than one set.  Seven sets over
+# bx = 344 (pooled: 22016 pooled pixels / 64): four blocks of two, the last takes one.  GPU only (tests/test_gpu_bits_mfma.py): 56 s and 45 s on the CPU emulation build (8 cores).
+LARGE_GRID = [
+    ("seven_sets", (86, 64, 32, 32), (448, 32, 1, 1), 2, 2, 0, 3, 4110),
+    ("seven_sets_pool_partial", (86, 64, 32, 32), (400, 32, 1, 1), 2, 4, 1, 3, 4111),          # 13 words: the last set is half a set, its last word half a word
+]
+
 # (geometry keywords, in_shuffle, pool)
 REFUSED = [
     (dict(x_shape=(1, 32, 8, 8), w_shape=(32, 32, 3, 3), padding=1), 0, 0),                # a 3x3: k_bitconv / k_bitconv_mfma3 keep it
@@ -114,14 +121,25 @@ def against_both(be, quartet, kernel, x_log, w, b, a_ref, groups, padding, order
     return hdr
 
 
-def check_block(be, case):
-    _, x_shape, w_shape, groups, s, pool, Wb, seed = BLOCKS[case]
+def check_block(be, case, table=None):
+    _, x_shape, w_shape, groups, s, pool, Wb, seed = (BLOCKS if table is None else table)[case]
     _, x_log, w, b, a_ref = make_inputs(x_shape, w_shape, groups, 0, 0, seed, Wb)
     assert (a_ref == 1).any() and (a_ref == -1).any()
     order = shuffle_order(w_shape[0], s) if s else None
     hdr = against_both(be, "mn_bitconv_mfma", "k_bitconv_mfma<%d>" % pool, x_log, w, b, a_ref, groups, 0, order, pool,
                        "%s %s groups %d shuffle %d pool %d W %d" % (x_shape, w_shape, groups, s, pool, Wb))
     assert (int(hdr[1]), int(hdr[4]), int(hdr[5])) == ((x_shape[1] // groups + 63) // 64, 32 * ((w_shape[0] + 31) // 32), (x_shape[1] + 31) // 32)
+    return hdr
+
+
+def check_large(be, case):
+    """One LARGE_GRID case: the library's own launch rule says that a block takes at least two sets and the last block fewer; then check_block -- both judges."""
+    import deploy_grid as DG
+    _, (N, _, H, Wd), w_shape, _, _, pool, _, _ = LARGE_GRID[case]
+    bx = DG.pixel_blocks(N * (H // 2) * (Wd // 2), 64) if pool else DG.pixel_blocks(N * H * Wd, 256)
+    DG.assert_uneven_deal(be, bx, ((w_shape[0] + 31) // 32 + 1) // 2)          # a set: the rows of two consecutive output words
+    hdr = check_block(be, case, LARGE_GRID)
+    assert (int(hdr[4]) // 32 + 1) // 2 == ((w_shape[0] + 31) // 32 + 1) // 2
 
 
 def check_refused(be, case, quartet="mn_bitconv_mfma", table=REFUSED):

@@ -47,9 +47,10 @@ def np_maxpool(a, k, s, p):
     """max-pool of an integer [N, C, H, W] array, floor mode; padding never wins (nn.MaxPool2d pads with -inf)."""
     N, Cc, H, W = a.shape
     Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
-    big = np.full((N, Cc, H + 2 * p + k, W + 2 * p + k), -128, dtype=np.int32)
+    dt = np.int8 if a.dtype == np.int8 else np.int32          # (+-1 codes stay bytes: -128 is still below every cell)
+    big = np.full((N, Cc, H + 2 * p + k, W + 2 * p + k), -128, dtype=dt)
     big[:, :, p:p + H, p:p + W] = a
-    out = np.full((N, Cc, Ho, Wo), -128, dtype=np.int32)
+    out = np.full((N, Cc, Ho, Wo), -128, dtype=dt)
     for dy in range(k):
         for dx in range(k):
             out = np.maximum(out, big[:, :, dy:dy + s * Ho:s, dx:dx + s * Wo:s])
@@ -93,6 +94,44 @@ def check_case(be, x_shape, w_shape, groups=1, padding=0, pool=0, alt=False, see
     print(name, x_shape, w_shape, "pool", pool, "W", W, "mismatches", int((got != ref).sum()), "of", got.size)
     assert got.shape == ref.shape and np.array_equal(got, ref), (name, int((got != ref).sum()), got.size)
     return name
+
+
+# Several output words per block (tests/deploy_grid.py): the smallest shapes at which a block of the popcount kernels walks ow0 .. ow1 over more than one word.
+# (id, check_case keywords, out_order shuffle, kernel).  Seven words over bx = 344: four blocks of two, the last takes one.  Wall time of the whole case on the CPU
+# emulation build (8 cores, judge included) beside each: all below 20 s, so tests/test_bits_nin_emu.py runs the table as well as tests/test_gpu_bits_nin.py.
+LARGE_GRID = [
+    ("k1", dict(x_shape=(86, 32, 32, 32), w_shape=(224, 32, 1, 1)), 4, "k_bitconv<1,1,0>"),                                        # emulated: 7 s
+    ("k3_grouped_partial_word", dict(x_shape=(86, 32, 32, 32), w_shape=(200, 16, 3, 3), groups=2, padding=1), 4, "k_bitconv<3,1,0>"),          # O % 32 = 8.  12 s
+    ("tile5", dict(x_shape=(86, 8, 32, 32), w_shape=(224, 8, 5, 5), padding=2), 0, "k_bitconv_tile<5,0>"),                         # 4 * 86 tiles of 16 x 16.  18 s
+    ("k1_pool3", dict(x_shape=(344, 32, 32, 32), w_shape=(224, 32, 1, 1), pool=2), 0, "k_bitconv1_pool3<8>"),                      # 344 * 256 pooled pixels.  14 s
+]
+
+
+def check_large(be, idx, seed=1600):
+    """One LARGE_GRID case: the library's own launch rule says that a block takes at least two output words and the last block fewer; then two runs into poisoned
+    buffers, identical, equal to the integer model bit for bit (position j holds channel order[j])."""
+    import deploy_grid as DG
+    from codes_cases import shuffle_order
+    cid, kw, s, kernel = LARGE_GRID[idx]
+    x_shape, w_shape, groups, padding, pool = kw["x_shape"], kw["w_shape"], kw.get("groups", 1), kw.get("padding", 0), kw.get("pool", 0)
+    N, _, H, Wd = x_shape
+    Oc = w_shape[0]
+    Ho, Wo = (pooled_size(H, 3, 2, 1), pooled_size(Wd, 3, 2, 1)) if pool == 2 else (H, Wd)
+    bx = DG.tile_blocks(N, H, Wd) if kernel.startswith("k_bitconv_tile") else DG.pixel_blocks(N * Ho * Wo, 256)
+    gy, per = DG.assert_uneven_deal(be, bx, (Oc + 31) // 32)
+    _, x_log, w, b, a_ref = B.make_inputs(x_shape, w_shape, groups, 0, padding, seed + idx, 3)
+    assert (a_ref == 1).any() and (a_ref == -1).any()
+    order = shuffle_order(Oc, s) if s else None
+    got, name = run_bitconv(be, x_log, w, b, groups, padding, pool, out_order=order)
+    again, _ = run_bitconv(be, x_log, w, b, groups, padding, pool, out_order=order)
+    assert name == kernel, name
+    assert np.array_equal(got, again), "two runs give identical bits"
+    ref = a_ref[:, order] if s else a_ref
+    if pool:
+        ref = np_maxpool(ref, *(POOLS[pool - 1]))
+    bad = int((got != ref).sum())
+    print(name, cid, x_shape, w_shape, "pool", pool, "shuffle", s, "grid.y", gy, "per", per, "mismatches", bad, "of", got.size)
+    assert got.shape == ref.shape and bad == 0, (name, bad, got.size)
 
 
 def check_consumer_order(be, seed=0):

@@ -66,15 +66,19 @@ def check_pack_roundtrip(be, Cc, seed=0):
 
 
 # ---------------------------------------------------------------------------------------------- one block
-def make_inputs(x_shape, w_shape, groups=1, padding=0, seed=0, **_):
-    """(codes uint8 [N, C, H, W] in 0..3, stored weights fp32 on the grid (2k - 3) / 3, exact accumulator int64 [N, O, H, W])."""
+def make_inputs(x_shape, w_shape, groups=1, padding=0, seed=0, conv=None, **_):
+    """(codes uint8 [N, C, H, W] in 0..3, stored weights fp32 on the grid (2k - 3) / 3, exact accumulator int64 [N, O, H, W]).  conv: another exact integer
+    convolution (x, k, padding, groups) for the sizes at which np_oracle's int64 one is too slow (deploy_grid.exact_conv)."""
     r = np.random.default_rng(seed)
     codes = r.integers(0, 4, size=x_shape).astype(np.uint8)
     codes[:, :, 0, 0] = 0                                            # whole-zero pixels and a saturated one
     codes[0, :, -1, -1] = N_LEVELS
     k = r.integers(0, 4, size=w_shape).astype(np.int64)
     w = (F(2) * (k.astype(F) / F(N_LEVELS)) - F(1)).astype(F)       # what the DoReFa weight quantizer stores
-    acc = O.conv2d_fwd(codes.astype(np.int64), 2 * k - N_LEVELS, None, padding=padding, groups=groups, acc=np.int64)
+    if conv is None:
+        acc = O.conv2d_fwd(codes.astype(np.int64), 2 * k - N_LEVELS, None, padding=padding, groups=groups, acc=np.int64)
+    else:
+        acc = conv(codes.astype(np.int64), 2 * k - N_LEVELS, padding, groups)
     assert np.abs(acc).max() <= 32767
     return codes, w, acc
 
@@ -197,6 +201,47 @@ def check_codeconv(be, x_shape, w_shape, groups=1, padding=0, seed=0, pools=(0, 
         assert (full[:, 1] == 0).all() and (full[:, 2] == N_LEVELS).all() and len(np.unique(full[:, 0])) == 1
     v0 = chan[2, 4]
     assert (acc[:, 4] == int(v0)).any() and (acc[:, 5] == int(chan[2, 5])).any(), "a code boundary sits on an attained accumulator value"
+
+
+# Several output words per block (tests/deploy_grid.py): the smallest shapes at which a block of k_codeconv walks ow0 .. ow1 over more than one word group.  Seven
+# groups over bx = 344: four blocks of two, the last takes one.  (id, check_codeconv keywords, out_order shuffle, kernel).  Wall time of the whole case on the CPU
+# emulation build (8 cores, judge included) beside each: below 20 s, so tests/test_codes_emulated.py runs the table as well as tests/test_gpu_codes.py.
+LARGE_GRID = [
+    ("k1", dict(x_shape=(86, 32, 32, 32), w_shape=(224, 32, 1, 1), seed=1500), 4, "k_codeconv<1,1,0>"),          # emulated: 9 s
+    ("k3_grouped_partial_word", dict(x_shape=(86, 32, 32, 32), w_shape=(200, 16, 3, 3), groups=2, padding=1, seed=1501), 4, "k_codeconv<3,1,0>"),          # O % 32 = 8.  17 s
+]
+
+
+def check_large(be, idx):
+    """One LARGE_GRID case: the library's own launch rule says that a block takes at least two word groups and the last block fewer; then the un-pooled block in the
+    consumer's order, twice into poisoned planes, against the judge."""
+    import deploy_grid as DG
+    cid, kw, s, kernel = LARGE_GRID[idx]
+    x_shape, w_shape, groups, padding, seed = kw["x_shape"], kw["w_shape"], kw.get("groups", 1), kw.get("padding", 0), kw["seed"]
+    N, _, H, Wd = x_shape
+    Oc = w_shape[0]
+    gy, per = DG.assert_uneven_deal(be, DG.pixel_blocks(N * H * Wd, 256), (Oc + 31) // 32)
+    codes, w, acc = make_inputs(x_shape, w_shape, groups, padding, seed)
+    chan = make_chan(acc, seed)
+    ref = judge(be, acc, chan, 0)
+    assert len(np.unique(ref)) == 4, "the case must produce all four codes"
+    full = chain_codes(acc, chan, 0)
+    assert (full[:, 1] == 0).all() and (full[:, 2] == N_LEVELS).all() and len(np.unique(full[:, 0])) == 1
+    assert (acc[:, 4] == int(chan[2, 4])).any() and (acc[:, 5] == int(chan[2, 5])).any(), "a code boundary sits on an attained accumulator value"
+    order = shuffle_order(Oc, s)
+    outs = []
+    for _ in range(2):
+        yp = codeconv_planes(be, codes, w, chan, groups, padding, order, 0)          # poisoned planes
+        name = be.lib.mn_last_kernel().decode()
+        outs.append(_host_u32(be, yp))
+    assert name == kernel, name
+    assert np.array_equal(outs[0], outs[1]), "two runs give identical planes"
+    if Oc % 32:
+        assert not (outs[0][:, -1] >> np.uint32(Oc % 32)).any(), "unused bits of the last output group are 0"
+    got, want = np_unpack_planes(outs[0], Oc), ref[:, order]
+    bad = int((got != want).sum())
+    print(name, cid, x_shape, w_shape, "groups", groups, "shuffle", s, "grid.y", gy, "per", per, "mismatches", bad, "of", got.size)
+    assert got.shape == want.shape and bad == 0, (bad, got.size)
 
 
 def check_nonfinite_counted(be, x_shape=(1, 32, 4, 4), w_shape=(32, 16, 1, 1), groups=2, seed=3):

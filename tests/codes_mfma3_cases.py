@@ -28,6 +28,12 @@ BLOCKS = [
     ("one_row", (2, 32, 1, 8), (32, 32, 3, 3), 1, 0, 0, 3306),                # a whole tap row outside everywhere
     ("one_column", (1, 32, 8, 1), (32, 32, 3, 3), 1, 0, 0, 3307),             # a whole tap column outside everywhere
 ]
+# Several spans per block (tests/deploy_grid.py): the smallest shapes at which a block of k_codeconv_mfma3 takes a second span (sp += gridDim.y).  Seven word groups
+# in spans of two: four spans over grid.y = 3 at bx = 688 -- block 0 takes spans 0 and 3.  GPU only (tests/test_gpu_codes_mfma3.py): 134 s and 110 s on the CPU emulation build.
+LARGE_GRID = [
+    ("four_spans", (43, 16, 64, 64), (224, 16, 3, 3), 1, 0, 0, 3310),
+    ("four_spans_shuffled_partial", (43, 16, 64, 64), (200, 16, 3, 3), 1, 4, None, 3311),          # O % 32 = 8
+]
 SPANS = {"nin_gc_l4": 8, "nin_gc_l7": 16, "nin_dense": 2}          # header word 2 where the issue names the span
 FILL_X, FILL_W, FILL_EXTREME = (1, 400, 3, 3), (32, 400, 3, 3), 32400          # the K bound: every code 3 against every weight code 3 / 0, all nine taps at the centre
 
@@ -101,9 +107,20 @@ def _against_both(be, codes, w, chan, groups, order, ref, what):
     return hdr
 
 
-def check_block(be, case):
-    cid, x_shape, w_shape, groups, s, dead, seed = BLOCKS[case]
-    codes, w, acc = make_inputs(x_shape, w_shape, groups, 1, seed)
+def check_large(be, case):
+    """One LARGE_GRID case: check_block -- the judge and mn_codeconv_fwd's planes; the exact accumulator comes from deploy_grid.exact_conv at this size --, and through
+    the library's own launch rule and the span the packer wrote into the table (header word 2) that some block of grid.y took a second span and some block did not."""
+    import deploy_grid as DG
+    _, (N, _, H, Wd), w_shape, _, _, _, _ = LARGE_GRID[case]
+    hdr = check_block(be, case, LARGE_GRID, DG.exact_conv)
+    OW = (w_shape[0] + 31) // 32
+    span = int(hdr[2])
+    DG.assert_uneven_rows(be, DG.pixel_blocks(N * H * Wd, 256), (OW + 1) >> 1, (OW + span - 1) // span)
+
+
+def check_block(be, case, table=None, conv=None):
+    cid, x_shape, w_shape, groups, s, dead, seed = (BLOCKS if table is None else table)[case]
+    codes, w, acc = make_inputs(x_shape, w_shape, groups, 1, seed, conv=conv)
     chan = make_chan(acc, seed)
     ref = judge_any(be, acc, chan, 0)
     assert len(np.unique(ref)) == 4, "the case must produce all four codes"
@@ -116,6 +133,7 @@ def check_block(be, case):
     assert int(hdr[1]) == (9 * (x_shape[1] // groups // 16) + 3) // 4 and int(hdr[4]) == 32 * ((w_shape[0] + 31) // 32)
     if cid in SPANS:
         assert int(hdr[2]) == SPANS[cid], ("span", int(hdr[2]))
+    return hdr
 
 
 def check_fill(be, kcode):

@@ -27,6 +27,13 @@ BLOCKS = [
     ("half_a_step", (1, 128, 8, 8), (64, 32, 1, 1), 4, 0, 0, 3104),              # half a k-step, two groups per output word
     ("dead_rows", (1, 64, 4, 8), (48, 32, 1, 1), 2, 0, 0, 3105),                 # 24 rows per group: dead rows
 ]
+# Several sets per block (tests/deploy_grid.py): the smallest shapes at which a block of k_codeconv_mfma walks set0 .. set1 over more than one set.  Seven sets over
+# bx = 344 (pooled: 22016 pooled pixels / 64): four blocks of two, the last takes one.  GPU only (tests/test_gpu_codes_mfma.py): 70 s and 52 s on the CPU
+# emulation build (8 cores).
+LARGE_GRID = [
+    ("seven_sets", (86, 64, 32, 32), (448, 32, 1, 1), 2, 2, 0, 3110),
+    ("seven_sets_pool_partial", (86, 64, 32, 32), (400, 32, 1, 1), 2, 4, 1, 3111),          # 13 words: the last set is half a set, its last word half a word
+]
 FILL_X, FILL_W, FILL_EXTREME = (1, K_BOUND_C, 2, 2), (32, K_BOUND_C, 1, 1), 32760          # the K bound: every code 3 against every weight code 3 / 0
 
 # (geometry keywords, (a_bits_in, w_bits, a_bits_out), pool)
@@ -112,8 +119,18 @@ def _against_both(be, codes, w, chan, groups, order, pool, ref, what):
     assert planes.shape == popc.shape and np.array_equal(planes, popc), "the planes of mn_codeconv_fwd, word for word"
 
 
-def check_block(be, case):
-    _, x_shape, w_shape, groups, s, pool, seed = BLOCKS[case]
+def check_large(be, case):
+    """One LARGE_GRID case: the library's own launch rule says that a block takes at least two sets and the last block fewer; then check_block -- the judge and
+    mn_codeconv_fwd's planes."""
+    import deploy_grid as DG
+    _, (N, _, H, Wd), w_shape, _, _, pool, _ = LARGE_GRID[case]
+    bx = DG.pixel_blocks(N * (H // 2) * (Wd // 2), 64) if pool else DG.pixel_blocks(N * H * Wd, 256)
+    DG.assert_uneven_deal(be, bx, ((w_shape[0] + 31) // 32 + 1) // 2)          # a set: the rows of two consecutive output words
+    check_block(be, case, LARGE_GRID)
+
+
+def check_block(be, case, table=None):
+    _, x_shape, w_shape, groups, s, pool, seed = (BLOCKS if table is None else table)[case]
     codes, w, acc = make_inputs(x_shape, w_shape, groups, 0, seed)
     chan = make_chan(acc, seed)
     ref = judge_any(be, acc, chan, pool)

@@ -24,6 +24,12 @@ BLOCKS = [
     ("k_bound_short_map", (1, K_BOUND_C, 4, 8), (32, K_BOUND_C, 5, 5), 0, "k_codeconv_tile<5,0>"),          # the K bound, five words rolled, a map shorter than the kernel
     ("shuffled_order", (2, 32, 16, 16), (64, 32, 5, 5), 4, "k_codeconv_tile<5,0>"),
 ]
+# Several output word groups per block (tests/deploy_grid.py): the smallest shape at which a block of k_codeconv_tile walks more than one group.  4 * 86 tiles of
+# 16 x 16, seven groups: four blocks of two, the last takes one; O % 32 = 8, the consumer's shuffle.  GPU only (tests/test_gpu_codes_nin.py): 24 s on the
+# CPU emulation build (8 cores).
+LARGE_GRID = [
+    ("seven_groups", (86, 8, 32, 32), (200, 8, 5, 5), 4, "k_codeconv_tile<5,0>"),
+]
 # the K-bound fills: every code 3 against every weight code 3 / 0.  On the 4 x 8 map of the case above a window holds at most 4 x 5 taps (acc = +-26100); the 5 x 8
 # map holds a whole window, so that acc = +-32625 = +-(145 * 25 * 9), the ends of the range, is attained
 FILLS = [((1, K_BOUND_C, 4, 8), 26100), ((1, K_BOUND_C, 5, 8), 32625)]
@@ -87,10 +93,19 @@ def tile_planes(be, codes, w, chan, order=None):
     return outs[0], name
 
 
-def check_block(be, case):
-    _, x_shape, w_shape, s, kernel = BLOCKS[case]
-    seed = 2100 + case
-    codes, w, acc = make_inputs(x_shape, w_shape, 1, 2, seed)
+def check_large(be, case):
+    """One LARGE_GRID case: the library's own launch rule says that a block takes at least two word groups and the last block fewer; then check_block, whose exact
+    accumulator comes from deploy_grid.exact_conv at this size."""
+    import deploy_grid as DG
+    _, (N, _, H, Wd), w_shape, _, _ = LARGE_GRID[case]
+    DG.assert_uneven_deal(be, DG.tile_blocks(N, H, Wd), (w_shape[0] + 31) // 32)
+    check_block(be, case, LARGE_GRID, 2150, DG.exact_conv)
+
+
+def check_block(be, case, table=None, seed0=2100, conv=None):
+    _, x_shape, w_shape, s, kernel = (BLOCKS if table is None else table)[case]
+    seed = seed0 + case
+    codes, w, acc = make_inputs(x_shape, w_shape, 1, 2, seed, conv=conv)
     chan = make_chan(acc, seed)
     ref = judge(be, acc, chan, 0)
     assert len(np.unique(ref)) == 4, "the case must produce all four codes"

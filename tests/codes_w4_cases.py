@@ -39,6 +39,17 @@ BLOCKS3 = [
     ("dead_rows", (1, 32, 8, 8), (48, 16, 3, 3), 2, 0, None, 4303),              # dead rows
     ("all_border", (1, 16, 2, 4), (32, 16, 3, 3), 1, 0, (2, 0), 4304),           # every pixel on the border
 ]
+# Several units per block (tests/deploy_grid.py) at 4 bits, the shapes of codes_mfma_cases.LARGE_GRID / codes_mfma3_cases.LARGE_GRID: seven sets over bx = 344
+# (four blocks of two, the last takes one); four spans of two word groups over grid.y = 3 at bx = 688 (block 0 takes spans 0 and 3).  GPU only (tests/test_gpu_codes_w4.py): 98 s,
+# 52 s, 110 s and 106 s on the CPU emulation build (8 cores).
+LARGE1 = [
+    ("seven_sets", (86, 64, 32, 32), (448, 32, 1, 1), 2, 2, 0, 4110),
+    ("seven_sets_pool_partial", (86, 64, 32, 32), (400, 32, 1, 1), 2, 4, 1, 4111),
+]
+LARGE3 = [
+    ("four_spans", (43, 16, 64, 64), (224, 16, 3, 3), 1, 0, (2, 0), 4310),
+    ("four_spans_shuffled_partial", (43, 16, 64, 64), (200, 16, 3, 3), 1, 4, None, 4311),
+]
 FILL1_X, FILL1_W, FILL1_EXTREME = (1, K_BOUND_C, 2, 2), (32, K_BOUND_C, 1, 1), 32625          # every code 15 against every weight code 15 / 0
 FILL3_X, FILL3_W, FILL3_EXTREME = (1, 16, 4, 4), (32, 16, 3, 3), 32400                        # ... the interior pixels attain it
 
@@ -62,15 +73,19 @@ def _lib():
 
 
 # ---------------------------------------------------------------------------------------------- inputs and the judge
-def make_inputs(x_shape, w_shape, groups=1, padding=0, seed=0):
-    """(codes uint8 [N, C, H, W] in 0..15, stored weights fp32 on the grid (2k - 15) / 15, exact accumulator int64 [N, O, H, W])."""
+def make_inputs(x_shape, w_shape, groups=1, padding=0, seed=0, conv=None):
+    """(codes uint8 [N, C, H, W] in 0..15, stored weights fp32 on the grid (2k - 15) / 15, exact accumulator int64 [N, O, H, W]).  conv: another exact integer
+    convolution (x, k, padding, groups) for the sizes at which np_oracle's int64 one is too slow (deploy_grid.exact_conv)."""
     r = np.random.default_rng(seed)
     codes = r.integers(0, N_LEVELS + 1, size=x_shape).astype(np.uint8)
     codes[:, :, 0, 0] = 0                                            # whole-zero pixels and a saturated one
     codes[0, :, -1, -1] = N_LEVELS
     k = r.integers(0, N_LEVELS + 1, size=w_shape).astype(np.int64)
     w = (F(2) * (k.astype(F) / F(N_LEVELS)) - F(1)).astype(F)       # what the DoReFa weight quantizer stores
-    acc = O.conv2d_fwd(codes.astype(np.int64), 2 * k - N_LEVELS, None, padding=padding, groups=groups, acc=np.int64)
+    if conv is None:
+        acc = O.conv2d_fwd(codes.astype(np.int64), 2 * k - N_LEVELS, None, padding=padding, groups=groups, acc=np.int64)
+    else:
+        acc = conv(codes.astype(np.int64), 2 * k - N_LEVELS, padding, groups)
     assert np.abs(acc).max() <= 32767
     return codes, w, acc
 
@@ -205,9 +220,9 @@ def _check_case_inputs(acc, chan, ref):
         assert set(np.unique(full[:, c][acc[:, c] == int(chan[2, c])])) <= {7, 8}
 
 
-def check_block1(be, case):
-    _, x_shape, w_shape, groups, s, pool, seed = BLOCKS1[case]
-    codes, w, acc = make_inputs(x_shape, w_shape, groups, 0, seed)
+def check_block1(be, case, table=None, conv=None):
+    _, x_shape, w_shape, groups, s, pool, seed = (BLOCKS1 if table is None else table)[case]
+    codes, w, acc = make_inputs(x_shape, w_shape, groups, 0, seed, conv=conv)
     chan = make_chan(acc, seed)
     ref = judge(be, acc, chan, pool)
     _check_case_inputs(acc, chan, ref)
@@ -216,9 +231,9 @@ def check_block1(be, case):
     assert int(hdr[1]) == (x_shape[1] // groups + 63) // 64 and int(hdr[4]) == 32 * ((w_shape[0] + 31) // 32) and int(hdr[5]) == (x_shape[1] + 31) // 32
 
 
-def check_block3(be, case):
-    _, x_shape, w_shape, groups, s, span_dead, seed = BLOCKS3[case]
-    codes, w, acc = make_inputs(x_shape, w_shape, groups, 1, seed)
+def check_block3(be, case, table=None, conv=None):
+    _, x_shape, w_shape, groups, s, span_dead, seed = (BLOCKS3 if table is None else table)[case]
+    codes, w, acc = make_inputs(x_shape, w_shape, groups, 1, seed, conv=conv)
     chan = make_chan(acc, seed)
     ref = judge(be, acc, chan, 0)
     _check_case_inputs(acc, chan, ref)
@@ -230,6 +245,27 @@ def check_block3(be, case):
         assert int(hdr[5]) > 0, ("dead rows", int(hdr[5]))
     else:
         assert (int(hdr[2]), int(hdr[5])) == span_dead, ("span, dead rows", int(hdr[2]), int(hdr[5]))
+    return hdr
+
+
+def check_large1(be, case):
+    """One LARGE1 case: the library's own launch rule says that a block takes at least two sets and the last block fewer; then check_block1 against the judge."""
+    import deploy_grid as DG
+    _, (N, _, H, Wd), w_shape, _, _, pool, _ = LARGE1[case]
+    bx = DG.pixel_blocks(N * (H // 2) * (Wd // 2), 64) if pool else DG.pixel_blocks(N * H * Wd, 256)
+    DG.assert_uneven_deal(be, bx, ((w_shape[0] + 31) // 32 + 1) // 2)          # a set: the rows of two consecutive output words
+    check_block1(be, case, LARGE1, DG.exact_conv)
+
+
+def check_large3(be, case):
+    """One LARGE3 case: check_block3 against the judge, and through the library's own launch rule and the span the packer wrote into the table (header word 2) that
+    some block of grid.y took a second span and some block did not."""
+    import deploy_grid as DG
+    _, (N, _, H, Wd), w_shape, _, _, _, _ = LARGE3[case]
+    hdr = check_block3(be, case, LARGE3, DG.exact_conv)
+    OW = (w_shape[0] + 31) // 32
+    span = int(hdr[2])
+    DG.assert_uneven_rows(be, DG.pixel_blocks(N * H * Wd, 256), (OW + 1) >> 1, (OW + span - 1) // span)
 
 
 def check_fill(be, form, kcode):

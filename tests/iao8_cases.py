@@ -260,6 +260,69 @@ def check_block(be, idx):
     _check(be, case, shuffle, pools, "%s %s -> %d k%d groups %d shuffle %d" % (name, x_shape, Oc, KS, groups, shuffle))
 
 
+# ---------------------------------------------------------------------------------------------- several sets per block (tests/deploy_grid.py)
+# The smallest shapes at which a block of k_i8conv takes more than one set: (id, x shape, O, KS, groups, out_order shuffle, pool, seed).  16 channels keep the judge
+# cheap; the pixels cannot shrink (the loop is entered once the pixel blocks alone fill the chip).  GPU only (tests/test_gpu_iao8.py): on the CPU emulation build
+# (8 cores) a case takes 44 to 114 s, against one to four seconds on the MI355X.
+LARGE_GRID = [
+    ("k1_nine_sets", (75, 16, 32, 32), 576, 1, 1, 0, 0, 4400),               # bx 300, 9 sets: 5 blocks of 2, the last takes 1.  Emulated: 46 s
+    ("k1_nine_sets_pool", (75, 16, 32, 32), 568, 1, 1, 4, 1, 4401),          # pooled: 19200 / 64 = 300 blocks; shuffle 4; the last set's last block half empty.  44 s
+    ("k3_nine_sets", (75, 16, 32, 32), 568, 3, 1, 4, 0, 4402),               # the 3x3 form, 16 channels per group.  114 s
+    ("k3_nine_sets_pool", (75, 16, 32, 32), 576, 3, 1, 0, 1, 4403),
+    # five sets dealt 3 + 2 over two rows: the last set, with positions past O that no row writes, is the SECOND of its block -- its bytes are whatever the read-back
+    # of the set before left in the LDS image (in the cases above the last set is the first of its block, or every byte of a set is overwritten)
+    ("k1_last_set_second", (256, 16, 32, 32), 312, 1, 1, 4, 0, 4404),        # bx 1024, 5 sets.  80 s
+    ("k1_last_set_second_pool", (256, 16, 32, 32), 312, 1, 1, 0, 1, 4405),   # pooled: 65536 / 64 = 1024 blocks
+]
+LARGE_HEAD = 25          # images make_case builds the block from (scales, bias, special channels, hardness); the rest of the batch is drawn from the same range
+
+
+def large_case(x_shape, Oc, KS, groups, seed):
+    """(case of the first LARGE_HEAD images -- the family's make_case, held to assert_case_is_hard --, codes int8 of the whole batch)."""
+    head = min(LARGE_HEAD, x_shape[0])
+    case = make_case((head,) + tuple(x_shape[1:]), Oc, KS, groups, seed)
+    assert_case_is_hard(case)
+    qmin, qmax = (int(v) for v in qrange(case["a_bits"]))
+    more = np.random.default_rng(seed + 500).integers(qmin, qmax + 1, size=(x_shape[0] - head,) + tuple(x_shape[1:])).astype(np.int8)
+    more[:, :, 0, 0] = 0          # (make_case's whole-zero pixel)
+    return case, np.concatenate([case["j"], more])
+
+
+def judge_chunks(case, j, pool):
+    """The judge on the whole batch, LARGE_HEAD images at a time: (first image, codes) per chunk.  The first chunk is the case's own accumulator."""
+    import deploy_grid as DG
+    for n0 in range(0, j.shape[0], LARGE_HEAD):
+        acc = DG.exact_conv(j[n0:n0 + LARGE_HEAD], case["k"], case["KS"] // 2, case["groups"])
+        if n0 == 0:
+            assert np.array_equal(acc, case["acc"])
+        assert np.abs(acc).max() < 2 ** 31
+        yield n0, chain_codes(acc, case["al"], case["b"], case["s_p"], case["s_out"], case["a_bits"], pool)
+
+
+def check_large(be, idx):
+    """One LARGE_GRID case through run_block (poisoned buffers, two identical runs, the kernel's name) against the judge, after proving through the library's own
+    launch rule that a block takes at least two sets and the last block fewer."""
+    import deploy_grid as DG
+    name, x_shape, Oc, KS, groups, shuffle, pool, seed = LARGE_GRID[idx]
+    case, j = large_case(x_shape, Oc, KS, groups, seed)
+    N, _, H, W = x_shape
+    OB = (Oc + 15) // 16
+    bx = DG.pixel_blocks(N * (H // 2) * (W // 2), 64) if pool else DG.pixel_blocks(N * H * W, 256)
+    nsets = (OB + 3) // 4
+    gy, per = DG.assert_uneven_deal(be, bx, nsets)
+    if "last_set_second" in name:
+        assert nsets - (gy - 1) * per >= 2 and Oc % 64, "the last block takes two sets at least, and the last of them has positions past O"
+    order = shuffle_order(Oc, shuffle) if shuffle else None
+    got, kname = run_block(be, dict(case, j=j), order, pool)
+    assert kname == "k_i8conv<%d,%d>" % (KS, pool), kname
+    bad = 0
+    for n0, ref in judge_chunks(case, j, pool):
+        want = expect_positions(ref, order, OB)
+        bad += int((got[n0:n0 + ref.shape[0]] != want).sum())
+    print(kname, name, x_shape, "->", Oc, "grid.y", gy, "per", per, "mismatches against the judge", bad, "of", got.size)
+    assert bad == 0, (bad, got.size)
+
+
 def check_extreme(be):
     name, x_shape, Oc = EXTREME
     case = make_case(x_shape, Oc, 1, 1, 4200, extreme=True)

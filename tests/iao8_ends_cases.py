@@ -260,6 +260,75 @@ def check_last_chain(be, idx):
     _check_last(be, case, order, name, widths[1] == 8)
 
 
+# ---------------------------------------------------------------------------------------------- several sets per block (tests/deploy_grid.py, iao8_cases.LARGE_GRID)
+# (id, x shape, O, KS, out_order shuffle): seed 5800 + index.  k_i8first gives every image ceil(H W / 256) blocks, so 8 x 8 images keep the judge cheap.  GPU only
+# (tests/test_gpu_iao8_ends.py): 31 s, 40 s and 71 s on the CPU emulation build (8 cores).
+LARGE_FIRST = [
+    ("f5_five_sets", (700, 3, 8, 8), 312, 5, 4),               # bx 700, 5 sets: blocks of 2, 2, 1; the last output block half empty
+    ("f5_last_set_second", (1024, 3, 8, 8), 312, 5, 0),        # bx 1024: blocks of 3 and 2 -- the last set, with positions past O, is the second of its block
+    ("f5_four_waves", (512, 3, 16, 16), 320, 5, 2),            # bx 512: blocks of 2, 2, 1; 256 pixels per image, so all four waves of a block have pixels (one at 8 x 8)
+]
+# (id, x shape, O, KS, groups): seed 5900 + index; a random out_order.  GPU only: 78 s on the CPU emulation build.
+LARGE_LAST = [
+    ("l1_five_sets", (130, 16, 32, 32), 312, 1, 1),            # bx 520, 5 sets: blocks of 2, 2, 1; O % 16 != 0
+]
+
+
+def check_large_first(be, idx):
+    import deploy_grid as DG
+    from iao8_cases import LARGE_HEAD
+    name, x_shape, Oc, KS, shuffle = LARGE_FIRST[idx]
+    seed = 5800 + idx
+    N, Cc, H, W = x_shape
+    head = first_case((LARGE_HEAD, Cc, H, W), Oc, KS, seed)
+    qmin, qmax = (int(v) for v in qrange(head["in_bits"]))
+    more = np.random.default_rng(seed + 500).integers(qmin, qmax + 1, size=(N - LARGE_HEAD, Cc, H, W)).astype(np.int8)
+    more[:, :, 0, 0] = 0          # (make_case's whole-zero pixel: make_image puts its -0.0 on a zero code)
+    case = dict(head, j=np.concatenate([head["j"], more]))
+    x, jx = make_image(case, seed)
+    OB = (Oc + 15) // 16
+    nsets = (OB + 3) // 4
+    gy, per = DG.assert_uneven_deal(be, N * DG.pixel_blocks(H * W, 256), nsets)
+    if "last_set_second" in name:
+        assert nsets - (gy - 1) * per >= 2 and Oc % 64, "the last block takes two sets at least, and the last of them has positions past O"
+    order = shuffle_order(Oc, shuffle) if shuffle else None
+    got, kname = run_first(be, case, x, order)
+    assert kname == "k_i8first<%d>" % KS, kname
+    bad = 0
+    for n0 in range(0, N, LARGE_HEAD):
+        acc = DG.exact_conv(jx[n0:n0 + LARGE_HEAD], head["k"], KS // 2, 1)
+        assert np.abs(acc).max() < 2 ** 31
+        if n0 == 0:
+            assert_case_is_hard(dict(head, j=jx[:LARGE_HEAD].astype(np.int8), acc=acc))
+        ref = chain_codes(acc, head["al"], head["b"], head["s_out"], head["s_out"], head["a_bits"], 0)
+        bad += int((got[n0:n0 + ref.shape[0]] != expect_positions(ref, order, OB)).sum())
+    print(kname, name, x_shape, "->", Oc, "grid.y", gy, "per", per, "mismatches against the judge", bad, "of", got.size)
+    assert bad == 0, (bad, got.size)
+
+
+def check_large_last(be, idx):
+    import deploy_grid as DG
+    from iao8_cases import LARGE_HEAD, large_case
+    name, x_shape, Oc, KS, groups = LARGE_LAST[idx]
+    seed = 5900 + idx
+    head, j = large_case(x_shape, Oc, KS, groups, seed)
+    case = dict(head, j=j)
+    N, _, H, W = x_shape
+    gy, per = DG.assert_uneven_deal(be, DG.pixel_blocks(N * H * W, 256), ((Oc + 15) // 16 + 3) // 4)
+    order = np.random.default_rng(seed).permutation(Oc)
+    for relu in (0, 1):
+        got, kname = run_last(be, case, order, relu)
+        assert kname == "k_i8conv_f32<%d>" % KS, kname
+        bad = 0
+        for n0 in range(0, N, LARGE_HEAD):
+            acc = DG.exact_conv(j[n0:n0 + LARGE_HEAD], head["k"], KS // 2, groups)
+            assert np.abs(acc).max() < 2 ** 31
+            want = chain_r(acc, head["al"], head["b"], relu)[:, order]
+            bad += int((got[n0:n0 + want.shape[0]].view(np.uint32) != np.ascontiguousarray(want).view(np.uint32)).sum())
+        print(kname, name, x_shape, "->", Oc, "relu", relu, "grid.y", gy, "per", per, "words that differ from the judge", bad, "of", got.size)
+        assert bad == 0, (bad, got.size)
+
+
 def check_vs_torch(kind, idx, widths):
     """The cap of the GPU cross-check holds for the judge itself at the geometries above: against the parent's fp32 arithmetic at most one step, on at most 1e-4 of
     the elements (CPU only)."""

@@ -41,6 +41,13 @@ def test_folded_pool(be, ksp, hw):
     SEEN.add(BN.check_folded_pool(be, *ksp, *hw, seed=1500 + hw[1]))
 
 
+@pytest.mark.parametrize("case", range(len(BN.LARGE_GRID)), ids=[c[0] for c in BN.LARGE_GRID])
+def test_several_output_words_per_block(be, case):
+    """The "several output words per block" cases (7 to 18 s each here; the emulator runs its blocks in order, so it shows a wrong loop, not a race between two
+    words -- that is what the GPU run of the same table is for)."""
+    BN.check_large(be, case)
+
+
 def test_refusals_keep_refusing(be):
     BN.check_refusals(be)
 

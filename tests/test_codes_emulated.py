@@ -30,3 +30,10 @@ def test_codeconv_nonfinite_constants_counted(be):
 @pytest.mark.parametrize("case", range(len(CC.UNSUPPORTED)))
 def test_codeconv_unsupported_is_enotsup(be, case):
     CC.check_unsupported(be, case)
+
+
+@pytest.mark.parametrize("case", range(len(CC.LARGE_GRID)), ids=[c[0] for c in CC.LARGE_GRID])
+def test_codeconv_several_word_groups_per_block(be, case):
+    """The "several word groups per block" cases (9 and 17 s here; the emulator runs its blocks in order, so it shows a wrong loop, not a race between two groups --
+    that is what the GPU run of the same table is for)."""
+    CC.check_large(be, case)

@@ -173,3 +173,13 @@ def test_compile_bits_refuses_what_it_does_not_cover():
     inference.prequantize_weights(I32)
     with pytest.raises(MicronetHipError):
         inference.wbwtab_compile_bits(inference.wbwtab_model_bn_fuse(I32, W=3).eval())
+
+
+@pytest.mark.parametrize("W", [3, 2])
+def test_compiled_plan_batch_256_equals_its_chunks(W):
+    """Batch 256, the batch behind the measured numbers: a block of every hidden kernel takes several units (tests/deploy_grid.py).  Logits and every kept stage equal
+    those of the same images in eight chunks of 32, the launch shape the tests above hold to the judge."""
+    import deploy_grid as DG
+    from micronet_amd import inference
+    F, _ = _nin_gc_folded(W)
+    DG.plan_whole_against_chunks(inference.wbwtab_compile_bits(F), "stage_bits")

@@ -106,3 +106,13 @@ def test_bit_ends_names_an_input_the_first_kernel_does_not_cover():
     P1 = inference.wbwtab_compile_bits(F, bit_ends=True)
     with pytest.raises(MicronetHipError, match=r"model\.0\.conv"):
         P1(x[:, :, :, :30].contiguous())
+
+
+@pytest.mark.parametrize("arch", ["nin_gc", "nin"])
+def test_plan_with_bit_ends_batch_256_equals_its_chunks(arch):
+    """Batch 256, the batch behind the measured numbers: a block of every hidden kernel takes several units (tests/deploy_grid.py).  Logits and every kept stage equal
+    those of the same images in eight chunks of 32, the launch shape the tests above hold to the judge."""
+    import deploy_grid as DG
+    from micronet_amd import inference
+    F, _ = _folded(arch, 3)
+    DG.plan_whole_against_chunks(inference.wbwtab_compile_bits(F, bit_ends=True), "stage_bits")

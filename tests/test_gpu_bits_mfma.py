@@ -29,3 +29,9 @@ def test_bitconv_mfma_invalid_is_einval(be):
 
 def test_bitconv_mfma_table_counters(be):
     MC.check_counters(be)
+
+
+@pytest.mark.parametrize("case", range(len(MC.LARGE_GRID)), ids=[c[0] for c in MC.LARGE_GRID])
+def test_bitconv_mfma_several_sets_per_block(be, case):
+    """The launch shape of the measured batches: a block walks more than one set, the last block fewer (proved through mn_deploy_grid_deal)."""
+    MC.check_large(be, case)

@@ -34,3 +34,9 @@ def test_bitconv_mfma3_invalid_is_einval(be):
 
 def test_bitconv_mfma3_table_counters(be):
     MC.check_counters(be)
+
+
+@pytest.mark.parametrize("case", range(len(MC.LARGE_GRID)), ids=[c[0] for c in MC.LARGE_GRID])
+def test_bitconv_mfma3_several_spans_per_block(be, case):
+    """The launch shape of the measured batches: some block takes a second span, some does not (proved through mn_deploy_grid_rows and the table's span)."""
+    MC.check_large(be, case)

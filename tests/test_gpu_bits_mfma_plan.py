@@ -96,3 +96,13 @@ def test_profile_of_one_forward(models):
     assert names.get(K3) == 2 and names.get("k_bitconv_mfma<0>") == 3 and names.get("k_bitconv_mfma<1>") == 2, names
     assert not [k for k in names if k.startswith("k_bitconv<")], names
     assert names.get("k_bits_pack") == 1 and names.get("k_bits_unpack") == 1, names
+
+
+@pytest.mark.parametrize("kw", FLAGS, ids=["blocks", "k3", "both", "both_bit_ends"])
+@pytest.mark.parametrize("key", ["nin_gc_w3", "nin"])
+def test_mfma_plan_batch_256_equals_its_chunks(models, key, kw):
+    """Batch 256, the batch behind the measured numbers: a block of every hidden kernel takes several units (tests/deploy_grid.py).  Logits and every kept stage equal
+    those of the same images in eight chunks of 32, the launch shape the tests above hold to the judge."""
+    import deploy_grid as DG
+    from micronet_amd import inference
+    DG.plan_whole_against_chunks(inference.wbwtab_compile_bits(models[key][0], **kw), "stage_bits")

@@ -57,6 +57,12 @@ def test_folded_pool(be, ksp, hw):
     SEEN.add(BN.check_folded_pool(be, *ksp, *hw, seed=1500 + hw[1]))
 
 
+@pytest.mark.parametrize("case", range(len(BN.LARGE_GRID)), ids=[c[0] for c in BN.LARGE_GRID])
+def test_several_output_words_per_block(be, case):
+    """The launch shape of the measured batches: a block walks more than one output word, the last block fewer (proved through mn_deploy_grid_deal)."""
+    BN.check_large(be, case)
+
+
 def test_refusals_keep_refusing(be):
     BN.check_refusals(be)
 
@@ -221,3 +227,13 @@ def test_compiled_plan_on_the_reference_folded_nin(W):
     print(key, "hidden sign mismatches", total, "logits rel", rel)
     if total == 0:
         assert rel <= 1e-5, rel
+
+
+@pytest.mark.parametrize("W", [3, 2])
+def test_compiled_plan_batch_256_equals_its_chunks(W):
+    """Batch 256, the batch behind the measured numbers: a block of every hidden kernel takes several units (tests/deploy_grid.py).  Logits and every kept stage equal
+    those of the same images in eight chunks of 32, the launch shape the tests above hold to the judge."""
+    import deploy_grid as DG
+    from micronet_amd import inference
+    F, _ = _nin_folded(W)
+    DG.plan_whole_against_chunks(inference.wbwtab_compile_bits(F), "stage_bits")

@@ -32,3 +32,9 @@ def test_codeconv_nonfinite_constants_counted(be):
 @pytest.mark.parametrize("case", range(len(CC.UNSUPPORTED)))
 def test_codeconv_unsupported_is_enotsup(be, case):
     CC.check_unsupported(be, case)
+
+
+@pytest.mark.parametrize("case", range(len(CC.LARGE_GRID)), ids=[c[0] for c in CC.LARGE_GRID])
+def test_codeconv_several_word_groups_per_block(be, case):
+    """The launch shape of the measured batches: a block walks more than one output word group, the last block fewer (proved through mn_deploy_grid_deal)."""
+    CC.check_large(be, case)

@@ -172,3 +172,10 @@ def test_code_ends_refuses_cpu_and_float64_inputs_and_uncovered_shapes():
         P1(x[:, :, :, :30].contiguous())
     with pytest.raises(MicronetHipError, match="eval-only"):
         P1.train()
+
+
+def test_plan_with_code_ends_batch_256_equals_its_chunks():
+    """Batch 256, the batch behind the measured numbers: a block of every hidden kernel takes several units (tests/deploy_grid.py).  Logits and every kept stage equal
+    those of the same images in eight chunks of 32, the launch shape the tests above hold to the judge."""
+    import deploy_grid as DG
+    DG.plan_whole_against_chunks(_deployed("spread")[2], "stage_codes")

@@ -142,3 +142,13 @@ def test_profile_of_one_forward(gc_full):
     assert not [k for k in names if k.startswith("k_codeconv<1,")], names
     assert names.get("k_codeconv<3,1,0>") == 2, names
     assert names.get("k_codes_pack") == 1 and names.get("k_codes_unpack") == 1, names
+
+
+@pytest.mark.parametrize("which,kw", [("gc_spread", {}), ("gc_spread", dict(code_ends=True)), ("nin_spread", dict(tile_blocks=True))], ids=["nin_gc", "nin_gc_code_ends", "nin"])
+def test_mfma_plan_batch_256_equals_its_chunks(which, kw, request):
+    """Batch 256, the batch behind the measured numbers: a block of every hidden kernel takes several units (tests/deploy_grid.py).  Logits and every kept stage equal
+    those of the same images in eight chunks of 32, the launch shape the tests above hold to the judge."""
+    import deploy_grid as DG
+    from micronet_amd import inference
+    I, _ = request.getfixturevalue(which)
+    DG.plan_whole_against_chunks(inference.dorefa_compile_codes(I, mfma_blocks=True, **kw), "stage_codes")

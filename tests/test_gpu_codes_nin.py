@@ -44,3 +44,9 @@ def test_codes_maxpool(be, case):
 
 def test_codes_maxpool_refused_is_enotsup(be):
     NC.check_pool_refused(be)
+
+
+@pytest.mark.parametrize("case", range(len(NC.LARGE_GRID)), ids=[c[0] for c in NC.LARGE_GRID])
+def test_codeconv_tile_several_word_groups_per_block(be, case):
+    """The launch shape of the measured batches: a block walks more than one output word group, the last block fewer (proved through mn_deploy_grid_deal)."""
+    NC.check_large(be, case)

@@ -201,3 +201,11 @@ def test_profile_of_one_forward(full):
             assert "k_codes_pack" not in names and "k_codes_unpack" not in names, names
         else:                 # the default plan: the model's own first and last block run on byte codes, one pack and one unpack between them and the planes
             assert names.get("k_codes_pack") == 1 and names.get("k_codes_unpack") == 1, names
+
+
+@pytest.mark.parametrize("ends", [0, 1], ids=["default", "code_ends"])
+def test_plan_batch_256_equals_its_chunks(spread, ends):
+    """Batch 256, the batch behind the measured numbers: a block of every hidden kernel takes several units (tests/deploy_grid.py).  Logits and every kept stage equal
+    those of the same images in eight chunks of 32, the launch shape the tests above hold to the judge."""
+    import deploy_grid as DG
+    DG.plan_whole_against_chunks(spread[1 + ends], "stage_codes")

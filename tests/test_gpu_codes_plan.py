@@ -175,3 +175,11 @@ def test_pack_codes_unpack_codes_helpers():
     assert planes.shape == (2, 3, 2, 4, 8) and planes.dtype == torch.int32
     assert np.array_equal(planes.cpu().numpy().view(np.uint32), CC.np_pack_planes(codes.cpu().numpy()))
     assert torch.equal(inference.unpack_codes(planes, 80), codes)
+
+
+@pytest.mark.parametrize("which", ["full", "spread"])
+def test_plan_batch_256_equals_its_chunks(which, request):
+    """Batch 256, the batch behind the measured numbers: a block of every hidden kernel takes several units (tests/deploy_grid.py).  Logits and every kept stage equal
+    those of the same images in eight chunks of 32, the launch shape the tests above hold to the judge."""
+    import deploy_grid as DG
+    DG.plan_whole_against_chunks(request.getfixturevalue(which)[1], "stage_codes")

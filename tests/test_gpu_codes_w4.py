@@ -46,3 +46,15 @@ def test_codeconv_w4_invalid_is_einval(be, form):
 @pytest.mark.parametrize("form", ["mfma", "mfma3"])
 def test_codeconv_w4_table_counters(be, form):
     W4.check_counters(be, form)
+
+
+@pytest.mark.parametrize("case", range(len(W4.LARGE1)), ids=[c[0] for c in W4.LARGE1])
+def test_codeconv_mfma_w4_several_sets_per_block(be, case):
+    """The launch shape of the measured batches: a block walks more than one set, the last block fewer (proved through mn_deploy_grid_deal)."""
+    W4.check_large1(be, case)
+
+
+@pytest.mark.parametrize("case", range(len(W4.LARGE3)), ids=[c[0] for c in W4.LARGE3])
+def test_codeconv_mfma3_w4_several_spans_per_block(be, case):
+    """The launch shape of the measured batches: some block takes a second span, some does not (proved through mn_deploy_grid_rows and the table's span)."""
+    W4.check_large3(be, case)

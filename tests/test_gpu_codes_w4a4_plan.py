@@ -161,3 +161,11 @@ def test_w4a4_refuses_code_ends_and_tile_blocks_on_the_gpu_model(full):
         inference.dorefa_compile_codes(I, code_ends=True)
     with pytest.raises(MicronetHipError, match=r"model\.1\.conv: the net has 4-bit codes"):
         inference.dorefa_compile_codes(I, tile_blocks=True)
+
+
+@pytest.mark.parametrize("which", ["full", "spread"])
+def test_w4a4_plan_batch_256_equals_its_chunks(which, request):
+    """Batch 256, the batch behind the measured numbers: a block of every hidden kernel takes several units (tests/deploy_grid.py).  Logits and every kept stage equal
+    those of the same images in eight chunks of 32, the launch shape the tests above hold to the judge."""
+    import deploy_grid as DG
+    DG.plan_whole_against_chunks(request.getfixturevalue(which)[1], "stage_codes")

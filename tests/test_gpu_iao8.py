@@ -43,3 +43,9 @@ def test_i8conv_invalid_is_einval(be):
 
 def test_i8conv_table_counters(be):
     IC.check_counters(be)
+
+
+@pytest.mark.parametrize("case", range(len(IC.LARGE_GRID)), ids=[c[0] for c in IC.LARGE_GRID])
+def test_i8conv_several_sets_per_block(be, case):
+    """The launch shape of the measured batches: a block walks more than one set, the last block fewer (proved through mn_deploy_grid_deal)."""
+    IC.check_large(be, case)

@@ -48,3 +48,15 @@ def test_ends_invalid_is_einval(be):
 
 def test_i8first_table_counters(be):
     EC.check_first_counters(be)
+
+
+@pytest.mark.parametrize("case", range(len(EC.LARGE_FIRST)), ids=[c[0] for c in EC.LARGE_FIRST])
+def test_i8first_several_sets_per_block(be, case):
+    """The launch shape of the measured batches: a block walks more than one set, the last block fewer (proved through mn_deploy_grid_deal)."""
+    EC.check_large_first(be, case)
+
+
+@pytest.mark.parametrize("case", range(len(EC.LARGE_LAST)), ids=[c[0] for c in EC.LARGE_LAST])
+def test_i8conv_f32_several_sets_per_block(be, case):
+    """The launch shape of the measured batches: a block walks more than one set, the last block fewer (proved through mn_deploy_grid_deal)."""
+    EC.check_large_last(be, case)

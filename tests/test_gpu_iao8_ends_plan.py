@@ -140,3 +140,10 @@ def test_weights_off_the_grid_are_refused_at_both_ends():
         conv.weight.data[3, 0, 0, 0] += 0.5 * conv.weight_quantizer.scale.reshape(-1)[3]
         with pytest.raises(MicronetHipError, match=r"model\.%d\.conv: 1 rows whose stored weights are off the grid" % layer):
             inference.iao_compile_int8(bad, byte_ends=True)
+
+
+def test_plan_batch_256_equals_its_chunks(compiled):
+    """Batch 256, the batch behind the measured numbers: a block of every hidden kernel takes several units (tests/deploy_grid.py).  Logits and every kept stage equal
+    those of the same images in eight chunks of 32, the launch shape the tests above hold to the judge."""
+    import deploy_grid as DG
+    DG.plan_whole_against_chunks(compiled[1], "stage_codes")

@@ -188,3 +188,10 @@ def test_small_cfg_is_refused_naming_the_layer():
         inference.iao_compile_int8(Fm)
     with torch.no_grad():
         assert Fm(x[:4]).shape == (4, 10)          # the caller still has the model
+
+
+def test_plan_batch_256_equals_its_chunks(compiled):
+    """Batch 256, the batch behind the measured numbers: a block of every hidden kernel takes several units (tests/deploy_grid.py).  Logits and every kept stage equal
+    those of the same images in eight chunks of 32, the launch shape the tests above hold to the judge."""
+    import deploy_grid as DG
+    DG.plan_whole_against_chunks(compiled[1], "stage_codes")
