@@ -494,8 +494,53 @@ def check_pool_sign8(be, shape=(3, 5, 8, 16), seed=0):
     assert np.array_equal(be.to_host(din), t.grad.numpy())
 
 
-def _check_pwb(be, g, wq, d_da, h8, a8, chan, sums, training, dW, dA, dx_ref, dw_ref, db_ref, db_tol, x_shape, w_shape, Oc):
-    """mn_conv2d_bwd_bnh (k_pwb: backward-data and backward-weight of the block in one launch, (da, h) read once) against the two-step path's results."""
+def bnh_fp64(da, h, chan, sums, training, x_phys, w, groups=1, in_shuffle=0):
+    """What the consumers of a pointwise BatchNorm+sign block's gradient must deliver, in fp64 from what they are handed: the full-size gradient da, the byte stash h,
+    the [8][O] constants (T, flip, L, U, A, B, gi, nnz) and the two sums.  acc = 2 h - nnz; dz = da under L <= acc flip <= U; zhat = A acc + B;
+    dy = gi (dz - k1 - zhat k2) with k = sums / n in training, 0 in eval; then the 1 x 1 conv's backward of dy, dx in the PHYSICAL channel order.
+    Returns (dx, dw, dbias, sum |dy| per channel)."""
+    D = np.float64
+    N, Oc, H, W = da.shape
+    assert chan.shape == (8, Oc) and w.shape[2:] == (1, 1)
+    cv = lambda k: chan[k].astype(D).reshape(1, -1, 1, 1)
+    acc = 2.0 * np.asarray(h).view(np.uint8).astype(D) - cv(7)
+    u = acc * cv(1)
+    with np.errstate(invalid="ignore"):
+        mask = (u >= cv(2)) & (u <= cv(3))
+    n = float(N * H * W)
+    sm = np.asarray(sums).astype(D)
+    k1, k2 = (sm[0] / n, sm[1] / n) if training else (np.zeros(Oc), np.zeros(Oc))
+    dy = np.where(mask, da.astype(D), 0.0)
+    dy -= k1.reshape(1, -1, 1, 1)
+    dy -= (acc * cv(4) + cv(5)) * k2.reshape(1, -1, 1, 1)
+    dy *= cv(6)
+    x_log = np.asarray(x_phys).astype(D)
+    Cin = x_log.shape[1]
+    if in_shuffle > 1:
+        x_log = np.ascontiguousarray(x_log.reshape(N, in_shuffle, Cin // in_shuffle, H, W).transpose(0, 2, 1, 3, 4).reshape(x_log.shape))
+    dx, dw, db = O.conv2d_bwd(dy, x_log, w.astype(D), groups=groups)
+    if in_shuffle > 1:
+        dx = np.ascontiguousarray(dx.reshape(N, Cin // in_shuffle, in_shuffle, H, W).transpose(0, 2, 1, 3, 4).reshape(x_log.shape))
+    return dx, dw, db, np.abs(dy).sum(axis=(0, 2, 3))
+
+
+def assert_bwd_fp64(what, dx, dw, db, ref64):
+    """dx / dW at 1e-5 of the fp64 result's maximum; dbias (a sum that cancels in front of a BatchNorm) at 1e-5 of the sum of magnitudes, per channel."""
+    dx64, dw64, db64, mdy = ref64
+    e_dx, e_dw = np.max(np.abs(dx - dx64)) / np.max(np.abs(dx64)), np.max(np.abs(dw - dw64)) / np.max(np.abs(dw64))
+    e_db = float(np.max(np.abs(db - db64) / (mdy + 1e-30))) if db is not None else 0.0
+    assert_bwd_fp64.worst = tuple(max(a, b) for a, b in zip(getattr(assert_bwd_fp64, "worst", (0.0, 0.0, 0.0)), (e_dx, e_dw, e_db)))       # (for reports)
+    assert np.isfinite(dx).all() and np.isfinite(dw).all() and np.abs(dx64).max() > 0 and np.abs(dw64).max() > 0
+    assert close(dx, dx64, 1e-5), (what + " dx vs fp64", e_dx)
+    assert close(dw, dw64, 1e-5), (what + " dw vs fp64", e_dw)
+    if db is not None:
+        assert np.all(np.abs(db - db64) <= 1e-5 * mdy + 1e-30), (what + " dbias vs fp64", e_db)
+    assert_bwd_fp64.count = getattr(assert_bwd_fp64, "count", 0) + 1
+
+
+def _check_pwb(be, g, wq, d_da, h8, a8, chan, sums, training, dW, dA, dx_ref, dw_ref, db_ref, db_tol, x_shape, w_shape, Oc, ref64=None):
+    """mn_conv2d_bwd_bnh (k_pwb: backward-data and backward-weight of the block in one launch, (da, h) read once) against the two-step path's results, and
+    (ref64: bnh_fp64's tuple) against the fp64 evaluation."""
     if not be.lib.mn_conv2d_bwd_bnh_supported(C.byref(g), C.byref(wq), 1 if a8 is not None else 0):
         return
     nb = int(be.lib.mn_conv2d_bwd_bnh_ws_bytes(C.byref(g)))
@@ -509,6 +554,8 @@ def _check_pwb(be, g, wq, d_da, h8, a8, chan, sums, training, dW, dA, dx_ref, dw
         assert close(be.to_host(dw3), dw_ref, 5e-6), ("k_pwb dw", np.max(np.abs(be.to_host(dw3) - dw_ref)) / np.max(np.abs(dw_ref)))
         if with_bias:
             assert np.max(np.abs(be.to_host(db3) - db_ref)) <= db_tol, "k_pwb dbias"
+        if ref64 is not None:
+            assert_bwd_fp64("k_pwb", be.to_host(dx3), be.to_host(dw3), be.to_host(db3) if with_bias else None, ref64)
     # ... with the BatchNorm-backward sums of an upstream BatchNorm+sign block as a by-product (mn_conv2d_bwd_bnh_up): dx / dw bit-identical to the plain launch, the
     # finished sums equal to mn_bnh_bwd_sums on (dx, upstream stash) up to the summation order
     N_, Cin, H_, W_ = x_shape
@@ -722,7 +769,11 @@ def check_qconv_bnsign(be, x_shape, w_shape, groups=1, bias=True, in_shuffle=0, 
                 sc_db = max(np.max(np.abs(be.to_host(dy))) * 1e-4, 1e-30)
                 assert np.max(np.abs(be.to_host(db2) - be.to_host(db_ref2))) <= sc_db * N * H * W
                 check_qconv_bnsign.pool_fold_checked = getattr(check_qconv_bnsign, "pool_fold_checked", 0) + 1
-                _check_pwb(be, g, wq, dGP, h8, a8, chan, sums, training, dW, dA, dx_ref2, be.to_host(dw_ref2), be.to_host(db_ref2), sc_db * N * H * W, x_shape, w.shape, Oc)
+                # ... and against fp64 directly: dy from (the torch-routed full-size gradient, h, the constants, the sums), contracted in fp64
+                ref64 = bnh_fp64(da, be.to_host(h8), be.to_host(chan), be.to_host(sums), training, a_in, w, groups, in_shuffle)
+                assert_bwd_fp64("pooled fold", be.to_host(dx2), be.to_host(dw2), be.to_host(db2), ref64)
+                _check_pwb(be, g, wq, dGP, h8, a8, chan, sums, training, dW, dA, dx_ref2, be.to_host(dw_ref2), be.to_host(db_ref2), sc_db * N * H * W, x_shape, w.shape, Oc,
+                           ref64=ref64)
         else:
           be.call("mn_qconv_bnsign_bwd_pooled", C.byref(g), C.byref(wq), be.ptr(dA), be.ptr(dW), be.ptr(dB), be.ptr(dG), be.ptr(dBe), be.ptr(save),
                 be.ptr(dGP), be.ptr(a8), int(training), be.ptr(dy), be.ptr(dgam), be.ptr(dbet), be.ptr(ws), nb, be.stream)
@@ -747,7 +798,12 @@ def check_qconv_bnsign(be, x_shape, w_shape, groups=1, bias=True, in_shuffle=0, 
             assert close(be.to_host(dw2), be.to_host(dw_ref2), 5e-6)
             sc_db = max(np.max(np.abs(be.to_host(dy))) * 1e-4, 1e-30)      # d bias in front of a BatchNorm is a sum that cancels to ~0
             assert np.max(np.abs(be.to_host(db2) - be.to_host(db_ref2))) <= sc_db * N * H * W
-            _check_pwb(be, g, wq, dDA, h8, None, chan, sums, training, dW, dA, dx_ref2, be.to_host(dw_ref2), be.to_host(db_ref2), sc_db * N * H * W, x_shape, w.shape, Oc)
+            ref64 = None
+            if w_shape[2] == 1:     # ... and against fp64 directly (pointwise blocks; the 3 x 3 family: k3s_bnh_cases)
+                ref64 = bnh_fp64(da, be.to_host(h8), be.to_host(chan), be.to_host(sums), training, a_in, w, groups, in_shuffle)
+                assert_bwd_fp64("fold", be.to_host(dx2), be.to_host(dw2), be.to_host(db2), ref64)
+            _check_pwb(be, g, wq, dDA, h8, None, chan, sums, training, dW, dA, dx_ref2, be.to_host(dw_ref2), be.to_host(db_ref2), sc_db * N * H * W, x_shape, w.shape, Oc,
+                       ref64=ref64)
     else:
         be.call("mn_qconv_bnsign_bwd", C.byref(g), C.byref(wq), be.ptr(dA), be.ptr(dW), be.ptr(dB), be.ptr(dG), be.ptr(dBe), be.ptr(save), be.ptr(dDA),
                 int(training), be.ptr(dy), be.ptr(dgam), be.ptr(dbet), be.ptr(ws), nb, be.stream)
@@ -1378,6 +1434,12 @@ def check_qconv_bnq(be, x_shape, w_shape, groups=1, bias=True, in_shuffle=0, tra
             if bias:
                 sc_db = max(np.max(np.abs(be.to_host(dy))) * 1e-4, 1e-30)      # d bias in front of a BatchNorm is a sum that cancels to ~0
                 assert np.max(np.abs(be.to_host(db4) - be.to_host(db_t))) <= sc_db * N * H * W, "k_pwb<3> dbias"
+            # ... and against the torch fp64 gradients of the fp64 dy directly
+            assert close(be.to_host(dx4), dx_ref, 1e-5), ("k_pwb<3> dx vs fp64", float(np.max(np.abs(be.to_host(dx4) - dx_ref)) / np.max(np.abs(dx_ref))))
+            assert close(be.to_host(dw4), dw_ref, 1e-5), ("k_pwb<3> dw vs fp64", float(np.max(np.abs(be.to_host(dw4) - dw_ref)) / np.max(np.abs(dw_ref))))
+            if bias:
+                e_db = np.abs(be.to_host(db4) - db_ref) / (np.abs(dy_ref).sum(axis=(0, 2, 3)) + 1e-30)
+                assert np.all(e_db <= 1e-5), ("k_pwb<3> dbias vs fp64", float(e_db.max()))
         if not pooled and sbits == 16:
             _check_pwb_up2(be, g, wq, r, dGY, dDQ, stash, chan, sums, out_bits, quant, training, dW, dX, a_bits, dx3, dw3, dx4, dw4, nb3, x_shape, w_shape, seed)
         check_qconv_bnq.pwb_checked = getattr(check_qconv_bnq, "pwb_checked", 0) + 1
@@ -1508,6 +1570,139 @@ PWB_CASES_WIDE = [
     dict(x_shape=(1, 128, 4, 16), w_shape=(128, 128, 1, 1)),
     dict(x_shape=(1, 128, 2, 32), w_shape=(128, 128, 1, 1), bias=False),
 ]
+
+
+def check_pwb_plain_sign(be, x_shape, w_shape, groups=1, bias=True, in_shuffle=0, seed=0, **_):
+    """mn_conv2d_bwd_codes with x_bits = 0 (k_pwb<0, 0, 0>): both gradients of a pointwise conv on SIGN codes from a plain fp32 gradient, against numpy fp64."""
+    r = np.random.default_rng(seed)
+    N, Cin, H, W = x_shape
+    Oc = w_shape[0]
+    a_in = np.where(r.standard_normal(x_shape) > 0, 1, -1).astype(np.int8)
+    w, wkw, _ = make_coded_weights(r, w_shape, 1)
+    gy = r.standard_normal((N, Oc, H, W)).astype(F)
+    g = be.geom(x_shape, w_shape, groups=groups)
+    g.in_shuffle = in_shuffle
+    wq = be.wq(**wkw)
+    assert be.lib.mn_conv2d_bwd_bnh_supported(C.byref(g), C.byref(wq), 0) == 1
+    nb = int(be.lib.mn_conv2d_bwd_bnh_ws_bytes(C.byref(g)))
+    dA, dW, dG = be.to_dev_i8(a_in), be.to_dev(w), be.to_dev(gy)
+    ws, dx, dw, db = be.empty(nb // 4 + 8), be.empty(x_shape), be.empty(w_shape), (be.empty(Oc) if bias else None)
+    be.call("mn_conv2d_bwd_codes", C.byref(g), C.byref(wq), be.ptr(dG), be.ptr(dW), be.ptr(dA), 0, be.ptr(dx), be.ptr(dw), be.ptr(db), be.ptr(ws), nb, be.stream)
+    assert be.lib.mn_last_kernel().decode() == "k_pwb<0, 0, 0>"
+    x_log = a_in.astype(np.float64)
+    if in_shuffle > 1:
+        x_log = np.ascontiguousarray(x_log.reshape(N, in_shuffle, Cin // in_shuffle, H, W).transpose(0, 2, 1, 3, 4).reshape(x_shape))
+    dx64, dw64, db64 = O.conv2d_bwd(gy, x_log, w.astype(np.float64), groups=groups)
+    if in_shuffle > 1:
+        dx64 = np.ascontiguousarray(dx64.reshape(N, Cin // in_shuffle, in_shuffle, H, W).transpose(0, 2, 1, 3, 4).reshape(x_shape))
+    assert_bwd_fp64("k_pwb<0, 0, 0>", be.to_host(dx), be.to_host(dw), be.to_host(db) if bias else None, (dx64, dw64, db64, np.abs(gy.astype(np.float64)).sum(axis=(0, 2, 3))))
+    check_pwb_plain_sign.count = getattr(check_pwb_plain_sign, "count", 0) + 1
+
+
+# Blocks of k_pwb that walk MANY steps.  plan_pwb: nsteps = N H W / 32, Z = min(256 / groups, nsteps) blocks per group, st_per_z = ceil(nsteps / Z); block z walks
+# n = clamp(nsteps - z st_per_z, 0, st_per_z) steps from rotation z % n with NS = 4 loads in flight (3: 32-bit stash, UP 2), the loop count rounded up to a multiple
+# of NS.  H W = 32 (4 x 8: pooled and up9 conditions hold), 128 channels per group.  blocks: {n: how many blocks of a group walk n steps} -- asserted from the
+# library's own splits entry (pwb_step_premise) before a case runs, so a changed launch rule fails the case instead of turning it into a one-step case.
+PWB_STEP_CASES = [
+    # every block n = 5: all five rotations; 5 is a multiple of neither 4 nor 3
+    dict(geom=dict(x_shape=(160, 1024, 4, 8), w_shape=(1024, 128, 1, 1), groups=8), st_per_z=5, blocks={5: 32}, claims=("long", "ragged")),
+    # 29 full blocks, one with n = 3, two empty
+    dict(geom=dict(x_shape=(148, 1024, 4, 8), w_shape=(1024, 128, 1, 1), groups=8, in_shuffle=8), st_per_z=5, blocks={5: 29, 3: 1, 0: 2},
+         claims=("long", "ragged", "short", "empty")),
+    # n = 10 and n = 7, one empty: steady state of the two-buffer pipeline
+    dict(geom=dict(x_shape=(307, 1024, 4, 8), w_shape=(1024, 128, 1, 1), groups=8), st_per_z=10, blocks={10: 30, 7: 1, 0: 1}, claims=("long", "ragged", "short", "empty")),
+    # 18 blocks of 2, one of 1, 13 empty
+    dict(geom=dict(x_shape=(37, 1024, 4, 8), w_shape=(1024, 128, 1, 1), groups=8), st_per_z=2, blocks={2: 18, 1: 1, 0: 13}, claims=("short", "empty")),
+    # Z = 128 (the L2 / L3 grid): 100 full blocks, 28 empty
+    dict(geom=dict(x_shape=(300, 256, 4, 8), w_shape=(256, 128, 1, 1), groups=2, in_shuffle=2), st_per_z=3, blocks={3: 100, 0: 28}, claims=("empty",)),
+    # Z = 256: 173 full blocks, one of 1, 82 empty
+    dict(geom=dict(x_shape=(520, 128, 4, 8), w_shape=(128, 128, 1, 1)), st_per_z=3, blocks={3: 173, 1: 1, 0: 82}, claims=("short", "empty")),
+]
+
+
+def pwb_step_premise(be, case, NS=4):
+    """The step distribution a PWB_STEP_CASES entry claims, recomputed from the Z the library reports for the geometry."""
+    gk = case["geom"]
+    N, Cin, H, W = gk["x_shape"]
+    groups = gk.get("groups", 1)
+    g = be.geom(gk["x_shape"], gk["w_shape"], groups=groups)
+    g.in_shuffle = gk.get("in_shuffle", 0)
+    wq = be.wq(mode=1)
+    Z = int(be.lib.mn_conv2d_bwd_bnh_up_splits(C.byref(g), C.byref(wq), 0, 128))
+    nsteps = N * H * W // 32
+    assert Z == min(256 // groups, nsteps), (Z, nsteps)
+    st = -(-nsteps // Z)
+    ns = [max(0, min(st, nsteps - z * st)) for z in range(Z)]
+    hist = {n: ns.count(n) for n in set(ns)}
+    assert st == case["st_per_z"] and hist == case["blocks"] and sum(ns) == nsteps, (st, hist)
+    claims = case["claims"]
+    assert ("long" in claims) == (max(ns) > NS), "a range longer than the prefetch depth"
+    assert ("ragged" in claims) == (max(ns) > NS and max(ns) % 4 != 0 and max(ns) % 3 != 0), "a long range that is no multiple of either prefetch depth"
+    assert ("short" in claims) == any(0 < n < st for n in ns), "a short last block"
+    assert ("empty" in claims) == (0 in ns), "a block without steps"
+    assert max(z % n for z, n in enumerate(ns) if n) == max(ns) - 1, "every rotation of the longest range is taken"
+    return ns
+
+
+def check_pwb_one_launch(be, x_shape, w_shape, groups=1, in_shuffle=0, training=True, seed=0, **_):
+    """ONE launch of mn_conv2d_bwd_bnh (k_pwb<1, 0, 0>) on synthetic operands -- random stash bytes, integer pass intervals (one empty, one that passes everything),
+    random sums -- against fp64 only: cheap enough for the emulator at a geometry whose blocks walk several steps."""
+    r = np.random.default_rng(seed)
+    N, Cin, H, W = x_shape
+    Oc = w_shape[0]
+    a_in = np.where(r.standard_normal(x_shape) > 0, 1, -1).astype(np.int8)
+    w, wkw, _ = make_coded_weights(r, w_shape, 1)
+    da = r.standard_normal((N, Oc, H, W)).astype(F)
+    nnz = r.integers(64, 129, Oc).astype(F)
+    h = np.floor(r.random((N, Oc, H, W)) * (nnz.reshape(1, -1, 1, 1) + 1)).astype(np.uint8)
+    flip = np.where(r.random(Oc) < 0.5, -1.0, 1.0).astype(F)
+    Lc, Uc = -np.floor(r.random(Oc) * 40).astype(F), np.floor(r.random(Oc) * 40).astype(F)
+    Lc[1], Uc[1] = 5.0, -5.0
+    Lc[2], Uc[2] = -1e9, 1e9
+    gi = (np.abs(r.standard_normal(Oc)) * 0.5 + 0.1).astype(F)
+    chan = np.stack([np.zeros(Oc, F), flip, Lc, Uc, (r.standard_normal(Oc) * 0.05).astype(F), (r.standard_normal(Oc) * 0.3).astype(F), gi, nnz]).astype(F)
+    sums = (r.standard_normal((2, Oc)) * np.sqrt(N * H * W)).astype(F)
+    g = be.geom(x_shape, w_shape, groups=groups)
+    g.in_shuffle = in_shuffle
+    wq = be.wq(**wkw)
+    assert be.lib.mn_conv2d_bwd_bnh_supported(C.byref(g), C.byref(wq), 0) == 1
+    nb = int(be.lib.mn_conv2d_bwd_bnh_ws_bytes(C.byref(g)))
+    dDA, dH, dCh, dS, dW, dA = be.to_dev(da), be.to_dev_u8(h), be.to_dev(chan), be.to_dev(sums), be.to_dev(w), be.to_dev_i8(a_in)
+    ws, dx, dw, db = be.empty(nb // 4 + 4), be.empty(x_shape), be.empty(w_shape), be.empty(Oc)
+    be.call("mn_conv2d_bwd_bnh", C.byref(g), C.byref(wq), be.ptr(dDA), be.ptr(dH), None, be.ptr(dCh), be.ptr(dS), int(training), be.ptr(dW), be.ptr(dA), be.ptr(dx),
+            be.ptr(dw), be.ptr(db), be.ptr(ws), nb, be.stream)
+    assert be.lib.mn_last_kernel().decode() == "k_pwb<1, 0, 0>"
+    assert_bwd_fp64("k_pwb one launch", be.to_host(dx), be.to_host(dw), be.to_host(db), bnh_fp64(da, h, chan, sums, training, a_in, w, groups, in_shuffle))
+
+
+def check_pwb_steps_bnsign(be, idx, mode, seed=0):
+    """One PWB_STEP_CASES entry through check_qconv_bnsign(stash=True): k_pwb<1 / 2, 0, 0>, their UP 1 forms and (un-pooled) UP 3, the two-step fold kernels and the
+    stash forward on the same ranges, each against fp64."""
+    case = PWB_STEP_CASES[idx]
+    pwb_step_premise(be, case)
+    b, b9, b64 = getattr(_check_pwb, "count", 0), getattr(_check_pwb_up9, "count", 0), getattr(assert_bwd_fp64, "count", 0)
+    check_qconv_bnsign(be, seed=seed, stash=True, training=mode != "eval", pooled=mode == "pooled", **case["geom"])
+    assert getattr(_check_pwb, "count", 0) - b == 1, "k_pwb did not take this geometry"
+    assert getattr(_check_pwb_up9, "count", 0) - b9 == (0 if mode == "pooled" else 1), "mn_conv2d_bwd_bnh_up9 runs on the un-pooled cases"
+    assert getattr(assert_bwd_fp64, "count", 0) - b64 == 3, "fold pair + k_pwb with and without dbias, each against fp64"
+
+
+def check_pwb_steps_bnq(be, idx, seed=0, **kw):
+    """One PWB_STEP_CASES entry through check_qconv_bnq: k_pwb<0, 1, 0>, <3, 1, 0 / 1> and (un-pooled, 16-bit stash) both UP 2 forms."""
+    case = PWB_STEP_CASES[idx]
+    pwb_step_premise(be, case, NS=3 if kw.get("a_bits") == 8 else 4)
+    b, b2 = getattr(check_qconv_bnq, "pwb_checked", 0), getattr(_check_pwb_up2, "count", 0)
+    check_qconv_bnq(be, seed=seed, **dict(case["geom"], **kw))
+    assert getattr(check_qconv_bnq, "pwb_checked", 0) - b == 1, "k_pwb did not take this geometry"
+    assert getattr(_check_pwb_up2, "count", 0) - b2 == (0 if (kw.get("pooled") or kw.get("a_bits") == 8) else 1), "the UP 2 forms run on the un-pooled 16-bit cases"
+
+
+def check_pwb_steps_plain_sign(be, idx, seed=0):
+    case = PWB_STEP_CASES[idx]
+    pwb_step_premise(be, case)
+    b = getattr(check_pwb_plain_sign, "count", 0)
+    check_pwb_plain_sign(be, seed=seed, **case["geom"])
+    assert getattr(check_pwb_plain_sign, "count", 0) - b == 1
 
 
 def check_pwb(be, pooled_too=True, light=False):

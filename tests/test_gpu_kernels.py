@@ -478,6 +478,27 @@ def test_kbit_block_backward_in_one_kernel(be):
     assert getattr(K.check_qconv_bnq, "pwb_checked", 0) - before == 3
 
 
+def test_plain_gradient_on_sign_codes_in_one_kernel(be):
+    """mn_conv2d_bwd_codes with x_bits = 0 (k_pwb<0, 0, 0>) against numpy fp64: one step per block, and a case with long, short and empty blocks."""
+    K.check_pwb_plain_sign(be, seed=460, **K.PWB_CASES[0])
+    K.check_pwb_steps_plain_sign(be, 1, seed=461)
+
+
+# blocks of k_pwb that walk many steps (K.PWB_STEP_CASES: index, mode): training everywhere but N = 37 (eval), pooled as well where the table has a shuffle
+@pytest.mark.parametrize("idx,mode", [(0, "train"), (1, "train"), (1, "pooled"), (2, "train"), (3, "eval"), (4, "train"), (4, "pooled"), (5, "train")])
+def test_pointwise_block_backward_many_steps(be, idx, mode):
+    K.check_pwb_steps_bnsign(be, idx, mode, seed=470 + idx)
+
+
+@pytest.mark.parametrize("idx,kw", [(1, dict()),                                        # W2A2, 16-bit stash: <0, 1, 0>, <3, 1, 0> and both UP 2 forms
+                                    (1, dict(a_bits=8, w_bits=8)),                      # W8A8, 32-bit stash: <3, 1, 1>, three loads in flight
+                                    (4, dict(pooled=True)),                             # pooled W2A2: the plain-gradient form on the Z = 128 grid
+                                    (3, dict(quant=0, training=False))],                # no quantizer behind the block, eval: mostly empty blocks
+                         ids=["w2a2", "w8a8", "pooled", "noquant-eval"])
+def test_kbit_block_backward_many_steps(be, idx, kw):
+    K.check_pwb_steps_bnq(be, idx, seed=480 + idx, **kw)
+
+
 # stashed block around a 3 x 3 convolution: h written by the k x k kernel, statistics / sign streamed from h (k_h_stats, k_h_sign)
 KXK_STASH_CASES = [
     dict(x_shape=(3, 32, 8, 8), w_shape=(64, 16, 3, 3), padding=1, groups=2),                    # the nin_gc L7 pattern

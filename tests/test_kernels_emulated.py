@@ -324,6 +324,18 @@ def test_kbit_block_backward_in_one_kernel(be):
     K.check_pwb_bnq(be)
 
 
+def test_plain_gradient_on_sign_codes_in_one_kernel(be):
+    """mn_conv2d_bwd_codes with x_bits = 0 (k_pwb<0, 0, 0>) against numpy fp64."""
+    K.check_pwb_plain_sign(be, seed=460, **K.PWB_CASES[0])
+
+
+def test_pointwise_block_backward_blocks_of_two_one_and_no_steps(be):
+    """ONE launch of mn_conv2d_bwd_bnh at N = 37 of K.PWB_STEP_CASES (18 blocks of 2 steps, one of 1, 13 without any, per group) against fp64 only; the other
+    many-step cases and the full judges on this one run on the GPU (a whole judge takes minutes here)."""
+    K.pwb_step_premise(be, K.PWB_STEP_CASES[3])
+    K.check_pwb_one_launch(be, seed=3, **K.PWB_STEP_CASES[3]["geom"])
+
+
 def test_conv_backward_with_bn_folded_in(be):
     """mn_conv2d_bwd_data_bnh / mn_conv2d_bwd_weight_bnh (dy formed in registers from (da, h)) on shapes the direct kernels cover."""
     K.check_qconv_bnsign(be, seed=250, stash=True, x_shape=(2, 128, 4, 8), w_shape=(128, 64, 1, 1), groups=2)
