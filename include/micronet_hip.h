@@ -1146,6 +1146,43 @@ int mn_i8first_pack(const mn_conv_geom* g, const float* w, const float* s_w, int
 int mn_i8first_fwd(const mn_conv_geom* g, int in_bits, int a_bits, int w_bits, const uint32_t* table, const float* x, int8_t* out_codes, mn_stream_t stream);
 int mn_i8conv_fwd_f32(const mn_conv_geom* g, int a_bits, int w_bits, const uint32_t* table, const int8_t* in_codes, float* y, int relu, mn_stream_t stream);
 
+/* The residual stages of the int8 deployment of BN-folded IAO ResNets (csrc/qgemm_iao8_res.h): strided convs with an optional ReLU, and the last conv of a block's
+ * residual_function fused with the block's QuantAdd, its ReLU and the quantizers of the block's consumers.  Codes, layout, acc, al and y as for mn_i8conv_fwd; every
+ * quantizer symmetric, Q(v; s, a) = clamp(rha(fl(v / s)), -2^(a-1), 2^(a-1) - 1); in_bits is the width of the input codes, out_bits that of the output codes.
+ * Conv stage (mn_i8res_conv_fwd): r = relu ? max(y, 0) : y, c = Q(r; s_out, out_bits); output pixel (h, w) reads input pixel (stride h + dy, stride w + dx), zero
+ * bytes outside the input map -> out_codes [N][ceil(O/16)][Ho*Wo][16], Ho = (H - 1) / stride + 1.  mn_last_kernel(): k_i8res_conv<KS,stride,relu>.
+ * Add stage (mn_i8res_add_fwd; stride 1): c_r = Q(y; s_add, add_bits) (no ReLU), c_s = the byte of shortcut_codes [N][ceil(O/16)][H*W][16] at the same channel and
+ * pixel (already a code at s_add), t = fl(fl(float(c_r) * s_add) + fl(float(c_s) * s_add)), v = max(t, 0), out_a = Q(v; s_out0, bits0) and, with nout == 2,
+ * out_b = Q(v; s_out1, bits1), each [N][ceil(O/16)][H*W][16].  The table is packed with s_out = s_add, out_bits = add_bits.  mn_last_kernel(): k_i8res_add<KS,nout>.
+ * The add stage takes s_add and its code range from *q alone: the table's own s_out and range (words 9 .. 11) are NOT consulted and cannot be checked without a device
+ * read, so a table packed at another scale or width goes undiagnosed -- packing it with s_out = s_add, out_bits = add_bits is the caller's duty.
+ * The quantizers of the add stage are read from *q on the host at the call and handed to the kernel by value.
+ * Covered (mn_i8res_supported): groups == 1, dilation 1, g->in_shuffle == 0, 1x1 / padding 0 with any C or 3x3 / padding 1 with C % 16 == 0, stride 1 or 2 with both
+ * directions equal, any O, H, W >= 1, widths 2 .. 8; the add stage stride 1 only.  Everything else is MN_ENOTSUP.  A null or misaligned tensor (codes and `table`
+ * 16-byte aligned), an invalid geometry, relu outside 0 / 1, nout outside 1 / 2 or not matching out_b, an s_add / s_out that is not finite and positive, a width of
+ * the add stage outside 2 .. 8, or an output that overlaps an input or the other output is MN_EINVAL; nothing is written in either case.  No entry allocates.
+ *   pack : as mn_i8conv_pack without out_order (w [O][C][KH][KW] on the grid k * s_w, s_w_stride 1 / 0, bias or null, s_a the conv's own activation scale, s_out the
+ *          scale of the output codes) -> `table` (mn_i8res_table_bytes bytes) in mn_i8conv_pack's layout, with its two counters in words 0 and 7 and
+ *          word 6 = out_bits | w_bits << 8.
+ * Every output byte is stored exactly once, as part of a whole 16-byte block assembled on chip: no atomics, no read-modify-write.  Positions >= O yield 0 bytes. */
+typedef struct mn_i8res_add {
+    float s_add;           /* the block's QuantAdd scale */
+    int32_t add_bits;
+    int32_t nout;          /* 1 or 2 output maps */
+    float s_out0;
+    int32_t bits0;
+    float s_out1;          /* read with nout == 2 */
+    int32_t bits1;
+} mn_i8res_add;
+int mn_i8res_supported(const mn_conv_geom* g, int in_bits, int out_bits, int w_bits);
+int64_t mn_i8res_table_bytes(const mn_conv_geom* g, int in_bits, int out_bits, int w_bits);
+int mn_i8res_pack(const mn_conv_geom* g, const float* w, const float* s_w, int s_w_stride, const float* bias, float s_a, float s_out, int in_bits, int out_bits, int w_bits,
+                  uint32_t* table, mn_stream_t stream);
+int mn_i8res_conv_fwd(const mn_conv_geom* g, int in_bits, int out_bits, int w_bits, const uint32_t* table, const int8_t* in_codes, int8_t* out_codes, int relu,
+                      mn_stream_t stream);
+int mn_i8res_add_fwd(const mn_conv_geom* g, int in_bits, int w_bits, const uint32_t* table, const int8_t* in_codes, const int8_t* shortcut_codes, const mn_i8res_add* q,
+                     int8_t* out_a, int8_t* out_b, mn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

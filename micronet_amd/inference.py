@@ -24,7 +24,8 @@ The results are ordinary modules of this package: in eval mode they run on the s
 
   * ``iao_compile_int8``: the BN-folded, pre-quantised symmetric IAO graph compiled into a flat plan that keeps ONE INT8 CODE per hidden activation
     (``csrc/qgemm_iao8.h``: byte codes against weight-code bytes on v_mfma_i32_16x16x64_i8, bias + ReLU + [2x2 max-pool] + the consumer's quantizer in the epilogue).
-    One kernel per hidden block; the two ends stay on the model's own modules."""
+    One kernel per hidden block; the two ends stay on the model's own modules.  A BN-folded IAO ResNet compiles by the same call (``csrc/qgemm_iao8_res.h``: strided
+    convs, shortcut convs and the QuantAdd on byte codes, one code map per consumer quantizer of a block's output)."""
 import copy
 
 import torch
@@ -1273,7 +1274,13 @@ def iao_int8_report(model, input_hw=(32, 32), byte_ends=False):
     """The ``report`` ``iao_compile_int8(model, byte_ends)`` would carry -- one row per stage: layer, kernel, geometry, folded pool, the consumer's shuffle folded into
     the stage (``out_order``), table bytes and the activation bytes per image the stage reads and writes at an ``input_hw`` input -- from the graph walk alone: no GPU,
     nothing packed.  With ``byte_ends`` the two end rows are the kinds ``int8_first`` / ``int8_last`` and no fp32 map stands between the rows.  Raises like
-    ``iao_compile_int8`` for whatever the int8 blocks do not cover (weights off the grid excepted: that is read from the packed tables)."""
+    ``iao_compile_int8`` for whatever the int8 blocks do not cover (weights off the grid excepted: that is read from the packed tables).
+
+    The reference ResNet tree takes the walk of ``_walk_iao8_res``: one row per conv -- kind ``int8`` (a conv stage) or ``int8_add`` (the last conv of a block with its
+    QuantAdd), between ``first`` (conv1 and its packs) and ``last`` (the unpack, avg_pool, fc) -- with kernel, geometry, ``stride``, ``relu``, ``shortcut``, the number
+    of output maps ``nout`` and their ``consumers``, table bytes and activation bytes in and out per image."""
+    if _is_ref_resnet(model):
+        return _walk_iao8_res(model, input_hw, byte_ends)[4]
     return _walk_iao8(model, input_hw, byte_ends)[5]
 
 
@@ -1415,9 +1422,15 @@ def iao_compile_int8(model, byte_ends=False):
     ``byte_ends=True``: the two ends run on the int8 kernels as well (``csrc/qgemm_iao8_ends.h``): the first conv quantises the fp32 image with its own activation
     quantizer on the way in and writes the first hidden block's codes, the last conv writes the fp32 map of the model's tail (``QuantAvgPool2d``, ...) straight from
     the last hidden codes.  The first block must be a BN-folded ``quant_inference`` block like the hidden ones with a geometry ``mn_i8first_supported`` covers (3x3 or
-    5x5, C * KS * KS <= 128, no pool behind it), the last one a geometry ``mn_i8conv_supported`` covers; anything else raises naming the layer."""
+    5x5, C * KS * KS <= 128, no pool behind it), the last one a geometry ``mn_i8conv_supported`` covers; anything else raises naming the layer.
+
+    The reference ResNet tree (BasicBlock and BottleNeck nets, ``bn_fuse=True``, folded and pre-quantised) returns an ``Int8ResPlan``: strided convs, shortcut convs
+    and the QuantAdd run on byte codes (``csrc/qgemm_iao8_res.h``), every block output is written once per consumer quantizer, and conv1, avg_pool and fc stay on the
+    model's own modules.  ``byte_ends=True`` raises for it."""
     import ctypes as C
     from micronet_amd import ops
+    if _is_ref_resnet(model):
+        return _compile_iao8_res(model, byte_ends)
     who = "iao_compile_int8(byte_ends=True)" if byte_ends else "iao_compile_int8"
     first, layers, last, tail, flatten, report, pack_shuffle, ends = _walk_iao8(model, byte_ends=byte_ends)
     _require_gpu(model, "iao_compile_int8")
@@ -1459,3 +1472,307 @@ def iao_compile_int8(model, byte_ends=False):
             raise _err("%s: %s.conv: %d rows whose stored weights are off the grid k * s_w (run prequantize_weights after iao_model_bn_fuse)" % (who, L["name"], off))
     pack = dict(s=layers[0]["s_a"], a_bits=layers[0]["in_bits"], order=_shuffle_order(layers[0]["cin"], pack_shuffle, dev) if pack_shuffle else None)
     return Int8Plan(first, layers, last, tail, flatten, report, pack, ends)
+
+
+# ------------------------------------------------------------------------------------------------ int8 deployment of BN-folded IAO ResNets (csrc/qgemm_iao8_res.h)
+_RESNET_STAGES = ("conv2_x", "conv3_x", "conv4_x", "conv5_x")
+
+
+def _is_ref_resnet(model):
+    """The reference ResNet tree: conv1, conv2_x .. conv5_x of blocks with residual_function / shortcut / add, avg_pool, fc."""
+    if not all(isinstance(getattr(model, n_, None), nn.Sequential) for n_ in ("conv1",) + _RESNET_STAGES) or not hasattr(model, "avg_pool") or not hasattr(model, "fc"):
+        return False
+    return all(hasattr(b_, "residual_function") and hasattr(b_, "shortcut") and hasattr(b_, "add") for n_ in _RESNET_STAGES for b_ in getattr(model, n_))
+
+
+def _res_geom(L, N=1, H=4, W=4):
+    """The ConvGeom of a ResNet stage's dict (square kernel, one stride) on an N x H x W input."""
+    from micronet_amd import _lib
+    return _lib.ConvGeom(N, L["cin"], H, W, L["cout"], L["k"], L["k"], L["stride"], L["stride"], L["pad"], L["pad"], 1, 1, 1, 0)
+
+
+def _walk_iao8_res(model, input_hw=(32, 32), byte_ends=False):
+    """The graph walk of ``iao_compile_int8`` on the reference ResNet tree (no GPU needed): (stem, stages, buffers, tail quantizer, report).
+
+    A VALUE -- conv1's output, or a block's output v = relu(add) -- has up to two consumers with a quantizer each: the next block's first conv, and the next block's
+    shortcut (its QuantAdd itself for an identity shortcut, else the shortcut conv's activation quantizer).  Its producer writes one code map per consumer quantizer
+    (``outs``); ``buffers[i]`` is the channel count of code map i.  The last block writes one map at avg_pool's activation quantizer."""
+    import ctypes as C
+    from micronet_amd import _lib
+    from micronet_amd.quantization.wqaq.iao import quantize
+    who = "iao_compile_int8"
+    if byte_ends:
+        raise _err("iao_compile_int8(byte_ends=True): conv1: a ResNet's first conv feeds two consumers with a quantizer each (the first block's conv and its shortcut); "
+                   "the two-output form of k_i8first is not built")
+
+    def conv_chain(nm, seq):
+        """[(name, conv, relu)] of a Sequential of BN-folded conv -> Identity [-> ReLU] groups."""
+        kids, out, i = list(seq.named_children()), [], 0
+        while i < len(kids):
+            n_, c_ = kids[i]
+            if not isinstance(c_, nn.Conv2d) or i + 1 >= len(kids) or not isinstance(kids[i + 1][1], nn.Identity):
+                raise _err("%s: %s.%s (%s): module order not recognised (expected BN-folded conv -> Identity [-> ReLU] groups; run iao_model_bn_fuse on a bn_fuse=True net)"
+                           % (who, nm, n_, type(c_).__name__))
+            relu = i + 2 < len(kids) and isinstance(kids[i + 2][1], nn.ReLU)
+            out.append((nm + "." + n_, c_, relu))
+            i += 3 if relu else 2
+        return out
+
+    def check_conv(nm, conv):
+        if not isinstance(conv, quantize.QuantConv2d) or isinstance(conv, quantize.QuantBNFuseConv2d):
+            raise _err("%s: %s (%s) is not a BN-folded IAO QuantConv2d (run iao_model_bn_fuse first)" % (who, nm, type(conv).__name__))
+        if not conv.quant_inference:
+            raise _err("%s: %s is not quant_inference: its stored weights are not on the grid (iao_model_bn_fuse + prequantize_weights)" % (who, nm))
+        _iao8_check_quantizer(conv.activation_quantizer, nm + ".activation_quantizer", True, who)
+        wq = conv.weight_quantizer
+        _iao8_check_quantizer(wq, nm + ".weight_quantizer", False, who)
+        if wq.scale.numel() not in (1, conv.out_channels):
+            raise _err("%s: %s.weight_quantizer carries %d scales for %d output channels" % (who, nm, wq.scale.numel(), conv.out_channels))
+        if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
+            raise _err("%s: %s: padding mode not covered by the int8 blocks" % (who, nm))
+        return wq
+
+    stem_chain = conv_chain("conv1", model.conv1)
+    if len(stem_chain) != 1 or not stem_chain[0][2]:
+        raise _err("%s: conv1: module order not recognised (expected one BN-folded conv -> Identity -> ReLU)" % who)
+    c0 = stem_chain[0][1]
+    if not isinstance(c0, quantize.QuantConv2d) or isinstance(c0, quantize.QuantBNFuseConv2d):
+        raise _err("%s: conv1.0 (%s) is not a BN-folded IAO QuantConv2d (run iao_model_bn_fuse first)" % (who, type(c0).__name__))
+    buffers = []
+
+    def new_map(producer, q, qname, channels):
+        buffers.append(channels)
+        producer["outs"].append(dict(q=q, consumer=qname, buf=len(buffers) - 1))
+        return len(buffers) - 1
+
+    def new_stage(nm, conv, relu, kind, src, sc=None, shortcut=None):
+        wq = check_conv(nm, conv)
+        one = lambda v: v[0] if v[0] == v[1] else -1
+        st = dict(name=nm, kind=kind, conv=conv, k=one(conv.kernel_size), pad=one(conv.padding), stride=one(conv.stride), cin=conv.in_channels, cout=conv.out_channels,
+                  groups=conv.groups, relu=int(relu), in_bits=conv.activation_quantizer.bits, w_bits=wq.bits, per_channel=wq.scale.numel() > 1, src=src, sc=sc,
+                  shortcut=shortcut, outs=[])
+        stages.append(st)
+        return st
+
+    stem = dict(name="conv1", cout=c0.out_channels, outs=[])
+    stages, cur = [], stem          # cur: the producer of the current block's input value
+    for sname in _RESNET_STAGES:
+        for bname, blk in getattr(model, sname).named_children():
+            nm = "%s.%s" % (sname, bname)
+            add = blk.add
+            if not isinstance(add, quantize.QuantAdd):
+                raise _err("%s: %s.add (%s) is not an IAO QuantAdd (prepare() quantises the residual add)" % (who, nm, type(add).__name__))
+            qadd = add.activation_quantizer
+            _iao8_check_quantizer(qadd, nm + ".add.activation_quantizer", True, who)
+            res, sc = conv_chain(nm + ".residual_function", blk.residual_function), conv_chain(nm + ".shortcut", blk.shortcut)
+            if len(res) < 2 or not all(r_ for _, _, r_ in res[:-1]) or res[-1][2] or len(sc) > 1 or (sc and sc[0][2]):
+                raise _err("%s: %s: module order not recognised (expected residual_function = conv -> Identity -> ReLU ... conv -> Identity and shortcut = empty or "
+                           "conv -> Identity)" % (who, nm))
+            cin = cur["cout"]
+            if res[0][1].in_channels != cin or (sc and sc[0][1].in_channels != cin):
+                raise _err("%s: %s reads %d channels, its producer %s writes %d" % (who, nm, res[0][1].in_channels, cur["name"], cin))
+            map_a = new_map(cur, res[0][1].activation_quantizer, res[0][0] + ".activation_quantizer", cin)
+            if sc:
+                map_b = new_map(cur, sc[0][1].activation_quantizer, sc[0][0] + ".activation_quantizer", cin)
+            else:
+                map_b = new_map(cur, qadd, nm + ".add.activation_quantizer", cin)          # the identity shortcut: already a code of the block's QuantAdd
+            src = map_a
+            for (cn, conv, _), (nn_, nxt, _) in zip(res[:-1], res[1:]):
+                st = new_stage(cn, conv, True, "int8", src)
+                src = new_map(st, nxt.activation_quantizer, nn_ + ".activation_quantizer", conv.out_channels)
+            if sc:
+                st = new_stage(sc[0][0], sc[0][1], False, "int8", map_b)
+                map_b = new_map(st, qadd, nm + ".add.activation_quantizer", sc[0][1].out_channels)
+            cur = new_stage(res[-1][0], res[-1][1], False, "int8_add", src, sc=map_b, shortcut="conv" if sc else "identity")
+            cur["add"], cur["add_name"] = qadd, nm + ".add"
+            if buffers[map_b] != cur["cout"]:
+                raise _err("%s: %s.add: the residual has %d channels, the shortcut %d" % (who, nm, cur["cout"], buffers[map_b]))
+    if not stages:
+        raise _err("%s: no residual block between conv1 and avg_pool" % who)
+    tail_q = getattr(model.avg_pool, "activation_quantizer", None)
+    _iao8_check_quantizer(tail_q, "avg_pool.activation_quantizer", True, who)
+    new_map(cur, tail_q, "avg_pool.activation_quantizer", cur["cout"])
+
+    # kernels, geometry rules and the report: one row per stage
+    lib = _lib.get_lib()
+    blocked = lambda c, h, w: (c + 15) // 16 * 16 * h * w
+    size = lambda v, k, s, p, d: (v + 2 * p - d * (k - 1) - 1) // s + 1
+    H0, W0 = (size(input_hw[i], c0.kernel_size[i], c0.stride[i], c0.padding[i], c0.dilation[i]) for i in (0, 1))
+    dims = {o["buf"]: (H0, W0) for o in stem["outs"]}
+    report = [dict(name="conv1", kind="first", kernel="the model's own block (fp32), k_i8_pack x %d" % len(stem["outs"]), k=c0.kernel_size[0], cin=c0.in_channels,
+                   cout=c0.out_channels, stride=c0.stride[0], relu=1, shortcut=None, nout=len(stem["outs"]), consumers=[o["consumer"] for o in stem["outs"]], table_bytes=0,
+                   act_bytes_in=4 * c0.in_channels * input_hw[0] * input_hw[1], act_bytes_out=4 * c0.out_channels * H0 * W0 + len(stem["outs"]) * blocked(c0.out_channels, H0, W0))]
+    for st in stages:
+        conv = st["conv"]
+        st["out_bits"] = [o["q"].bits for o in st["outs"]]
+        st["a_bits"] = st["add"].bits if st["kind"] == "int8_add" else st["out_bits"][0]          # the width of the codes the conv's epilogue forms
+        g = _lib.ConvGeom(1, conv.in_channels, 4, 4, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.stride[1], conv.padding[0],
+                          conv.padding[1], conv.dilation[0], conv.dilation[1], conv.groups, 0)
+        what = ("%dx%d, stride %s, padding %s, dilation %s, groups %d, %d input channels" % (conv.kernel_size[0], conv.kernel_size[1], conv.stride, conv.padding,
+                                                                                            conv.dilation, conv.groups, conv.in_channels))
+        if st["kind"] == "int8" and st["relu"] and st["stride"] == 1 and st["in_bits"] == st["a_bits"]:
+            st["api"] = "i8conv"          # the stride-1 ReLU convs keep running on the hidden blocks' kernel
+            if not lib.mn_i8conv_supported(C.byref(g), st["a_bits"], st["w_bits"]):
+                raise _err("%s: %s: geometry not covered by mn_i8conv_supported (%s: 1x1 / padding 0 with groups 1 or C / groups %% 16 == 0, or 3x3 / padding 1 with "
+                           "C / groups %% 16 == 0; stride 1)" % (who, st["name"], what))
+            st["table_bytes"] = int(lib.mn_i8conv_table_bytes(C.byref(g), st["a_bits"], st["w_bits"]))
+            kernel = _i8conv_kernel_name(st["k"], 0)
+        else:
+            st["api"] = "res_add" if st["kind"] == "int8_add" else "res_conv"
+            if not lib.mn_i8res_supported(C.byref(g), st["in_bits"], st["a_bits"], st["w_bits"]) or (st["api"] == "res_add" and st["stride"] != 1):
+                raise _err("%s: %s: geometry not covered by mn_i8res_supported (%s: groups 1, dilation 1, 1x1 / padding 0 with any C or 3x3 / padding 1 with C %% 16 == 0, "
+                           "stride 1 or 2 in both directions; the conv in front of a QuantAdd: stride 1)" % (who, st["name"], what))
+            st["table_bytes"] = int(lib.mn_i8res_table_bytes(C.byref(g), st["in_bits"], st["a_bits"], st["w_bits"]))
+            kernel = ("k_i8res_add<%d,%d>" % (st["k"], len(st["outs"]))) if st["api"] == "res_add" else "k_i8res_conv<%d,%d,%d>" % (st["k"], st["stride"], st["relu"])
+        H, W = dims[st["src"]]
+        Ho, Wo = (H - 1) // st["stride"] + 1, (W - 1) // st["stride"] + 1
+        if st["sc"] is not None and dims[st["sc"]] != (Ho, Wo):
+            raise _err("%s: %s: the residual map is %d x %d, the shortcut's %d x %d" % (who, st["add_name"], Ho, Wo, dims[st["sc"]][0], dims[st["sc"]][1]))
+        for o in st["outs"]:
+            dims[o["buf"]] = (Ho, Wo)
+        report.append(dict(name=st["name"], kind=st["kind"], kernel=kernel, k=st["k"], cin=st["cin"], cout=st["cout"], stride=st["stride"], relu=st["relu"],
+                           shortcut=st["shortcut"], nout=len(st["outs"]), consumers=[o["consumer"] for o in st["outs"]], table_bytes=st["table_bytes"],
+                           act_bytes_in=blocked(st["cin"], H, W) + (blocked(st["cout"], Ho, Wo) if st["sc"] is not None else 0),
+                           act_bytes_out=len(st["outs"]) * blocked(st["cout"], Ho, Wo)))
+    Hl, Wl = dims[cur["outs"][0]["buf"]]
+    fc_out = getattr(model.fc, "out_features", 0)
+    report.append(dict(name="avg_pool", kind="last", kernel="k_i8_unpack, the model's own avg_pool and fc (fp32)", k=0, cin=cur["cout"], cout=fc_out, stride=1, relu=0,
+                       shortcut=None, nout=1, consumers=[], table_bytes=0, act_bytes_in=blocked(cur["cout"], Hl, Wl) + 4 * cur["cout"] * Hl * Wl, act_bytes_out=4 * fc_out))
+    return stem, stages, buffers, tail_q, report
+
+
+class Int8ResPlan(_Plan):
+    """What ``iao_compile_int8`` returns for a ResNet: the model's own conv1 (fp32) -> ``mn_i8_pack_codes`` once per consumer quantizer of its output -> one int8 kernel
+    per conv (``mn_i8conv_fwd`` for the stride-1 ReLU convs, ``mn_i8res_conv_fwd`` for the strided ones and the shortcut convs, ``mn_i8res_add_fwd`` for the last conv
+    of a block with its QuantAdd, ReLU and the next block's quantizers) -> ``mn_i8_unpack_codes`` at avg_pool's scale -> the model's own avg_pool and fc.  Eval only;
+    owns the packed tables and one set of byte buffers per input shape.  ``layers[i]`` keeps what stage i was packed from (w, s_w, bias, s_a, s_add, s_out per output
+    map, the widths, src / sc / outs buffer numbers) for the tests' judge; ``buffers[b]`` is the channel count of code map b; ``stem`` the packs behind conv1."""
+
+    who = "iao_compile_int8"
+
+    def __init__(self, conv1, stages, avg_pool, fc, report, stem, buffers, tail):
+        super().__init__(conv1, stages, None, [avg_pool, fc], True, report)
+        self.stem, self.buffers, self.tail_q = stem, buffers, tail          # tail: dict(buf, s, C)
+        self.stage_codes = []
+
+    def _plan_buffers(self, shape, device):
+        """Every code map, the geometry of every stage and the fp32 map in front of avg_pool for one conv1 output shape."""
+        N, Cc, H, W = shape
+        if Cc != self.stem["cout"]:
+            raise _err("iao_compile_int8: conv1 produced %d channels, the first block reads %d" % (Cc, self.stem["cout"]))
+        dims = {o["buf"]: (H, W) for o in self.stem["outs"]}
+        geoms = []
+        for L in self.layers:
+            h, w = dims[L["src"]]
+            geoms.append(_res_geom(L, N, h, w))
+            for o in L["outs"]:
+                dims[o["buf"]] = ((h - 1) // L["stride"] + 1, (w - 1) // L["stride"] + 1)
+        bufs = [torch.empty((N, (c + 15) // 16, dims[b][0] * dims[b][1], 16), dtype=torch.int8, device=device) for b, c in enumerate(self.buffers)]
+        ht, wt = dims[self.tail_q["buf"]]
+        return bufs, geoms, torch.empty((N, self.tail_q["C"], ht, wt), dtype=torch.float32, device=device)
+
+    @staticmethod
+    def _add_params(L):
+        from micronet_amd import _lib
+        q = _lib.I8ResAdd()
+        q.s_add, q.add_bits, q.nout = L["s_add"], L["a_bits"], len(L["outs"])
+        q.s_out0, q.bits0 = L["s_out"][0], L["out_bits"][0]
+        q.s_out1, q.bits1 = (L["s_out"][1], L["out_bits"][1]) if len(L["outs"]) == 2 else (L["s_out"][0], L["out_bits"][0])
+        return q
+
+    def _launch(self, L, g, src, sc, outs, st):
+        import ctypes as C
+        from micronet_amd import ops
+        if L["api"] == "i8conv":
+            ops._call("mn_i8conv_fwd", C.byref(g), L["a_bits"], L["w_bits"], ops._p(L["table"]), ops._p(src), ops._p(outs[0]), 0, st)
+        elif L["api"] == "res_conv":
+            ops._call("mn_i8res_conv_fwd", C.byref(g), L["in_bits"], L["a_bits"], L["w_bits"], ops._p(L["table"]), ops._p(src), ops._p(outs[0]), L["relu"], st)
+        else:
+            q = self._add_params(L)
+            ops._call("mn_i8res_add_fwd", C.byref(g), L["in_bits"], L["w_bits"], ops._p(L["table"]), ops._p(src), ops._p(sc), C.byref(q), ops._p(outs[0]),
+                      ops._p(outs[1]) if len(outs) == 2 else None, st)
+
+    def run_stage(self, i, codes, N, H, W, shortcut=None):
+        """Stage ``i`` alone on blocked input codes [N, ceil(cin / 16), H * W, 16] (int8, GPU; an add stage also takes the shortcut's codes [N, ceil(cout / 16), H * W, 16]):
+        the list of its blocked output maps, freshly allocated and poisoned (tests)."""
+        from micronet_amd import ops
+        L = self.layers[i]
+        ok = lambda t, c, hw: torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int8 and tuple(t.shape) == (N, (c + 15) // 16, hw, 16)
+        Ho, Wo = (H - 1) // L["stride"] + 1, (W - 1) // L["stride"] + 1
+        if not ok(codes, L["cin"], H * W) or (L["api"] == "res_add") != (shortcut is not None) or (shortcut is not None and not ok(shortcut, L["cout"], Ho * Wo)):
+            raise _err("iao_compile_int8: run_stage needs int8 GPU codes [N, ceil(C / 16), H * W, 16] (and the shortcut's codes for an add stage, for no other)")
+        outs = [torch.full((N, (L["cout"] + 15) // 16, Ho * Wo, 16), 77, dtype=torch.int8, device=codes.device) for _ in L["outs"]]
+        with torch.cuda.device(codes.device):
+            self._launch(L, _res_geom(L, N, H, W), codes.contiguous(), shortcut.contiguous() if shortcut is not None else None, outs, ops._s())
+        return outs
+
+    @torch.no_grad()
+    def forward(self, x):
+        from micronet_amd import ops
+        a = self.first(x)
+        if not (type(a) is torch.Tensor and a.is_cuda and a.dtype == torch.float32 and a.dim() == 4):
+            raise _err("iao_compile_int8: conv1 did not produce a float32 GPU map (the input must be a float32 GPU tensor; no CPU fallback)")
+        a = a.contiguous()
+        N, Cc, H, W = a.shape
+        with torch.cuda.device(a.device):
+            bufs, geoms, y = self._shape_buffers(a.shape, a.device)
+            st = ops._s()
+            for o in self.stem["outs"]:
+                ops._call("mn_i8_pack_codes", ops._p(a), N, Cc, H * W, o["s"], o["bits"], None, ops._p(bufs[o["buf"]]), st)
+            for L, g in zip(self.layers, geoms):
+                self._launch(L, g, bufs[L["src"]], bufs[L["sc"]] if L["sc"] is not None else None, [bufs[o["buf"]] for o in L["outs"]], st)
+            if self.keep_stages:
+                self.stage_codes = [b.clone() for b in bufs]
+            n_, c_, h_, w_ = y.shape
+            ops._call("mn_i8_unpack_codes", ops._p(bufs[self.tail_q["buf"]]), n_, c_, h_ * w_, self.tail_q["s"], ops._p(y), st)
+        y = self.tail[0](y)
+        return self.tail[1](y.view(y.size(0), -1))
+
+
+@torch.no_grad()
+def _compile_iao8_res(model, byte_ends=False):
+    import ctypes as C
+    import math
+    from micronet_amd import ops
+    who = "iao_compile_int8"
+    stem, stages, buffers, tail_q, report = _walk_iao8_res(model, byte_ends=byte_ends)
+    _require_gpu(model, who)
+    dev = stages[0]["conv"].weight.device
+    # every scale the plan needs, in ONE host read
+    qs = [o["q"] for o in stem["outs"]]
+    for L in stages:
+        qs += [L["conv"].activation_quantizer] + [o["q"] for o in L["outs"]] + ([L["add"]] if "add" in L else [])
+    vals = torch.cat([q.scale.detach().float().reshape(-1)[:1] for q in qs]).tolist()
+    scale = {id(q): v for q, v in zip(qs, vals)}
+    for o in stem["outs"]:
+        q = o.pop("q")
+        o["s"], o["bits"] = scale[id(q)], q.bits
+    with torch.cuda.device(dev):
+        for L in stages:
+            conv = L.pop("conv")
+            L["w"] = conv.weight.detach().float().contiguous()
+            L["s_w"] = conv.weight_quantizer.scale.detach().float().reshape(-1).contiguous()
+            L["bias"] = conv.bias.detach().float().contiguous() if conv.bias is not None else None
+            L["s_a"] = scale[id(conv.activation_quantizer)]
+            L["s_out"] = [scale[id(o.pop("q"))] for o in L["outs"]]
+            L["s_add"] = scale[id(L.pop("add"))] if "add" in L else None
+            L["table"] = torch.empty(L["table_bytes"] // 4, dtype=torch.int32, device=dev)
+            s_tab = L["s_add"] if L["api"] == "res_add" else L["s_out"][0]          # the scale of the codes the conv's epilogue forms
+            if L["api"] == "i8conv":
+                ops._call("mn_i8conv_pack", C.byref(_res_geom(L)), ops._p(L["w"]), ops._p(L["s_w"]), 1 if L["per_channel"] else 0, ops._p(L["bias"]), L["s_a"], s_tab, s_tab,
+                          L["a_bits"], L["w_bits"], None, ops._p(L["table"]), ops._s())
+            else:
+                ops._call("mn_i8res_pack", C.byref(_res_geom(L)), ops._p(L["w"]), ops._p(L["s_w"]), 1 if L["per_channel"] else 0, ops._p(L["bias"]), L["s_a"], s_tab,
+                          L["in_bits"], L["a_bits"], L["w_bits"], ops._p(L["table"]), ops._s())
+        counters = torch.stack([L["table"][[0, 7]] for L in stages]).tolist()          # ... and every table's two counters in one more
+    for L, (bad, off) in zip(stages, counters):
+        if bad:
+            raise _err("%s: %s: %d rows or scales with a non-finite or non-positive constant (al, bias, s_w, s_a, s_out)" % (who, L["name"], bad))
+        if off:
+            raise _err("%s: %s: %d rows whose stored weights are off the grid k * s_w (run prequantize_weights after iao_model_bn_fuse)" % (who, L["name"], off))
+        for s in L["s_out"] + ([L["s_add"]] if L["s_add"] is not None else []):
+            if not (math.isfinite(s) and s > 0):
+                raise _err("%s: %s: a consumer's scale %r is not finite and positive" % (who, L["name"], s))
+    last = stages[-1]
+    tail = dict(buf=last["outs"][0]["buf"], s=last["s_out"][0], C=last["cout"])
+    return Int8ResPlan(model.conv1, stages, model.avg_pool, model.fc, report, stem, buffers, tail)

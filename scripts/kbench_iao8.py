@@ -10,7 +10,12 @@ max|F| and the argmax agreement; and the designed HBM bytes per image per hidden
     python scripts/kbench_iao8.py --byte-ends [...] [--out profiles/iao8_ends_inference.json]
 
 adds ``E = inference.iao_compile_int8(F, byte_ends=True)`` (the first conv writes bytes, the classifier reads them) as a third path alternated with the two: its
-yardstick is ``P`` in the same run (``E_over_P``), and its per-kernel times stand beside P's."""
+yardstick is ``P`` in the same run (``E_over_P``), and its per-kernel times stand beside P's.
+
+    python scripts/kbench_iao8.py --resnet18 [...] [--out profiles/iao8_resnet_inference.json]
+
+runs the same comparison on a BN-folded IAO W8A8 resnet18: ``F`` writes and re-reads an fp32 map around every conv, ReLU and QuantAdd, ``P`` keeps byte codes from the
+pack behind conv1 to the unpack in front of avg_pool (strided convs, shortcut convs and the QuantAdd on bytes: csrc/qgemm_iao8_res.h)."""
 import argparse
 import importlib
 import json
@@ -58,6 +63,19 @@ def designed_bytes_per_image(P):
     return rows
 
 
+def designed_bytes_per_image_resnet(P):
+    """The stages of a ResNet plan, per image, arithmetic from the shapes.  fp32-map path (F): a conv reads an fp32 map and writes one (4 B per input and per output
+    element), a ReLU reads and writes it (8 B per element); a QuantAdd reads the residual and the shortcut and writes the sum (12 B), the block's ReLU reads and
+    writes it (8 B).  int8 path (P): ``act_bytes_in`` / ``act_bytes_out`` of the report (an add stage reads its input and the shortcut, and writes ``nout`` maps)."""
+    rows = []
+    for r in P.report[1:-1]:
+        n_out = r["act_bytes_out"] // r["nout"]
+        n_in = r["act_bytes_in"] - (n_out if r["kind"] == "int8_add" else 0)
+        fp32 = 4 * n_in + 4 * n_out + (8 * n_out if r["relu"] else 0) + (20 * n_out if r["kind"] == "int8_add" else 0)
+        rows.append(dict(name=r["name"], kernel=r["kernel"], int8_bytes=r["act_bytes_in"] + r["act_bytes_out"], fp32_path_bytes=fp32, table_bytes=r["table_bytes"]))
+    return rows
+
+
 def q(v):
     return dict(median=statistics.median(v), min=min(v), max=max(v), p25=statistics.quantiles(v, n=4)[0], p75=statistics.quantiles(v, n=4)[2])
 
@@ -68,14 +86,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--byte-ends", action="store_true", help="also time the byte_ends plan, against the default plan of the same run")
-    ap.add_argument("--out", default=None, help="default: profiles/iao8_inference.json, with --byte-ends profiles/iao8_ends_inference.json")
+    ap.add_argument("--resnet18", action="store_true", help="the BN-folded IAO W8A8 resnet18 instead of nin_gc (no --byte-ends: not built for ResNets)")
+    ap.add_argument("--out", default=None, help="default: profiles/iao8_inference.json, with --byte-ends profiles/iao8_ends_inference.json, with --resnet18 "
+                                                "profiles/iao8_resnet_inference.json")
     args = ap.parse_args()
-    args.out = args.out or os.path.join("profiles", "iao8_ends_inference.json" if args.byte_ends else "iao8_inference.json")
+    if args.resnet18 and args.byte_ends:
+        ap.error("--resnet18 and --byte-ends exclude each other")
+    args.out = args.out or os.path.join("profiles", "iao8_resnet_inference.json" if args.resnet18 else "iao8_ends_inference.json" if args.byte_ends else "iao8_inference.json")
+    arch = "resnet18" if args.resnet18 else "nin_gc"
     from micronet_amd import _lib, inference
     from micronet_amd.train import build_model, make_optimizer, synth_batch, train_step
     Q = importlib.import_module("micronet.compression.quantization.wqaq.iao.quantize")
     # two training steps give the observers a range and the scales a meaning; then the fold and the pre-quantisation
-    T = Q.prepare(build_model("nin_gc"), inplace=True, a_bits=8, w_bits=8, q_type=0, q_level=0, weight_observer=0, bn_fuse=True).cuda().train()
+    T = Q.prepare(build_model(arch), inplace=True, a_bits=8, w_bits=8, q_type=0, q_level=0, weight_observer=0, bn_fuse=True).cuda().train()
     opt = make_optimizer(T, 0.01, 1e-5)
     xt, yt = synth_batch(32, device="cuda")
     for _ in range(2):
@@ -87,8 +110,8 @@ def main():
     P = inference.iao_compile_int8(F)
     E = inference.iao_compile_int8(F, byte_ends=True) if args.byte_ends else None
     lib = _lib.get_lib()
-    res = dict(model="nin_gc", a_bits=8, w_bits=8, warmup=args.warmup, iters=args.iters, device=torch.cuda.get_device_name(0), report=P.report,
-               designed_bytes_per_image=designed_bytes_per_image(P), batches={})
+    res = dict(model=arch, a_bits=8, w_bits=8, warmup=args.warmup, iters=args.iters, device=torch.cuda.get_device_name(0), report=P.report,
+               designed_bytes_per_image=(designed_bytes_per_image_resnet if args.resnet18 else designed_bytes_per_image)(P), batches={})
     if E is not None:
         res["ends_report"] = E.report
     with torch.no_grad():
