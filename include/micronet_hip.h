@@ -1183,6 +1183,41 @@ int mn_i8res_conv_fwd(const mn_conv_geom* g, int in_bits, int out_bits, int w_bi
 int mn_i8res_add_fwd(const mn_conv_geom* g, int in_bits, int w_bits, const uint32_t* table, const int8_t* in_codes, const int8_t* shortcut_codes, const mn_i8res_add* q,
                      int8_t* out_a, int8_t* out_b, mn_stream_t stream);
 
+/* The hidden blocks of the int8 deployment with ZERO POINTS (csrc/qgemm_iao8_zp.h): the stage of mn_i8conv_fwd where any of its quantizers is asymmetric.  A
+ * quantizer is (s, z, asym, bits); its code range [lo, hi] is -2^(b-1) .. 2^(b-1) - 1 (symmetric activation), +-(2^(b-1) - 1) (symmetric weight), 0 .. 2^b - 1
+ * (asymmetric activation), 0 .. 2^b - 2 (asymmetric weight); code(r; s, z) = clamp(rha(fl(fl(r / s) - z)), lo, hi) and the value of a code c is fl(fl(c + z) * s).
+ * The stored byte is c - h, h = 0 (symmetric), 2^(b-1) (asymmetric activation), 2^(b-1) - 1 (asymmetric weight); e = z + h.  Layout as for mn_i8conv_fwd, tail
+ * channels the byte 0.  With j an input byte and k = rint(fl(fl(w / s_w) - z_w)) - h_w a weight byte,
+ *   S = sum over the in-bounds taps and the group's real channels of (j + e_a)(k + e_w[o]), exact in int32 (zero padding is the VALUE 0 and adds nothing);
+ *   y = fl(fl(float(S) * al) + b[o]), al = fl(s_a * s_w[o]); r = max(y, 0); c = code(r; s_out, z_out);
+ *   pool == 1: c1 = code(r; s_p, z_p) per sub-pixel, m = the window's largest c1, v = fl(fl(m + z_p) * s_p), c = code(v; s_out, z_out);  output byte = c - h_out.
+ * With every quantizer symmetric and every z = 0 this is mn_i8conv_fwd's chain bit for bit.  Covered (mn_i8zconv_supported): what mn_i8conv_supported covers (the rule
+ * sees no zero point); a_bits is the width of the output codes.  Error codes, alignment and "a refused call writes nothing" as for mn_i8conv_*; no entry allocates.
+ *   pack : w, s_w, s_w_stride, bias, out_order as for mn_i8conv_pack; z_w[o * s_w_stride] the weight zero points (null: 0), w_asym the weight quantizer's flag; q_a the
+ *          conv's own activation quantizer, q_p the pool's (pass q_out where there is no pool; its width must be q_out's), q_out the consumer's, read on the host at the
+ *          call -> `table` (private layout, mn_i8zconv_table_bytes(g, q_out->bits, w_bits) bytes).  Header words the caller may read back once, all 0 for a valid
+ *          table: [0] and [7] as for mn_i8conv_pack (a weight is off the grid when |w / s_w - z_w - rint| > 1e-3 or its code lies outside lo .. hi); [13] zero points
+ *          that are not integers of magnitude <= 65535 (each of z_a, z_p, z_out, plus the rows with such a z_w); [14] rows with
+ *          Cg * taps * (2^(in-1) + |e_a|) * (2^(w-1) - 1 + |e_w[o]|) > INT_MAX, in = q_a->bits (S would not be exact in int32); [15] 1 for a 3x3 stage whose input
+ *          quantizer has no code for the value 0 (-z_a outside lo .. hi: zero padding has no byte).  Word 6 = a_bits | w_bits << 8 | in_bits << 16.
+ *   fwd  : as mn_i8conv_fwd.  mn_last_kernel(): k_i8zconv<KS,pool>.
+ * mn_i8z_pack_codes: fp32 NCHW x -> bytes code(x; q) - h in the layout above, position j holding channel out_order[j]; tail channels and bad entries the byte 0.
+ * mn_i8z_unpack_codes: bytes -> fp32 NCHW fl(fl(byte + h + z) * s).  q->s finite and positive, q->z an integer of magnitude <= 65535, q->asym 0 / 1, else MN_EINVAL;
+ * q->bits outside 2 .. 8 is MN_ENOTSUP.  mn_last_kernel(): k_i8z_pack / k_i8z_unpack. */
+typedef struct mn_i8z_quant {
+    float s;               /* scale */
+    float z;               /* zero point (integer-valued) */
+    int32_t asym;          /* 0: symmetric, 1: asymmetric code range */
+    int32_t bits;
+} mn_i8z_quant;
+int mn_i8zconv_supported(const mn_conv_geom* g, int a_bits, int w_bits);
+int64_t mn_i8zconv_table_bytes(const mn_conv_geom* g, int a_bits, int w_bits);
+int mn_i8zconv_pack(const mn_conv_geom* g, const float* w, const float* s_w, const float* z_w, int s_w_stride, const float* bias, const mn_i8z_quant* q_a,
+                    const mn_i8z_quant* q_p, const mn_i8z_quant* q_out, int w_asym, int w_bits, const int32_t* out_order, uint32_t* table, mn_stream_t stream);
+int mn_i8zconv_fwd(const mn_conv_geom* g, int a_bits, int w_bits, const uint32_t* table, const int8_t* in_codes, int8_t* out_codes, int pool, mn_stream_t stream);
+int mn_i8z_pack_codes(const float* x, int64_t N, int64_t C, int64_t HW, const mn_i8z_quant* q, const int32_t* out_order, int8_t* codes, mn_stream_t stream);
+int mn_i8z_unpack_codes(const int8_t* codes, int64_t N, int64_t C, int64_t HW, const mn_i8z_quant* q, float* y, mn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -760,5 +760,6 @@ extern "C" int mn_bits_maxpool(const uint32_t* bits_in, int64_t N, int64_t Cw, i
 #include "qgemm_bits_mfma.h"      // mn_bitconv_mfma_*: the int8-MFMA form of the 1x1 hidden bit blocks
 #include "qgemm_bits_mfma3.h"     // mn_bitconv_mfma3_*: the int8-MFMA form of the 3x3 hidden bit blocks
 #include "qgemm_iao8.h"           // mn_i8conv_* / mn_i8_*: the int8 deployment of the BN-folded IAO hidden blocks (byte codes, i8 MFMA)
+#include "qgemm_iao8_zp.h"        // mn_i8zconv_* / mn_i8z_*: the same blocks with zero points (asymmetric quantizers)
 #include "qgemm_iao8_ends.h"      // mn_i8first_* / mn_i8conv_fwd_f32: the two ends of that deployment (fp32 image in, fp32 map out)
 #include "qgemm_iao8_res.h"       // mn_i8res_*: the residual stages of that deployment (strided convs, QuantAdd on bytes)

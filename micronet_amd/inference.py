@@ -25,7 +25,8 @@ The results are ordinary modules of this package: in eval mode they run on the s
   * ``iao_compile_int8``: the BN-folded, pre-quantised symmetric IAO graph compiled into a flat plan that keeps ONE INT8 CODE per hidden activation
     (``csrc/qgemm_iao8.h``: byte codes against weight-code bytes on v_mfma_i32_16x16x64_i8, bias + ReLU + [2x2 max-pool] + the consumer's quantizer in the epilogue).
     One kernel per hidden block; the two ends stay on the model's own modules.  A BN-folded IAO ResNet compiles by the same call (``csrc/qgemm_iao8_res.h``: strided
-    convs, shortcut convs and the QuantAdd on byte codes, one code map per consumer quantizer of a block's output)."""
+    convs, shortcut convs and the QuantAdd on byte codes, one code map per consumer quantizer of a block's output).  ``zero_points=True`` admits asymmetric
+    quantizers on the sequential nets (``csrc/qgemm_iao8_zp.h``: the zero points as integer offsets of the exact int32 sum)."""
 import copy
 
 import torch
@@ -1110,23 +1111,39 @@ def _i8conv_kernel_name(k, pool):
     return "k_i8conv<%d,%d>" % (k, pool)
 
 
-def _iao8_check_quantizer(q, nm, per_tensor, who="iao_compile_int8"):
-    """A quantizer the int8 blocks cover: symmetric (zero point 0), 2 .. 8 bits; ``per_tensor``: exactly one scale."""
+def _i8zconv_kernel_name(k, pool):
+    """The kernel mn_i8zconv_fwd reports for a hidden block with a zero point (csrc/qgemm_iao8_zp.h)."""
+    return "k_i8zconv<%d,%d>" % (k, pool)
+
+
+def _iao8_check_quantizer(q, nm, per_tensor, who="iao_compile_int8", zero_points=False):
+    """A quantizer the int8 blocks cover: symmetric (zero point 0), 2 .. 8 bits; ``per_tensor``: exactly one scale.  ``zero_points``: an ``AsymmetricQuantizer`` is
+    covered as well (``per_tensor``: exactly one zero point), its ``q_type`` attribute agreeing with its class.  Returns 1 for an asymmetric quantizer, else 0."""
     from micronet_amd.quantization.wqaq.iao import quantize
     if not isinstance(q, quantize.Quantizer):
         raise _err("%s: %s is not an IAO quantizer" % (who, nm))
     if q.bits == 32 or not 2 <= q.bits <= 8:
         raise _err("%s: %s has %d bits; the int8 blocks cover code widths 2 .. 8" % (who, nm, q.bits))
-    if q._q_type_static != 0 or q.q_type != 0 or bool((q.zero_point != 0).any()):
+    if zero_points and q.q_type != q._q_type_static:
+        raise _err("%s: %s (%s) carries q_type %s, its class q_type %d: the quantizer never updated its parameters, or the attribute was changed"
+                   % (who, nm, type(q).__name__, q.q_type, q._q_type_static))
+    asym = int(zero_points and q._q_type_static == 1)
+    if not asym and (q._q_type_static != 0 or q.q_type != 0 or bool((q.zero_point != 0).any())):
         raise _err("%s: %s is asymmetric; a zero byte must be the value 0 (symmetric quantizers only)" % (who, nm))
     if per_tensor and q.scale.numel() != 1:
         raise _err("%s: %s carries %d scales; a per-tensor activation scale must be a single value" % (who, nm, q.scale.numel()))
+    if asym and per_tensor and q.zero_point.numel() != 1:
+        raise _err("%s: %s carries %d zero points; a per-tensor activation zero point must be a single value" % (who, nm, q.zero_point.numel()))
+    return asym
 
 
-def _iao8_check_weights(conv, nm, who="iao_compile_int8"):
-    """The weight quantizer and padding mode of a conv the int8 blocks contract: symmetric, 2 .. 8 bits, one scale per layer or per output channel, zero padding."""
+def _iao8_check_weights(conv, nm, who="iao_compile_int8", zero_points=False):
+    """The weight quantizer and padding mode of a conv the int8 blocks contract: symmetric (``zero_points``: or asymmetric, as many zero points as scales), 2 .. 8
+    bits, one scale per layer or per output channel, zero padding."""
     wq = conv.weight_quantizer
-    _iao8_check_quantizer(wq, nm + ".conv.weight_quantizer", False, who)
+    asym = _iao8_check_quantizer(wq, nm + ".conv.weight_quantizer", False, who, zero_points)
+    if asym and wq.zero_point.numel() != wq.scale.numel():
+        raise _err("%s: %s.conv.weight_quantizer carries %d zero points for %d scales" % (who, nm, wq.zero_point.numel(), wq.scale.numel()))
     if wq.scale.numel() not in (1, conv.out_channels):
         raise _err("%s: %s.conv.weight_quantizer carries %d scales for %d output channels" % (who, nm, wq.scale.numel(), conv.out_channels))
     if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
@@ -1134,9 +1151,12 @@ def _iao8_check_weights(conv, nm, who="iao_compile_int8"):
     return wq
 
 
-def _walk_iao8(model, input_hw=(32, 32), byte_ends=False):
+def _walk_iao8(model, input_hw=(32, 32), byte_ends=False, zero_points=False):
     """The graph walk of ``iao_compile_int8`` (no GPU needed): (first, layers, last, tail, flatten, report, pack_shuffle, ends); ``ends``: None, or with ``byte_ends``
-    the layer dicts (first, last) of the two end blocks."""
+    the layer dicts (first, last) of the two end blocks.  ``zero_points``: asymmetric quantizers are admitted; a layer whose input, weight, pool or consumer quantizer
+    is asymmetric carries ``zp`` = True and takes the kernels of csrc/qgemm_iao8_zp.h."""
+    if zero_points and byte_ends:
+        raise _err("iao_compile_int8(zero_points=True): byte_ends=True is not covered together with zero points (the int8 end kernels take symmetric quantizers only)")
     import ctypes as C
     from micronet_amd import _lib
     from micronet_amd.quantization.wqaq.dorefa.quantize import _is_ref_block
@@ -1160,7 +1180,7 @@ def _walk_iao8(model, input_hw=(32, 32), byte_ends=False):
             raise _err("%s: %s.conv (%s) is not a BN-folded IAO QuantConv2d (run iao_model_bn_fuse first)" % (who, nm, type(conv).__name__))
         if not conv.quant_inference:
             raise _err("%s: %s.conv is not quant_inference: its stored weights are not on the grid (iao_model_bn_fuse + prequantize_weights)" % (who, nm))
-        _iao8_check_quantizer(conv.activation_quantizer, nm + ".conv.activation_quantizer", True, who)
+        _iao8_check_quantizer(conv.activation_quantizer, nm + ".conv.activation_quantizer", True, who, zero_points)
         return conv
 
     if not isinstance(getattr(first, "conv", None), nn.Conv2d):
@@ -1186,11 +1206,11 @@ def _walk_iao8(model, input_hw=(32, 32), byte_ends=False):
                 raise _err("iao_compile_int8: %s: a max-pool directly behind the first block is not covered (its producer is not an int8 block)" % nm)
             if layers[-1]["pool"]:
                 raise _err("iao_compile_int8: %s: a second max-pool behind one block" % nm)
-            _iao8_check_quantizer(child.activation_quantizer, nm + ".activation_quantizer", True)
+            _iao8_check_quantizer(child.activation_quantizer, nm + ".activation_quantizer", True, zero_points=zero_points)
             layers[-1]["pool"], layers[-1]["pool_module"], layers[-1]["pool_name"] = 1, child, nm
             continue
         conv = block_conv(nm, child)
-        wq = _iao8_check_weights(conv, nm)
+        wq = _iao8_check_weights(conv, nm, zero_points=zero_points)
         one = lambda v: v[0] if v[0] == v[1] else -1
         g = _lib.ConvGeom(1, conv.in_channels, 4, 4, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.stride[1], conv.padding[0],
                           conv.padding[1], conv.dilation[0], conv.dilation[1], conv.groups, 0)
@@ -1210,17 +1230,22 @@ def _walk_iao8(model, input_hw=(32, 32), byte_ends=False):
     if not layers:
         raise _err("iao_compile_int8: no hidden block between %s and %s" % (nm_first, nm_last))
     # the consumer of every hidden block: the next hidden conv's activation quantizer, or the last conv's
+    is_asym = lambda q: int(zero_points and q._q_type_static == 1)
     for L, nxt in zip(layers, [M["conv"] for M in layers[1:]] + [last_conv]):
         L["consumer"] = nxt.activation_quantizer
         L["a_bits"] = nxt.activation_quantizer.bits
+        L["asym_a"], L["asym_w"] = is_asym(L["conv"].activation_quantizer), is_asym(L["conv"].weight_quantizer)
+        L["asym_out"] = is_asym(nxt.activation_quantizer)
+        L["asym_p"] = is_asym(L["pool_module"].activation_quantizer) if L["pool"] else L["asym_out"]
+        L["zp"] = bool(L["asym_a"] or L["asym_w"] or L["asym_out"] or L["asym_p"])
         if L["pool"] and L["pool_module"].activation_quantizer.bits != L["a_bits"]:
             raise _err("iao_compile_int8: %s: the pool's quantizer has %d bits, its consumer %d: one code width per block"
                        % (L["pool_name"], L["pool_module"].activation_quantizer.bits, L["a_bits"]))
     blocked = lambda c, h, w: (c + 15) // 16 * 16 * h * w
     geom = lambda conv, h, w, shuffle=0: _lib.ConvGeom(1, conv.in_channels, h, w, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0],
                                                        conv.stride[1], conv.padding[0], conv.padding[1], conv.dilation[0], conv.dilation[1], conv.groups, shuffle)
-    report = [dict(name=nm_first, kind="first", kernel="the model's own block (fp32), k_i8_pack", k=c0.kernel_size[0], cin=c0.in_channels, cout=c0.out_channels,
-                   groups=c0.groups, pool=0, out_order=("shuffle %d" % pack_shuffle) if pack_shuffle else "identity", table_bytes=0,
+    report = [dict(name=nm_first, kind="first", kernel="the model's own block (fp32), %s" % ("k_i8z_pack" if layers[0]["asym_a"] else "k_i8_pack"),
+                   k=c0.kernel_size[0], cin=c0.in_channels, cout=c0.out_channels, groups=c0.groups, pool=0, out_order=("shuffle %d" % pack_shuffle) if pack_shuffle else "identity", table_bytes=0,
                    act_bytes_in=4 * c0.in_channels * input_hw[0] * input_hw[1], act_bytes_out=4 * c0.out_channels * H * W + blocked(c0.out_channels, H, W))]
     ends = None
     if byte_ends:
@@ -1244,12 +1269,13 @@ def _walk_iao8(model, input_hw=(32, 32), byte_ends=False):
             if H % 2 or W % 2:
                 raise _err("iao_compile_int8: %s: the 2x2 max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
             H, W = H // 2, W // 2
-        L["table_bytes"] = int(_lib.get_lib().mn_i8conv_table_bytes(C.byref(g), L["a_bits"], L["w_bits"]))
-        report.append(dict(name=L["name"], kind="int8", kernel=_i8conv_kernel_name(L["k"], L["pool"]), k=L["k"], cin=L["cin"], cout=L["cout"], groups=L["groups"],
-                           pool=L["pool"], out_order=("shuffle %d" % L["shuffle"]) if L["shuffle"] else "identity", table_bytes=L["table_bytes"], act_bytes_in=nin,
+        table_bytes = _lib.get_lib().mn_i8zconv_table_bytes if L["zp"] else _lib.get_lib().mn_i8conv_table_bytes
+        L["table_bytes"] = int(table_bytes(C.byref(g), L["a_bits"], L["w_bits"]))
+        report.append(dict(name=L["name"], kind="int8", kernel=(_i8zconv_kernel_name if L["zp"] else _i8conv_kernel_name)(L["k"], L["pool"]), k=L["k"], cin=L["cin"],
+                           cout=L["cout"], groups=L["groups"], pool=L["pool"], out_order=("shuffle %d" % L["shuffle"]) if L["shuffle"] else "identity", table_bytes=L["table_bytes"], act_bytes_in=nin,
                            act_bytes_out=blocked(L["cout"], H, W)))
-    report.append(dict(name=nm_last, kind="last", kernel="k_i8_unpack, the model's own block (fp32)", k=last_conv.kernel_size[0], cin=last_conv.in_channels,
-                       cout=last_conv.out_channels, groups=last_conv.groups, pool=0, out_order="identity", table_bytes=0,
+    report.append(dict(name=nm_last, kind="last", kernel="%s, the model's own block (fp32)" % ("k_i8z_unpack" if layers[-1]["asym_out"] else "k_i8_unpack"),
+                       k=last_conv.kernel_size[0], cin=last_conv.in_channels, cout=last_conv.out_channels, groups=last_conv.groups, pool=0, out_order="identity", table_bytes=0,
                        act_bytes_in=blocked(last_conv.in_channels, H, W) + 4 * last_conv.in_channels * H * W, act_bytes_out=4 * last_conv.out_channels * H * W))
     if byte_ends:
         # the last block: the hidden kernel's contraction, stopped at r and written as the fp32 map of the tail (mn_i8conv_fwd_f32)
@@ -1270,7 +1296,7 @@ def _walk_iao8(model, input_hw=(32, 32), byte_ends=False):
     return first, layers, last, tail, flatten, report, pack_shuffle, ends
 
 
-def iao_int8_report(model, input_hw=(32, 32), byte_ends=False):
+def iao_int8_report(model, input_hw=(32, 32), byte_ends=False, zero_points=False):
     """The ``report`` ``iao_compile_int8(model, byte_ends)`` would carry -- one row per stage: layer, kernel, geometry, folded pool, the consumer's shuffle folded into
     the stage (``out_order``), table bytes and the activation bytes per image the stage reads and writes at an ``input_hw`` input -- from the graph walk alone: no GPU,
     nothing packed.  With ``byte_ends`` the two end rows are the kinds ``int8_first`` / ``int8_last`` and no fp32 map stands between the rows.  Raises like
@@ -1278,10 +1304,19 @@ def iao_int8_report(model, input_hw=(32, 32), byte_ends=False):
 
     The reference ResNet tree takes the walk of ``_walk_iao8_res``: one row per conv -- kind ``int8`` (a conv stage) or ``int8_add`` (the last conv of a block with its
     QuantAdd), between ``first`` (conv1 and its packs) and ``last`` (the unpack, avg_pool, fc) -- with kernel, geometry, ``stride``, ``relu``, ``shortcut``, the number
-    of output maps ``nout`` and their ``consumers``, table bytes and activation bytes in and out per image."""
+    of output maps ``nout`` and their ``consumers``, table bytes and activation bytes in and out per image.
+
+    ``zero_points=True``: the walk of ``iao_compile_int8(model, zero_points=True)``: a stage with an asymmetric quantizer reports ``k_i8zconv<KS,pool>``, and the two
+    end rows name ``k_i8z_pack`` / ``k_i8z_unpack`` where their quantizer is asymmetric; a symmetric net reports as without it."""
     if _is_ref_resnet(model):
+        if zero_points:
+            raise _err(_ZP_RESNET)
         return _walk_iao8_res(model, input_hw, byte_ends)[4]
-    return _walk_iao8(model, input_hw, byte_ends)[5]
+    return _walk_iao8(model, input_hw, byte_ends, zero_points)[5]
+
+
+_ZP_RESNET = ("iao_compile_int8(zero_points=True): the reference ResNet tree is not covered with zero points (its strided and QuantAdd stages take symmetric "
+              "quantizers only)")
 
 
 class Int8Plan(_Plan):
@@ -1289,6 +1324,11 @@ class Int8Plan(_Plan):
     block (2x2 max-pool and the consumer's channel shuffle folded in) -> ``mn_i8_unpack_codes`` at the last conv's scale -> the model's own last block and tail (its
     quantizer reproduces the same codes: fl(fl(c s) / s) rounds back to c).  Eval only; owns the packed weight tables and one set of byte buffers per input shape.
     ``layers[i]`` keeps what the table was packed from (w, s_w, bias, s_a, s_p, s_out, a_bits, w_bits, pool, shuffle) for the tests' judge.
+
+    A plan compiled with ``zero_points=True`` runs a stage with an asymmetric quantizer on ``mn_i8zconv_fwd`` (``layers[i]["zp"]``; bytes are code - h, see
+    ``csrc/qgemm_iao8_zp.h``), packs with ``mn_i8z_pack_codes`` and unpacks with ``mn_i8z_unpack_codes`` where that end's quantizer is asymmetric (``pack["q"]``,
+    ``pack["unpack_q"]``), and ``layers[i]`` additionally keeps the zero points ``z_a``, ``z_w`` (a tensor like ``s_w``), ``z_p``, ``z_out`` and the flags ``asym_a``,
+    ``asym_w``, ``asym_p``, ``asym_out``.
 
     With ``byte_ends`` (``ends`` is set) neither end runs the model's own modules: ``mn_i8first_fwd`` takes the fp32 image to the first hidden block's codes, the hidden
     stages run unchanged, ``mn_i8conv_fwd_f32`` takes the last hidden codes to the fp32 map [N][O][H * W] of the model's tail: no ``k_i8_pack``, no ``k_i8_unpack``
@@ -1383,8 +1423,13 @@ class Int8Plan(_Plan):
         Ho, Wo = (H // 2, W // 2) if L["pool"] else (H, W)
         out = torch.full((N, (L["cout"] + 15) // 16, Ho * Wo, 16), 77, dtype=torch.int8, device=codes.device)
         with torch.cuda.device(codes.device):
-            ops._call("mn_i8conv_fwd", C.byref(g), L["a_bits"], L["w_bits"], ops._p(L["table"]), ops._p(codes), ops._p(out), int(L["pool"]), ops._s())
+            ops._call(self._stage_entry(L), C.byref(g), L["a_bits"], L["w_bits"], ops._p(L["table"]), ops._p(codes), ops._p(out), int(L["pool"]), ops._s())
         return out
+
+    @staticmethod
+    def _stage_entry(L):
+        """The forward of a hidden stage: the zero-point kernels where one of its quantizers is asymmetric."""
+        return "mn_i8zconv_fwd" if L.get("zp") else "mn_i8conv_fwd"
 
     @torch.no_grad()
     def forward(self, x):
@@ -1400,18 +1445,24 @@ class Int8Plan(_Plan):
         with torch.cuda.device(a.device):
             bufs, geoms, y = self._shape_buffers(a.shape, a.device)
             st = ops._s()
-            ops._call("mn_i8_pack_codes", ops._p(a), N, Cc, H * W, self.pack["s"], self.pack["a_bits"], ops._p(self.pack["order"]), ops._p(bufs[0]), st)
+            if self.pack.get("q") is not None:
+                ops._call("mn_i8z_pack_codes", ops._p(a), N, Cc, H * W, C.byref(self.pack["q"]), ops._p(self.pack["order"]), ops._p(bufs[0]), st)
+            else:
+                ops._call("mn_i8_pack_codes", ops._p(a), N, Cc, H * W, self.pack["s"], self.pack["a_bits"], ops._p(self.pack["order"]), ops._p(bufs[0]), st)
             for i, L in enumerate(self.layers):
-                ops._call("mn_i8conv_fwd", C.byref(geoms[i]), L["a_bits"], L["w_bits"], ops._p(L["table"]), ops._p(bufs[i]), ops._p(bufs[i + 1]), int(L["pool"]), st)
+                ops._call(self._stage_entry(L), C.byref(geoms[i]), L["a_bits"], L["w_bits"], ops._p(L["table"]), ops._p(bufs[i]), ops._p(bufs[i + 1]), int(L["pool"]), st)
             if self.keep_stages:
                 self.stage_codes = [b.clone() for b in bufs]
             n_, c_, h_, w_ = y.shape
-            ops._call("mn_i8_unpack_codes", ops._p(bufs[-1]), n_, c_, h_ * w_, self.layers[-1]["s_out"], ops._p(y), st)
+            if self.pack.get("unpack_q") is not None:
+                ops._call("mn_i8z_unpack_codes", ops._p(bufs[-1]), n_, c_, h_ * w_, C.byref(self.pack["unpack_q"]), ops._p(y), st)
+            else:
+                ops._call("mn_i8_unpack_codes", ops._p(bufs[-1]), n_, c_, h_ * w_, self.layers[-1]["s_out"], ops._p(y), st)
         return self._finish(self.last(y))
 
 
 @torch.no_grad()
-def iao_compile_int8(model, byte_ends=False):
+def iao_compile_int8(model, byte_ends=False, zero_points=False):
     """``model``: the result of ``iao_model_bn_fuse`` + ``prequantize_weights`` on a symmetric IAO net, on the GPU (the reference's ``nin_gc``, or an ``nn.Sequential``
     of its block kinds).  Returns an ``Int8Plan`` that keeps every hidden activation as one int8 code and contracts on v_mfma_i32_16x16x64_i8
     (``csrc/qgemm_iao8.h``); the two ends stay on the model's own modules.  ``.report`` lists the stages.  Scales are read from the quantizer buffers and the table
@@ -1426,15 +1477,25 @@ def iao_compile_int8(model, byte_ends=False):
 
     The reference ResNet tree (BasicBlock and BottleNeck nets, ``bn_fuse=True``, folded and pre-quantised) returns an ``Int8ResPlan``: strided convs, shortcut convs
     and the QuantAdd run on byte codes (``csrc/qgemm_iao8_res.h``), every block output is written once per consumer quantizer, and conv1, avg_pool and fc stay on the
-    model's own modules.  ``byte_ends=True`` raises for it."""
+    model's own modules.  ``byte_ends=True`` raises for it.
+
+    ``zero_points=True``: a net prepared with ``q_type=1`` compiles as well.  Asymmetric quantizers (``AsymmetricQuantizer``, 2 .. 8 bits, an activation quantizer with
+    a single zero point, a weight quantizer with as many zero points as scales) are admitted; a hidden stage any of whose four quantizers -- input activation, weight,
+    pool, consumer -- is asymmetric runs on ``mn_i8zconv_fwd`` (``csrc/qgemm_iao8_zp.h``: bytes are code - h, the zero points enter as integer offsets of an exact
+    int32 sum), every other stage on ``mn_i8conv_fwd`` as before, and a symmetric net gives the plan and report it gives without the keyword.  The table counters
+    additionally refuse, naming the layer: a zero point that is not an integer of magnitude <= 65535, a sum that would not fit int32, and a 3x3 stage whose input
+    quantizer has no code for the value 0 ("zero padding has no byte").  Not covered, each raising: together with ``byte_ends=True``; the reference ResNet tree."""
     import ctypes as C
-    from micronet_amd import ops
+    from micronet_amd import _lib, ops
     if _is_ref_resnet(model):
+        if zero_points:
+            raise _err(_ZP_RESNET)
         return _compile_iao8_res(model, byte_ends)
     who = "iao_compile_int8(byte_ends=True)" if byte_ends else "iao_compile_int8"
-    first, layers, last, tail, flatten, report, pack_shuffle, ends = _walk_iao8(model, byte_ends=byte_ends)
+    first, layers, last, tail, flatten, report, pack_shuffle, ends = _walk_iao8(model, byte_ends=byte_ends, zero_points=zero_points)
     _require_gpu(model, "iao_compile_int8")
     scale = lambda q: float(q.scale.detach().float().reshape(-1)[0])          # (compile time: the one place a host read-back is allowed)
+    zero = lambda q: float(q.zero_point.detach().float().reshape(-1)[0])
     dev = layers[0]["conv"].weight.device
 
     def packed_from(L, conv):
@@ -1442,6 +1503,8 @@ def iao_compile_int8(model, byte_ends=False):
         L["s_w"] = conv.weight_quantizer.scale.detach().float().reshape(-1).contiguous()
         L["bias"] = conv.bias.detach().float().contiguous() if conv.bias is not None else None
         L["s_a"] = scale(conv.activation_quantizer)
+        L["z_a"] = zero(conv.activation_quantizer)
+        L["z_w"] = conv.weight_quantizer.zero_point.detach().float().reshape(-1).contiguous()
         L["out_order"] = _shuffle_order(L["cout"], L["shuffle"], dev) if L["shuffle"] else None
         L["table"] = torch.empty(L["table_bytes"] // 4, dtype=torch.int32, device=dev)
 
@@ -1459,18 +1522,38 @@ def iao_compile_int8(model, byte_ends=False):
         for L in layers:
             conv, pool_m = L.pop("conv"), L.pop("pool_module")
             packed_from(L, conv)
-            L["s_out"] = scale(L.pop("consumer"))
-            L["s_p"] = scale(pool_m.activation_quantizer) if pool_m is not None else L["s_out"]
-            ops._call("mn_i8conv_pack", C.byref(_block_geom(L)), ops._p(L["w"]), ops._p(L["s_w"]), 1 if L["per_channel"] else 0, ops._p(L["bias"]), L["s_a"], L["s_p"],
-                      L["s_out"], L["a_bits"], L["w_bits"], ops._p(L["out_order"]), ops._p(L["table"]), ops._s())
+            consumer = L.pop("consumer")
+            L["s_out"], L["z_out"] = scale(consumer), zero(consumer)
+            L["s_p"], L["z_p"] = (scale(pool_m.activation_quantizer), zero(pool_m.activation_quantizer)) if pool_m is not None else (L["s_out"], L["z_out"])
+            if L["zp"]:
+                qa, qp, qo = (_lib.I8ZQuant(L["s_a"], L["z_a"], L["asym_a"], L["in_bits"]), _lib.I8ZQuant(L["s_p"], L["z_p"], L["asym_p"], L["a_bits"]),
+                              _lib.I8ZQuant(L["s_out"], L["z_out"], L["asym_out"], L["a_bits"]))
+                ops._call("mn_i8zconv_pack", C.byref(_block_geom(L)), ops._p(L["w"]), ops._p(L["s_w"]), ops._p(L["z_w"]), 1 if L["per_channel"] else 0, ops._p(L["bias"]),
+                          C.byref(qa), C.byref(qp), C.byref(qo), L["asym_w"], L["w_bits"], ops._p(L["out_order"]), ops._p(L["table"]), ops._s())
+            else:
+                ops._call("mn_i8conv_pack", C.byref(_block_geom(L)), ops._p(L["w"]), ops._p(L["s_w"]), 1 if L["per_channel"] else 0, ops._p(L["bias"]), L["s_a"], L["s_p"],
+                          L["s_out"], L["a_bits"], L["w_bits"], ops._p(L["out_order"]), ops._p(L["table"]), ops._s())
         packed = ([ends[0]] if ends else []) + layers + ([ends[1]] if ends else [])
-        counters = torch.stack([L["table"][[0, 7]] for L in packed]).tolist()
-    for L, (bad, off) in zip(packed, counters):
+        # (words 13 .. 15 are counters of the zero-point tables alone; the others' headers hold 0 there)
+        counters = torch.stack([L["table"][[0, 7, 13, 14, 15]] for L in packed]).tolist()
+    for L, (bad, off, zbad, wide, nopad) in zip(packed, counters):
         if bad:
             raise _err("%s: %s.conv: %d rows or scales with a non-finite or non-positive constant (al, bias, s_w, s_a, s_p, s_out)" % (who, L["name"], bad))
+        if L.get("zp") and zbad:
+            raise _err("%s: %s.conv: %d zero points (of the input, pool and consumer quantizers and the rows' z_w) that are not integers of magnitude <= 65535"
+                       % (who, L["name"], zbad))
         if off:
             raise _err("%s: %s.conv: %d rows whose stored weights are off the grid k * s_w (run prequantize_weights after iao_model_bn_fuse)" % (who, L["name"], off))
+        if L.get("zp") and wide:
+            raise _err("%s: %s.conv: %d rows whose sum over %d channels x %d taps does not fit int32 at these zero points" % (who, L["name"], wide, L["cin"] // L["groups"],
+                                                                                                                     L["k"] * L["k"]))
+        if L.get("zp") and nopad:
+            raise _err("%s: %s.conv: zero padding has no byte: the value 0 is not a code of the input quantizer (zero point %g) of this 3x3 stage" % (who, L["name"], L["z_a"]))
     pack = dict(s=layers[0]["s_a"], a_bits=layers[0]["in_bits"], order=_shuffle_order(layers[0]["cin"], pack_shuffle, dev) if pack_shuffle else None)
+    if layers[0].get("asym_a"):
+        pack["q"] = _lib.I8ZQuant(layers[0]["s_a"], layers[0]["z_a"], 1, layers[0]["in_bits"])
+    if layers[-1].get("asym_out"):
+        pack["unpack_q"] = _lib.I8ZQuant(layers[-1]["s_out"], layers[-1]["z_out"], 1, layers[-1]["a_bits"])
     return Int8Plan(first, layers, last, tail, flatten, report, pack, ends)
 
 

@@ -15,7 +15,14 @@ yardstick is ``P`` in the same run (``E_over_P``), and its per-kernel times stan
     python scripts/kbench_iao8.py --resnet18 [...] [--out profiles/iao8_resnet_inference.json]
 
 runs the same comparison on a BN-folded IAO W8A8 resnet18: ``F`` writes and re-reads an fp32 map around every conv, ReLU and QuantAdd, ``P`` keeps byte codes from the
-pack behind conv1 to the unpack in front of avg_pool (strided convs, shortcut convs and the QuantAdd on bytes: csrc/qgemm_iao8_res.h)."""
+pack behind conv1 to the unpack in front of avg_pool (strided convs, shortcut convs and the QuantAdd on bytes: csrc/qgemm_iao8_res.h).
+
+    python scripts/kbench_iao8.py --asym [...] [--out profiles/iao8_zp_inference.json]
+
+prepares nin_gc with ``q_type=1`` (asymmetric quantizers) and compiles it with ``zero_points=True`` (csrc/qgemm_iao8_zp.h): ``F`` is that net's own eval-mode folded
+model.  The symmetric net's plan is compiled in the same process as well and its kernels profiled once per batch (``S_kernels``), so that k_i8zconv stands beside
+k_i8conv on the same geometry under the same clocks (``zconv_over_conv_us``).  That second net is trained and compiled for this comparison alone: neither its plan
+nor its folded model is timed end to end (the symmetric P / F stands in profiles/iao8_inference.json)."""
 import argparse
 import importlib
 import json
@@ -89,31 +96,44 @@ def main():
     ap.add_argument("--resnet18", action="store_true", help="the BN-folded IAO W8A8 resnet18 instead of nin_gc (no --byte-ends: not built for ResNets)")
     ap.add_argument("--out", default=None, help="default: profiles/iao8_inference.json, with --byte-ends profiles/iao8_ends_inference.json, with --resnet18 "
                                                 "profiles/iao8_resnet_inference.json")
+    ap.add_argument("--asym", action="store_true", help="nin_gc prepared with q_type=1, compiled with zero_points=True (no --byte-ends, no --resnet18: not built)")
     args = ap.parse_args()
     if args.resnet18 and args.byte_ends:
         ap.error("--resnet18 and --byte-ends exclude each other")
-    args.out = args.out or os.path.join("profiles", "iao8_resnet_inference.json" if args.resnet18 else "iao8_ends_inference.json" if args.byte_ends else "iao8_inference.json")
+    if args.asym and (args.resnet18 or args.byte_ends):
+        ap.error("--asym excludes --resnet18 and --byte-ends")
+    args.out = args.out or os.path.join("profiles", "iao8_zp_inference.json" if args.asym else "iao8_resnet_inference.json" if args.resnet18 else
+                                        "iao8_ends_inference.json" if args.byte_ends else "iao8_inference.json")
     arch = "resnet18" if args.resnet18 else "nin_gc"
     from micronet_amd import _lib, inference
     from micronet_amd.train import build_model, make_optimizer, synth_batch, train_step
     Q = importlib.import_module("micronet.compression.quantization.wqaq.iao.quantize")
-    # two training steps give the observers a range and the scales a meaning; then the fold and the pre-quantisation
-    T = Q.prepare(build_model(arch), inplace=True, a_bits=8, w_bits=8, q_type=0, q_level=0, weight_observer=0, bn_fuse=True).cuda().train()
-    opt = make_optimizer(T, 0.01, 1e-5)
-    xt, yt = synth_batch(32, device="cuda")
-    for _ in range(2):
-        train_step(T, opt, xt, yt)
-    T.eval()
-    F = inference.iao_model_bn_fuse(T)
-    inference.prequantize_weights(F)
-    F.eval()
-    P = inference.iao_compile_int8(F)
+
+    def folded(q_type):
+        # two training steps give the observers a range and the scales a meaning; then the fold and the pre-quantisation
+        T = Q.prepare(build_model(arch), inplace=True, a_bits=8, w_bits=8, q_type=q_type, q_level=0, weight_observer=0, bn_fuse=True).cuda().train()
+        opt = make_optimizer(T, 0.01, 1e-5)
+        xt, yt = synth_batch(32, device="cuda")
+        for _ in range(2):
+            train_step(T, opt, xt, yt)
+        T.eval()
+        Fm = inference.iao_model_bn_fuse(T)
+        inference.prequantize_weights(Fm)
+        return Fm.eval()
+
+    F = folded(1 if args.asym else 0)
+    P = inference.iao_compile_int8(F, zero_points=True) if args.asym else inference.iao_compile_int8(F)
     E = inference.iao_compile_int8(F, byte_ends=True) if args.byte_ends else None
+    S = inference.iao_compile_int8(folded(0)) if args.asym else None          # the symmetric plan: its kernels on the same geometries, under the same clocks
     lib = _lib.get_lib()
     res = dict(model=arch, a_bits=8, w_bits=8, warmup=args.warmup, iters=args.iters, device=torch.cuda.get_device_name(0), report=P.report,
                designed_bytes_per_image=(designed_bytes_per_image_resnet if args.resnet18 else designed_bytes_per_image)(P), batches={})
     if E is not None:
         res["ends_report"] = E.report
+    if S is not None:
+        res["q_type"] = 1
+        res["zero_points"] = [dict(name=L["name"], z_a=L["z_a"], z_out=L["z_out"], z_p=L["z_p"], z_w_min=float(L["z_w"].min()), z_w_max=float(L["z_w"].max()))
+                              for L in P.layers]
     with torch.no_grad():
         for bs in [int(v) for v in args.batches.split(",")]:
             x, _ = synth_batch(bs, device="cuda")
@@ -139,6 +159,15 @@ def main():
             print("batch %d: F %.3f ms (min %.3f)  P %.3f ms (min %.3f)  speed %.2fx  max|P-F|/max|F| %.2e" % (bs, mf, min(tf), mp, min(tp), mf / mp,
                                                                                                            res["batches"][str(bs)]["max_abs_diff_over_max_F"]), flush=True)
             print("  P kernels (us per launch):", {n: v["us_per_launch"] for n, v in kp.items()}, flush=True)
+            if S is not None:
+                for _ in range(args.warmup):
+                    S(x)
+                ks = profile(lib, _lib, S, x)
+                pairs = {n: dict(zconv_us=v["us_per_launch"], conv_us=ks[n.replace("k_i8zconv", "k_i8conv")]["us_per_launch"],
+                                 ratio=v["us_per_launch"] / ks[n.replace("k_i8zconv", "k_i8conv")]["us_per_launch"])
+                         for n, v in kp.items() if n.startswith("k_i8zconv<") and n.replace("k_i8zconv", "k_i8conv") in ks}
+                res["batches"][str(bs)].update(S_kernel_ms_total=sum(v["ms"] for v in ks.values()), S_kernels=ks, zconv_over_conv_us=pairs)
+                print("  k_i8zconv against k_i8conv (us per launch, same geometry):", {n: (v["zconv_us"], v["conv_us"]) for n, v in pairs.items()}, flush=True)
             if E is not None:
                 ke, me = profile(lib, _lib, E, x), statistics.median(te)
                 res["batches"][str(bs)].update(E_ms=q(te), E_img_s=bs / me * 1e3, E_over_P=mp / me, E_over_F=mf / me,
