@@ -1183,6 +1183,42 @@ int mn_i8res_conv_fwd(const mn_conv_geom* g, int in_bits, int out_bits, int w_bi
 int mn_i8res_add_fwd(const mn_conv_geom* g, int in_bits, int w_bits, const uint32_t* table, const int8_t* in_codes, const int8_t* shortcut_codes, const mn_i8res_add* q,
                      int8_t* out_a, int8_t* out_b, mn_stream_t stream);
 
+/* The two ends of the int8 deployment of BN-folded IAO ResNets (csrc/qgemm_iao8_e2e.h): the first conv writes one code map per consumer quantizer of its output, the
+ * classifier -- QuantAdaptiveAvgPool2d((1, 1)) + QuantLinear -- reads the last block's codes and writes the fp32 logits.  Q(v; s, a) as for mn_i8res_*.
+ * First block (mn_i8first_fwd2): mn_i8first_fwd's contract bit for bit up to r = max(y, 0); then out_a = Q(r; s_out0, bits0) and, with nout == 2,
+ * out_b = Q(r; s_out1, bits1), each [N][ceil(O/16)][H*W][16].  `table` is mn_i8first_pack's, packed with s_out = s_out0, a_bits = bits0 (al and b do not depend on
+ * the consumer; its words 8 .. 11 are not read); the output quantizers are read from *q on the host at the call and handed to the kernel by value.  With nout == 1
+ * the bytes are mn_i8first_fwd's.  MN_ENOTSUP where mn_i8first_supported refuses; a null or misaligned tensor (x 4-byte, codes and `table` 16-byte aligned), an invalid
+ * geometry, nout outside 1 / 2 or not matching out_b, a scale that is not finite and positive, a width outside 2 .. 8, or an output that overlaps x, the table or
+ * the other output is MN_EINVAL; nothing is written in either case.  Every 16-byte block is stored once and whole: no atomics, no read-modify-write; positions >= O
+ * are 0.  mn_last_kernel(): k_i8first2<KS,nout>.
+ * Pooled classifier (mn_i8poolfc_*): in_codes c [N][ceil(C/16)][HW][16] at avg_pool's scale s_p (width p_bits);
+ *   m[n, ch] = (float)(sum_p (double)fl(float(c) * s_p) / (double)HW)   (mn_iao_fq_avgpool_fwd with k = H = W on the de-quantised map; the double sum is exact)
+ *   j = Q(m; s_fc, a_bits); acc[n, o] = sum_ch j k[o, ch], k = rint(w / s_w[o]), exact in int32; y[n, o] = fl(fl(float(acc) * al[o]) + b[o]), al = fl(s_fc * s_w[o]),
+ * a null bias 0 -> y fp32 [N][O], each element stored once.  Covered (mn_i8poolfc_supported): 1 <= O <= 64, 1 <= HW <= 4096, 2 <= p_bits, a_bits, w_bits <= 8,
+ * C * 2^(a_bits-1) * (2^(w_bits-1) - 1) <= INT_MAX, N * ceil(C/16) * HW <= 2^40; everything else is MN_ENOTSUP; a null or misaligned tensor (y 4-byte, codes and
+ * `table` 16-byte aligned), N, C, HW or O <= 0, s_w_stride outside 0 / 1 or an output that overlaps the input or the table is MN_EINVAL; nothing is written in either
+ * case.  No entry allocates.
+ *   pack : w [O][C] on the grid k * s_w, s_w[o * s_w_stride] (s_w_stride 1 / 0), bias [O] or null -> `table` (private layout, mn_i8poolfc_table_bytes bytes).  Word 0
+ *          counts the rows with a non-finite al or b or a bad s_w plus each of s_p, s_fc that is non-finite or <= 0, word 7 the rows with a weight off the grid
+ *          (|w / s_w - rint| > 1e-3) or beyond 2^(w-1) - 1: a table with either non-zero must not be used.  Word 6 = a_bits | w_bits << 8 | p_bits << 16.
+ *   fwd  : mn_last_kernel(): k_i8poolfc. */
+typedef struct mn_i8first_outs {
+    int32_t nout;          /* 1 or 2 output maps */
+    float s_out0;
+    int32_t bits0;
+    float s_out1;          /* read with nout == 2 */
+    int32_t bits1;
+} mn_i8first_outs;
+int mn_i8first_fwd2(const mn_conv_geom* g, int in_bits, int w_bits, const uint32_t* table, const float* x, const mn_i8first_outs* q, int8_t* out_a, int8_t* out_b,
+                    mn_stream_t stream);
+int mn_i8poolfc_supported(int64_t N, int64_t C, int64_t HW, int64_t O, int p_bits, int a_bits, int w_bits);
+int64_t mn_i8poolfc_table_bytes(int64_t C, int64_t O, int p_bits, int a_bits, int w_bits);
+int mn_i8poolfc_pack(int64_t C, int64_t O, const float* w, const float* s_w, int s_w_stride, const float* bias, float s_p, float s_fc, int p_bits, int a_bits, int w_bits,
+                     uint32_t* table, mn_stream_t stream);
+int mn_i8poolfc_fwd(int64_t N, int64_t C, int64_t HW, int64_t O, int p_bits, int a_bits, int w_bits, const uint32_t* table, const int8_t* in_codes, float* y,
+                    mn_stream_t stream);
+
 /* The hidden blocks of the int8 deployment with ZERO POINTS (csrc/qgemm_iao8_zp.h): the stage of mn_i8conv_fwd where any of its quantizers is asymmetric.  A
  * quantizer is (s, z, asym, bits); its code range [lo, hi] is -2^(b-1) .. 2^(b-1) - 1 (symmetric activation), +-(2^(b-1) - 1) (symmetric weight), 0 .. 2^b - 1
  * (asymmetric activation), 0 .. 2^b - 2 (asymmetric weight); code(r; s, z) = clamp(rha(fl(fl(r / s) - z)), lo, hi) and the value of a code c is fl(fl(c + z) * s).

@@ -41,13 +41,17 @@ class I8ResAdd(C.Structure):
     """mn_i8res_add: the quantizers of the add stage of the int8 ResNet deployment."""
 
 
+class I8FirstOuts(C.Structure):
+    """mn_i8first_outs: the output quantizers of the two-output first block of the int8 ResNet deployment."""
+
+
 class I8ZQuant(C.Structure):
     """mn_i8z_quant: one quantizer (scale, zero point, asymmetric flag, bits) of the int8 deployment with zero points."""
 
 
 # C struct name -> class: the one thing stated here and not read from the header (the classes get their _fields_ below)
 STRUCTS = {"mn_conv_geom": ConvGeom, "mn_actq": ActQ, "mn_wq": WQ, "mn_prof_entry": ProfEntry, "mn_adam_tensor": AdamTensor, "mn_i8res_add": I8ResAdd,
-           "mn_i8z_quant": I8ZQuant}
+           "mn_i8z_quant": I8ZQuant, "mn_i8first_outs": I8FirstOuts}
 
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double}
 _RETURNS = dict(_SCALARS, **{"void": None, "const char*": C.c_char_p})

@@ -763,3 +763,4 @@ extern "C" int mn_bits_maxpool(const uint32_t* bits_in, int64_t N, int64_t Cw, i
 #include "qgemm_iao8_zp.h"        // mn_i8zconv_* / mn_i8z_*: the same blocks with zero points (asymmetric quantizers)
 #include "qgemm_iao8_ends.h"      // mn_i8first_* / mn_i8conv_fwd_f32: the two ends of that deployment (fp32 image in, fp32 map out)
 #include "qgemm_iao8_res.h"       // mn_i8res_*: the residual stages of that deployment (strided convs, QuantAdd on bytes)
+#include "qgemm_iao8_e2e.h"       // mn_i8first_fwd2 / mn_i8poolfc_*: a ResNet's two ends (two-output first conv, pooled classifier on bytes)

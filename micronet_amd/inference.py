@@ -1296,7 +1296,7 @@ def _walk_iao8(model, input_hw=(32, 32), byte_ends=False, zero_points=False):
     return first, layers, last, tail, flatten, report, pack_shuffle, ends
 
 
-def iao_int8_report(model, input_hw=(32, 32), byte_ends=False, zero_points=False):
+def iao_int8_report(model, input_hw=(32, 32), byte_ends=False, zero_points=False, end_to_end=False):
     """The ``report`` ``iao_compile_int8(model, byte_ends)`` would carry -- one row per stage: layer, kernel, geometry, folded pool, the consumer's shuffle folded into
     the stage (``out_order``), table bytes and the activation bytes per image the stage reads and writes at an ``input_hw`` input -- from the graph walk alone: no GPU,
     nothing packed.  With ``byte_ends`` the two end rows are the kinds ``int8_first`` / ``int8_last`` and no fp32 map stands between the rows.  Raises like
@@ -1307,14 +1307,22 @@ def iao_int8_report(model, input_hw=(32, 32), byte_ends=False, zero_points=False
     of output maps ``nout`` and their ``consumers``, table bytes and activation bytes in and out per image.
 
     ``zero_points=True``: the walk of ``iao_compile_int8(model, zero_points=True)``: a stage with an asymmetric quantizer reports ``k_i8zconv<KS,pool>``, and the two
-    end rows name ``k_i8z_pack`` / ``k_i8z_unpack`` where their quantizer is asymmetric; a symmetric net reports as without it."""
+    end rows name ``k_i8z_pack`` / ``k_i8z_unpack`` where their quantizer is asymmetric; a symmetric net reports as without it.
+
+    ``end_to_end=True`` (the reference ResNet tree only): the walk of ``iao_compile_int8(model, end_to_end=True)``: row 0 is the kind ``int8_first`` on
+    ``k_i8first2<KS,nout>``, the last row the kind ``int8_last`` on ``k_i8poolfc``, both with table bytes and activation bytes (fp32 image in, ``nout`` byte maps out;
+    bytes in, 4 O out); every row between them is the default report's."""
     if _is_ref_resnet(model):
         if zero_points:
             raise _err(_ZP_RESNET)
-        return _walk_iao8_res(model, input_hw, byte_ends)[4]
-    return _walk_iao8(model, input_hw, byte_ends, zero_points)[5]
+        return _walk_iao8_res(model, input_hw, byte_ends, end_to_end)[4]
+    report = _walk_iao8(model, input_hw, byte_ends, zero_points)[5]
+    if end_to_end:
+        raise _err(_E2E_RESNET)
+    return report
 
 
+_E2E_RESNET = "iao_compile_int8(end_to_end=True): covered for the reference ResNet tree only (nin_gc's form is byte_ends=True)"
 _ZP_RESNET = ("iao_compile_int8(zero_points=True): the reference ResNet tree is not covered with zero points (its strided and QuantAdd stages take symmetric "
               "quantizers only)")
 
@@ -1462,7 +1470,7 @@ class Int8Plan(_Plan):
 
 
 @torch.no_grad()
-def iao_compile_int8(model, byte_ends=False, zero_points=False):
+def iao_compile_int8(model, byte_ends=False, zero_points=False, end_to_end=False):
     """``model``: the result of ``iao_model_bn_fuse`` + ``prequantize_weights`` on a symmetric IAO net, on the GPU (the reference's ``nin_gc``, or an ``nn.Sequential``
     of its block kinds).  Returns an ``Int8Plan`` that keeps every hidden activation as one int8 code and contracts on v_mfma_i32_16x16x64_i8
     (``csrc/qgemm_iao8.h``); the two ends stay on the model's own modules.  ``.report`` lists the stages.  Scales are read from the quantizer buffers and the table
@@ -1479,6 +1487,14 @@ def iao_compile_int8(model, byte_ends=False, zero_points=False):
     and the QuantAdd run on byte codes (``csrc/qgemm_iao8_res.h``), every block output is written once per consumer quantizer, and conv1, avg_pool and fc stay on the
     model's own modules.  ``byte_ends=True`` raises for it.
 
+    ``end_to_end=True`` (the reference ResNet tree only; every other model raises, nin_gc's form being ``byte_ends=True``): the two ends of the ``Int8ResPlan`` run
+    on bytes as well (``csrc/qgemm_iao8_e2e.h``).  ``mn_i8first_fwd2`` takes the fp32 image through conv1 to one code map per consumer quantizer, the stages run
+    unchanged, ``mn_i8poolfc_fwd`` takes the last block's codes through avg_pool and fc to the fp32 logits: no fp32 activation map, no pack, no unpack.  conv1 must
+    be a BN-folded ``quant_inference`` ``QuantConv2d`` with ReLU, a symmetric single-scale activation quantizer and a geometry ``mn_i8first_supported`` covers (3x3
+    or 5x5, stride 1), avg_pool a ``QuantAdaptiveAvgPool2d`` to 1 x 1, fc a ``quant_inference`` ``QuantLinear`` (set ``model.fc.quant_inference = True`` before
+    ``prequantize_weights``: ``iao_model_bn_fuse`` marks the convs only) with symmetric quantizers that ``mn_i8poolfc_supported`` covers (at most 64 outputs); every refusal raises ``iao_compile_int8(end_to_end=True): <layer>: <rule>``.  Together with ``byte_ends``
+    or ``zero_points`` the message of that keyword wins.
+
     ``zero_points=True``: a net prepared with ``q_type=1`` compiles as well.  Asymmetric quantizers (``AsymmetricQuantizer``, 2 .. 8 bits, an activation quantizer with
     a single zero point, a weight quantizer with as many zero points as scales) are admitted; a hidden stage any of whose four quantizers -- input activation, weight,
     pool, consumer -- is asymmetric runs on ``mn_i8zconv_fwd`` (``csrc/qgemm_iao8_zp.h``: bytes are code - h, the zero points enter as integer offsets of an exact
@@ -1490,9 +1506,11 @@ def iao_compile_int8(model, byte_ends=False, zero_points=False):
     if _is_ref_resnet(model):
         if zero_points:
             raise _err(_ZP_RESNET)
-        return _compile_iao8_res(model, byte_ends)
+        return _compile_iao8_res(model, byte_ends, end_to_end)
     who = "iao_compile_int8(byte_ends=True)" if byte_ends else "iao_compile_int8"
     first, layers, last, tail, flatten, report, pack_shuffle, ends = _walk_iao8(model, byte_ends=byte_ends, zero_points=zero_points)
+    if end_to_end:
+        raise _err(_E2E_RESNET)
     _require_gpu(model, "iao_compile_int8")
     scale = lambda q: float(q.scale.detach().float().reshape(-1)[0])          # (compile time: the one place a host read-back is allowed)
     zero = lambda q: float(q.zero_point.detach().float().reshape(-1)[0])
@@ -1574,8 +1592,10 @@ def _res_geom(L, N=1, H=4, W=4):
     return _lib.ConvGeom(N, L["cin"], H, W, L["cout"], L["k"], L["k"], L["stride"], L["stride"], L["pad"], L["pad"], 1, 1, 1, 0)
 
 
-def _walk_iao8_res(model, input_hw=(32, 32), byte_ends=False):
-    """The graph walk of ``iao_compile_int8`` on the reference ResNet tree (no GPU needed): (stem, stages, buffers, tail quantizer, report).
+def _walk_iao8_res(model, input_hw=(32, 32), byte_ends=False, end_to_end=False):
+    """The graph walk of ``iao_compile_int8`` on the reference ResNet tree (no GPU needed): (stem, stages, buffers, tail quantizer, report).  ``end_to_end``: conv1,
+    avg_pool and fc are held to the rules of the byte ends (csrc/qgemm_iao8_e2e.h), ``stem["ends"]`` = (first, last) are their layer dicts and the two end rows of the
+    report are the kinds ``int8_first`` / ``int8_last``.
 
     A VALUE -- conv1's output, or a block's output v = relu(add) -- has up to two consumers with a quantizer each: the next block's first conv, and the next block's
     shortcut (its QuantAdd itself for an identity shortcut, else the shortcut conv's activation quantizer).  Its producer writes one code map per consumer quantizer
@@ -1719,6 +1739,51 @@ def _walk_iao8_res(model, input_hw=(32, 32), byte_ends=False):
                            act_bytes_out=len(st["outs"]) * blocked(st["cout"], Ho, Wo)))
     Hl, Wl = dims[cur["outs"][0]["buf"]]
     fc_out = getattr(model.fc, "out_features", 0)
+    if end_to_end:
+        who2 = "iao_compile_int8(end_to_end=True)"
+
+        def held(layer, rule, *a):
+            """``rule(*a)`` with its refusal re-raised as who2: <layer>: <rule>."""
+            try:
+                return rule(*a)
+            except _lib.MicronetHipError as e:
+                raise _err("%s: %s: %s" % (who2, layer, str(e).split(": ", 1)[-1]))
+        wq0 = held("conv1.0", check_conv, "conv1.0", c0)
+        one = lambda v: v[0] if v[0] == v[1] else -1
+        Lf = dict(name="conv1.0", conv=c0, k=one(c0.kernel_size), pad=one(c0.padding), stride=one(c0.stride), cin=c0.in_channels, cout=c0.out_channels,
+                  in_bits=c0.activation_quantizer.bits, w_bits=wq0.bits, per_channel=wq0.scale.numel() > 1, outs=stem["outs"], out_bits=[o["q"].bits for o in stem["outs"]])
+        g0 = _lib.ConvGeom(1, c0.in_channels, input_hw[0], input_hw[1], c0.out_channels, c0.kernel_size[0], c0.kernel_size[1], c0.stride[0], c0.stride[1], c0.padding[0],
+                           c0.padding[1], c0.dilation[0], c0.dilation[1], c0.groups, 0)
+        if not 1 <= len(stem["outs"]) <= 2 or not lib.mn_i8first_supported(C.byref(g0), Lf["in_bits"], Lf["out_bits"][0], Lf["w_bits"]):
+            raise _err("%s: conv1.0: geometry not covered by mn_i8first_supported (%dx%d, stride %s, padding %s, dilation %s, groups %d, %d input channels: 3x3 or 5x5, "
+                       "stride 1, dilation 1, padding (k - 1) / 2, groups 1, C * k * k <= 128)" % (who2, c0.kernel_size[0], c0.kernel_size[1], c0.stride, c0.padding,
+                                                                                                     c0.dilation, c0.groups, c0.in_channels))
+        Lf["table_bytes"] = int(lib.mn_i8first_table_bytes(C.byref(g0), Lf["in_bits"], Lf["out_bits"][0], Lf["w_bits"]))
+        pool, fc = model.avg_pool, model.fc
+        if not isinstance(pool, quantize.QuantAdaptiveAvgPool2d) or pool.output_size not in (1, (1, 1)):
+            raise _err("%s: avg_pool: (%s) is not a QuantAdaptiveAvgPool2d to 1 x 1" % (who2, type(pool).__name__))
+        if not isinstance(fc, quantize.QuantLinear):
+            raise _err("%s: fc: (%s) is not an IAO QuantLinear" % (who2, type(fc).__name__))
+        if not fc.quant_inference:
+            raise _err("%s: fc: is not quant_inference: its stored weights are not on the grid (prequantize_weights)" % who2)
+        held("fc", _iao8_check_quantizer, fc.activation_quantizer, "fc.activation_quantizer", True, who)
+        held("fc", _iao8_check_quantizer, fc.weight_quantizer, "fc.weight_quantizer", False, who)
+        if fc.weight_quantizer.scale.numel() not in (1, fc.out_features):
+            raise _err("%s: fc: fc.weight_quantizer carries %d scales for %d outputs" % (who2, fc.weight_quantizer.scale.numel(), fc.out_features))
+        if fc.in_features != cur["cout"]:
+            raise _err("%s: fc: in_features is %d, the last block %s writes %d channels" % (who2, fc.in_features, cur["name"], cur["cout"]))
+        Ll = dict(name="fc", fc=fc, cin=fc.in_features, cout=fc.out_features, p_bits=tail_q.bits, a_bits=fc.activation_quantizer.bits, w_bits=fc.weight_quantizer.bits,
+                  per_channel=fc.weight_quantizer.scale.numel() > 1)
+        if not lib.mn_i8poolfc_supported(1, Ll["cin"], Hl * Wl, Ll["cout"], Ll["p_bits"], Ll["a_bits"], Ll["w_bits"]):
+            raise _err("%s: fc: shape not covered by mn_i8poolfc_supported (%d channels, a %d x %d map, %d outputs: 1 <= O <= 64, H * W <= 4096, "
+                       "C * 2^(a-1) * (2^(w-1) - 1) <= INT_MAX)" % (who2, Ll["cin"], Hl, Wl, Ll["cout"]))
+        Ll["table_bytes"] = int(lib.mn_i8poolfc_table_bytes(Ll["cin"], Ll["cout"], Ll["p_bits"], Ll["a_bits"], Ll["w_bits"]))
+        stem["ends"] = (Lf, Ll)
+        report[0] = dict(report[0], kind="int8_first", kernel="k_i8first2<%d,%d>" % (Lf["k"], len(stem["outs"])), table_bytes=Lf["table_bytes"],
+                         act_bytes_out=len(stem["outs"]) * blocked(c0.out_channels, H0, W0))
+        report.append(dict(name="avg_pool", kind="int8_last", kernel="k_i8poolfc", k=0, cin=cur["cout"], cout=fc_out, stride=1, relu=0, shortcut=None, nout=1, consumers=[],
+                           table_bytes=Ll["table_bytes"], act_bytes_in=blocked(cur["cout"], Hl, Wl), act_bytes_out=4 * fc_out))
+        return stem, stages, buffers, tail_q, report
     report.append(dict(name="avg_pool", kind="last", kernel="k_i8_unpack, the model's own avg_pool and fc (fp32)", k=0, cin=cur["cout"], cout=fc_out, stride=1, relu=0,
                        shortcut=None, nout=1, consumers=[], table_bytes=0, act_bytes_in=blocked(cur["cout"], Hl, Wl) + 4 * cur["cout"] * Hl * Wl, act_bytes_out=4 * fc_out))
     return stem, stages, buffers, tail_q, report
@@ -1729,13 +1794,21 @@ class Int8ResPlan(_Plan):
     per conv (``mn_i8conv_fwd`` for the stride-1 ReLU convs, ``mn_i8res_conv_fwd`` for the strided ones and the shortcut convs, ``mn_i8res_add_fwd`` for the last conv
     of a block with its QuantAdd, ReLU and the next block's quantizers) -> ``mn_i8_unpack_codes`` at avg_pool's scale -> the model's own avg_pool and fc.  Eval only;
     owns the packed tables and one set of byte buffers per input shape.  ``layers[i]`` keeps what stage i was packed from (w, s_w, bias, s_a, s_add, s_out per output
-    map, the widths, src / sc / outs buffer numbers) for the tests' judge; ``buffers[b]`` is the channel count of code map b; ``stem`` the packs behind conv1."""
+    map, the widths, src / sc / outs buffer numbers) for the tests' judge; ``buffers[b]`` is the channel count of code map b; ``stem`` the packs behind conv1.
+
+    A plan compiled with ``end_to_end=True`` (``ends`` is set) runs neither the model's own conv1 nor its avg_pool and fc: ``mn_i8first_fwd2`` takes the fp32 image to
+    the stem's code maps, the stages run unchanged, ``mn_i8poolfc_fwd`` takes the last block's codes to the fp32 logits (``csrc/qgemm_iao8_e2e.h``): no pack, no unpack,
+    no fp32 activation map.  ``ends`` = (first, last) keeps what the two tables were packed from (first: w, s_w, bias, s_a, s_out and out_bits per output map, in_bits,
+    w_bits; last: w, s_w, bias, s_p, s_fc, p_bits, a_bits, w_bits) for the tests' judge.  Its ``report`` is the walk's at 32 x 32 until the plan runs, then that of
+    the image size it last ran on (``iao_int8_report(model, (H, W), end_to_end=True)``: the activation bytes, and whether the pooled map fits, depend on it)."""
 
     who = "iao_compile_int8"
 
-    def __init__(self, conv1, stages, avg_pool, fc, report, stem, buffers, tail):
+    def __init__(self, conv1, stages, avg_pool, fc, report, stem, buffers, tail, ends=None, report_of=None):
         super().__init__(conv1, stages, None, [avg_pool, fc], True, report)
         self.stem, self.buffers, self.tail_q = stem, buffers, tail          # tail: dict(buf, s, C)
+        self.ends = ends                  # None, or the layer dicts (first, last) of an end_to_end plan
+        self._report_of, self._reports = report_of, {}          # end_to_end: (H, W) -> the report at that image size
         self.stage_codes = []
 
     def _plan_buffers(self, shape, device):
@@ -1752,6 +1825,8 @@ class Int8ResPlan(_Plan):
                 dims[o["buf"]] = ((h - 1) // L["stride"] + 1, (w - 1) // L["stride"] + 1)
         bufs = [torch.empty((N, (c + 15) // 16, dims[b][0] * dims[b][1], 16), dtype=torch.int8, device=device) for b, c in enumerate(self.buffers)]
         ht, wt = dims[self.tail_q["buf"]]
+        if self.ends:          # the logits, and the pooled map's size in place of an fp32 map
+            return bufs, geoms, (torch.empty((N, self.ends[1]["cout"]), dtype=torch.float32, device=device), ht * wt)
         return bufs, geoms, torch.empty((N, self.tail_q["C"], ht, wt), dtype=torch.float32, device=device)
 
     @staticmethod
@@ -1789,9 +1864,74 @@ class Int8ResPlan(_Plan):
             self._launch(L, _res_geom(L, N, H, W), codes.contiguous(), shortcut.contiguous() if shortcut is not None else None, outs, ops._s())
         return outs
 
+    def _image(self, x):
+        Lf = self.ends[0] if self.ends else None
+        if not (Lf and type(x) is torch.Tensor and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == Lf["cin"]):
+            raise _err("iao_compile_int8(end_to_end=True): the input must be a float32 GPU image [N, %s, H, W] of an end_to_end plan (no CPU fallback)"
+                       % (Lf["cin"] if Lf else "C"))
+        return x.contiguous()
+
+    def _first(self, x, outs, st):
+        import ctypes as C
+        from micronet_amd import _lib, ops
+        Lf, (N, _, H, W) = self.ends[0], x.shape
+        q = _lib.I8FirstOuts()
+        q.nout, q.s_out0, q.bits0 = len(outs), Lf["s_out"][0], Lf["out_bits"][0]
+        q.s_out1, q.bits1 = (Lf["s_out"][1], Lf["out_bits"][1]) if len(outs) == 2 else (Lf["s_out"][0], Lf["out_bits"][0])
+        ops._call("mn_i8first_fwd2", C.byref(_res_geom(Lf, N, H, W)), Lf["in_bits"], Lf["w_bits"], ops._p(Lf["table"]), ops._p(x), C.byref(q), ops._p(outs[0]),
+                  ops._p(outs[1]) if len(outs) == 2 else None, st)
+
+    def _last(self, codes, N, HW, y, st):
+        from micronet_amd import ops
+        Ll = self.ends[1]
+        ops._call("mn_i8poolfc_fwd", N, Ll["cin"], HW, Ll["cout"], Ll["p_bits"], Ll["a_bits"], Ll["w_bits"], ops._p(Ll["table"]), ops._p(codes), ops._p(y), st)
+
+    def run_first(self, x):
+        """conv1 alone on the fp32 image (end_to_end): the list of the blocked code maps [N, ceil(cout / 16), H * W, 16] the first block reads, one per consumer
+        quantizer, freshly allocated and poisoned (tests)."""
+        from micronet_amd import ops
+        x = self._image(x)
+        Lf, (N, _, H, W) = self.ends[0], x.shape
+        outs = [torch.full((N, (Lf["cout"] + 15) // 16, H * W, 16), 77, dtype=torch.int8, device=x.device) for _ in Lf["outs"]]
+        with torch.cuda.device(x.device):
+            self._first(x, outs, ops._s())
+        return outs
+
+    def run_last(self, codes, N, H, W):
+        """avg_pool and fc alone on the last block's blocked codes [N, ceil(cin / 16), H * W, 16] (end_to_end): the fp32 logits [N, cout], freshly allocated and
+        poisoned (tests)."""
+        from micronet_amd import ops
+        Ll = self.ends[1] if self.ends else None
+        if not (Ll and torch.is_tensor(codes) and codes.is_cuda and codes.dtype == torch.int8 and tuple(codes.shape) == (N, (Ll["cin"] + 15) // 16, H * W, 16)):
+            raise _err("iao_compile_int8(end_to_end=True): run_last needs an end_to_end plan and int8 GPU codes [N, ceil(C / 16), H * W, 16]")
+        y = torch.full((N, Ll["cout"]), float("nan"), dtype=torch.float32, device=codes.device)
+        with torch.cuda.device(codes.device):
+            self._last(codes.contiguous(), N, H * W, y, ops._s())
+        return y
+
+    def _forward_ends(self, x):
+        from micronet_amd import ops
+        x = self._image(x)
+        N, _, H, W = x.shape
+        if (H, W) not in self._reports:
+            self._reports[(H, W)] = self._report_of((H, W))          # (raises where the pooled map of this image size is not covered)
+        self.report = self._reports[(H, W)]
+        with torch.cuda.device(x.device):
+            bufs, geoms, (y, hw) = self._shape_buffers((N, self.stem["cout"], H, W), x.device)          # (stride 1, padding (k - 1) / 2: conv1 keeps H x W)
+            st = ops._s()
+            self._first(x, [bufs[o["buf"]] for o in self.stem["outs"]], st)
+            for L, g in zip(self.layers, geoms):
+                self._launch(L, g, bufs[L["src"]], bufs[L["sc"]] if L["sc"] is not None else None, [bufs[o["buf"]] for o in L["outs"]], st)
+            if self.keep_stages:
+                self.stage_codes = [b.clone() for b in bufs]
+            self._last(bufs[self.tail_q["buf"]], N, hw, y, st)
+        return y.clone()          # (the buffer belongs to the plan: never handed out)
+
     @torch.no_grad()
     def forward(self, x):
         from micronet_amd import ops
+        if self.ends:
+            return self._forward_ends(x)
         a = self.first(x)
         if not (type(a) is torch.Tensor and a.is_cuda and a.dtype == torch.float32 and a.dim() == 4):
             raise _err("iao_compile_int8: conv1 did not produce a float32 GPU map (the input must be a float32 GPU tensor; no CPU fallback)")
@@ -1813,18 +1953,21 @@ class Int8ResPlan(_Plan):
 
 
 @torch.no_grad()
-def _compile_iao8_res(model, byte_ends=False):
+def _compile_iao8_res(model, byte_ends=False, end_to_end=False):
     import ctypes as C
     import math
     from micronet_amd import ops
-    who = "iao_compile_int8"
-    stem, stages, buffers, tail_q, report = _walk_iao8_res(model, byte_ends=byte_ends)
+    who = "iao_compile_int8(end_to_end=True)" if end_to_end else "iao_compile_int8"
+    stem, stages, buffers, tail_q, report = _walk_iao8_res(model, byte_ends=byte_ends, end_to_end=end_to_end)
+    ends = stem.pop("ends", None)
     _require_gpu(model, who)
     dev = stages[0]["conv"].weight.device
     # every scale the plan needs, in ONE host read
     qs = [o["q"] for o in stem["outs"]]
     for L in stages:
         qs += [L["conv"].activation_quantizer] + [o["q"] for o in L["outs"]] + ([L["add"]] if "add" in L else [])
+    if ends:
+        qs += [ends[0]["conv"].activation_quantizer, ends[1]["fc"].activation_quantizer]
     vals = torch.cat([q.scale.detach().float().reshape(-1)[:1] for q in qs]).tolist()
     scale = {id(q): v for q, v in zip(qs, vals)}
     for o in stem["outs"]:
@@ -1847,15 +1990,31 @@ def _compile_iao8_res(model, byte_ends=False):
             else:
                 ops._call("mn_i8res_pack", C.byref(_res_geom(L)), ops._p(L["w"]), ops._p(L["s_w"]), 1 if L["per_channel"] else 0, ops._p(L["bias"]), L["s_a"], s_tab,
                           L["in_bits"], L["a_bits"], L["w_bits"], ops._p(L["table"]), ops._s())
-        counters = torch.stack([L["table"][[0, 7]] for L in stages]).tolist()          # ... and every table's two counters in one more
-    for L, (bad, off) in zip(stages, counters):
+        if ends:
+            Lf, Ll = ends
+            conv, fc = Lf.pop("conv"), Ll.pop("fc")
+            for L, m in ((Lf, conv), (Ll, fc)):
+                L["w"] = m.weight.detach().float().contiguous()
+                L["s_w"] = m.weight_quantizer.scale.detach().float().reshape(-1).contiguous()
+                L["bias"] = m.bias.detach().float().contiguous() if m.bias is not None else None
+                L["table"] = torch.empty(L["table_bytes"] // 4, dtype=torch.int32, device=dev)
+            Lf["s_a"], Lf["s_out"] = scale[id(conv.activation_quantizer)], [o["s"] for o in stem["outs"]]
+            ops._call("mn_i8first_pack", C.byref(_res_geom(Lf)), ops._p(Lf["w"]), ops._p(Lf["s_w"]), 1 if Lf["per_channel"] else 0, ops._p(Lf["bias"]), Lf["s_a"],
+                      Lf["s_out"][0], Lf["in_bits"], Lf["out_bits"][0], Lf["w_bits"], None, ops._p(Lf["table"]), ops._s())
+            Ll["s_p"], Ll["s_fc"] = stages[-1]["s_out"][0], scale[id(fc.activation_quantizer)]
+            ops._call("mn_i8poolfc_pack", Ll["cin"], Ll["cout"], ops._p(Ll["w"]), ops._p(Ll["s_w"]), 1 if Ll["per_channel"] else 0, ops._p(Ll["bias"]), Ll["s_p"], Ll["s_fc"],
+                      Ll["p_bits"], Ll["a_bits"], Ll["w_bits"], ops._p(Ll["table"]), ops._s())
+        packed = stages + (list(ends) if ends else [])
+        counters = torch.stack([L["table"][[0, 7]] for L in packed]).tolist()          # ... and every table's two counters in one more
+    for L, (bad, off) in zip(packed, counters):
         if bad:
             raise _err("%s: %s: %d rows or scales with a non-finite or non-positive constant (al, bias, s_w, s_a, s_out)" % (who, L["name"], bad))
         if off:
             raise _err("%s: %s: %d rows whose stored weights are off the grid k * s_w (run prequantize_weights after iao_model_bn_fuse)" % (who, L["name"], off))
-        for s in L["s_out"] + ([L["s_add"]] if L["s_add"] is not None else []):
+        for s in L.get("s_out", []) + ([L["s_add"]] if L.get("s_add") is not None else []):
             if not (math.isfinite(s) and s > 0):
                 raise _err("%s: %s: a consumer's scale %r is not finite and positive" % (who, L["name"], s))
     last = stages[-1]
     tail = dict(buf=last["outs"][0]["buf"], s=last["s_out"][0], C=last["cout"])
-    return Int8ResPlan(model.conv1, stages, model.avg_pool, model.fc, report, stem, buffers, tail)
+    report_of = (lambda hw: _walk_iao8_res(model, hw, end_to_end=True)[4]) if ends else None
+    return Int8ResPlan(model.conv1, stages, model.avg_pool, model.fc, report, stem, buffers, tail, ends, report_of)
