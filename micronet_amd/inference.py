@@ -28,6 +28,7 @@ The results are ordinary modules of this package: in eval mode they run on the s
     convs, shortcut convs and the QuantAdd on byte codes, one code map per consumer quantizer of a block's output).  ``zero_points=True`` admits asymmetric
     quantizers on the sequential nets (``csrc/qgemm_iao8_zp.h``: the zero points as integer offsets of the exact int32 sum)."""
 import copy
+import ctypes as C
 
 import torch
 import torch.nn as nn
@@ -215,10 +216,29 @@ def _require_gpu(model, who):
             raise _err("%s: the model is on %s: micronet_amd runs on MI355X only (no CPU fallback)" % (who, p_.device))
 
 
-def _block_geom(L, N=1, H=4, W=4):
-    """The ConvGeom of a hidden layer's dict (square kernel, stride 1) on an N x H x W input; the shape-independent calls take the default."""
+def _one(v):
+    """The value of a pair that is the same in both directions, else -1."""
+    return v[0] if v[0] == v[1] else -1
+
+
+def _out_size(v, k, s, p, d):
+    """The output extent of a conv along one direction."""
+    return (v + 2 * p - d * (k - 1) - 1) // s + 1
+
+
+def _conv_geom(conv, N=1, H=4, W=4, in_shuffle=0):
+    """The ConvGeom of a conv module's own fields on an N x H x W input; the shape-independent calls take the default."""
     from micronet_amd import _lib
-    return _lib.ConvGeom(N, L["cin"], H, W, L["cout"], L["k"], L["k"], 1, 1, L["pad"], L["pad"], 1, 1, L["groups"], 0)
+    return _lib.ConvGeom(N, conv.in_channels, H, W, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.stride[1], conv.padding[0],
+                         conv.padding[1], conv.dilation[0], conv.dilation[1], conv.groups, in_shuffle)
+
+
+def _block_geom(L, N=1, H=4, W=4):
+    """The ConvGeom of a layer's dict (square kernel; stride 1 and one group where the dict names neither) on an N x H x W input; the shape-independent calls take
+    the default."""
+    from micronet_amd import _lib
+    s = L.get("stride", 1)
+    return _lib.ConvGeom(N, L["cin"], H, W, L["cout"], L["k"], L["k"], s, s, L["pad"], L["pad"], 1, 1, L.get("groups", 1), 0)
 
 
 class _Plan(nn.Module):
@@ -338,10 +358,8 @@ class BitPlan(_Plan):
         N, Cc, H, W = shape
         g0 = None
         if self.bit_ends:
-            import ctypes as C
             conv = self.first.conv
-            g0 = _lib.ConvGeom(N, conv.in_channels, H, W, Cc, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.stride[1], conv.padding[0], conv.padding[1],
-                               conv.dilation[0], conv.dilation[1], conv.groups, 0)
+            g0 = _conv_geom(conv, N, H, W)          # (Cc is conv.out_channels: forward hands over the first conv's own output shape)
             if not _lib.get_lib().mn_conv2d_first_sign_bits_supported(C.byref(g0)):
                 raise _err("wbwtab_compile_bits(bit_ends=True): %s.conv: a %d x %d x %d x %d input is not covered by mn_conv2d_first_sign_bits (W %% 4 == 0, H * W %% 32 == 0, "
                            "the image strip in LDS)" % (self.report[0]["name"], N, conv.in_channels, H, W))
@@ -371,7 +389,6 @@ class BitPlan(_Plan):
 
     @torch.no_grad()
     def forward(self, x):
-        import ctypes as C
         from micronet_amd import ops
         from micronet_amd.sign_tensor import SignTensor
         if self.bit_ends:
@@ -419,12 +436,10 @@ class BitPlan(_Plan):
 def _check_ends(who, first, nm_first, last, nm_last, first_kernel, first_supported, last_kernel, last_supported):
     """Both ends must be covered by their kernels -- never a silent byte path.  Shape-independent part (the input shape is checked by the plan).  ``first_supported(g)``
     / ``last_supported(cin, hw, cout)``: the library's verdicts; ``*_kernel``: the names in the messages."""
-    from micronet_amd import _lib
     conv = first.conv
     if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
         raise _err("%s: %s.conv: padding mode not covered by %s" % (who, nm_first, first_kernel))
-    g = _lib.ConvGeom(1, conv.in_channels, 8, 8, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.stride[1], conv.padding[0], conv.padding[1],
-                      conv.dilation[0], conv.dilation[1], conv.groups, 0)
+    g = _conv_geom(conv, 1, 8, 8)
     if not first_supported(g):
         raise _err("%s: %s.conv: not covered by %s (%dx%d, stride %d, padding %d, dilation %d, groups %d, %d taps per output: needs \"same\" padding, stride 1, groups 1, "
                    "at most 76 taps)" % (who, nm_first, first_kernel, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.padding[0], conv.dilation[0], conv.groups,
@@ -440,7 +455,6 @@ def _check_ends(who, first, nm_first, last, nm_last, first_kernel, first_support
 
 def _check_bit_ends(first, nm_first, last, nm_last):
     """``bit_ends=True``: ``_check_ends`` for the two bit kernels, and no channel shuffle in front of the last conv."""
-    import ctypes as C
     from micronet_amd import _lib
     lib = _lib.get_lib()
     _check_ends("wbwtab_compile_bits(bit_ends=True)", first, nm_first, last, nm_last, "mn_conv2d_first_sign_bits", lambda g: lib.mn_conv2d_first_sign_bits_supported(C.byref(g)),
@@ -453,7 +467,6 @@ def _walk_bits(model, bit_ends=False, mfma_blocks=False, mfma_k3=False):
     """The graph walk of ``wbwtab_compile_bits`` (no GPU needed): (first, layers, last, tail, flatten, report).  ``mfma_blocks``: a hidden block
     ``mn_bitconv_mfma_supported`` covers, whose fold is 0 or 1, runs on the MFMA form (``layer["mfma"]``); ``mfma_k3``: a hidden 3x3 block ``mn_bitconv_mfma3_supported``
     covers, with no folded pool, runs on the 3x3 MFMA form (``layer["mfma3"]``).  Neither refuses anything: a block they do not cover keeps its kernel."""
-    import ctypes as C
     from micronet_amd import _lib
     from micronet_amd.nn import Conv2dFirst
     from micronet_amd.quantization.wbwtab import quantize
@@ -506,7 +519,7 @@ def _walk_bits(model, bit_ends=False, mfma_blocks=False, mfma_k3=False):
             raise _err("wbwtab_compile_bits: %s.conv: stride / dilation other than 1 (or non-zero padding mode) is not covered by the bit kernels" % nm)
         k, pad = conv.kernel_size[0], conv.padding[0]
         shuffle = _shuffle_in_front("wbwtab_compile_bits", nm, child, conv)
-        g = _lib.ConvGeom(1, conv.in_channels, 4, 4, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], 1, 1, conv.padding[0], conv.padding[1], 1, 1, conv.groups, 0)
+        g = _conv_geom(conv)          # (stride and dilation are 1: anything else was refused above)
         if not _lib.get_lib().mn_bitconv_supported(C.byref(g)):
             raise _err("wbwtab_compile_bits: %s.conv: geometry not covered by mn_bitconv_supported (%dx%d, padding %d, groups %d)" % (nm, k, conv.kernel_size[1], pad, conv.groups))
         if shuffle:
@@ -566,7 +579,6 @@ def wbwtab_compile_bits(model, bit_ends=False, mfma_blocks=False, mfma_k3=False)
     (C / groups % 16 == 0) with no folded pool is packed and run in its int8-MFMA form (``mn_bitconv_mfma3_*``); a pooled 3x3 block keeps ``k_bitconv``, one whose pool
     runs as ``mn_bits_maxpool`` behind it still moves.  Neither flag refuses anything, both compose with ``bit_ends``; the layer dicts gain the keys ``"mfma"`` /
     ``"mfma3"`` under their flag only.  Off by default; with them off nothing changes."""
-    import ctypes as C
     from micronet_amd import _lib, ops
     first, layers, last, tail, flatten, report = _walk_bits(model, bit_ends, mfma_blocks, mfma_k3)
     _require_gpu(model, "wbwtab_compile_bits")
@@ -674,10 +686,8 @@ class CodePlan(_Plan):
         B = self.bits
         g0 = None
         if self.code_ends:
-            import ctypes as C
             conv = self.first.conv
-            g0 = _lib.ConvGeom(N, conv.in_channels, H, W, Cc, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.stride[1], conv.padding[0], conv.padding[1],
-                               conv.dilation[0], conv.dilation[1], conv.groups, 0)
+            g0 = _conv_geom(conv, N, H, W)          # (Cc is conv.out_channels: forward hands over the first conv's own output shape)
             if not _lib.get_lib().mn_conv2d_first_codes_supported(C.byref(g0), CODE_BITS):
                 raise _err("dorefa_compile_codes(code_ends=True): %s.conv: a %d x %d x %d x %d input is not covered by mn_conv2d_first_codes (W %% 4 == 0, H * W %% 32 == 0, "
                            "the image strip in LDS)" % (self.report[0]["name"], N, conv.in_channels, H, W))
@@ -712,7 +722,6 @@ class CodePlan(_Plan):
 
     def _run_layers(self, bufs, geoms, mids, st):
         """One launch per hidden block (two where a max-pool runs on the planes behind it)."""
-        import ctypes as C
         from micronet_amd import ops
         B = self.bits
         for i, L in enumerate(self.layers):
@@ -731,7 +740,6 @@ class CodePlan(_Plan):
 
     @torch.no_grad()
     def forward(self, x):
-        import ctypes as C
         from micronet_amd import ops
         from micronet_amd.sign_tensor import QActTensor
         if self.code_ends:
@@ -775,7 +783,6 @@ class CodePlan(_Plan):
 def _check_code_ends(first, nm_first, last, nm_last):
     """``code_ends=True``: ``_check_ends`` for the two plane kernels, and no channel shuffle in front of the last conv (the walk has already refused a pool behind the
     first block, other than 2-bit codes out of it, and a block's shuffle in front of the last block)."""
-    import ctypes as C
     from micronet_amd import _lib
     lib = _lib.get_lib()
     _check_ends("dorefa_compile_codes(code_ends=True)", first, nm_first, last, nm_last, "mn_conv2d_first_codes",
@@ -792,7 +799,6 @@ def _walk_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False, mf
     ``mn_codeconv_mfma3_supported`` covers, with no folded pool, runs on the 3x3 MFMA form (``layer["mfma3"]``); it refuses nothing either.  The net's code width is that
     of the first hidden block's conv, W2A2 or W4A4 (``report[i]["planes"]``); every quantised block must have it.  A 4-bit net runs on the two MFMA forms alone, whatever
     the two flags say: a hidden block neither covers, ``code_ends`` and ``tile_blocks`` raise."""
-    import ctypes as C
     from micronet_amd import _lib
     from micronet_amd.nn import Conv2dFirst
     from micronet_amd.quantization.wqaq.dorefa import quantize
@@ -827,7 +833,7 @@ def _walk_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False, mf
         conv = blk.conv
         if tuple(conv.stride) != (1, 1) or tuple(conv.dilation) != (1, 1) or conv.padding_mode != "zeros" or isinstance(conv.padding, str):
             raise _err("dorefa_compile_codes: %s.conv: stride / dilation other than 1 (or non-zero padding mode) is not covered by the code kernels" % nm)
-        g = _lib.ConvGeom(1, conv.in_channels, 4, 4, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], 1, 1, conv.padding[0], conv.padding[1], 1, 1, conv.groups, 0)
+        g = _conv_geom(conv)          # (stride and dilation are 1: anything else was refused above)
         if wide:
             if not (_lib.get_lib().mn_codeconv_mfma_supported(C.byref(g), B, B, B) or _lib.get_lib().mn_codeconv_mfma3_supported(C.byref(g), B, B, B)):
                 ks, cg, n = tuple(conv.kernel_size), conv.in_channels // conv.groups, 2 ** B - 1
@@ -939,7 +945,7 @@ def _walk_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=False, mf
         if tile_blocks:
             layers[-1].update(tile=nm in tiled, pool_ksp=None, wants_consumer=wants)
         if mfma_blocks or mfma_k3 or wide:
-            g = _lib.ConvGeom(1, conv.in_channels, 4, 4, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], 1, 1, conv.padding[0], conv.padding[1], 1, 1, conv.groups, 0)
+            g = _conv_geom(conv)
             if mfma_blocks or wide:
                 layers[-1]["mfma"] = bool(_lib.get_lib().mn_codeconv_mfma_supported(C.byref(g), B, B, B))
             if mfma_k3 or wide:
@@ -1028,7 +1034,6 @@ def dorefa_compile_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=
     or 128 channels per group, a 3x3 / padding 1 block 16 channels per group and no folded pool (K * 15 * 15 <= 32767, the int16 range the thresholds are searched
     over).  Any other hidden block, ``code_ends=True`` and ``tile_blocks=True`` raise ``MicronetHipError`` naming the layer; so does a net of mixed widths or of any
     other width.  The stored weights must lie on the 4-bit grid (2k - 15) / 15.  Nothing changes for a W2A2 net."""
-    import ctypes as C
     from micronet_amd import _lib, ops
     from micronet_amd.quantization.wqaq.dorefa.quantize import _weight_is_coded
     first, layers, last, tail, flatten, report = _walk_codes(model, code_ends, tile_blocks, mfma_blocks, mfma_k3)
@@ -1106,14 +1111,25 @@ def dorefa_compile_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=
 
 
 # ------------------------------------------------------------------------------------------------ int8 deployment of the BN-folded IAO graph (csrc/qgemm_iao8.h)
-def _i8conv_kernel_name(k, pool):
-    """The kernel mn_i8conv_fwd reports for a hidden block (csrc/qgemm_iao8.h)."""
-    return "k_i8conv<%d,%d>" % (k, pool)
+def _i8conv_kernel_name(k, pool, zp=False):
+    """The kernel mn_i8conv_fwd reports for a hidden block (csrc/qgemm_iao8.h); ``zp``: mn_i8zconv_fwd, for a block with a zero point (csrc/qgemm_iao8_zp.h)."""
+    return ("k_i8zconv<%d,%d>" if zp else "k_i8conv<%d,%d>") % (k, pool)
 
 
-def _i8zconv_kernel_name(k, pool):
-    """The kernel mn_i8zconv_fwd reports for a hidden block with a zero point (csrc/qgemm_iao8_zp.h)."""
-    return "k_i8zconv<%d,%d>" % (k, pool)
+def _blocked(c, h, w):
+    """The bytes of a code map of c channels on an h x w map: whole 16-channel blocks."""
+    return (c + 15) // 16 * 16 * h * w
+
+
+def _code_map(N, c, hw, device, fill=None):
+    """A blocked code map [N, ceil(c / 16), hw, 16] of int8; ``fill``: the poison of a map handed to the tests."""
+    shape = (N, (c + 15) // 16, hw, 16)
+    return torch.empty(shape, dtype=torch.int8, device=device) if fill is None else torch.full(shape, fill, dtype=torch.int8, device=device)
+
+
+def _is_code_map(t, N, c, hw):
+    """An int8 GPU tensor of the shape ``_code_map`` makes for c channels."""
+    return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int8 and tuple(t.shape) == (N, (c + 15) // 16, hw, 16)
 
 
 def _iao8_check_quantizer(q, nm, per_tensor, who="iao_compile_int8", zero_points=False):
@@ -1137,17 +1153,30 @@ def _iao8_check_quantizer(q, nm, per_tensor, who="iao_compile_int8", zero_points
     return asym
 
 
+def _iao8_check_conv(conv, nm, who="iao_compile_int8", zero_points=False, fold_only=False):
+    """A conv the int8 blocks deploy: a BN-folded IAO ``QuantConv2d`` that is ``quant_inference``, its activation quantizer covered with a single scale.  ``nm``,
+    here and in ``_iao8_check_weights``: the conv's own path in the model.  ``fold_only``: the first rule alone, for a conv that stays on the model's own module."""
+    from micronet_amd.quantization.wqaq.iao import quantize
+    if not isinstance(conv, quantize.QuantConv2d) or isinstance(conv, quantize.QuantBNFuseConv2d):
+        raise _err("%s: %s (%s) is not a BN-folded IAO QuantConv2d (run iao_model_bn_fuse first)" % (who, nm, type(conv).__name__))
+    if fold_only:
+        return
+    if not conv.quant_inference:
+        raise _err("%s: %s is not quant_inference: its stored weights are not on the grid (iao_model_bn_fuse + prequantize_weights)" % (who, nm))
+    _iao8_check_quantizer(conv.activation_quantizer, nm + ".activation_quantizer", True, who, zero_points)
+
+
 def _iao8_check_weights(conv, nm, who="iao_compile_int8", zero_points=False):
     """The weight quantizer and padding mode of a conv the int8 blocks contract: symmetric (``zero_points``: or asymmetric, as many zero points as scales), 2 .. 8
     bits, one scale per layer or per output channel, zero padding."""
     wq = conv.weight_quantizer
-    asym = _iao8_check_quantizer(wq, nm + ".conv.weight_quantizer", False, who, zero_points)
+    asym = _iao8_check_quantizer(wq, nm + ".weight_quantizer", False, who, zero_points)
     if asym and wq.zero_point.numel() != wq.scale.numel():
-        raise _err("%s: %s.conv.weight_quantizer carries %d zero points for %d scales" % (who, nm, wq.zero_point.numel(), wq.scale.numel()))
+        raise _err("%s: %s.weight_quantizer carries %d zero points for %d scales" % (who, nm, wq.zero_point.numel(), wq.scale.numel()))
     if wq.scale.numel() not in (1, conv.out_channels):
-        raise _err("%s: %s.conv.weight_quantizer carries %d scales for %d output channels" % (who, nm, wq.scale.numel(), conv.out_channels))
+        raise _err("%s: %s.weight_quantizer carries %d scales for %d output channels" % (who, nm, wq.scale.numel(), conv.out_channels))
     if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
-        raise _err("%s: %s.conv: padding mode not covered by the int8 blocks" % (who, nm))
+        raise _err("%s: %s: padding mode not covered by the int8 blocks" % (who, nm))
     return wq
 
 
@@ -1157,7 +1186,6 @@ def _walk_iao8(model, input_hw=(32, 32), byte_ends=False, zero_points=False):
     is asymmetric carries ``zp`` = True and takes the kernels of csrc/qgemm_iao8_zp.h."""
     if zero_points and byte_ends:
         raise _err("iao_compile_int8(zero_points=True): byte_ends=True is not covered together with zero points (the int8 end kernels take symmetric quantizers only)")
-    import ctypes as C
     from micronet_amd import _lib
     from micronet_amd.quantization.wqaq.dorefa.quantize import _is_ref_block
     from micronet_amd.quantization.wqaq.iao import quantize
@@ -1176,11 +1204,7 @@ def _walk_iao8(model, input_hw=(32, 32), byte_ends=False, zero_points=False):
         conv, bn, act = getattr(child, "conv", None), getattr(child, "bn", None), getattr(child, "relu", None)
         if not (_is_ref_block(child) and isinstance(bn, nn.Identity) and type(act) in (nn.ReLU, quantize.ReLUAfterFusedConv)):
             raise _err("%s: %s (%s): module order not recognised (expected a BN-folded conv -> Identity -> ReLU block)" % (who, nm, type(child).__name__))
-        if not isinstance(conv, quantize.QuantConv2d) or isinstance(conv, quantize.QuantBNFuseConv2d):
-            raise _err("%s: %s.conv (%s) is not a BN-folded IAO QuantConv2d (run iao_model_bn_fuse first)" % (who, nm, type(conv).__name__))
-        if not conv.quant_inference:
-            raise _err("%s: %s.conv is not quant_inference: its stored weights are not on the grid (iao_model_bn_fuse + prequantize_weights)" % (who, nm))
-        _iao8_check_quantizer(conv.activation_quantizer, nm + ".conv.activation_quantizer", True, who, zero_points)
+        _iao8_check_conv(conv, nm + ".conv", who, zero_points)
         return conv
 
     if not isinstance(getattr(first, "conv", None), nn.Conv2d):
@@ -1189,10 +1213,9 @@ def _walk_iao8(model, input_hw=(32, 32), byte_ends=False, zero_points=False):
     c0 = first.conv
     if byte_ends:
         block_conv(nm_first, first, ends_who)          # the first block is an int8 block too: the image goes through its own activation quantizer
-        _iao8_check_weights(c0, nm_first, ends_who)
-        _iao8_check_weights(last_conv, nm_last, ends_who)
-    size = lambda v, k, s, p, d: (v + 2 * p - d * (k - 1) - 1) // s + 1
-    H, W = (size(input_hw[i], c0.kernel_size[i], c0.stride[i], c0.padding[i], c0.dilation[i]) for i in (0, 1))
+        _iao8_check_weights(c0, nm_first + ".conv", ends_who)
+        _iao8_check_weights(last_conv, nm_last + ".conv", ends_who)
+    H, W = (_out_size(input_hw[i], c0.kernel_size[i], c0.stride[i], c0.padding[i], c0.dilation[i]) for i in (0, 1))
     layers, pack_shuffle = [], 0
     for nm, child in items[1:last_i]:
         if isinstance(child, nn.MaxPool2d):
@@ -1210,14 +1233,11 @@ def _walk_iao8(model, input_hw=(32, 32), byte_ends=False, zero_points=False):
             layers[-1]["pool"], layers[-1]["pool_module"], layers[-1]["pool_name"] = 1, child, nm
             continue
         conv = block_conv(nm, child)
-        wq = _iao8_check_weights(conv, nm, zero_points=zero_points)
-        one = lambda v: v[0] if v[0] == v[1] else -1
-        g = _lib.ConvGeom(1, conv.in_channels, 4, 4, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.stride[1], conv.padding[0],
-                          conv.padding[1], conv.dilation[0], conv.dilation[1], conv.groups, 0)
-        if not _lib.get_lib().mn_i8conv_supported(C.byref(g), conv.activation_quantizer.bits, wq.bits):
+        wq = _iao8_check_weights(conv, nm + ".conv", zero_points=zero_points)
+        if not _lib.get_lib().mn_i8conv_supported(C.byref(_conv_geom(conv)), conv.activation_quantizer.bits, wq.bits):
             raise _err("iao_compile_int8: %s.conv: geometry not covered by mn_i8conv_supported (%dx%d, stride %d, padding %d, dilation %d, groups %d, %d channels per group: "
                        "1x1 / padding 0 with groups 1 or C / groups %% 16 == 0, or 3x3 / padding 1 with C / groups %% 16 == 0; stride 1)"
-                       % (nm, conv.kernel_size[0], conv.kernel_size[1], one(conv.stride), one(conv.padding), one(conv.dilation), conv.groups, conv.in_channels // conv.groups))
+                       % (nm, conv.kernel_size[0], conv.kernel_size[1], _one(conv.stride), _one(conv.padding), _one(conv.dilation), conv.groups, conv.in_channels // conv.groups))
         s = _shuffle_in_front("iao_compile_int8", nm, child, conv)
         if s:
             _check_shuffle_divides("iao_compile_int8", nm, conv, s)
@@ -1241,17 +1261,14 @@ def _walk_iao8(model, input_hw=(32, 32), byte_ends=False, zero_points=False):
         if L["pool"] and L["pool_module"].activation_quantizer.bits != L["a_bits"]:
             raise _err("iao_compile_int8: %s: the pool's quantizer has %d bits, its consumer %d: one code width per block"
                        % (L["pool_name"], L["pool_module"].activation_quantizer.bits, L["a_bits"]))
-    blocked = lambda c, h, w: (c + 15) // 16 * 16 * h * w
-    geom = lambda conv, h, w, shuffle=0: _lib.ConvGeom(1, conv.in_channels, h, w, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0],
-                                                       conv.stride[1], conv.padding[0], conv.padding[1], conv.dilation[0], conv.dilation[1], conv.groups, shuffle)
     report = [dict(name=nm_first, kind="first", kernel="the model's own block (fp32), %s" % ("k_i8z_pack" if layers[0]["asym_a"] else "k_i8_pack"),
                    k=c0.kernel_size[0], cin=c0.in_channels, cout=c0.out_channels, groups=c0.groups, pool=0, out_order=("shuffle %d" % pack_shuffle) if pack_shuffle else "identity", table_bytes=0,
-                   act_bytes_in=4 * c0.in_channels * input_hw[0] * input_hw[1], act_bytes_out=4 * c0.out_channels * H * W + blocked(c0.out_channels, H, W))]
+                   act_bytes_in=4 * c0.in_channels * input_hw[0] * input_hw[1], act_bytes_out=4 * c0.out_channels * H * W + _blocked(c0.out_channels, H, W))]
     ends = None
     if byte_ends:
         # the first block: an int8 block whose input is the fp32 image (mn_i8first_*), its consumer the first hidden conv's activation quantizer
         bits = (c0.activation_quantizer.bits, layers[0]["in_bits"], c0.weight_quantizer.bits)
-        g = geom(c0, input_hw[0], input_hw[1], _shuffle_in_front(ends_who, nm_first, first, c0))
+        g = _conv_geom(c0, 1, input_hw[0], input_hw[1], _shuffle_in_front(ends_who, nm_first, first, c0))
         if not _lib.get_lib().mn_i8first_supported(C.byref(g), *bits):
             raise _err("%s: %s.conv: geometry not covered by mn_i8first_supported (%dx%d, stride %s, padding %s, dilation %s, groups %d, %d input channels, in_shuffle %d, "
                        "a %d x %d image: groups 1, no channel shuffle, 3x3 or 5x5 / stride 1 / dilation 1 / padding (KS - 1) / 2, C * KS * KS <= 128 and an LDS tile "
@@ -1261,28 +1278,28 @@ def _walk_iao8(model, input_hw=(32, 32), byte_ends=False, zero_points=False):
         Lf = dict(name=nm_first, conv=c0, k=c0.kernel_size[0], pad=c0.padding[0], cin=c0.in_channels, cout=c0.out_channels, groups=1, pool=0, shuffle=pack_shuffle,
                   in_bits=bits[0], a_bits=bits[1], w_bits=bits[2], per_channel=c0.weight_quantizer.scale.numel() > 1, consumer=layers[0]["conv"].activation_quantizer,
                   table_bytes=int(_lib.get_lib().mn_i8first_table_bytes(C.byref(g), *bits)))
-        report[0] = dict(report[0], kind="int8_first", kernel="k_i8first<%d>" % Lf["k"], table_bytes=Lf["table_bytes"], act_bytes_out=blocked(Lf["cout"], H, W))
+        report[0] = dict(report[0], kind="int8_first", kernel="k_i8first<%d>" % Lf["k"], table_bytes=Lf["table_bytes"], act_bytes_out=_blocked(Lf["cout"], H, W))
     for L in layers:
         g = _block_geom(L)
-        nin = blocked(L["cin"], H, W)
+        nin = _blocked(L["cin"], H, W)
         if L["pool"]:
             if H % 2 or W % 2:
                 raise _err("iao_compile_int8: %s: the 2x2 max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
             H, W = H // 2, W // 2
         table_bytes = _lib.get_lib().mn_i8zconv_table_bytes if L["zp"] else _lib.get_lib().mn_i8conv_table_bytes
         L["table_bytes"] = int(table_bytes(C.byref(g), L["a_bits"], L["w_bits"]))
-        report.append(dict(name=L["name"], kind="int8", kernel=(_i8zconv_kernel_name if L["zp"] else _i8conv_kernel_name)(L["k"], L["pool"]), k=L["k"], cin=L["cin"],
+        report.append(dict(name=L["name"], kind="int8", kernel=_i8conv_kernel_name(L["k"], L["pool"], L["zp"]), k=L["k"], cin=L["cin"],
                            cout=L["cout"], groups=L["groups"], pool=L["pool"], out_order=("shuffle %d" % L["shuffle"]) if L["shuffle"] else "identity", table_bytes=L["table_bytes"], act_bytes_in=nin,
-                           act_bytes_out=blocked(L["cout"], H, W)))
+                           act_bytes_out=_blocked(L["cout"], H, W)))
     report.append(dict(name=nm_last, kind="last", kernel="%s, the model's own block (fp32)" % ("k_i8z_unpack" if layers[-1]["asym_out"] else "k_i8_unpack"),
                        k=last_conv.kernel_size[0], cin=last_conv.in_channels, cout=last_conv.out_channels, groups=last_conv.groups, pool=0, out_order="identity", table_bytes=0,
-                       act_bytes_in=blocked(last_conv.in_channels, H, W) + 4 * last_conv.in_channels * H * W, act_bytes_out=4 * last_conv.out_channels * H * W))
+                       act_bytes_in=_blocked(last_conv.in_channels, H, W) + 4 * last_conv.in_channels * H * W, act_bytes_out=4 * last_conv.out_channels * H * W))
     if byte_ends:
         # the last block: the hidden kernel's contraction, stopped at r and written as the fp32 map of the tail (mn_i8conv_fwd_f32)
         bits = (last_conv.activation_quantizer.bits, last_conv.weight_quantizer.bits)
         if _shuffle_in_front(ends_who, nm_last, last, last_conv):
             raise _err("%s: %s: a channel shuffle in front of the last block is not covered (folding it into the last hidden block is not built)" % (ends_who, nm_last))
-        g = geom(last_conv, 4, 4)
+        g = _conv_geom(last_conv)
         if not _lib.get_lib().mn_i8conv_supported(C.byref(g), *bits):
             raise _err("%s: %s.conv: geometry not covered by mn_i8conv_supported, the rule of mn_i8conv_fwd_f32 (%dx%d, stride %s, padding %s, dilation %s, groups %d, "
                        "%d channels per group: 1x1 / padding 0 with groups 1 or C / groups %% 16 == 0, or 3x3 / padding 1 with C / groups %% 16 == 0; stride 1)"
@@ -1291,7 +1308,7 @@ def _walk_iao8(model, input_hw=(32, 32), byte_ends=False, zero_points=False):
         Ll = dict(name=nm_last, conv=last_conv, k=last_conv.kernel_size[0], pad=last_conv.padding[0], cin=last_conv.in_channels, cout=last_conv.out_channels,
                   groups=last_conv.groups, pool=0, shuffle=0, a_bits=bits[0], w_bits=bits[1], per_channel=last_conv.weight_quantizer.scale.numel() > 1, relu=1,
                   table_bytes=int(_lib.get_lib().mn_i8conv_table_bytes(C.byref(g), *bits)))
-        report[-1] = dict(report[-1], kind="int8_last", kernel="k_i8conv_f32<%d>" % Ll["k"], table_bytes=Ll["table_bytes"], act_bytes_in=blocked(Ll["cin"], H, W))
+        report[-1] = dict(report[-1], kind="int8_last", kernel="k_i8conv_f32<%d>" % Ll["k"], table_bytes=Ll["table_bytes"], act_bytes_in=_blocked(Ll["cin"], H, W))
         ends = (Lf, Ll)
     return first, layers, last, tail, flatten, report, pack_shuffle, ends
 
@@ -1327,6 +1344,31 @@ _ZP_RESNET = ("iao_compile_int8(zero_points=True): the reference ResNet tree is 
               "quantizers only)")
 
 
+def _iao8_ends_image(ends, x, keyword):
+    """The fp32 image a plan with int8 ends (``keyword``: byte_ends or end_to_end) takes, contiguous."""
+    Lf = ends[0] if ends else None
+    if not (Lf and type(x) is torch.Tensor and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == Lf["cin"]):
+        raise _err("iao_compile_int8(%s=True): the input must be a float32 GPU image [N, %s, H, W] of %s %s plan (no CPU fallback)"
+                   % (keyword, Lf["cin"] if Lf else "C", "an" if keyword[0] in "aeiou" else "a", keyword))
+    return x.contiguous()
+
+
+def _iao8_ends_codes(ends, codes, N, H, W, keyword):
+    """The last end's dict and the blocked codes ``run_last`` takes, contiguous."""
+    Ll = ends[1] if ends else None
+    if not (Ll and _is_code_map(codes, N, Ll["cin"], H * W)):
+        raise _err("iao_compile_int8(%s=True): run_last needs %s %s plan and int8 GPU codes [N, ceil(C / 16), H * W, 16]"
+                   % (keyword, "an" if keyword[0] in "aeiou" else "a", keyword))
+    return Ll, codes.contiguous()
+
+
+def _two_outs(q, L, nout):
+    """The fields ``I8ResAdd`` and ``I8FirstOuts`` share: the scale and width of each output map; one map: the second pair repeats the first."""
+    i = 1 if nout == 2 else 0
+    q.nout, q.s_out0, q.bits0, q.s_out1, q.bits1 = nout, L["s_out"][0], L["out_bits"][0], L["s_out"][i], L["out_bits"][i]
+    return q
+
+
 class Int8Plan(_Plan):
     """What ``iao_compile_int8`` returns: the model's own first block (fp32) -> ``mn_i8_pack_codes`` at the second conv's scale -> one ``mn_i8conv_fwd`` per hidden
     block (2x2 max-pool and the consumer's channel shuffle folded in) -> ``mn_i8_unpack_codes`` at the last conv's scale -> the model's own last block and tail (its
@@ -1356,7 +1398,7 @@ class Int8Plan(_Plan):
         N, Cc, H, W = shape
         if Cc != self.layers[0]["cin"]:
             raise _err("iao_compile_int8: %s produced %d channels, %s reads %d" % (self.report[0]["name"], Cc, self.layers[0]["name"], self.layers[0]["cin"]))
-        bufs, geoms = [torch.empty((N, (Cc + 15) // 16, H * W, 16), dtype=torch.int8, device=device)], []
+        bufs, geoms = [_code_map(N, Cc, H * W, device)], []
         if self.ends:
             geoms.append(_block_geom(self.ends[0], N, H, W))          # (stride 1, padding (k - 1) / 2: the image has the first block's H x W)
         for L in self.layers:
@@ -1365,83 +1407,78 @@ class Int8Plan(_Plan):
                 if H % 2 or W % 2:
                     raise _err("iao_compile_int8: %s: the 2x2 max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
                 H, W = H // 2, W // 2
-            bufs.append(torch.empty((N, (L["cout"] + 15) // 16, H * W, 16), dtype=torch.int8, device=device))
+            bufs.append(_code_map(N, L["cout"], H * W, device))
         if self.ends:
             geoms.append(_block_geom(self.ends[1], N, H, W))
         return (bufs, geoms, torch.empty((N, (self.ends[1] if self.ends else self.layers[-1])["cout"], H, W), dtype=torch.float32, device=device))
 
-    def _image(self, x):
-        Lf = self.ends[0] if self.ends else None
-        if not (Lf and type(x) is torch.Tensor and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == Lf["cin"]):
-            raise _err("iao_compile_int8(byte_ends=True): the input must be a float32 GPU image [N, %s, H, W] of a byte_ends plan (no CPU fallback)"
-                       % (Lf["cin"] if Lf else "C"))
-        return x.contiguous()
+    def _first(self, g, x, out, st):
+        """The first end (byte_ends): the fp32 image to the first hidden stage's codes."""
+        from micronet_amd import ops
+        Lf = self.ends[0]
+        ops._call("mn_i8first_fwd", C.byref(g), Lf["in_bits"], Lf["a_bits"], Lf["w_bits"], ops._p(Lf["table"]), ops._p(x), ops._p(out), st)
+
+    def _stage(self, L, g, src, out, st):
+        """A hidden stage: the zero-point kernels where one of its quantizers is asymmetric."""
+        from micronet_amd import ops
+        ops._call("mn_i8zconv_fwd" if L.get("zp") else "mn_i8conv_fwd", C.byref(g), L["a_bits"], L["w_bits"], ops._p(L["table"]), ops._p(src), ops._p(out),
+                  int(L["pool"]), st)
+
+    def _last(self, g, codes, y, st):
+        """The last end (byte_ends): the last hidden codes to the fp32 map of the tail."""
+        from micronet_amd import ops
+        Ll = self.ends[1]
+        ops._call("mn_i8conv_fwd_f32", C.byref(g), Ll["a_bits"], Ll["w_bits"], ops._p(Ll["table"]), ops._p(codes), ops._p(y), Ll["relu"], st)
 
     def run_first(self, x):
         """The first block alone on the fp32 image (byte_ends): the blocked codes [N, ceil(cout / 16), H * W, 16] the first hidden stage reads, freshly allocated
         (tests)."""
-        import ctypes as C
         from micronet_amd import ops
-        x = self._image(x)
+        x = _iao8_ends_image(self.ends, x, "byte_ends")
         Lf, (N, _, H, W) = self.ends[0], x.shape
-        out = torch.full((N, (Lf["cout"] + 15) // 16, H * W, 16), 77, dtype=torch.int8, device=x.device)
+        out = _code_map(N, Lf["cout"], H * W, x.device, fill=77)
         with torch.cuda.device(x.device):
-            ops._call("mn_i8first_fwd", C.byref(_block_geom(Lf, N, H, W)), Lf["in_bits"], Lf["a_bits"], Lf["w_bits"], ops._p(Lf["table"]), ops._p(x), ops._p(out), ops._s())
+            self._first(_block_geom(Lf, N, H, W), x, out, ops._s())
         return out
 
     def run_last(self, codes, N, H, W):
         """The last block alone on blocked input codes [N, ceil(cin / 16), H * W, 16] (byte_ends): the fp32 map [N, cout, H, W] of the tail, freshly allocated (tests)."""
-        import ctypes as C
         from micronet_amd import ops
-        Ll = self.ends[1] if self.ends else None
-        if not (Ll and torch.is_tensor(codes) and codes.is_cuda and codes.dtype == torch.int8 and tuple(codes.shape) == (N, (Ll["cin"] + 15) // 16, H * W, 16)):
-            raise _err("iao_compile_int8(byte_ends=True): run_last needs a byte_ends plan and int8 GPU codes [N, ceil(C / 16), H * W, 16]")
-        codes = codes.contiguous()
+        Ll, codes = _iao8_ends_codes(self.ends, codes, N, H, W, "byte_ends")
         out = torch.full((N, Ll["cout"], H, W), float("nan"), dtype=torch.float32, device=codes.device)
         with torch.cuda.device(codes.device):
-            ops._call("mn_i8conv_fwd_f32", C.byref(_block_geom(Ll, N, H, W)), Ll["a_bits"], Ll["w_bits"], ops._p(Ll["table"]), ops._p(codes), ops._p(out), Ll["relu"],
-                      ops._s())
+            self._last(_block_geom(Ll, N, H, W), codes, out, ops._s())
         return out
 
     def _forward_ends(self, x):
-        import ctypes as C
         from micronet_amd import ops
-        x = self._image(x)
-        (Lf, Ll), (N, _, H, W) = self.ends, x.shape
+        x = _iao8_ends_image(self.ends, x, "byte_ends")
+        N, _, H, W = x.shape
         with torch.cuda.device(x.device):
-            bufs, geoms, y = self._shape_buffers((N, Lf["cout"], H, W), x.device)
+            bufs, geoms, y = self._shape_buffers((N, self.ends[0]["cout"], H, W), x.device)
             st = ops._s()
-            ops._call("mn_i8first_fwd", C.byref(geoms[0]), Lf["in_bits"], Lf["a_bits"], Lf["w_bits"], ops._p(Lf["table"]), ops._p(x), ops._p(bufs[0]), st)
+            self._first(geoms[0], x, bufs[0], st)
             for i, L in enumerate(self.layers):
-                ops._call("mn_i8conv_fwd", C.byref(geoms[i + 1]), L["a_bits"], L["w_bits"], ops._p(L["table"]), ops._p(bufs[i]), ops._p(bufs[i + 1]), int(L["pool"]), st)
+                self._stage(L, geoms[i + 1], bufs[i], bufs[i + 1], st)
             if self.keep_stages:
                 self.stage_codes = [b.clone() for b in bufs]
-            ops._call("mn_i8conv_fwd_f32", C.byref(geoms[-1]), Ll["a_bits"], Ll["w_bits"], ops._p(Ll["table"]), ops._p(bufs[-1]), ops._p(y), Ll["relu"], st)
+            self._last(geoms[-1], bufs[-1], y, st)
         return self._finish(y if len(self.tail) else y.clone())          # (the buffer belongs to the plan: never handed out)
 
     def run_stage(self, i, codes, N, H, W):
         """Hidden stage ``i`` alone on blocked input codes [N, ceil(cin / 16), H * W, 16] (int8, GPU): its blocked output codes, freshly allocated (tests)."""
-        import ctypes as C
         from micronet_amd import ops
         L = self.layers[i]
-        if not (torch.is_tensor(codes) and codes.is_cuda and codes.dtype == torch.int8 and tuple(codes.shape) == (N, (L["cin"] + 15) // 16, H * W, 16)):
+        if not _is_code_map(codes, N, L["cin"], H * W):
             raise _err("iao_compile_int8: run_stage needs int8 GPU codes [N, ceil(C / 16), H * W, 16]")
-        codes = codes.contiguous()
-        g = _block_geom(L, N, H, W)
         Ho, Wo = (H // 2, W // 2) if L["pool"] else (H, W)
-        out = torch.full((N, (L["cout"] + 15) // 16, Ho * Wo, 16), 77, dtype=torch.int8, device=codes.device)
+        out = _code_map(N, L["cout"], Ho * Wo, codes.device, fill=77)
         with torch.cuda.device(codes.device):
-            ops._call(self._stage_entry(L), C.byref(g), L["a_bits"], L["w_bits"], ops._p(L["table"]), ops._p(codes), ops._p(out), int(L["pool"]), ops._s())
+            self._stage(L, _block_geom(L, N, H, W), codes.contiguous(), out, ops._s())
         return out
-
-    @staticmethod
-    def _stage_entry(L):
-        """The forward of a hidden stage: the zero-point kernels where one of its quantizers is asymmetric."""
-        return "mn_i8zconv_fwd" if L.get("zp") else "mn_i8conv_fwd"
 
     @torch.no_grad()
     def forward(self, x):
-        import ctypes as C
         from micronet_amd import ops
         if self.ends:
             return self._forward_ends(x)
@@ -1458,7 +1495,7 @@ class Int8Plan(_Plan):
             else:
                 ops._call("mn_i8_pack_codes", ops._p(a), N, Cc, H * W, self.pack["s"], self.pack["a_bits"], ops._p(self.pack["order"]), ops._p(bufs[0]), st)
             for i, L in enumerate(self.layers):
-                ops._call(self._stage_entry(L), C.byref(geoms[i]), L["a_bits"], L["w_bits"], ops._p(L["table"]), ops._p(bufs[i]), ops._p(bufs[i + 1]), int(L["pool"]), st)
+                self._stage(L, geoms[i], bufs[i], bufs[i + 1], st)
             if self.keep_stages:
                 self.stage_codes = [b.clone() for b in bufs]
             n_, c_, h_, w_ = y.shape
@@ -1467,6 +1504,42 @@ class Int8Plan(_Plan):
             else:
                 ops._call("mn_i8_unpack_codes", ops._p(bufs[-1]), n_, c_, h_ * w_, self.layers[-1]["s_out"], ops._p(y), st)
         return self._finish(self.last(y))
+
+
+def _iao8_constants(qs):
+    """{id(q): (scale, zero point)} of the per-tensor quantizers ``qs``, in ONE host read (compile time: the one place a host read-back is allowed)."""
+    vals = torch.cat([t.detach().float().reshape(-1)[:1] for q in qs for t in (q.scale, q.zero_point)]).tolist()
+    return {id(q): (vals[2 * i], vals[2 * i + 1]) for i, q in enumerate(qs)}
+
+
+def _iao8_packed_from(L, m, dev):
+    """The fields of a layer's dict its table is packed from, and the empty table: ``m`` is the conv, or the fc."""
+    L["w"] = m.weight.detach().float().contiguous()
+    L["s_w"] = m.weight_quantizer.scale.detach().float().reshape(-1).contiguous()
+    L["bias"] = m.bias.detach().float().contiguous() if m.bias is not None else None
+    L["table"] = torch.empty(L["table_bytes"] // 4, dtype=torch.int32, device=dev)
+
+
+def _iao8_counters(packed):
+    """The counters of every packed table, in one host read: header words 0 and 7, and 13 .. 15, which count in the zero-point tables alone (the other tables keep
+    what they like there: ``_iao8_check_counters`` reads them under ``zp`` only)."""
+    return torch.stack([L["table"][[0, 7, 13, 14, 15]] for L in packed]).tolist()
+
+
+def _iao8_check_counters(who, nm, L, row, scales, zp=False):
+    """Refuse a table whose counters ``row`` are not all 0; ``nm``: the displayed name, ``scales``: the activation scales the table was packed with, ``zp``: a
+    zero-point table."""
+    bad, off, zbad, wide, nopad = row
+    if bad:
+        raise _err("%s: %s: %d rows or scales with a non-finite or non-positive constant (al, bias, s_w, %s)" % (who, nm, bad, scales))
+    if zp and zbad:
+        raise _err("%s: %s: %d zero points (of the input, pool and consumer quantizers and the rows' z_w) that are not integers of magnitude <= 65535" % (who, nm, zbad))
+    if off:
+        raise _err("%s: %s: %d rows whose stored weights are off the grid k * s_w (run prequantize_weights after iao_model_bn_fuse)" % (who, nm, off))
+    if zp and wide:
+        raise _err("%s: %s: %d rows whose sum over %d channels x %d taps does not fit int32 at these zero points" % (who, nm, wide, L["cin"] // L["groups"], L["k"] * L["k"]))
+    if zp and nopad:
+        raise _err("%s: %s: zero padding has no byte: the value 0 is not a code of the input quantizer (zero point %g) of this 3x3 stage" % (who, nm, L["z_a"]))
 
 
 @torch.no_grad()
@@ -1501,7 +1574,6 @@ def iao_compile_int8(model, byte_ends=False, zero_points=False, end_to_end=False
     int32 sum), every other stage on ``mn_i8conv_fwd`` as before, and a symmetric net gives the plan and report it gives without the keyword.  The table counters
     additionally refuse, naming the layer: a zero point that is not an integer of magnitude <= 65535, a sum that would not fit int32, and a 3x3 stage whose input
     quantizer has no code for the value 0 ("zero padding has no byte").  Not covered, each raising: together with ``byte_ends=True``; the reference ResNet tree."""
-    import ctypes as C
     from micronet_amd import _lib, ops
     if _is_ref_resnet(model):
         if zero_points:
@@ -1512,25 +1584,22 @@ def iao_compile_int8(model, byte_ends=False, zero_points=False, end_to_end=False
     if end_to_end:
         raise _err(_E2E_RESNET)
     _require_gpu(model, "iao_compile_int8")
-    scale = lambda q: float(q.scale.detach().float().reshape(-1)[0])          # (compile time: the one place a host read-back is allowed)
-    zero = lambda q: float(q.zero_point.detach().float().reshape(-1)[0])
     dev = layers[0]["conv"].weight.device
+    packed = ([ends[0]] if ends else []) + layers + ([ends[1]] if ends else [])
+    const = _iao8_constants([q for L in packed for q in (L["conv"].activation_quantizer, L.get("consumer"), getattr(L.get("pool_module"), "activation_quantizer", None))
+                             if q is not None])
 
     def packed_from(L, conv):
-        L["w"] = conv.weight.detach().float().contiguous()
-        L["s_w"] = conv.weight_quantizer.scale.detach().float().reshape(-1).contiguous()
-        L["bias"] = conv.bias.detach().float().contiguous() if conv.bias is not None else None
-        L["s_a"] = scale(conv.activation_quantizer)
-        L["z_a"] = zero(conv.activation_quantizer)
+        _iao8_packed_from(L, conv, dev)
+        L["s_a"], L["z_a"] = const[id(conv.activation_quantizer)]
         L["z_w"] = conv.weight_quantizer.zero_point.detach().float().reshape(-1).contiguous()
         L["out_order"] = _shuffle_order(L["cout"], L["shuffle"], dev) if L["shuffle"] else None
-        L["table"] = torch.empty(L["table_bytes"] // 4, dtype=torch.int32, device=dev)
 
     with torch.cuda.device(dev):
         if ends:
             Lf, Ll = ends
             packed_from(Lf, Lf.pop("conv"))
-            Lf["s_out"] = scale(Lf.pop("consumer"))
+            Lf["s_out"] = const[id(Lf.pop("consumer"))][0]
             ops._call("mn_i8first_pack", C.byref(_block_geom(Lf)), ops._p(Lf["w"]), ops._p(Lf["s_w"]), 1 if Lf["per_channel"] else 0, ops._p(Lf["bias"]), Lf["s_a"],
                       Lf["s_out"], Lf["in_bits"], Lf["a_bits"], Lf["w_bits"], ops._p(Lf["out_order"]), ops._p(Lf["table"]), ops._s())
             packed_from(Ll, Ll.pop("conv"))
@@ -1540,9 +1609,8 @@ def iao_compile_int8(model, byte_ends=False, zero_points=False, end_to_end=False
         for L in layers:
             conv, pool_m = L.pop("conv"), L.pop("pool_module")
             packed_from(L, conv)
-            consumer = L.pop("consumer")
-            L["s_out"], L["z_out"] = scale(consumer), zero(consumer)
-            L["s_p"], L["z_p"] = (scale(pool_m.activation_quantizer), zero(pool_m.activation_quantizer)) if pool_m is not None else (L["s_out"], L["z_out"])
+            L["s_out"], L["z_out"] = const[id(L.pop("consumer"))]
+            L["s_p"], L["z_p"] = const[id(pool_m.activation_quantizer)] if pool_m is not None else (L["s_out"], L["z_out"])
             if L["zp"]:
                 qa, qp, qo = (_lib.I8ZQuant(L["s_a"], L["z_a"], L["asym_a"], L["in_bits"]), _lib.I8ZQuant(L["s_p"], L["z_p"], L["asym_p"], L["a_bits"]),
                               _lib.I8ZQuant(L["s_out"], L["z_out"], L["asym_out"], L["a_bits"]))
@@ -1551,22 +1619,9 @@ def iao_compile_int8(model, byte_ends=False, zero_points=False, end_to_end=False
             else:
                 ops._call("mn_i8conv_pack", C.byref(_block_geom(L)), ops._p(L["w"]), ops._p(L["s_w"]), 1 if L["per_channel"] else 0, ops._p(L["bias"]), L["s_a"], L["s_p"],
                           L["s_out"], L["a_bits"], L["w_bits"], ops._p(L["out_order"]), ops._p(L["table"]), ops._s())
-        packed = ([ends[0]] if ends else []) + layers + ([ends[1]] if ends else [])
-        # (words 13 .. 15 are counters of the zero-point tables alone; the others' headers hold 0 there)
-        counters = torch.stack([L["table"][[0, 7, 13, 14, 15]] for L in packed]).tolist()
-    for L, (bad, off, zbad, wide, nopad) in zip(packed, counters):
-        if bad:
-            raise _err("%s: %s.conv: %d rows or scales with a non-finite or non-positive constant (al, bias, s_w, s_a, s_p, s_out)" % (who, L["name"], bad))
-        if L.get("zp") and zbad:
-            raise _err("%s: %s.conv: %d zero points (of the input, pool and consumer quantizers and the rows' z_w) that are not integers of magnitude <= 65535"
-                       % (who, L["name"], zbad))
-        if off:
-            raise _err("%s: %s.conv: %d rows whose stored weights are off the grid k * s_w (run prequantize_weights after iao_model_bn_fuse)" % (who, L["name"], off))
-        if L.get("zp") and wide:
-            raise _err("%s: %s.conv: %d rows whose sum over %d channels x %d taps does not fit int32 at these zero points" % (who, L["name"], wide, L["cin"] // L["groups"],
-                                                                                                                     L["k"] * L["k"]))
-        if L.get("zp") and nopad:
-            raise _err("%s: %s.conv: zero padding has no byte: the value 0 is not a code of the input quantizer (zero point %g) of this 3x3 stage" % (who, L["name"], L["z_a"]))
+        counters = _iao8_counters(packed)
+    for L, row in zip(packed, counters):
+        _iao8_check_counters(who, L["name"] + ".conv", L, row, "s_a, s_p, s_out", zp=L.get("zp"))
     pack = dict(s=layers[0]["s_a"], a_bits=layers[0]["in_bits"], order=_shuffle_order(layers[0]["cin"], pack_shuffle, dev) if pack_shuffle else None)
     if layers[0].get("asym_a"):
         pack["q"] = _lib.I8ZQuant(layers[0]["s_a"], layers[0]["z_a"], 1, layers[0]["in_bits"])
@@ -1586,12 +1641,6 @@ def _is_ref_resnet(model):
     return all(hasattr(b_, "residual_function") and hasattr(b_, "shortcut") and hasattr(b_, "add") for n_ in _RESNET_STAGES for b_ in getattr(model, n_))
 
 
-def _res_geom(L, N=1, H=4, W=4):
-    """The ConvGeom of a ResNet stage's dict (square kernel, one stride) on an N x H x W input."""
-    from micronet_amd import _lib
-    return _lib.ConvGeom(N, L["cin"], H, W, L["cout"], L["k"], L["k"], L["stride"], L["stride"], L["pad"], L["pad"], 1, 1, 1, 0)
-
-
 def _walk_iao8_res(model, input_hw=(32, 32), byte_ends=False, end_to_end=False):
     """The graph walk of ``iao_compile_int8`` on the reference ResNet tree (no GPU needed): (stem, stages, buffers, tail quantizer, report).  ``end_to_end``: conv1,
     avg_pool and fc are held to the rules of the byte ends (csrc/qgemm_iao8_e2e.h), ``stem["ends"]`` = (first, last) are their layer dicts and the two end rows of the
@@ -1600,7 +1649,6 @@ def _walk_iao8_res(model, input_hw=(32, 32), byte_ends=False, end_to_end=False):
     A VALUE -- conv1's output, or a block's output v = relu(add) -- has up to two consumers with a quantizer each: the next block's first conv, and the next block's
     shortcut (its QuantAdd itself for an identity shortcut, else the shortcut conv's activation quantizer).  Its producer writes one code map per consumer quantizer
     (``outs``); ``buffers[i]`` is the channel count of code map i.  The last block writes one map at avg_pool's activation quantizer."""
-    import ctypes as C
     from micronet_amd import _lib
     from micronet_amd.quantization.wqaq.iao import quantize
     who = "iao_compile_int8"
@@ -1622,25 +1670,14 @@ def _walk_iao8_res(model, input_hw=(32, 32), byte_ends=False, end_to_end=False):
         return out
 
     def check_conv(nm, conv):
-        if not isinstance(conv, quantize.QuantConv2d) or isinstance(conv, quantize.QuantBNFuseConv2d):
-            raise _err("%s: %s (%s) is not a BN-folded IAO QuantConv2d (run iao_model_bn_fuse first)" % (who, nm, type(conv).__name__))
-        if not conv.quant_inference:
-            raise _err("%s: %s is not quant_inference: its stored weights are not on the grid (iao_model_bn_fuse + prequantize_weights)" % (who, nm))
-        _iao8_check_quantizer(conv.activation_quantizer, nm + ".activation_quantizer", True, who)
-        wq = conv.weight_quantizer
-        _iao8_check_quantizer(wq, nm + ".weight_quantizer", False, who)
-        if wq.scale.numel() not in (1, conv.out_channels):
-            raise _err("%s: %s.weight_quantizer carries %d scales for %d output channels" % (who, nm, wq.scale.numel(), conv.out_channels))
-        if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
-            raise _err("%s: %s: padding mode not covered by the int8 blocks" % (who, nm))
-        return wq
+        _iao8_check_conv(conv, nm, who)
+        return _iao8_check_weights(conv, nm, who)
 
     stem_chain = conv_chain("conv1", model.conv1)
     if len(stem_chain) != 1 or not stem_chain[0][2]:
         raise _err("%s: conv1: module order not recognised (expected one BN-folded conv -> Identity -> ReLU)" % who)
     c0 = stem_chain[0][1]
-    if not isinstance(c0, quantize.QuantConv2d) or isinstance(c0, quantize.QuantBNFuseConv2d):
-        raise _err("%s: conv1.0 (%s) is not a BN-folded IAO QuantConv2d (run iao_model_bn_fuse first)" % (who, type(c0).__name__))
+    _iao8_check_conv(c0, "conv1.0", who, fold_only=True)          # (all the default plan asks of conv1: it runs on the model's own module)
     buffers = []
 
     def new_map(producer, q, qname, channels):
@@ -1650,8 +1687,7 @@ def _walk_iao8_res(model, input_hw=(32, 32), byte_ends=False, end_to_end=False):
 
     def new_stage(nm, conv, relu, kind, src, sc=None, shortcut=None):
         wq = check_conv(nm, conv)
-        one = lambda v: v[0] if v[0] == v[1] else -1
-        st = dict(name=nm, kind=kind, conv=conv, k=one(conv.kernel_size), pad=one(conv.padding), stride=one(conv.stride), cin=conv.in_channels, cout=conv.out_channels,
+        st = dict(name=nm, kind=kind, conv=conv, k=_one(conv.kernel_size), pad=_one(conv.padding), stride=_one(conv.stride), cin=conv.in_channels, cout=conv.out_channels,
                   groups=conv.groups, relu=int(relu), in_bits=conv.activation_quantizer.bits, w_bits=wq.bits, per_channel=wq.scale.numel() > 1, src=src, sc=sc,
                   shortcut=shortcut, outs=[])
         stages.append(st)
@@ -1698,19 +1734,16 @@ def _walk_iao8_res(model, input_hw=(32, 32), byte_ends=False, end_to_end=False):
 
     # kernels, geometry rules and the report: one row per stage
     lib = _lib.get_lib()
-    blocked = lambda c, h, w: (c + 15) // 16 * 16 * h * w
-    size = lambda v, k, s, p, d: (v + 2 * p - d * (k - 1) - 1) // s + 1
-    H0, W0 = (size(input_hw[i], c0.kernel_size[i], c0.stride[i], c0.padding[i], c0.dilation[i]) for i in (0, 1))
+    H0, W0 = (_out_size(input_hw[i], c0.kernel_size[i], c0.stride[i], c0.padding[i], c0.dilation[i]) for i in (0, 1))
     dims = {o["buf"]: (H0, W0) for o in stem["outs"]}
     report = [dict(name="conv1", kind="first", kernel="the model's own block (fp32), k_i8_pack x %d" % len(stem["outs"]), k=c0.kernel_size[0], cin=c0.in_channels,
                    cout=c0.out_channels, stride=c0.stride[0], relu=1, shortcut=None, nout=len(stem["outs"]), consumers=[o["consumer"] for o in stem["outs"]], table_bytes=0,
-                   act_bytes_in=4 * c0.in_channels * input_hw[0] * input_hw[1], act_bytes_out=4 * c0.out_channels * H0 * W0 + len(stem["outs"]) * blocked(c0.out_channels, H0, W0))]
+                   act_bytes_in=4 * c0.in_channels * input_hw[0] * input_hw[1], act_bytes_out=4 * c0.out_channels * H0 * W0 + len(stem["outs"]) * _blocked(c0.out_channels, H0, W0))]
     for st in stages:
         conv = st["conv"]
         st["out_bits"] = [o["q"].bits for o in st["outs"]]
         st["a_bits"] = st["add"].bits if st["kind"] == "int8_add" else st["out_bits"][0]          # the width of the codes the conv's epilogue forms
-        g = _lib.ConvGeom(1, conv.in_channels, 4, 4, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.stride[1], conv.padding[0],
-                          conv.padding[1], conv.dilation[0], conv.dilation[1], conv.groups, 0)
+        g = _conv_geom(conv)
         what = ("%dx%d, stride %s, padding %s, dilation %s, groups %d, %d input channels" % (conv.kernel_size[0], conv.kernel_size[1], conv.stride, conv.padding,
                                                                                             conv.dilation, conv.groups, conv.in_channels))
         if st["kind"] == "int8" and st["relu"] and st["stride"] == 1 and st["in_bits"] == st["a_bits"]:
@@ -1735,8 +1768,8 @@ def _walk_iao8_res(model, input_hw=(32, 32), byte_ends=False, end_to_end=False):
             dims[o["buf"]] = (Ho, Wo)
         report.append(dict(name=st["name"], kind=st["kind"], kernel=kernel, k=st["k"], cin=st["cin"], cout=st["cout"], stride=st["stride"], relu=st["relu"],
                            shortcut=st["shortcut"], nout=len(st["outs"]), consumers=[o["consumer"] for o in st["outs"]], table_bytes=st["table_bytes"],
-                           act_bytes_in=blocked(st["cin"], H, W) + (blocked(st["cout"], Ho, Wo) if st["sc"] is not None else 0),
-                           act_bytes_out=len(st["outs"]) * blocked(st["cout"], Ho, Wo)))
+                           act_bytes_in=_blocked(st["cin"], H, W) + (_blocked(st["cout"], Ho, Wo) if st["sc"] is not None else 0),
+                           act_bytes_out=len(st["outs"]) * _blocked(st["cout"], Ho, Wo)))
     Hl, Wl = dims[cur["outs"][0]["buf"]]
     fc_out = getattr(model.fc, "out_features", 0)
     if end_to_end:
@@ -1749,11 +1782,9 @@ def _walk_iao8_res(model, input_hw=(32, 32), byte_ends=False, end_to_end=False):
             except _lib.MicronetHipError as e:
                 raise _err("%s: %s: %s" % (who2, layer, str(e).split(": ", 1)[-1]))
         wq0 = held("conv1.0", check_conv, "conv1.0", c0)
-        one = lambda v: v[0] if v[0] == v[1] else -1
-        Lf = dict(name="conv1.0", conv=c0, k=one(c0.kernel_size), pad=one(c0.padding), stride=one(c0.stride), cin=c0.in_channels, cout=c0.out_channels,
+        Lf = dict(name="conv1.0", conv=c0, k=_one(c0.kernel_size), pad=_one(c0.padding), stride=_one(c0.stride), cin=c0.in_channels, cout=c0.out_channels,
                   in_bits=c0.activation_quantizer.bits, w_bits=wq0.bits, per_channel=wq0.scale.numel() > 1, outs=stem["outs"], out_bits=[o["q"].bits for o in stem["outs"]])
-        g0 = _lib.ConvGeom(1, c0.in_channels, input_hw[0], input_hw[1], c0.out_channels, c0.kernel_size[0], c0.kernel_size[1], c0.stride[0], c0.stride[1], c0.padding[0],
-                           c0.padding[1], c0.dilation[0], c0.dilation[1], c0.groups, 0)
+        g0 = _conv_geom(c0, 1, input_hw[0], input_hw[1])
         if not 1 <= len(stem["outs"]) <= 2 or not lib.mn_i8first_supported(C.byref(g0), Lf["in_bits"], Lf["out_bits"][0], Lf["w_bits"]):
             raise _err("%s: conv1.0: geometry not covered by mn_i8first_supported (%dx%d, stride %s, padding %s, dilation %s, groups %d, %d input channels: 3x3 or 5x5, "
                        "stride 1, dilation 1, padding (k - 1) / 2, groups 1, C * k * k <= 128)" % (who2, c0.kernel_size[0], c0.kernel_size[1], c0.stride, c0.padding,
@@ -1780,12 +1811,12 @@ def _walk_iao8_res(model, input_hw=(32, 32), byte_ends=False, end_to_end=False):
         Ll["table_bytes"] = int(lib.mn_i8poolfc_table_bytes(Ll["cin"], Ll["cout"], Ll["p_bits"], Ll["a_bits"], Ll["w_bits"]))
         stem["ends"] = (Lf, Ll)
         report[0] = dict(report[0], kind="int8_first", kernel="k_i8first2<%d,%d>" % (Lf["k"], len(stem["outs"])), table_bytes=Lf["table_bytes"],
-                         act_bytes_out=len(stem["outs"]) * blocked(c0.out_channels, H0, W0))
+                         act_bytes_out=len(stem["outs"]) * _blocked(c0.out_channels, H0, W0))
         report.append(dict(name="avg_pool", kind="int8_last", kernel="k_i8poolfc", k=0, cin=cur["cout"], cout=fc_out, stride=1, relu=0, shortcut=None, nout=1, consumers=[],
-                           table_bytes=Ll["table_bytes"], act_bytes_in=blocked(cur["cout"], Hl, Wl), act_bytes_out=4 * fc_out))
+                           table_bytes=Ll["table_bytes"], act_bytes_in=_blocked(cur["cout"], Hl, Wl), act_bytes_out=4 * fc_out))
         return stem, stages, buffers, tail_q, report
     report.append(dict(name="avg_pool", kind="last", kernel="k_i8_unpack, the model's own avg_pool and fc (fp32)", k=0, cin=cur["cout"], cout=fc_out, stride=1, relu=0,
-                       shortcut=None, nout=1, consumers=[], table_bytes=0, act_bytes_in=blocked(cur["cout"], Hl, Wl) + 4 * cur["cout"] * Hl * Wl, act_bytes_out=4 * fc_out))
+                       shortcut=None, nout=1, consumers=[], table_bytes=0, act_bytes_in=_blocked(cur["cout"], Hl, Wl) + 4 * cur["cout"] * Hl * Wl, act_bytes_out=4 * fc_out))
     return stem, stages, buffers, tail_q, report
 
 
@@ -1820,33 +1851,24 @@ class Int8ResPlan(_Plan):
         geoms = []
         for L in self.layers:
             h, w = dims[L["src"]]
-            geoms.append(_res_geom(L, N, h, w))
+            geoms.append(_block_geom(L, N, h, w))
             for o in L["outs"]:
                 dims[o["buf"]] = ((h - 1) // L["stride"] + 1, (w - 1) // L["stride"] + 1)
-        bufs = [torch.empty((N, (c + 15) // 16, dims[b][0] * dims[b][1], 16), dtype=torch.int8, device=device) for b, c in enumerate(self.buffers)]
+        bufs = [_code_map(N, c, dims[b][0] * dims[b][1], device) for b, c in enumerate(self.buffers)]
         ht, wt = dims[self.tail_q["buf"]]
         if self.ends:          # the logits, and the pooled map's size in place of an fp32 map
             return bufs, geoms, (torch.empty((N, self.ends[1]["cout"]), dtype=torch.float32, device=device), ht * wt)
         return bufs, geoms, torch.empty((N, self.tail_q["C"], ht, wt), dtype=torch.float32, device=device)
 
-    @staticmethod
-    def _add_params(L):
-        from micronet_amd import _lib
-        q = _lib.I8ResAdd()
-        q.s_add, q.add_bits, q.nout = L["s_add"], L["a_bits"], len(L["outs"])
-        q.s_out0, q.bits0 = L["s_out"][0], L["out_bits"][0]
-        q.s_out1, q.bits1 = (L["s_out"][1], L["out_bits"][1]) if len(L["outs"]) == 2 else (L["s_out"][0], L["out_bits"][0])
-        return q
-
     def _launch(self, L, g, src, sc, outs, st):
-        import ctypes as C
-        from micronet_amd import ops
+        from micronet_amd import _lib, ops
         if L["api"] == "i8conv":
             ops._call("mn_i8conv_fwd", C.byref(g), L["a_bits"], L["w_bits"], ops._p(L["table"]), ops._p(src), ops._p(outs[0]), 0, st)
         elif L["api"] == "res_conv":
             ops._call("mn_i8res_conv_fwd", C.byref(g), L["in_bits"], L["a_bits"], L["w_bits"], ops._p(L["table"]), ops._p(src), ops._p(outs[0]), L["relu"], st)
         else:
-            q = self._add_params(L)
+            q = _two_outs(_lib.I8ResAdd(), L, len(L["outs"]))
+            q.s_add, q.add_bits = L["s_add"], L["a_bits"]
             ops._call("mn_i8res_add_fwd", C.byref(g), L["in_bits"], L["w_bits"], ops._p(L["table"]), ops._p(src), ops._p(sc), C.byref(q), ops._p(outs[0]),
                       ops._p(outs[1]) if len(outs) == 2 else None, st)
 
@@ -1855,30 +1877,20 @@ class Int8ResPlan(_Plan):
         the list of its blocked output maps, freshly allocated and poisoned (tests)."""
         from micronet_amd import ops
         L = self.layers[i]
-        ok = lambda t, c, hw: torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int8 and tuple(t.shape) == (N, (c + 15) // 16, hw, 16)
         Ho, Wo = (H - 1) // L["stride"] + 1, (W - 1) // L["stride"] + 1
-        if not ok(codes, L["cin"], H * W) or (L["api"] == "res_add") != (shortcut is not None) or (shortcut is not None and not ok(shortcut, L["cout"], Ho * Wo)):
+        if (not _is_code_map(codes, N, L["cin"], H * W) or (L["api"] == "res_add") != (shortcut is not None)
+                or (shortcut is not None and not _is_code_map(shortcut, N, L["cout"], Ho * Wo))):
             raise _err("iao_compile_int8: run_stage needs int8 GPU codes [N, ceil(C / 16), H * W, 16] (and the shortcut's codes for an add stage, for no other)")
-        outs = [torch.full((N, (L["cout"] + 15) // 16, Ho * Wo, 16), 77, dtype=torch.int8, device=codes.device) for _ in L["outs"]]
+        outs = [_code_map(N, L["cout"], Ho * Wo, codes.device, fill=77) for _ in L["outs"]]
         with torch.cuda.device(codes.device):
-            self._launch(L, _res_geom(L, N, H, W), codes.contiguous(), shortcut.contiguous() if shortcut is not None else None, outs, ops._s())
+            self._launch(L, _block_geom(L, N, H, W), codes.contiguous(), shortcut.contiguous() if shortcut is not None else None, outs, ops._s())
         return outs
 
-    def _image(self, x):
-        Lf = self.ends[0] if self.ends else None
-        if not (Lf and type(x) is torch.Tensor and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == Lf["cin"]):
-            raise _err("iao_compile_int8(end_to_end=True): the input must be a float32 GPU image [N, %s, H, W] of an end_to_end plan (no CPU fallback)"
-                       % (Lf["cin"] if Lf else "C"))
-        return x.contiguous()
-
     def _first(self, x, outs, st):
-        import ctypes as C
         from micronet_amd import _lib, ops
         Lf, (N, _, H, W) = self.ends[0], x.shape
-        q = _lib.I8FirstOuts()
-        q.nout, q.s_out0, q.bits0 = len(outs), Lf["s_out"][0], Lf["out_bits"][0]
-        q.s_out1, q.bits1 = (Lf["s_out"][1], Lf["out_bits"][1]) if len(outs) == 2 else (Lf["s_out"][0], Lf["out_bits"][0])
-        ops._call("mn_i8first_fwd2", C.byref(_res_geom(Lf, N, H, W)), Lf["in_bits"], Lf["w_bits"], ops._p(Lf["table"]), ops._p(x), C.byref(q), ops._p(outs[0]),
+        q = _two_outs(_lib.I8FirstOuts(), Lf, len(outs))
+        ops._call("mn_i8first_fwd2", C.byref(_block_geom(Lf, N, H, W)), Lf["in_bits"], Lf["w_bits"], ops._p(Lf["table"]), ops._p(x), C.byref(q), ops._p(outs[0]),
                   ops._p(outs[1]) if len(outs) == 2 else None, st)
 
     def _last(self, codes, N, HW, y, st):
@@ -1890,9 +1902,9 @@ class Int8ResPlan(_Plan):
         """conv1 alone on the fp32 image (end_to_end): the list of the blocked code maps [N, ceil(cout / 16), H * W, 16] the first block reads, one per consumer
         quantizer, freshly allocated and poisoned (tests)."""
         from micronet_amd import ops
-        x = self._image(x)
+        x = _iao8_ends_image(self.ends, x, "end_to_end")
         Lf, (N, _, H, W) = self.ends[0], x.shape
-        outs = [torch.full((N, (Lf["cout"] + 15) // 16, H * W, 16), 77, dtype=torch.int8, device=x.device) for _ in Lf["outs"]]
+        outs = [_code_map(N, Lf["cout"], H * W, x.device, fill=77) for _ in Lf["outs"]]
         with torch.cuda.device(x.device):
             self._first(x, outs, ops._s())
         return outs
@@ -1901,17 +1913,15 @@ class Int8ResPlan(_Plan):
         """avg_pool and fc alone on the last block's blocked codes [N, ceil(cin / 16), H * W, 16] (end_to_end): the fp32 logits [N, cout], freshly allocated and
         poisoned (tests)."""
         from micronet_amd import ops
-        Ll = self.ends[1] if self.ends else None
-        if not (Ll and torch.is_tensor(codes) and codes.is_cuda and codes.dtype == torch.int8 and tuple(codes.shape) == (N, (Ll["cin"] + 15) // 16, H * W, 16)):
-            raise _err("iao_compile_int8(end_to_end=True): run_last needs an end_to_end plan and int8 GPU codes [N, ceil(C / 16), H * W, 16]")
+        Ll, codes = _iao8_ends_codes(self.ends, codes, N, H, W, "end_to_end")
         y = torch.full((N, Ll["cout"]), float("nan"), dtype=torch.float32, device=codes.device)
         with torch.cuda.device(codes.device):
-            self._last(codes.contiguous(), N, H * W, y, ops._s())
+            self._last(codes, N, H * W, y, ops._s())
         return y
 
     def _forward_ends(self, x):
         from micronet_amd import ops
-        x = self._image(x)
+        x = _iao8_ends_image(self.ends, x, "end_to_end")
         N, _, H, W = x.shape
         if (H, W) not in self._reports:
             self._reports[(H, W)] = self._report_of((H, W))          # (raises where the pooled map of this image size is not covered)
@@ -1954,7 +1964,6 @@ class Int8ResPlan(_Plan):
 
 @torch.no_grad()
 def _compile_iao8_res(model, byte_ends=False, end_to_end=False):
-    import ctypes as C
     import math
     from micronet_amd import ops
     who = "iao_compile_int8(end_to_end=True)" if end_to_end else "iao_compile_int8"
@@ -1968,49 +1977,39 @@ def _compile_iao8_res(model, byte_ends=False, end_to_end=False):
         qs += [L["conv"].activation_quantizer] + [o["q"] for o in L["outs"]] + ([L["add"]] if "add" in L else [])
     if ends:
         qs += [ends[0]["conv"].activation_quantizer, ends[1]["fc"].activation_quantizer]
-    vals = torch.cat([q.scale.detach().float().reshape(-1)[:1] for q in qs]).tolist()
-    scale = {id(q): v for q, v in zip(qs, vals)}
+    scale = {i: s for i, (s, _) in _iao8_constants(qs).items()}
     for o in stem["outs"]:
         q = o.pop("q")
         o["s"], o["bits"] = scale[id(q)], q.bits
     with torch.cuda.device(dev):
         for L in stages:
             conv = L.pop("conv")
-            L["w"] = conv.weight.detach().float().contiguous()
-            L["s_w"] = conv.weight_quantizer.scale.detach().float().reshape(-1).contiguous()
-            L["bias"] = conv.bias.detach().float().contiguous() if conv.bias is not None else None
+            _iao8_packed_from(L, conv, dev)
             L["s_a"] = scale[id(conv.activation_quantizer)]
             L["s_out"] = [scale[id(o.pop("q"))] for o in L["outs"]]
             L["s_add"] = scale[id(L.pop("add"))] if "add" in L else None
-            L["table"] = torch.empty(L["table_bytes"] // 4, dtype=torch.int32, device=dev)
             s_tab = L["s_add"] if L["api"] == "res_add" else L["s_out"][0]          # the scale of the codes the conv's epilogue forms
             if L["api"] == "i8conv":
-                ops._call("mn_i8conv_pack", C.byref(_res_geom(L)), ops._p(L["w"]), ops._p(L["s_w"]), 1 if L["per_channel"] else 0, ops._p(L["bias"]), L["s_a"], s_tab, s_tab,
+                ops._call("mn_i8conv_pack", C.byref(_block_geom(L)), ops._p(L["w"]), ops._p(L["s_w"]), 1 if L["per_channel"] else 0, ops._p(L["bias"]), L["s_a"], s_tab, s_tab,
                           L["a_bits"], L["w_bits"], None, ops._p(L["table"]), ops._s())
             else:
-                ops._call("mn_i8res_pack", C.byref(_res_geom(L)), ops._p(L["w"]), ops._p(L["s_w"]), 1 if L["per_channel"] else 0, ops._p(L["bias"]), L["s_a"], s_tab,
+                ops._call("mn_i8res_pack", C.byref(_block_geom(L)), ops._p(L["w"]), ops._p(L["s_w"]), 1 if L["per_channel"] else 0, ops._p(L["bias"]), L["s_a"], s_tab,
                           L["in_bits"], L["a_bits"], L["w_bits"], ops._p(L["table"]), ops._s())
         if ends:
             Lf, Ll = ends
             conv, fc = Lf.pop("conv"), Ll.pop("fc")
-            for L, m in ((Lf, conv), (Ll, fc)):
-                L["w"] = m.weight.detach().float().contiguous()
-                L["s_w"] = m.weight_quantizer.scale.detach().float().reshape(-1).contiguous()
-                L["bias"] = m.bias.detach().float().contiguous() if m.bias is not None else None
-                L["table"] = torch.empty(L["table_bytes"] // 4, dtype=torch.int32, device=dev)
+            _iao8_packed_from(Lf, conv, dev)
+            _iao8_packed_from(Ll, fc, dev)
             Lf["s_a"], Lf["s_out"] = scale[id(conv.activation_quantizer)], [o["s"] for o in stem["outs"]]
-            ops._call("mn_i8first_pack", C.byref(_res_geom(Lf)), ops._p(Lf["w"]), ops._p(Lf["s_w"]), 1 if Lf["per_channel"] else 0, ops._p(Lf["bias"]), Lf["s_a"],
+            ops._call("mn_i8first_pack", C.byref(_block_geom(Lf)), ops._p(Lf["w"]), ops._p(Lf["s_w"]), 1 if Lf["per_channel"] else 0, ops._p(Lf["bias"]), Lf["s_a"],
                       Lf["s_out"][0], Lf["in_bits"], Lf["out_bits"][0], Lf["w_bits"], None, ops._p(Lf["table"]), ops._s())
             Ll["s_p"], Ll["s_fc"] = stages[-1]["s_out"][0], scale[id(fc.activation_quantizer)]
             ops._call("mn_i8poolfc_pack", Ll["cin"], Ll["cout"], ops._p(Ll["w"]), ops._p(Ll["s_w"]), 1 if Ll["per_channel"] else 0, ops._p(Ll["bias"]), Ll["s_p"], Ll["s_fc"],
                       Ll["p_bits"], Ll["a_bits"], Ll["w_bits"], ops._p(Ll["table"]), ops._s())
         packed = stages + (list(ends) if ends else [])
-        counters = torch.stack([L["table"][[0, 7]] for L in packed]).tolist()          # ... and every table's two counters in one more
-    for L, (bad, off) in zip(packed, counters):
-        if bad:
-            raise _err("%s: %s: %d rows or scales with a non-finite or non-positive constant (al, bias, s_w, s_a, s_out)" % (who, L["name"], bad))
-        if off:
-            raise _err("%s: %s: %d rows whose stored weights are off the grid k * s_w (run prequantize_weights after iao_model_bn_fuse)" % (who, L["name"], off))
+        counters = _iao8_counters(packed)          # ... and every table's counters in one more
+    for L, row in zip(packed, counters):
+        _iao8_check_counters(who, L["name"], L, row, "s_a, s_out")
         for s in L.get("s_out", []) + ([L["s_add"]] if L.get("s_add") is not None else []):
             if not (math.isfinite(s) and s > 0):
                 raise _err("%s: %s: a consumer's scale %r is not finite and positive" % (who, L["name"], s))
