@@ -1087,6 +1087,32 @@ int mn_conv2d_first_codes(const mn_conv_geom* g, const float* x, const float* w,
 int mn_planesconv1x1_small_supported(int64_t C, int64_t HW, int64_t O, int a_bits);
 int mn_planesconv1x1_small_fwd(const uint32_t* planes, int a_bits, const float* w, const float* bias, float* y, int64_t N, int64_t C, int64_t HW, int64_t O,
                                mn_stream_t stream);
+/* ------------------------------------------------------------------ DoReFa W8A8 hidden blocks on byte maps (csrc/qgemm_codes_w8.h)
+ * What a hidden stage of a pre-quantised DoReFa W8A8 net computes in eval mode -- [channel shuffle] -> QuantConv2d -> BatchNorm -> ReLU -> [2x2 max-pool] -> the next
+ * conv's 8-bit activation quantizer -- with one byte per hidden activation:
+ *   map  : int8 [N][ceil(C/16)][H*W][16], 16-byte aligned; byte d of block cb at a pixel is (code - 128) of channel 16 cb + d, tail channels 0x80 (the code 0).
+ *   acc  : sum j (2k - 255) over the in-bounds taps and the group's channels (j the activation code 0 .. 255, k the weight code: w = (2k - 255) / 255), exact in int32,
+ *          formed as 2 sum a w' + sum a + Kc[o] with a = j - 128, w' = k - 128 on v_mfma_i32_16x16x64_i8 and v_dot4_i32_i8.
+ *   code : the chain of mn_qa_fwd(in_f32 = 0) on float(acc) with the block's [9][O] constants `chan` and s = 1 / 255, element by element (no thresholds); pool == 1:
+ *          the maximum of the window's four post-ReLU values, then the code.  Output byte = code - 128.
+ * Covered (mn_code8conv_supported, which the other three follow): a_bits_in = w_bits = a_bits_out = 8; 1x1 / stride 1 / padding 0 with groups == 1 and any C, or
+ * C / groups % 16 == 0; 3x3 / stride 1 / padding 1 with C / groups % 16 == 0; dilation 1, g->in_shuffle 0 / 1 (a consumer's shuffle is folded into its PRODUCER
+ * through `out_order`); any O; C / groups * KH * KW <= 33025.  Everything else is MN_ENOTSUP, as is pool outside 0 / 1; a null or misaligned tensor (maps and `table`
+ * 16-byte aligned), an invalid geometry (N <= 0, ...) or odd H / W with pool is MN_EINVAL; nothing is written in either case.  No entry allocates.
+ *   pack : w = the stored fp32 weights [O][C/groups][KH][KW] on the grid (2k - 255) / 255, chan as for mn_codeconv_pack, row j computes channel out_order[j] (null:
+ *          identity) -> `table` (private layout, mn_code8conv_table_bytes bytes).  Word 0 counts the rows whose constants are non-finite (or beyond 1e9), word 7 the
+ *          out_order entries out of range plus the rows with a weight off the grid: both 0 for a valid table (the caller may read them back once).  Word 6 =
+ *          8 | 8 << 8 | 8 << 16.
+ *   fwd  : in_codes [N][ceil(C/16)][H*W][16] -> out_codes [N][ceil(O/16)][Ho*Wo][16] (pool == 1: Ho = H / 2, Wo = W / 2).  Every 16-byte block is stored once, whole:
+ *          no atomics, no read-modify-write.  Positions >= O and bad out_order entries yield 0x80 bytes.  mn_last_kernel(): k_code8conv<KS,pool>.
+ * mn_code8_pack_codes: uint8 NCHW codes -> the map (tail channels 0x80); mn_code8_unpack_codes: the map -> uint8 NCHW codes.  N, C, HW > 0, else MN_EINVAL. */
+int mn_code8conv_supported(const mn_conv_geom* g, int a_bits_in, int w_bits, int a_bits_out);
+int64_t mn_code8conv_table_bytes(const mn_conv_geom* g, int a_bits_in, int w_bits, int a_bits_out);
+int mn_code8conv_pack(const mn_conv_geom* g, const float* w, const float* chan, int a_bits_in, int w_bits, int a_bits_out, const int32_t* out_order, uint32_t* table,
+                      mn_stream_t stream);
+int mn_code8conv_fwd(const mn_conv_geom* g, const uint32_t* table, const int8_t* in_codes, int8_t* out_codes, int pool, mn_stream_t stream);
+int mn_code8_pack_codes(const uint8_t* codes, int64_t N, int64_t C, int64_t HW, int8_t* map, mn_stream_t stream);
+int mn_code8_unpack_codes(const int8_t* map, int64_t N, int64_t C, int64_t HW, uint8_t* codes, mn_stream_t stream);
 /* ------------------------------------------------------------------ int8 deployment of the BN-folded IAO hidden blocks: byte codes on v_mfma_i32_16x16x64_i8
  * What a hidden stage of a BN-folded, pre-quantised IAO net computes in eval mode -- [channel shuffle] -> QuantConv2d -> ReLU -> [QuantMaxPool2d 2x2 / 2] -> the next
  * conv's activation quantizer, every quantizer symmetric (zero point 0), code widths 2 .. 8 -- on byte codes:

@@ -22,6 +22,10 @@ The results are ordinary modules of this package: in eval mode they run on the s
     thresholds per channel).  One kernel per hidden block, packed codes in, packed codes out; same codes in every hidden stage as the eval-mode model.
     ``tile_blocks=True`` adds plain ``nin``: its dense 5x5 block on an LDS tile and its 3x3 / stride 2 max-pools on the planes.
 
+  * ``dorefa_compile_bytes``: a pre-quantised DoReFa W8A8 ``quant_inference=True`` net -- the reference's CPU configuration -- compiled into a flat plan that keeps
+    ONE BYTE per hidden activation (``csrc/qgemm_codes_w8.h``: activation and weight codes as offset bytes on v_mfma_i32_16x16x64_i8, the block's fp32 chain evaluated
+    on the exact int32 sum).  One kernel per hidden block; the two ends stay on the model's own modules.
+
   * ``iao_compile_int8``: the BN-folded, pre-quantised symmetric IAO graph compiled into a flat plan that keeps ONE INT8 CODE per hidden activation
     (``csrc/qgemm_iao8.h``: byte codes against weight-code bytes on v_mfma_i32_16x16x64_i8, bias + ReLU + [2x2 max-pool] + the consumer's quantizer in the epilogue).
     One kernel per hidden block; the two ends stay on the model's own modules.  A BN-folded IAO ResNet compiles by the same call (``csrc/qgemm_iao8_res.h``: strided
@@ -1108,6 +1112,232 @@ def dorefa_compile_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=
     if nonfinite:
         raise _err("dorefa_compile_codes(code_ends=True): %s.bn: %d output channels with a non-finite (or beyond 1e9) BatchNorm constant: no thresholds" % (nm, nonfinite))
     return CodePlan(first, layers, last, tail, flatten, report, code_ends=True, first_table=table, first_chan=chan)
+
+
+# ------------------------------------------------------------------------------------------------ byte deployment of DoReFa W8A8 nets (csrc/qgemm_codes_w8.h)
+BYTE_BITS = 8          # the one width of the byte blocks: a_bits = w_bits = 8
+
+
+def _code8conv_kernel_name(k, pool):
+    """The kernel mn_code8conv_fwd reports for a hidden block (csrc/qgemm_codes_w8.h)."""
+    return "k_code8conv<%d,%d>" % (k, pool)
+
+
+def pack_code_map(t):
+    """uint8 8-bit activation codes [N, C, H, W] (or an 8-bit QActTensor) -> the byte map of the W8A8 blocks: int8 [N, ceil(C / 16), H * W, 16], byte = code - 128,
+    tail channels 0x80 (the code 0)."""
+    from micronet_amd import ops
+    from micronet_amd.sign_tensor import QActTensor
+    if isinstance(t, QActTensor) and t.bits == BYTE_BITS:
+        t = t.codes
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 4):
+        raise _err("pack_code_map: needs an 8-bit QActTensor or a uint8 code tensor [N, C, H, W] on the GPU (no CPU fallback)")
+    c = t.contiguous()
+    N, Cc, H, W = c.shape
+    m = _code_map(N, Cc, H * W, c.device)
+    ops._call("mn_code8_pack_codes", ops._p(c), N, Cc, H * W, ops._p(m), ops._s())
+    return m
+
+
+def unpack_code_map(m, C_, H, W):
+    """The inverse of ``pack_code_map``: uint8 codes [N, C, H, W]."""
+    from micronet_amd import ops
+    if not (torch.is_tensor(m) and m.dim() == 4 and _is_code_map(m, m.shape[0], int(C_), int(H) * int(W))):
+        raise _err("unpack_code_map: needs an int8 byte map [N, ceil(C / 16), H * W, 16] on the GPU")
+    m = m.contiguous()
+    out = torch.empty((m.shape[0], int(C_), int(H), int(W)), dtype=torch.uint8, device=m.device)
+    ops._call("mn_code8_unpack_codes", ops._p(m), m.shape[0], int(C_), int(H) * int(W), ops._p(out), ops._s())
+    return out
+
+
+class Byte8Plan(_Plan):
+    """What ``dorefa_compile_bytes`` returns: first block (fp32 conv + BatchNorm + ReLU + the next conv's 8-bit quantizer, the model's own module) -> byte-map pack -> n
+    byte blocks (2x2 max-pools folded in) -> unpack -> last block and tail (the model's own modules).  Eval only; owns the packed weight tables (and the per-channel
+    constants they were packed from: ``layers[i]["chan"]``) and one set of byte maps [N, ceil(C / 16), H * W, 16] (byte = code - 128) per input shape.
+    ``keep_stages``: forward leaves a copy of every stage's map in ``stage_codes``."""
+
+    who = "dorefa_compile_bytes"
+
+    def __init__(self, first, layers, last, tail, flatten, report):
+        super().__init__(first, layers, last, tail, flatten, report)          # layers: dicts of geometry, table, chan, pool, out_order
+        self.stage_codes = []
+
+    def _plan_buffers(self, shape, device):
+        """The byte maps, the geometry of every block and the uint8 buffer in front of the last block, for one first-block output shape."""
+        N, Cc, H, W = shape
+        bufs, geoms = [_code_map(N, Cc, H * W, device)], []
+        for L in self.layers:
+            geoms.append(_block_geom(L, N, H, W))
+            if L["pool"]:
+                if H % 2 or W % 2:
+                    raise _err("dorefa_compile_bytes: %s: the 2x2 max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
+                H, W = H // 2, W // 2
+            bufs.append(_code_map(N, L["cout"], H * W, device))
+            Cc = L["cout"]
+        return bufs, geoms, torch.empty((N, Cc, H, W), dtype=torch.uint8, device=device)
+
+    @torch.no_grad()
+    def forward(self, x):
+        from micronet_amd import ops
+        from micronet_amd.sign_tensor import QActTensor
+        a = self.first(x)
+        if not (isinstance(a, QActTensor) and a.bits == BYTE_BITS):
+            raise _err("dorefa_compile_bytes: %s did not hand over 8-bit activation codes (the input must be a contiguous float32 GPU tensor with H * W %% 8 == 0)"
+                       % self.report[0]["name"])
+        codes = a.codes.contiguous()
+        N, Cc, H, W = codes.shape
+        with torch.cuda.device(codes.device):
+            bufs, geoms, c8 = self._shape_buffers(codes.shape, codes.device)
+            st = ops._s()
+            ops._call("mn_code8_pack_codes", ops._p(codes), N, Cc, H * W, ops._p(bufs[0]), st)
+            for i, L in enumerate(self.layers):          # one launch per hidden block
+                ops._call("mn_code8conv_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(bufs[i + 1]), int(L["pool"]), st)
+            if self.keep_stages:
+                self.stage_codes = [b.clone() for b in bufs]
+            n_, c_, h_, w_ = c8.shape
+            ops._call("mn_code8_unpack_codes", ops._p(bufs[-1]), n_, c_, h_ * w_, ops._p(c8), st)
+        # (materialize: a consumer that does not read codes re-quantises 10 j s to j -- the middle of the code's bin)
+        return self._finish(self.last(QActTensor(c8, BYTE_BITS, lambda: c8.float() * (10.0 / 255.0))))
+
+
+def _walk_bytes(model):
+    """The graph walk of ``dorefa_compile_bytes`` (no GPU needed): (first, layers, last, tail, flatten, report).  It accepts what ``_walk_codes`` accepts without its
+    flags -- the first block on the fp32 first conv handing over codes, conv -> BatchNorm -> ReLU hidden blocks with fused 2x2 max-pools and channel shuffles folded
+    into the producer, a last block -- at a_bits = w_bits = 8 in every quantised block."""
+    from micronet_amd import _lib
+    from micronet_amd.nn import Conv2dFirst
+    from micronet_amd.quantization.wqaq.dorefa import quantize
+    who, B = "dorefa_compile_bytes", BYTE_BITS
+    seq, prefix, flatten = _net_sequence(model, who)
+    blocks = [(prefix + n_, m) for n_, m in seq.named_children() if quantize._is_ref_block(m) and isinstance(getattr(m, "conv", None), nn.Conv2d)]
+    if len(blocks) < 3:
+        raise _err("%s: module order not recognised (needs a first block, at least one quantised hidden block and a last block)" % who)
+    for nm, blk in blocks[1:]:
+        conv = blk.conv
+        if not isinstance(conv, quantize.QuantConv2d):
+            raise _err("%s: %s.conv is not a DoReFa QuantConv2d" % (who, nm))
+        ab, wb = conv.activation_quantizer.a_bits, conv.weight_quantizer.w_bits
+        if (ab, wb) != (B, B):
+            raise _err("%s: %s.conv has a_bits = %d, w_bits = %d; only W8A8 nets are deployed on bytes, every quantised block at 8 bits (a W2A2 or W4A4 net: "
+                       "dorefa_compile_codes)" % (who, nm, ab, wb))
+        if not conv.quant_inference:
+            raise _err("%s: %s.conv is not a quant_inference=True layer (prepare(..., quant_inference=True), then prequantize_weights)" % (who, nm))
+    for nm, blk in blocks[1:-1]:
+        conv = blk.conv
+        if tuple(conv.stride) != (1, 1) or tuple(conv.dilation) != (1, 1) or conv.padding_mode != "zeros" or isinstance(conv.padding, str):
+            raise _err("%s: %s.conv: stride / dilation other than 1 (or non-zero padding mode) is not covered by the byte kernels" % (who, nm))
+        if not _lib.get_lib().mn_code8conv_supported(C.byref(_conv_geom(conv)), B, B, B):
+            ks, cg = tuple(conv.kernel_size), conv.in_channels // conv.groups
+            raise _err("%s: %s.conv: geometry not covered by mn_code8conv_supported (%dx%d, padding %d, groups %d, %d channels per group: needs 1x1 / padding 0 that is "
+                       "dense or has C / groups %% 16 == 0, or 3x3 / padding 1 with C / groups %% 16 == 0, and C / groups * taps <= 33025)"
+                       % (who, nm, ks[0], ks[1], conv.padding[0], conv.groups, cg))
+    first = last = None
+    layers, tail, report = [], [], []
+    for name, child in seq.named_children():
+        nm = prefix + name
+        if last is not None:
+            tail.append(child)
+            continue
+        if isinstance(child, nn.MaxPool2d):
+            if _pool_kind(child) != (2, 2, 0):
+                raise _err("%s: %s: max-pool (kernel %s, stride %s, padding %s, ceil_mode %s) is not covered by the byte kernels (2x2 / 2 / 0, floor mode)"
+                           % (who, nm, child.kernel_size, child.stride, child.padding, child.ceil_mode))
+            if not layers or layers[-1]["pool"] or not getattr(child, "_mn_fused_pool", False):
+                raise _err("%s: %s: a 2x2 max-pool is folded only into the byte block directly in front of it" % (who, nm))
+            layers[-1]["pool"], layers[-1]["stage"] = 1, name
+            continue
+        if not any(child is b for _, b in blocks):
+            raise _err("%s: %s (%s): module order not recognised (expected conv -> bn -> relu blocks and 2x2 max-pools up to the last block)" % (who, nm, type(child).__name__))
+        conv, bn = child.conv, getattr(child, "bn", None)
+        if not isinstance(bn, quantize.BatchNorm2dReLU):
+            raise _err("%s: %s: conv -> BatchNorm -> ReLU not fused (prepare(..., fuse_bn_act=True, fuse_blocks=True))" % (who, nm))
+        K = conv.in_channels // conv.groups * conv.kernel_size[0] * conv.kernel_size[1]
+        if first is None:
+            if type(conv) is not Conv2dFirst or getattr(child, "channel_shuffle_flag", 0):
+                raise _err("%s: %s: the first block must be the fp32 first conv" % (who, nm))
+            if bn.q_out_bits != B or bn.q_pool:
+                raise _err("%s: %s: the first block must hand over un-pooled 8-bit activation codes (it emits %s%s)"
+                           % (who, nm, ("%d-bit codes" % bn.q_out_bits) if bn.q_out_bits else "fp32", ", pooled" if bn.q_pool else ""))
+            first = child
+            report.append(dict(name=nm, kind="first", K=K, blocks=0, kernel="first conv + k_qa_fwd, k_code8_pack", pooled=False, out_order="identity", stage=name))
+            continue
+        shuffle = _shuffle_in_front(who, nm, child, conv)
+        if child is blocks[-1][1]:
+            if shuffle:
+                raise _err("%s: %s: a channel shuffle in front of the last block is not covered" % (who, nm))
+            last = child
+            rep_last = dict(name=nm, kind="last", K=K, blocks=(conv.in_channels + 15) // 16, kernel="k_code8_unpack, last block on byte codes", pooled=False,
+                            out_order="identity", stage=name)
+            continue
+        # ---- a hidden block: conv on bytes -> bn -> relu -> [pool] -> the next conv's quantizer
+        if bn.q_out_bits != B:
+            raise _err("%s: %s: its output is not handed over as 8-bit codes to the next quantised conv" % (who, nm))
+        if shuffle:
+            _check_shuffle_divides(who, nm, conv, shuffle)
+            if not layers:
+                raise _err("%s: %s: a channel shuffle directly behind the first block is not covered (its producer is not a byte block)" % (who, nm))
+            layers[-1]["shuffle"] = shuffle          # folded into the producer's row order
+        layers.append(dict(name=nm, conv=conv, bn=bn, k=conv.kernel_size[0], pad=conv.padding[0], cin=conv.in_channels, cout=conv.out_channels, groups=conv.groups,
+                           pool=0, want_pool=bool(bn.q_pool), shuffle=0, stage=name))
+    if first is None or last is None:
+        raise _err("%s: module order not recognised (no %s block found)" % (who, "first" if first is None else "last"))
+    for L in layers:
+        if L.pop("want_pool") != bool(L["pool"]):
+            raise _err("%s: %s: the block pools its output but no 2x2 max-pool follows it (or the reverse)" % (who, L["name"]))
+        report.append(dict(name=L["name"], kind="byte", K=L["cin"] // L["groups"] * L["k"] * L["k"], blocks=(L["cin"] + 15) // 16,
+                           kernel=_code8conv_kernel_name(L["k"], L["pool"]), pooled=bool(L["pool"]),
+                           out_order=("shuffle %d" % L["shuffle"]) if L["shuffle"] > 1 else "identity", stage=L["stage"]))
+    report.append(rep_last)
+    return first, layers, last, tail, flatten, report
+
+
+def dorefa_bytes_report(model):
+    """The ``report`` ``dorefa_compile_bytes(model)`` would carry -- one row per stage: name, kind ("first" / "byte" / "last"), K, blocks (16-channel blocks of the
+    stage's input map), kernel, pooled, out_order, stage -- from the graph walk alone: no GPU, nothing packed.  Raises like ``dorefa_compile_bytes``."""
+    return _walk_bytes(model)[5]
+
+
+@torch.no_grad()
+def dorefa_compile_bytes(model):
+    """``model``: a DoReFa W8A8 net -- the reference's CPU configuration -- prepared with ``quant_inference=True`` after ``prequantize_weights``, on the GPU (the
+    reference's ``nin_gc``, or an ``nn.Sequential`` of the same block kinds).  Returns a ``Byte8Plan`` that keeps ONE BYTE per hidden activation
+    (``csrc/qgemm_codes_w8.h``: activation and weight codes as offset bytes on v_mfma_i32_16x16x64_i8, the block's BatchNorm + ReLU + [pool] + quantizer evaluated on
+    the exact int32 sum); ``.report`` lists the stages.  Where the model's own 8-bit eval forward rounds its fp32 accumulation, a code may differ from the plan's by
+    one step.  Anything the byte kernels do not cover raises ``MicronetHipError`` naming the layer and the rule."""
+    from micronet_amd import _lib, ops
+    from micronet_amd.quantization.wqaq.dorefa.quantize import _weight_is_coded
+    first, layers, last, tail, flatten, report = _walk_bytes(model)
+    for L in layers:
+        if not _weight_is_coded(L["conv"]):
+            raise _err("dorefa_compile_bytes: %s.conv: the stored weights were not found on the 8-bit grid (2k - 255) / 255 (run inference.prequantize_weights on the GPU "
+                       "model first)" % L["name"])
+    _require_gpu(model, "dorefa_compile_bytes")
+    lib, B = _lib.get_lib(), BYTE_BITS
+    for L in layers:
+        conv, bn = L.pop("conv"), L.pop("bn")
+        dev = conv.weight.device
+        if not (bn.affine and bn.track_running_stats and bn.momentum is not None):
+            raise _err("dorefa_compile_bytes: %s.bn: needs affine parameters, running statistics and a momentum" % L["name"])
+        with torch.cuda.device(dev):
+            # the [9][O] constants of the block's eval-mode BatchNorm (as dorefa_compile_codes obtains them for a block the stash conv does not cover); rows alpha / bias
+            # become the epilogue's: alpha = fl(1/255 * 1/255), the fp32 product of the weight and the activation scale
+            chan = _bn_chan_constants(bn, L["cout"], ops._chk(bn.weight.detach(), "weight"), ops._chk(bn.bias.detach(), "bias"))
+            sc = torch.tensor(1.0 / 255.0, dtype=torch.float32, device=dev)
+            chan[0] = sc * sc
+            chan[1] = conv.bias.detach().float() if conv.bias is not None else 0.0
+            chan[6], chan[7] = chan[0] * chan[3], (chan[1] - chan[2]) * chan[3]
+            g = _block_geom(L)
+            table = torch.empty(int(lib.mn_code8conv_table_bytes(C.byref(g), B, B, B)) // 4, dtype=torch.int32, device=dev)
+            order = _shuffle_order(L["cout"], L["shuffle"], dev) if L["shuffle"] > 1 else None
+            ops._call("mn_code8conv_pack", C.byref(g), ops._p(conv.weight.detach().float().contiguous()), ops._p(chan), B, B, B, ops._p(order), ops._p(table), ops._s())
+        L["table"], L["chan"], L["out_order"] = table, chan, order
+    for L in layers:          # (compile time: the one place a host read-back is allowed)
+        nonfinite, bad = int(L["table"][0]), int(L["table"][7])
+        if nonfinite:
+            raise _err("dorefa_compile_bytes: %s.bn: %d output channels with a non-finite (or beyond 1e9) BatchNorm constant" % (L["name"], nonfinite))
+        if bad:
+            raise _err("dorefa_compile_bytes: %s.conv: %d table rows with a weight off the 8-bit grid or a bad channel order" % (L["name"], bad))
+    return Byte8Plan(first, layers, last, tail, flatten, report)
 
 
 # ------------------------------------------------------------------------------------------------ int8 deployment of the BN-folded IAO graph (csrc/qgemm_iao8.h)
