@@ -1113,6 +1113,25 @@ int mn_code8conv_pack(const mn_conv_geom* g, const float* w, const float* chan, 
 int mn_code8conv_fwd(const mn_conv_geom* g, const uint32_t* table, const int8_t* in_codes, int8_t* out_codes, int pool, mn_stream_t stream);
 int mn_code8_pack_codes(const uint8_t* codes, int64_t N, int64_t C, int64_t HW, int8_t* map, mn_stream_t stream);
 int mn_code8_unpack_codes(const int8_t* map, int64_t N, int64_t C, int64_t HW, uint8_t* codes, mn_stream_t stream);
+/* The two ends of the W8A8 byte plan on the byte map (inference.dorefa_compile_bytes(model, byte_ends=True)).
+ *   first : map = (the 8-bit code of relu(bn(conv(x, w) + bias))) - 128 of the un-quantised first block, in ONE launch.  The accumulation is the first-layer forward's
+ *           (k_c1b_fwd), so the value that is coded is its y bit for bit, and the code is the one mn_qa_fwd(in_f32 = 1, a_bits = 8) gives for that y: the chain itself
+ *           is evaluated per element (no thresholds, no finiteness gate -- non-finite constants or a NaN bias give what that entry point gives).  chan = the [9][O]
+ *           constants of mn_qa_chan_from_save (rows 2 .. 5 are read), read directly: there is no table.  map: int8 [N][ceil(O/16)][H*W][16], 16-byte aligned; every
+ *           16-byte block is stored once and whole, channels >= O are 0x80; neither y nor uint8 codes are written.  Covered: what
+ *           mn_conv2d_first_sign_bits_supported covers (the image strip under the same LDS cap); more than 128 output channels run as channel blocks of 128.  Null /
+ *           misaligned tensor or an invalid geometry (N <= 0, ...): MN_EINVAL; a valid geometry that is not covered: MN_ENOTSUP.  Nothing is written in either case.
+ *           mn_last_kernel(): k_c1b_fwd<MT,5>, MT = 1 (O <= 64) or 2.
+ *   last  : y [N][O][H*W] = fl(fl((float)acc * alpha[o]) + bias[o]) of the last quantised conv read from the byte map, acc the exact int32 sum of mn_code8conv_fwd;
+ *           plain NCHW fp32, no ReLU (BatchNorm and ReLU stay with the caller).  `table` is mn_code8conv_pack's for this geometry with a_bits_out = 8, chan rows 0 / 1 =
+ *           alpha / bias (the other rows are not read: pass the identity) and a NULL out_order.  Covered (mn_code8conv_f32_supported): what mn_code8conv_supported
+ *           covers with KH = KW = 1 and groups == 1 -- any C <= 33025, any O.  table and in_codes 16-byte aligned, y 4-byte aligned; null / misaligned / invalid
+ *           geometry: MN_EINVAL, not covered: MN_ENOTSUP, nothing written in either case.  Channels >= O and pixels >= N H W are never written.  mn_last_kernel():
+ *           k_code8conv_f32. */
+int mn_conv2d_first_bytes_supported(const mn_conv_geom* g);
+int mn_conv2d_first_bytes(const mn_conv_geom* g, const float* x, const float* w, const float* bias, const float* chan, int8_t* map, mn_stream_t stream);
+int mn_code8conv_f32_supported(const mn_conv_geom* g);
+int mn_code8conv_fwd_f32(const mn_conv_geom* g, const uint32_t* table, const int8_t* in_codes, float* y, mn_stream_t stream);
 /* ------------------------------------------------------------------ int8 deployment of the BN-folded IAO hidden blocks: byte codes on v_mfma_i32_16x16x64_i8
  * What a hidden stage of a BN-folded, pre-quantised IAO net computes in eval mode -- [channel shuffle] -> QuantConv2d -> ReLU -> [QuantMaxPool2d 2x2 / 2] -> the next
  * conv's activation quantizer, every quantizer symmetric (zero point 0), code widths 2 .. 8 -- on byte codes:

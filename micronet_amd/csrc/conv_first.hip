@@ -59,7 +59,8 @@ struct C1Params {
     const float* bn_save; // [2][O] mean, invstd
     const float* bn_gamma;
     const float* bn_beta;
-    void* codes;          // EPI 1: int8 sign codes; EPI 2: uint8 codes of the next conv's a-bit quantizer
+    void* codes;          // EPI 1: int8 sign codes; EPI 2: uint8 codes of the next conv's a-bit quantizer; EPI 5: the byte map int8 [N][ceil(O / 16)][H W][16] of the
+                          // 8-bit DoReFa code - 128 (qgemm_codes_w8.h), with `chan` and `qs`, nothing else written
     uint8_t* mask4;       // [N][O][H W / 4]: low nibble = pass bits of 4 consecutive pixels (EPI 1: |z| < 1; EPI 2: z > 0), high nibble (EPI 2): ... and the clamp test
     int mask_shift;       // backward: which nibble (4: the gradient is w.r.t. the QUANTISED activation)
     uint32_t* bits;       // k_c1b_fwd<MT, EPI 3>: sign(conv + bias) as activation bits [N][ceil(O / 32)][H][W] (qgemm_bits.hip), nothing else written
@@ -214,6 +215,7 @@ __global__ __launch_bounds__(256, 2) void k_c1_fwd(const C1Params p) {
 constexpr float C1C_S = (float)(1.0 / 3.0);          // dorefa_scale(2): the scale of the 2-bit code EPI 4 writes
 #define C1B_KP 96            // padded K (3 K steps of 32)
 #define C1B_LD 104           // u16 per im2col row: 96 + 8 pad (208-byte rows: the 16 rows of a fragment read cover all banks)
+#define C1Y_LD 68            // EPI 5: floats per parked channel row, 64 pixels + 4 pad (16-byte aligned quads; the transposed read walks consecutive words)
 template <int MT, int EPI = 0>
 __global__ __launch_bounds__(256, 2) void k_c1b_fwd(const C1Params p) {
     HIP_DYNAMIC_SHARED(float, smem)
@@ -222,6 +224,7 @@ __global__ __launch_bounds__(256, 2) void k_c1b_fwd(const C1Params p) {
     uint16_t* x2 = reinterpret_cast<uint16_t*>(x01 + p.C * p.CS + 1);                               // [C CS + 1] term 2
     uint16_t* im = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(smem) + p.xt_bytes);          // [3 terms][64][C1B_LD]
     int* ktab = reinterpret_cast<int*>(im + 3 * 64 * C1B_LD);                                      // [96] patch offset of im2col row k (-1: padding)
+    static_assert(EPI != 5 || 4 * 16 * MT * C1Y_LD * 4 <= 3 * 64 * C1B_LD * 2, "EPI 5 parks 64 MT channels x 64 pixels in the im2col tile: MT <= 2");
     const int tid = threadIdx.x, lane = tid & 63, wave = mn_uniform(tid >> 6), j = lane & 15, kg = lane >> 4;
     uint32_t b = blockIdx.x;
     const int strip = b % p.strips; b /= p.strips;
@@ -248,6 +251,11 @@ __global__ __launch_bounds__(256, 2) void k_c1b_fwd(const C1Params p) {
         for (int i = tid; i < 64 * MT; i += 256) {
             const int m = cblk * 64 * MT + i, mc = m < p.O ? m : p.O - 1;
             bc[i] = make_float4(p.bn_save[mc], p.bn_save[p.O + mc], p.bn_gamma[mc], p.bn_beta[mc]);
+        }
+    if (EPI == 5)          // (the same bytes) rows 2 .. 5 of the block's [9][O] constants: mean, invstd, gamma, beta
+        for (int i = tid; i < 64 * MT; i += 256) {
+            const int m = cblk * 64 * MT + i, mc = m < p.O ? m : p.O - 1;
+            bc[i] = make_float4(p.chan[2 * p.O + mc], p.chan[3 * p.O + mc], p.chan[4 * p.O + mc], p.chan[5 * p.O + mc]);
         }
     // A fragments: three exact bf16 terms of w[m0 + t * 16 + j][ks * 32 + kg * 8 .. + 7].  The block's weight rows are one contiguous range: they come through LDS
     // (the tile buffer, not yet in use: 128 rows x K <= 76 floats fit) the rows of WR waves per round, read from memory coalesced -- a lane fetching its 24 MT
@@ -519,6 +527,50 @@ __global__ __launch_bounds__(256, 2) void k_c1b_fwd(const C1Params p) {
                     }
                     if (gw < OW && px < npix) p.planes[(((int64_t)n * OW + gw) * 2 + pl) * p.H * p.W + row0 * p.W + px] = word;
                 }
+            }
+            continue;
+        }
+        if (EPI == 5) {
+            // the 8-bit DoReFa code of the plain epilogue's acc + bb as the byte map of qgemm_codes_w8.h (int8 [N][ceil(O / 16)][H W][16], byte = code - 128), neither y
+            // nor uint8 codes written.  255 thresholds per channel do not fit LDS, so the chain itself -- qa_code_of<1>, what k_qa_fwd<1, 0, 0> runs -- is evaluated per
+            // element, whatever the constants are.  After the MFMAs a lane holds 4 channels x 4 pixels per tile; a 16-byte block wants 16 channels of ONE pixel.  Every
+            // wave parks its 16 MT channels x 64 pixels (+ bias) in its own part of the im2col tile -- all waves are past their MFMAs behind this barrier, the next
+            // expand is behind the one at the top of the loop -- and reads them back transposed: lane = pixel, one 16-channel block per trip of a ROLLED loop (the
+            // chain's division unrolled over the accumulators is what spilled in EPI 4).  A wave reads only what it wrote itself: a wave barrier in between, no second
+            // block barrier.  Each block is assembled in four registers and stored once and whole, consecutive lanes = consecutive pixels (1 KB per wave and block).
+            __syncthreads();
+            float* const wst = reinterpret_cast<float*>(im) + wave * (16 * MT * C1Y_LD);
+#pragma unroll
+            for (int t = 0; t < MT; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = t * 16 + kg * 4 + r;
+                    const float bb = bs[ch0 + row];
+                    *reinterpret_cast<f32x4*>(wst + row * C1Y_LD + 4 * j) = f32x4{acc[0][t][r] + bb, acc[1][t][r] + bb, acc[2][t][r] + bb, acc[3][t][r] + bb};
+                }
+            MN_WAVE_SYNC();
+            const int px = chunk * 64 + lane, OB = (p.O + 15) >> 4;
+            u32x4* const map = reinterpret_cast<u32x4*>(p.codes);
+#pragma unroll 1
+            for (int i = 0; i < MT; ++i) {
+                const int gb = (cblk * 4 + wave) * MT + i;          // the 16-channel block of the map
+                u32x4 v = u32x4{0u, 0u, 0u, 0u};
+#pragma unroll 1
+                for (int dw = 0; dw < 4; ++dw) {
+                    uint32_t word = 0u;
+#pragma unroll 1
+                    for (int e = 0; e < 4; ++e) {
+                        const int row = i * 16 + dw * 4 + e;
+                        const float4 c = bc[ch0 + row];
+                        QaCh k;
+                        k.alpha = 1.f; k.bias = 0.f; k.mean = c.x; k.invstd = c.y; k.ga = c.z; k.be = c.w; k.A = 0.f; k.B = 0.f; k.gi = 0.f;
+                        // channels beyond O: the code 0 (the tail bytes of the last block are 0x80)
+                        const uint32_t code = gb * 16 + dw * 4 + e < p.O ? qa_code_of<1>(wst[row * C1Y_LD + lane], k, p.qs) : 0u;
+                        word = (word >> 8) | ((code ^ 0x80u) << 24);
+                    }
+                    v = u32x4{v[1], v[2], v[3], word};          // (a rolled loop cannot index registers: the four dwords rotate into place)
+                }
+                if (gb < OB && px < npix) map[((int64_t)n * OB + gb) * (p.H * p.W) + row0 * p.W + px] = v;
             }
             continue;
         }
@@ -1205,9 +1257,10 @@ static size_t c1b_codes_fit_bytes(const C1Params& p) {          // c1b_fit_bytes
 static size_t c1b_codes_lds_bytes(const C1Params& p) { return c1b_codes_fit_bytes(p) - p.xs_bytes + p.xt_bytes; }
 // k_c1b_fwd<4, 4> does not fit the register file (124 bytes of scratch per lane; <1 .. 3, 4>: none) and is not built: more than 192 output channels run as blocks of
 // 128 on <2, 4> -- the same accumulation per channel, the image strip expanded once more per extra block
-static int plan_c1_codes(const mn_conv_geom* g, C1Plan* pl) {
-    if (!plan_c1(g, pl) || c1b_codes_fit_bytes(pl->p) > 80 * 1024) return 0;
-    if (pl->MT == 4) {
+// plan_c1 under the LDS size `fit` of an epilogue built up to MT = max_mt: a wider first conv runs as channel blocks of 128 on MT = 2
+static int plan_c1_blocks128(const mn_conv_geom* g, C1Plan* pl, size_t (*fit)(const C1Params&), int max_mt) {
+    if (!plan_c1(g, pl) || fit(pl->p) > 80 * 1024) return 0;
+    if (pl->MT > max_mt) {
         pl->MT = 2;
         pl->cblks = (g->O + 127) / 128;
         pl->p.Opad = pl->cblks * 128;
@@ -1217,6 +1270,7 @@ static int plan_c1_codes(const mn_conv_geom* g, C1Plan* pl) {
     }
     return 1;
 }
+static int plan_c1_codes(const mn_conv_geom* g, C1Plan* pl) { return plan_c1_blocks128(g, pl, c1b_codes_fit_bytes, 3); }
 int c1_codes_supported(const mn_conv_geom* g, int a_bits_out) {
     C1Plan pl;
     return a_bits_out == 2 && plan_c1_codes(g, &pl);
@@ -1249,6 +1303,32 @@ int c1_fwd_codes(const mn_conv_geom* g, const float* x, const float* w, const fl
 #undef C1B_LAUNCH
     mn_prof_end(s);
     MN_CHECK_LAUNCH("mn_conv2d_first_codes");
+    return MN_OK;
+}
+// the deployed first block of a DoReFa W8A8 net (inference.dorefa_compile_bytes(byte_ends=True)): the 8-bit code of relu(bn(conv + bias)) straight to the byte map of
+// qgemm_codes_w8.h.  k_c1b_fwd<MT, 5> parks the block's accumulators in the im2col tile, which holds 128 channels x 64 pixels: more than 128 output channels run as
+// blocks of 128 on <2, 5> -- the same accumulation per channel, the image strip expanded once more per extra block (the rule of plan_c1_codes above 192).  The LDS
+// layout is the plain forward's (the four chain constants take the place of the fused block's BatchNorm constants), and so is the cap.
+static int plan_c1_bytes(const mn_conv_geom* g, C1Plan* pl) { return plan_c1_blocks128(g, pl, c1b_fit_bytes, 2); }
+int c1_bytes_supported(const mn_conv_geom* g) {
+    C1Plan pl;
+    return plan_c1_bytes(g, &pl);
+}
+int c1_fwd_bytes(const mn_conv_geom* g, const float* x, const float* w, const float* bias, const float* chan, int8_t* map, hipStream_t s) {
+    C1Plan pl;
+    if (!plan_c1_bytes(g, &pl)) MN_FAIL(MN_ENOTSUP, "mn_conv2d_first_bytes: geometry not covered by the first-layer forward (k_c1b_fwd)");
+    C1Params& p = pl.p;
+    p.x = x; p.bias = bias; p.y = nullptr; p.gy = nullptr; p.part = nullptr; p.dbpart = nullptr; p.want_db = 0; p.da = nullptr;
+    p.relu = 0; p.mm = nullptr; p.mask4 = nullptr; p.wp = w; p.bits = nullptr; p.planes = nullptr; p.ctab = nullptr;
+    p.chan = chan; p.codes = map; p.qs = dorefa_scale(8);
+    const size_t lds_b = c1b_lds_bytes(p);
+    mn_set_last_kernel("k_c1b_fwd<%d,5>", pl.MT);
+    mn_prof_bytes(16.0 * g->N * ((g->O + 15) / 16) * g->H * g->W + 4.0 * g->N * g->C * g->H * g->W);
+    mn_prof_begin(s);
+    if (pl.MT == 2) { raise_lds_limit((const void*)k_c1b_fwd<2, 5>, lds_b); hipLaunchKernelGGL((k_c1b_fwd<2, 5>), dim3(pl.grid_f), dim3(256), lds_b, s, p); }
+    else { raise_lds_limit((const void*)k_c1b_fwd<1, 5>, lds_b); hipLaunchKernelGGL((k_c1b_fwd<1, 5>), dim3(pl.grid_f), dim3(256), lds_b, s, p); }
+    mn_prof_end(s);
+    MN_CHECK_LAUNCH("mn_conv2d_first_bytes");
     return MN_OK;
 }
 int c1_fwd_act(const mn_conv_geom* g, const float* x, const float* w, const float* bias, float* y, int relu, float* mm, void* ws, int64_t ws_bytes, hipStream_t s) {

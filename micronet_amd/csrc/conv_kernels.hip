@@ -1001,6 +1001,18 @@ extern "C" int mn_conv2d_first_codes(const mn_conv_geom* g, const float* x, cons
     if (!mn_conv2d_first_codes_supported(g, 2)) MN_FAIL(MN_ENOTSUP, "mn_conv2d_first_codes: geometry not covered by the first-layer forward (mn_conv2d_first_codes_supported)");
     return c1_fwd_codes(g, x, w, bias, table, planes, (hipStream_t)stream);
 }
+extern "C" int mn_conv2d_first_bytes_supported(const mn_conv_geom* g) {
+    if (!g || check_geom(g, "mn_conv2d_first_bytes_supported") != MN_OK) return 0;
+    return c1_supported(g, 0) && c1_bytes_supported(g);
+}
+extern "C" int mn_conv2d_first_bytes(const mn_conv_geom* g, const float* x, const float* w, const float* bias, const float* chan, int8_t* map, mn_stream_t stream) {
+    int rc = check_geom(g, "mn_conv2d_first_bytes");
+    if (rc) return rc;
+    if (!x || !w || !chan || !map || (((uintptr_t)map) & 15) || (((uintptr_t)x | (uintptr_t)w | (uintptr_t)bias | (uintptr_t)chan) & 3))
+        MN_FAIL(MN_EINVAL, "mn_conv2d_first_bytes: null tensor / map not 16-byte aligned / fp32 tensor not 4-byte aligned");
+    if (!mn_conv2d_first_bytes_supported(g)) MN_FAIL(MN_ENOTSUP, "mn_conv2d_first_bytes: geometry not covered by the first-layer forward (mn_conv2d_first_bytes_supported)");
+    return c1_fwd_bytes(g, x, w, bias, chan, map, (hipStream_t)stream);
+}
 extern "C" int mn_conv2d_bwd_first_mask_gram(const mn_conv_geom* g, const float* da, const uint8_t* mask4, int quant, const float* save, const float* gamma,
                                              const float* w, const float* bias, const double* gram, const float* x, float* dw, float* dbias, float* dgamma,
                                              float* dbeta, void* ws, int64_t ws_bytes, mn_stream_t stream) {

@@ -437,9 +437,10 @@ class BitPlan(_Plan):
         return self._finish(y)
 
 
-def _check_ends(who, first, nm_first, last, nm_last, first_kernel, first_supported, last_kernel, last_supported):
+def _check_ends(who, first, nm_first, last, nm_last, first_kernel, first_supported, last_kernel, last_supported, last_needs="at most 16 outputs"):
     """Both ends must be covered by their kernels -- never a silent byte path.  Shape-independent part (the input shape is checked by the plan).  ``first_supported(g)``
-    / ``last_supported(cin, hw, cout)``: the library's verdicts; ``*_kernel``: the names in the messages."""
+    / ``last_supported(cin, hw, cout)``: the library's verdicts; ``*_kernel``: the names in the messages, ``last_needs``: what the classifier kernel asks beyond 1x1 /
+    stride 1 / no padding / groups 1."""
     conv = first.conv
     if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
         raise _err("%s: %s.conv: padding mode not covered by %s" % (who, nm_first, first_kernel))
@@ -453,8 +454,9 @@ def _check_ends(who, first, nm_first, last, nm_last, first_kernel, first_support
     if not (conv.padding_mode == "zeros" and not isinstance(conv.padding, str) and one(conv.kernel_size, 1) and one(conv.stride, 1) and one(conv.padding, 0) and
             one(conv.dilation, 1) and conv.groups == 1 and last_supported(conv.in_channels, 4, conv.out_channels)):
         raise _err("%s: %s.conv: the last conv is not the small 1x1 classifier %s covers (%dx%d, stride %d, padding %s, groups %d, %d -> %d channels: needs 1x1, stride 1, "
-                   "no padding, groups 1, at most 16 outputs)"
-                   % (who, nm_last, last_kernel, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.padding, conv.groups, conv.in_channels, conv.out_channels))
+                   "no padding, groups 1, %s)"
+                   % (who, nm_last, last_kernel, conv.kernel_size[0], conv.kernel_size[1], conv.stride[0], conv.padding, conv.groups, conv.in_channels, conv.out_channels,
+                      last_needs))
 
 
 def _check_bit_ends(first, nm_first, last, nm_last):
@@ -1154,17 +1156,31 @@ class Byte8Plan(_Plan):
     """What ``dorefa_compile_bytes`` returns: first block (fp32 conv + BatchNorm + ReLU + the next conv's 8-bit quantizer, the model's own module) -> byte-map pack -> n
     byte blocks (2x2 max-pools folded in) -> unpack -> last block and tail (the model's own modules).  Eval only; owns the packed weight tables (and the per-channel
     constants they were packed from: ``layers[i]["chan"]``) and one set of byte maps [N, ceil(C / 16), H * W, 16] (byte = code - 128) per input shape.
-    ``keep_stages``: forward leaves a copy of every stage's map in ``stage_codes``."""
+    ``keep_stages``: forward leaves a copy of every stage's map in ``stage_codes``.  ``byte_ends``: the first conv's kernel writes the first stage's map itself
+    (no fp32 map, no uint8 codes, no pack; ``first_chan`` holds the first block's [9][O] constants) and the last conv reads the last stage's map (no unpack, no
+    uint8 buffer; ``last`` is then the layer dict of the classifier with its packed ``table``); what follows the last conv inside its block, and the tail, run
+    unchanged."""
 
     who = "dorefa_compile_bytes"
 
-    def __init__(self, first, layers, last, tail, flatten, report):
+    def __init__(self, first, layers, last, tail, flatten, report, first_chan=None, last_layer=None):
         super().__init__(first, layers, last, tail, flatten, report)          # layers: dicts of geometry, table, chan, pool, out_order
+        self.byte_ends = last_layer is not None
+        self.first_chan, self.last_layer = first_chan, last_layer
         self.stage_codes = []
 
     def _plan_buffers(self, shape, device):
-        """The byte maps, the geometry of every block and the uint8 buffer in front of the last block, for one first-block output shape."""
+        """The byte maps and the geometry of every block for one first-block output shape; then the uint8 buffer in front of the last block, or with ``byte_ends``
+        the geometries of the two end kernels and the classifier's fp32 output."""
+        from micronet_amd import _lib
         N, Cc, H, W = shape
+        lib, g0 = _lib.get_lib(), None
+        if self.byte_ends:
+            conv = self.first.conv
+            g0 = _conv_geom(conv, N, H, W)          # (Cc is conv.out_channels: forward hands over the first conv's own output shape)
+            if not lib.mn_conv2d_first_bytes_supported(C.byref(g0)):
+                raise _err("dorefa_compile_bytes(byte_ends=True): %s.conv: a %d x %d x %d x %d input is not covered by mn_conv2d_first_bytes (W %% 4 == 0, H * W %% 32 == 0, "
+                           "the image strip in LDS)" % (self.report[0]["name"], N, conv.in_channels, H, W))
         bufs, geoms = [_code_map(N, Cc, H * W, device)], []
         for L in self.layers:
             geoms.append(_block_geom(L, N, H, W))
@@ -1174,12 +1190,43 @@ class Byte8Plan(_Plan):
                 H, W = H // 2, W // 2
             bufs.append(_code_map(N, L["cout"], H * W, device))
             Cc = L["cout"]
-        return bufs, geoms, torch.empty((N, Cc, H, W), dtype=torch.uint8, device=device)
+        if not self.byte_ends:
+            return bufs, geoms, torch.empty((N, Cc, H, W), dtype=torch.uint8, device=device)
+        gl = _block_geom(self.last_layer, N, H, W)
+        if not lib.mn_code8conv_f32_supported(C.byref(gl)):
+            raise _err("dorefa_compile_bytes(byte_ends=True): %s.conv: a %d-channel %d x %d map is not covered by mn_code8conv_fwd_f32" % (self.report[-1]["name"], Cc, H, W))
+        return bufs, geoms, (g0, gl, torch.empty((N, gl.O, H, W), dtype=torch.float32, device=device))          # (the classifier's fp32 output in place of the uint8 buffer)
+
+    def _run_layers(self, bufs, geoms, st):
+        """One launch per hidden block; ``keep_stages``: a copy of every stage's map."""
+        from micronet_amd import ops
+        for i, L in enumerate(self.layers):
+            ops._call("mn_code8conv_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(bufs[i + 1]), int(L["pool"]), st)
+        if self.keep_stages:
+            self.stage_codes = [b.clone() for b in bufs]
+
+    def _forward_ends(self, x):
+        """fp32 image -> mn_conv2d_first_bytes -> the byte blocks -> mn_code8conv_fwd_f32 -> the last block's BatchNorm + ReLU -> tail."""
+        from micronet_amd import ops
+        conv = self.first.conv
+        if not (type(x) is torch.Tensor and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == conv.in_channels):
+            raise _err("dorefa_compile_bytes(byte_ends=True): the input must be a float32 GPU tensor [N, %d, H, W] (no CPU fallback)" % conv.in_channels)
+        x = x.contiguous()
+        with torch.cuda.device(x.device):
+            bufs, geoms, (g0, gl, y) = self._shape_buffers((x.shape[0], conv.out_channels, x.shape[2], x.shape[3]), x.device)
+            st = ops._s()
+            ops._call("mn_conv2d_first_bytes", C.byref(g0), ops._p(x), ops._p(ops._chk(conv.weight.detach(), "weight")), ops._p(ops._chk(conv.bias, "bias")),
+                      ops._p(self.first_chan), ops._p(bufs[0]), st)
+            self._run_layers(bufs, geoms, st)
+            ops._call("mn_code8conv_fwd_f32", C.byref(gl), ops._p(self.last_layer["table"]), ops._p(bufs[-1]), ops._p(y), st)
+        return self._finish(self._after_conv(self.last, self.last.conv, y))          # (BatchNorm + ReLU)
 
     @torch.no_grad()
     def forward(self, x):
         from micronet_amd import ops
         from micronet_amd.sign_tensor import QActTensor
+        if self.byte_ends:
+            return self._forward_ends(x)
         a = self.first(x)
         if not (isinstance(a, QActTensor) and a.bits == BYTE_BITS):
             raise _err("dorefa_compile_bytes: %s did not hand over 8-bit activation codes (the input must be a contiguous float32 GPU tensor with H * W %% 8 == 0)"
@@ -1190,20 +1237,33 @@ class Byte8Plan(_Plan):
             bufs, geoms, c8 = self._shape_buffers(codes.shape, codes.device)
             st = ops._s()
             ops._call("mn_code8_pack_codes", ops._p(codes), N, Cc, H * W, ops._p(bufs[0]), st)
-            for i, L in enumerate(self.layers):          # one launch per hidden block
-                ops._call("mn_code8conv_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(bufs[i + 1]), int(L["pool"]), st)
-            if self.keep_stages:
-                self.stage_codes = [b.clone() for b in bufs]
+            self._run_layers(bufs, geoms, st)
             n_, c_, h_, w_ = c8.shape
             ops._call("mn_code8_unpack_codes", ops._p(bufs[-1]), n_, c_, h_ * w_, ops._p(c8), st)
         # (materialize: a consumer that does not read codes re-quantises 10 j s to j -- the middle of the code's bin)
         return self._finish(self.last(QActTensor(c8, BYTE_BITS, lambda: c8.float() * (10.0 / 255.0))))
 
 
-def _walk_bytes(model):
+def _first_bytes_kernel_name(cout):
+    """The kernel mn_conv2d_first_bytes reports (csrc/conv_first.hip: 64 MT channels per block, more than 128 as blocks of 128)."""
+    return "k_c1b_fwd<%d,5>" % (1 if cout <= 64 else 2)
+
+
+def _check_byte_ends(first, nm_first, last, nm_last):
+    """``byte_ends=True``: ``_check_ends`` for the two byte-map kernels (the walk has already refused a pool behind the first block, other than 8-bit codes out of it,
+    and a channel shuffle in front of the last block)."""
+    from micronet_amd import _lib
+    lib = _lib.get_lib()
+    _check_ends("dorefa_compile_bytes(byte_ends=True)", first, nm_first, last, nm_last, "mn_conv2d_first_bytes", lambda g: lib.mn_conv2d_first_bytes_supported(C.byref(g)),
+                "mn_code8conv_fwd_f32", lambda cin, hw, cout: lib.mn_code8conv_f32_supported(C.byref(_block_geom(dict(cin=cin, cout=cout, k=1, pad=0), 1, 1, hw))),
+                "at most 33025 input channels")
+
+
+def _walk_bytes(model, byte_ends=False):
     """The graph walk of ``dorefa_compile_bytes`` (no GPU needed): (first, layers, last, tail, flatten, report).  It accepts what ``_walk_codes`` accepts without its
     flags -- the first block on the fp32 first conv handing over codes, conv -> BatchNorm -> ReLU hidden blocks with fused 2x2 max-pools and channel shuffles folded
-    into the producer, a last block -- at a_bits = w_bits = 8 in every quantised block."""
+    into the producer, a last block -- at a_bits = w_bits = 8 in every quantised block.  ``byte_ends``: both ends must be covered by their byte-map kernels
+    (``_check_byte_ends``); the first and the last row of the report name them."""
     from micronet_amd import _lib
     from micronet_amd.nn import Conv2dFirst
     from micronet_amd.quantization.wqaq.dorefa import quantize
@@ -1288,31 +1348,61 @@ def _walk_bytes(model):
                            kernel=_code8conv_kernel_name(L["k"], L["pool"]), pooled=bool(L["pool"]),
                            out_order=("shuffle %d" % L["shuffle"]) if L["shuffle"] > 1 else "identity", stage=L["stage"]))
     report.append(rep_last)
+    if byte_ends:
+        _check_byte_ends(first, report[0]["name"], last, rep_last["name"])
+        report[0]["kernel"], rep_last["kernel"] = _first_bytes_kernel_name(first.conv.out_channels), "k_code8conv_f32"
     return first, layers, last, tail, flatten, report
 
 
-def dorefa_bytes_report(model):
-    """The ``report`` ``dorefa_compile_bytes(model)`` would carry -- one row per stage: name, kind ("first" / "byte" / "last"), K, blocks (16-channel blocks of the
-    stage's input map), kernel, pooled, out_order, stage -- from the graph walk alone: no GPU, nothing packed.  Raises like ``dorefa_compile_bytes``."""
-    return _walk_bytes(model)[5]
+def dorefa_bytes_report(model, byte_ends=False):
+    """The ``report`` ``dorefa_compile_bytes(model, byte_ends)`` would carry -- one row per stage: name, kind ("first" / "byte" / "last"), K, blocks (16-channel blocks
+    of the stage's input map), kernel, pooled, out_order, stage -- from the graph walk alone: no GPU, nothing packed.  Raises like ``dorefa_compile_bytes``."""
+    return _walk_bytes(model, byte_ends)[5]
+
+
+def _code8_identity_chan(conv, dev):
+    """The [9][O] constants of a conv alone on 8-bit codes: alpha = fl(1/255 * 1/255), the fp32 product of the weight and the activation scale, the conv's bias, and
+    the rows of an identity BatchNorm."""
+    sc = torch.tensor(1.0 / 255.0, dtype=torch.float32, device=dev)
+    chan = torch.zeros((9, conv.out_channels), dtype=torch.float32, device=dev)
+    chan[0], chan[3], chan[4], chan[8] = sc * sc, 1.0, 1.0, 1.0
+    if conv.bias is not None:
+        chan[1] = conv.bias.detach().float()
+    chan[6], chan[7] = chan[0], chan[1]
+    return chan
+
+
+def _code8_pack(L, conv, chan, order=None):
+    """mn_code8conv_pack of a layer dict's geometry: the table of ``conv``'s stored weights with the constants ``chan``, rows in ``order``."""
+    from micronet_amd import _lib, ops
+    g, B = _block_geom(L), BYTE_BITS
+    table = torch.empty(int(_lib.get_lib().mn_code8conv_table_bytes(C.byref(g), B, B, B)) // 4, dtype=torch.int32, device=conv.weight.device)
+    ops._call("mn_code8conv_pack", C.byref(g), ops._p(conv.weight.detach().float().contiguous()), ops._p(chan), B, B, B, ops._p(order), ops._p(table), ops._s())
+    return table
 
 
 @torch.no_grad()
-def dorefa_compile_bytes(model):
+def dorefa_compile_bytes(model, byte_ends=False):
     """``model``: a DoReFa W8A8 net -- the reference's CPU configuration -- prepared with ``quant_inference=True`` after ``prequantize_weights``, on the GPU (the
     reference's ``nin_gc``, or an ``nn.Sequential`` of the same block kinds).  Returns a ``Byte8Plan`` that keeps ONE BYTE per hidden activation
     (``csrc/qgemm_codes_w8.h``: activation and weight codes as offset bytes on v_mfma_i32_16x16x64_i8, the block's BatchNorm + ReLU + [pool] + quantizer evaluated on
     the exact int32 sum); ``.report`` lists the stages.  Where the model's own 8-bit eval forward rounds its fp32 accumulation, a code may differ from the plan's by
-    one step.  Anything the byte kernels do not cover raises ``MicronetHipError`` naming the layer and the rule."""
-    from micronet_amd import _lib, ops
+    one step.  Anything the byte kernels do not cover raises ``MicronetHipError`` naming the layer and the rule.  ``byte_ends=True``: the first conv
+    writes the first stage's byte map in one launch (``mn_conv2d_first_bytes``) and the classifier conv reads the last stage's map (``mn_code8conv_fwd_f32``: the
+    exact integer sum where the default path accumulates in fp32) -- no fp32 map, no uint8 codes, no pack / unpack launch; same bytes in every stage, logits within
+    the float contract.  Off by default until the gain is measured; with it off nothing changes."""
+    from micronet_amd import ops
     from micronet_amd.quantization.wqaq.dorefa.quantize import _weight_is_coded
-    first, layers, last, tail, flatten, report = _walk_bytes(model)
-    for L in layers:
+    first, layers, last, tail, flatten, report = _walk_bytes(model, byte_ends)
+    last_layer = None
+    if byte_ends:          # the classifier as a layer dict of its own: packed and read back with the others
+        conv = last.conv
+        last_layer = dict(name=report[-1]["name"], conv=conv, k=1, pad=0, cin=conv.in_channels, cout=conv.out_channels, groups=1, pool=0, shuffle=0)
+    for L in layers + ([last_layer] if byte_ends else []):
         if not _weight_is_coded(L["conv"]):
             raise _err("dorefa_compile_bytes: %s.conv: the stored weights were not found on the 8-bit grid (2k - 255) / 255 (run inference.prequantize_weights on the GPU "
                        "model first)" % L["name"])
     _require_gpu(model, "dorefa_compile_bytes")
-    lib, B = _lib.get_lib(), BYTE_BITS
     for L in layers:
         conv, bn = L.pop("conv"), L.pop("bn")
         dev = conv.weight.device
@@ -1322,22 +1412,28 @@ def dorefa_compile_bytes(model):
             # the [9][O] constants of the block's eval-mode BatchNorm (as dorefa_compile_codes obtains them for a block the stash conv does not cover); rows alpha / bias
             # become the epilogue's: alpha = fl(1/255 * 1/255), the fp32 product of the weight and the activation scale
             chan = _bn_chan_constants(bn, L["cout"], ops._chk(bn.weight.detach(), "weight"), ops._chk(bn.bias.detach(), "bias"))
-            sc = torch.tensor(1.0 / 255.0, dtype=torch.float32, device=dev)
-            chan[0] = sc * sc
-            chan[1] = conv.bias.detach().float() if conv.bias is not None else 0.0
+            chan[0], chan[1] = _code8_identity_chan(conv, dev)[:2]
             chan[6], chan[7] = chan[0] * chan[3], (chan[1] - chan[2]) * chan[3]
-            g = _block_geom(L)
-            table = torch.empty(int(lib.mn_code8conv_table_bytes(C.byref(g), B, B, B)) // 4, dtype=torch.int32, device=dev)
             order = _shuffle_order(L["cout"], L["shuffle"], dev) if L["shuffle"] > 1 else None
-            ops._call("mn_code8conv_pack", C.byref(g), ops._p(conv.weight.detach().float().contiguous()), ops._p(chan), B, B, B, ops._p(order), ops._p(table), ops._s())
+            table = _code8_pack(L, conv, chan, order)
         L["table"], L["chan"], L["out_order"] = table, chan, order
-    for L in layers:          # (compile time: the one place a host read-back is allowed)
+    first_chan = None
+    if byte_ends:
+        bn, conv = first.bn, last_layer.pop("conv")
+        if not (bn.affine and bn.track_running_stats and bn.momentum is not None):
+            raise _err("dorefa_compile_bytes(byte_ends=True): %s.bn: needs affine parameters, running statistics and a momentum" % report[0]["name"])
+        with torch.cuda.device(conv.weight.device):
+            # the first block's [9][O] constants, read by the kernel as they are (no table, no finiteness gate: the chain is evaluated itself)
+            first_chan = _bn_chan_constants(bn, first.conv.out_channels, ops._chk(bn.weight.detach(), "weight"), ops._chk(bn.bias.detach(), "bias"))
+            last_layer["chan"], last_layer["out_order"] = _code8_identity_chan(conv, conv.weight.device), None
+            last_layer["table"] = _code8_pack(last_layer, conv, last_layer["chan"])
+    for L in layers + ([last_layer] if byte_ends else []):          # (compile time: the one place a host read-back is allowed)
         nonfinite, bad = int(L["table"][0]), int(L["table"][7])
         if nonfinite:
             raise _err("dorefa_compile_bytes: %s.bn: %d output channels with a non-finite (or beyond 1e9) BatchNorm constant" % (L["name"], nonfinite))
         if bad:
             raise _err("dorefa_compile_bytes: %s.conv: %d table rows with a weight off the 8-bit grid or a bad channel order" % (L["name"], bad))
-    return Byte8Plan(first, layers, last, tail, flatten, report)
+    return Byte8Plan(first, layers, last, tail, flatten, report, first_chan, last_layer)
 
 
 # ------------------------------------------------------------------------------------------------ int8 deployment of the BN-folded IAO graph (csrc/qgemm_iao8.h)

@@ -12,6 +12,15 @@ per hidden block (arithmetic from the shapes: each operand read or written once)
 alternates the default plan (``code_ends=False``: the yardstick) and ``dorefa_compile_codes(I, code_ends=True)`` the same way and reports the per-kernel times of
 the launches replaced (first conv, k_qa_fwd, k_codes_pack, k_codes_unpack, the classifier on byte codes) beside the two new ones.
 
+    python scripts/kbench_codes.py --byte-ends [--batches 256,1024] [--warmup 5] [--iters 20] [--out profiles/codes_w8_ends.json]
+
+is the same protocol on W8A8 nin_gc: the default byte plan (``dorefa_compile_bytes(I)``: the yardstick) against ``dorefa_compile_bytes(I, byte_ends=True)``; the launches
+replaced are the first conv, k_qa_fwd, k_code8_pack, k_code8_unpack and the classifier on uint8 codes, the new ones k_c1b_fwd<2,5> and k_code8conv_f32.  The first
+conv's bytes are equal by construction; the logits may differ within the float contract (the exact integer sum against an fp32 accumulation), so the largest
+difference and the largest logit are recorded beside ``bit_equal``.  The freshly initialised net this tool builds gives all-zero logits (``max_abs_logit`` 0): the
+equality fields then say nothing about the classifier's arithmetic, which tests/test_gpu_codes_w8_ends_plan.py holds to an fp64 judge on trained weights; the
+timings do not depend on the values.
+
     python scripts/kbench_codes.py --arch nin [--batches 256,1024] [--warmup 5] [--iters 20] [--out profiles/codes_nin.json]
 
 is the first protocol on PLAIN nin: ``P = dorefa_compile_codes(I, tile_blocks=True)`` (the dense 5x5 block on an LDS tile, the two 3x3 / 2 max-pools on planes).
@@ -93,20 +102,27 @@ def q(v):
 
 ENDS_REPLACED = ("k_c1b_fwd<", "k_c1_fwd<", "k_qa_fwd", "k_codes_pack", "k_codes_unpack", "k_sconv_fwd")          # the default plan's two ends
 ENDS_NEW = ("k_c1b_fwd<", "k_planesconv1x1_small")
+BYTE_ENDS_REPLACED = ("k_c1b_fwd<", "k_c1_fwd<", "k_qa_fwd", "k_code8_pack", "k_code8_unpack", "k_sconv_fwd")          # the default byte plan's two ends
+BYTE_ENDS_NEW = ("k_c1b_fwd<", "k_code8conv_f32")
 
 
-def main_code_ends(args):
-    """The default plan P0 against the plan with both ends on planes P1, alternated in one process."""
+def main_code_ends(args, byte=False):
+    """The default plan P0 against the plan with both ends on planes (``byte``: W8A8, on the byte map) P1, alternated in one process."""
     from micronet.compression.quantization.wqaq.dorefa import quantize as Q
     from micronet_amd import _lib, inference
     from micronet_amd.train import build_model, synth_batch
     torch.manual_seed(0)
-    I = Q.prepare(build_model("nin_gc"), inplace=True, a_bits=2, w_bits=2, quant_inference=True).cuda()
+    bits, label = (8, "byte_ends") if byte else (2, "code_ends")
+    replaced, new = (BYTE_ENDS_REPLACED, BYTE_ENDS_NEW) if byte else (ENDS_REPLACED, ENDS_NEW)
+    I = Q.prepare(build_model("nin_gc"), inplace=True, a_bits=bits, w_bits=bits, quant_inference=True).cuda()
     inference.prequantize_weights(I)
     I.eval()
-    P0, P1 = inference.dorefa_compile_codes(I), inference.dorefa_compile_codes(I, code_ends=True)
+    if byte:
+        P0, P1 = inference.dorefa_compile_bytes(I), inference.dorefa_compile_bytes(I, byte_ends=True)
+    else:
+        P0, P1 = inference.dorefa_compile_codes(I), inference.dorefa_compile_codes(I, code_ends=True)
     lib = _lib.get_lib()
-    res = dict(model="nin_gc", a_bits=2, w_bits=2, warmup=args.warmup, iters=args.iters, device=torch.cuda.get_device_name(0), report=P1.report, batches={})
+    res = dict(model="nin_gc", a_bits=bits, w_bits=bits, warmup=args.warmup, iters=args.iters, device=torch.cuda.get_device_name(0), report=P1.report, batches={})
     with torch.no_grad():
         for bs in [int(v) for v in args.batches.split(",")]:
             x, _ = synth_batch(bs, device="cuda")
@@ -121,10 +137,12 @@ def main_code_ends(args):
             us = lambda k, names: {n: round(1e3 * v["ms"] / max(1, v["launches"]), 2) for n, v in k.items() if n.startswith(names)}
             med0, med1 = statistics.median(t0), statistics.median(t1)
             res["batches"][str(bs)] = dict(P0_ms=q(t0), P1_ms=q(t1), P0_img_s=bs / med0 * 1e3, P1_img_s=bs / med1 * 1e3, P1_over_P0=med0 / med1,
-                                           bit_equal=bool(torch.equal(ref, got)), replaced_us=us(k0, ENDS_REPLACED), new_us=us(k1, ENDS_NEW),
+                                           bit_equal=bool(torch.equal(ref, got)), replaced_us=us(k0, replaced), new_us=us(k1, new),
                                            P0_kernel_ms_total=sum(v["ms"] for v in k0.values()), P1_kernel_ms_total=sum(v["ms"] for v in k1.values()),
                                            P0_kernels=k0, P1_kernels=k1)
-            print("batch %d: default plan %.3f ms (min %.3f)  code_ends %.3f ms (min %.3f)  speed %.2fx  bit-equal %s" % (bs, med0, min(t0), med1, min(t1), med0 / med1,
+            if byte:          # (the exact integer sum against an fp32 accumulation: equal within the float contract, not to the bit)
+                res["batches"][str(bs)].update(max_abs_logit_diff=float((ref - got).abs().max()), max_abs_logit=float(ref.abs().max()))
+            print("batch %d: default plan %.3f ms (min %.3f)  %s %.3f ms (min %.3f)  speed %.2fx  bit-equal %s" % (bs, med0, min(t0), label, med1, min(t1), med0 / med1,
                                                                                                                   torch.equal(ref, got)), flush=True)
             print("  replaced (us):", res["batches"][str(bs)]["replaced_us"], " new (us):", res["batches"][str(bs)]["new_us"], flush=True)
     os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
@@ -308,6 +326,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--code-ends", action="store_true", help="the default plan against dorefa_compile_codes(I, code_ends=True)")
+    ap.add_argument("--byte-ends", action="store_true", help="W8A8: the default byte plan against dorefa_compile_bytes(I, byte_ends=True)")
     ap.add_argument("--mfma-blocks", action="store_true", help="I, the default plan and dorefa_compile_codes(I, mfma_blocks=True)")
     ap.add_argument("--mfma-k3", action="store_true", help="I, the mfma_blocks plan and dorefa_compile_codes(I, mfma_blocks=True, mfma_k3=True); works with --arch nin")
     ap.add_argument("--arch", default="nin_gc", choices=("nin_gc", "nin"), help="nin: plain nin, compiled with tile_blocks=True")
@@ -316,6 +335,12 @@ def main():
                     help="with --bits 4: two --mfma-k3 results, of the parent commit and of this tree, recorded under two_bit_check")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.byte_ends:
+        if args.code_ends or args.mfma_blocks or args.mfma_k3 or args.arch != "nin_gc" or args.bits != 2 or args.two_bit_check:
+            ap.error("--byte-ends is its own protocol, on W8A8 nin_gc")
+        if args.out is None:
+            args.out = os.path.join("profiles", "codes_w8_ends.json")
+        return main_code_ends(args, byte=True)
     if args.bits == 4:
         if args.code_ends or args.mfma_blocks or args.mfma_k3 or args.arch != "nin_gc":
             ap.error("--bits 4 is its own protocol, on nin_gc")
