@@ -1132,6 +1132,34 @@ int mn_conv2d_first_bytes_supported(const mn_conv_geom* g);
 int mn_conv2d_first_bytes(const mn_conv_geom* g, const float* x, const float* w, const float* bias, const float* chan, int8_t* map, mn_stream_t stream);
 int mn_code8conv_f32_supported(const mn_conv_geom* g);
 int mn_code8conv_fwd_f32(const mn_conv_geom* g, const uint32_t* table, const int8_t* in_codes, float* y, mn_stream_t stream);
+/* A ResNet's BasicBlocks on the W8A8 byte plan (csrc/qgemm_codes_w8_res.h; inference.dorefa_compile_bytes on the reference's ResNet).  Map, acc and the chain are those of
+ * mn_code8conv_*; every table is mn_code8conv_pack's with a null out_order (position j = channel j), built through the geometry gate of this family.
+ *   quant : fp32 NCHW x -> map [N][ceil(C/16)][HW][16], byte = (the 8-bit DoReFa activation code rha(clamp(0.1 x, 0, 1) * 255) of mn_qa_fwd) - 128, tail channels 0x80, in
+ *           one launch.  x 4-byte, map 16-byte aligned; N, C, HW > 0, else MN_EINVAL.  mn_last_kernel(): k_code8_quant.
+ *   conv  : conv -> BatchNorm -> ReLU -> 8-bit code, bytes in, bytes out.  Covered (mn_code8res_conv_supported, which table_bytes / pack / fwd follow): widths 8 / 8 / 8;
+ *           groups 1, dilation 1, g->in_shuffle 0; 3x3 / padding 1 with C % 16 == 0 or 1x1 / padding 0 with any C; stride 1 or 2, the same in both directions; any O;
+ *           C * KH * KW <= 33025.  Output pixel (h, w) reads input pixel (stride h + dy, stride w + dx), Ho = (H - 1) / stride + 1; a tap outside the INPUT map reads the
+ *           code 0.  out_codes [N][ceil(O/16)][Ho*Wo][16], positions >= O are 0x80.  mn_last_kernel(): k_code8res_conv<KS,stride>.
+ *   add   : the block's end in one launch.  With acc_b the branch conv `g` (stride 1) on in_codes and `table`:
+ *             z = chain_b(acc_b) up to and including its BatchNorm (no ReLU);
+ *             r = shortcut == 1 ? res_f32[n][o][h][w] (the block's fp32 input, NCHW with O channels: needs O == C)
+ *               : shortcut == 2 ? chain_s(acc_s) up to its BatchNorm, acc_s the 1x1 / padding 0 / stride 1 | 2 conv `gs` on sc_codes (the block INPUT's map) and `table_s`
+ *               : 0;
+ *             a = relu(fl(z + r));   out_codes (if not null): byte = code8(a) - 128, positions >= O 0x80;   out_f32 (if not null): a, NCHW [N][O][H][W], no tail.
+ *           gs must have the branch's N and O and an output map of the branch's H x W.  At least one output; the arguments of the other shortcut kinds are ignored.
+ *           mn_last_kernel(): k_code8res_add<KS,shortcut>.
+ * Not covered (other widths, groups != 1, stride 3, 5x5, a 3x3 with C % 16 != 0, shortcut outside 0 .. 2, an identity shortcut with O != C, a shortcut of another
+ * size, a strided branch conv in the add stage): MN_ENOTSUP.  Null / misaligned pointer (tables and byte maps 16-byte, fp32 maps 4-byte aligned), an invalid geometry, no
+ * output requested or an output that overlaps an input: MN_EINVAL.  Nothing is written in either case.  Every output element is stored once: no atomics, no
+ * read-modify-write.  No entry allocates. */
+int mn_code8_quant_map(const float* x, int64_t N, int64_t C, int64_t HW, int8_t* map, mn_stream_t stream);
+int mn_code8res_conv_supported(const mn_conv_geom* g, int a_bits_in, int w_bits, int a_bits_out);
+int64_t mn_code8res_conv_table_bytes(const mn_conv_geom* g, int a_bits_in, int w_bits, int a_bits_out);
+int mn_code8res_conv_pack(const mn_conv_geom* g, const float* w, const float* chan, int a_bits_in, int w_bits, int a_bits_out, uint32_t* table, mn_stream_t stream);
+int mn_code8res_conv_fwd(const mn_conv_geom* g, const uint32_t* table, const int8_t* in_codes, int8_t* out_codes, mn_stream_t stream);
+int mn_code8res_add_supported(const mn_conv_geom* g, int shortcut, const mn_conv_geom* gs, int a_bits_in, int w_bits, int a_bits_out);
+int mn_code8res_add_fwd(const mn_conv_geom* g, const uint32_t* table, const int8_t* in_codes, int shortcut, const float* res_f32, const mn_conv_geom* gs,
+                        const uint32_t* table_s, const int8_t* sc_codes, int8_t* out_codes, float* out_f32, mn_stream_t stream);
 /* ------------------------------------------------------------------ int8 deployment of the BN-folded IAO hidden blocks: byte codes on v_mfma_i32_16x16x64_i8
  * What a hidden stage of a BN-folded, pre-quantised IAO net computes in eval mode -- [channel shuffle] -> QuantConv2d -> ReLU -> [QuantMaxPool2d 2x2 / 2] -> the next
  * conv's activation quantizer, every quantizer symmetric (zero point 0), code widths 2 .. 8 -- on byte codes:

@@ -24,7 +24,9 @@ The results are ordinary modules of this package: in eval mode they run on the s
 
   * ``dorefa_compile_bytes``: a pre-quantised DoReFa W8A8 ``quant_inference=True`` net -- the reference's CPU configuration -- compiled into a flat plan that keeps
     ONE BYTE per hidden activation (``csrc/qgemm_codes_w8.h``: activation and weight codes as offset bytes on v_mfma_i32_16x16x64_i8, the block's fp32 chain evaluated
-    on the exact int32 sum).  One kernel per hidden block; the two ends stay on the model's own modules.
+    on the exact int32 sum).  One kernel per hidden block; the two ends stay on the model's own modules.  A W8A8 ResNet of BasicBlocks compiles by the same call
+    (``csrc/qgemm_codes_w8_res.h``: strided byte convs, and the block's end -- second conv, BatchNorm, identity or conv shortcut, add, ReLU -- in one launch that
+    writes the next block's bytes and / or the fp32 map the next identity shortcut reads).
 
   * ``iao_compile_int8``: the BN-folded, pre-quantised symmetric IAO graph compiled into a flat plan that keeps ONE INT8 CODE per hidden activation
     (``csrc/qgemm_iao8.h``: byte codes against weight-code bytes on v_mfma_i32_16x16x64_i8, bias + ReLU + [2x2 max-pool] + the consumer's quantizer in the epilogue).
@@ -1356,7 +1358,11 @@ def _walk_bytes(model, byte_ends=False):
 
 def dorefa_bytes_report(model, byte_ends=False):
     """The ``report`` ``dorefa_compile_bytes(model, byte_ends)`` would carry -- one row per stage: name, kind ("first" / "byte" / "last"), K, blocks (16-channel blocks
-    of the stage's input map), kernel, pooled, out_order, stage -- from the graph walk alone: no GPU, nothing packed.  Raises like ``dorefa_compile_bytes``."""
+    of the stage's input map), kernel, pooled, out_order, stage -- from the graph walk alone: no GPU, nothing packed.  Raises like ``dorefa_compile_bytes``.  The
+    reference's ResNet of BasicBlocks: rows of name, kind ("first" / "quant" / "conv" / "add" / "last"), K, blocks, kernel, stride, shortcut ("identity" / "conv" / None)
+    and outputs (``_walk_bytes_res``)."""
+    if _is_ref_resnet(model):
+        return _walk_bytes_res(model, byte_ends)[1]
     return _walk_bytes(model, byte_ends)[5]
 
 
@@ -1390,9 +1396,17 @@ def dorefa_compile_bytes(model, byte_ends=False):
     one step.  Anything the byte kernels do not cover raises ``MicronetHipError`` naming the layer and the rule.  ``byte_ends=True``: the first conv
     writes the first stage's byte map in one launch (``mn_conv2d_first_bytes``) and the classifier conv reads the last stage's map (``mn_code8conv_fwd_f32``: the
     exact integer sum where the default path accumulates in fp32) -- no fp32 map, no uint8 codes, no pack / unpack launch; same bytes in every stage, logits within
-    the float contract.  Off by default until the gain is measured; with it off nothing changes."""
+    the float contract.  Off by default until the gain is measured; with it off nothing changes.
+
+    The reference's ``ResNet`` of ``BasicBlock``s (resnet18 / resnet34, any ``num_block``), W8A8, ``quant_inference=True``, pre-quantised, in eval mode, compiles to a
+    ``Byte8ResPlan`` (``csrc/qgemm_codes_w8_res.h``): the model's own conv1, one launch that quantises its fp32 map to bytes, two launches per block (its first conv at
+    stride 1 or 2; its second conv with BatchNorm, identity or conv shortcut, add and ReLU), the model's own avg_pool and fc.  A BottleNeck, another block structure,
+    another width, a conv that is not ``quant_inference`` or a BatchNorm without affine parameters or running statistics raises, naming the layer;
+    ``byte_ends=True`` raises (not built)."""
     from micronet_amd import ops
     from micronet_amd.quantization.wqaq.dorefa.quantize import _weight_is_coded
+    if _is_ref_resnet(model):
+        return _compile_bytes_res(model, byte_ends)
     first, layers, last, tail, flatten, report = _walk_bytes(model, byte_ends)
     last_layer = None
     if byte_ends:          # the classifier as a layer dict of its own: packed and read back with the others
@@ -1434,6 +1448,200 @@ def dorefa_compile_bytes(model, byte_ends=False):
         if bad:
             raise _err("dorefa_compile_bytes: %s.conv: %d table rows with a weight off the 8-bit grid or a bad channel order" % (L["name"], bad))
     return Byte8Plan(first, layers, last, tail, flatten, report, first_chan, last_layer)
+
+
+# ------------------------------------------------------------------------------------------------ DoReFa W8A8 ResNets on bytes (csrc/qgemm_codes_w8_res.h)
+def _walk_bytes_res(model, byte_ends=False, input_hw=(32, 32)):
+    """The graph walk of ``dorefa_compile_bytes`` on the reference's ResNet of BasicBlocks (no GPU needed): (stages, report).  Every block becomes two stages -- its
+    first conv (``kind`` "conv": conv -> bn -> relu -> the second conv's codes, stride 1 or 2) and its end ("add": the second conv, its BatchNorm, the shortcut, the
+    add and the ReLU in one launch).  An add stage writes the byte map when a block follows, and the fp32 map only when the next block's shortcut is the identity or
+    the consumer is avg_pool.  ``input_hw`` only sizes the maps the geometry rules are asked about."""
+    from micronet_amd import _lib
+    from micronet_amd.quantization.wqaq.dorefa import quantize
+    who, B, lib = "dorefa_compile_bytes", BYTE_BITS, _lib.get_lib()
+    if byte_ends:
+        raise _err("%s(byte_ends=True): conv1 / avg_pool: a ResNet's ends on bytes (the stem writing bytes, avg_pool + fc reading them) are not built" % who)
+    stem = [m for m in model.conv1.children()]
+    if not stem or not isinstance(stem[0], nn.Conv2d) or isinstance(stem[0], quantize.QuantConv2d):
+        raise _err("%s: conv1: module order not recognised (expected the un-quantised first conv -> BatchNorm -> ReLU)" % who)
+    c0 = stem[0]
+
+    def check_conv(nm, conv):
+        if not isinstance(conv, quantize.QuantConv2d):
+            raise _err("%s: %s is not a DoReFa QuantConv2d" % (who, nm))
+        ab, wb = conv.activation_quantizer.a_bits, conv.weight_quantizer.w_bits
+        if (ab, wb) != (B, B):
+            raise _err("%s: %s has a_bits = %d, w_bits = %d; only W8A8 nets are deployed on bytes, every quantised conv at 8 bits" % (who, nm, ab, wb))
+        if not conv.quant_inference:
+            raise _err("%s: %s is not a quant_inference=True layer (prepare(..., quant_inference=True), then prequantize_weights)" % (who, nm))
+        if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
+            raise _err("%s: %s: padding mode %r is not covered by the byte kernels" % (who, nm, conv.padding_mode))
+
+    def check_bn(nm, bn):
+        if not isinstance(bn, nn.BatchNorm2d) or not (bn.affine and bn.track_running_stats and bn.momentum is not None):
+            raise _err("%s: %s: needs a BatchNorm2d with affine parameters, running statistics and a momentum" % (who, nm))
+
+    def stage(nm, kind, conv, bn):
+        return dict(name=nm, kind=kind, conv=conv, bn=bn, k=_one(conv.kernel_size), pad=_one(conv.padding), stride=_one(conv.stride), cin=conv.in_channels,
+                    cout=conv.out_channels, groups=conv.groups, shortcut=None, outputs=["bytes"])
+
+    what = lambda c: "%dx%d, stride %s, padding %s, dilation %s, groups %d, %d input channels" % (c.kernel_size[0], c.kernel_size[1], c.stride, c.padding, c.dilation,
+                                                                                                 c.groups, c.in_channels)
+    rule = "groups 1, dilation 1, 3x3 / padding 1 with C %% 16 == 0 or 1x1 / padding 0, stride 1 or 2 in both directions, C * taps <= 33025"
+    H, W = (_out_size(input_hw[i], c0.kernel_size[i], c0.stride[i], c0.padding[i], c0.dilation[i]) for i in (0, 1))
+    stages, cin = [], c0.out_channels
+    blocks = [("%s.%s" % (sn, bn_), b) for sn in _RESNET_STAGES for bn_, b in getattr(model, sn).named_children()]
+    if not blocks:
+        raise _err("%s: no residual block between conv1 and avg_pool" % who)
+    for nm, blk in blocks:
+        if type(blk).__name__ == "BottleNeck":
+            raise _err("%s: %s: BottleNeck blocks are not built (BasicBlock: resnet18 / resnet34)" % (who, nm))
+        rf, sc = list(blk.residual_function.children()), list(blk.shortcut.children())
+        if not (len(rf) == 5 and isinstance(rf[0], nn.Conv2d) and isinstance(rf[1], nn.BatchNorm2d) and isinstance(rf[2], nn.ReLU) and isinstance(rf[3], nn.Conv2d)
+                and isinstance(rf[4], nn.BatchNorm2d) and (not sc or (len(sc) == 2 and isinstance(sc[0], nn.Conv2d) and isinstance(sc[1], nn.BatchNorm2d)))
+                and type(blk.add).__name__ == "Add"):
+            raise _err("%s: %s: module order not recognised (expected residual_function = conv, bn, relu, conv, bn, shortcut = empty or conv, bn, and an Add)" % (who, nm))
+        named = [(nm + ".residual_function.0", rf[0], rf[1]), (nm + ".residual_function.3", rf[3], rf[4])] + ([(nm + ".shortcut.0", sc[0], sc[1])] if sc else [])
+        for cn, conv, bn in named:
+            check_conv(cn, conv)
+            check_bn(cn[:-1] + str(int(cn[-1]) + 1), bn)
+        if rf[0].in_channels != cin or (sc and sc[0].in_channels != cin) or (not sc and rf[3].out_channels != cin) or rf[3].in_channels != rf[0].out_channels:
+            raise _err("%s: %s: the channel counts of the block do not chain (its input has %d channels)" % (who, nm, cin))
+        A, E = stage(named[0][0], "conv", rf[0], rf[1]), stage(named[1][0], "add", rf[3], rf[4])
+        ga = _block_geom(A, 1, H, W)
+        if not lib.mn_code8res_conv_supported(C.byref(ga), B, B, B):
+            raise _err("%s: %s: geometry not covered by mn_code8res_conv_supported (%s: %s)" % (who, A["name"], what(rf[0]), rule))
+        Hi, Wi, H, W = H, W, (H - 1) // A["stride"] + 1, (W - 1) // A["stride"] + 1
+        E["shortcut"] = "conv" if sc else "identity"
+        gs = None
+        if sc:
+            E["sconv"], E["sbn"], E["s_name"], E["s_cin"], E["s_stride"] = sc[0], sc[1], named[2][0], sc[0].in_channels, _one(sc[0].stride)
+            gs = _lib.ConvGeom(1, cin, Hi, Wi, sc[0].out_channels, sc[0].kernel_size[0], sc[0].kernel_size[1], sc[0].stride[0], sc[0].stride[1], sc[0].padding[0],
+                               sc[0].padding[1], sc[0].dilation[0], sc[0].dilation[1], sc[0].groups, 0)
+        if not lib.mn_code8res_add_supported(C.byref(_block_geom(E, 1, H, W)), 2 if sc else 1, C.byref(gs) if sc else None, B, B, B):
+            raise _err("%s: %s: the block's end is not covered by mn_code8res_add_supported (%s%s: %s; the conv in front of the add at stride 1, an identity shortcut "
+                       "with as many channels as the block writes, a conv shortcut 1x1 / padding 0 whose map has the size of the residual's)"
+                       % (who, E["name"], what(rf[3]), ("; shortcut " + what(sc[0])) if sc else "", rule))
+        if stages:          # the producer's outputs follow from this consumer
+            stages[-1]["outputs"] = ["bytes"] + ([] if sc else ["f32"])
+        stages += [A, E]
+        cin = E["cout"]
+    stages[-1]["outputs"] = ["f32"]          # avg_pool reads the fp32 map
+    if getattr(model.fc, "in_features", cin) != cin:
+        raise _err("%s: fc: in_features is %d, the last block writes %d channels" % (who, model.fc.in_features, cin))
+    report = [dict(name="conv1", kind="first", K=c0.in_channels // c0.groups * c0.kernel_size[0] * c0.kernel_size[1], blocks=0, kernel="the model's own block (fp32)",
+                   stride=_one(c0.stride), shortcut=None, outputs=["f32"]),
+              dict(name="conv1 -> " + stages[0]["name"], kind="quant", K=0, blocks=(c0.out_channels + 15) // 16, kernel="k_code8_quant", stride=1, shortcut=None,
+                   outputs=["bytes"])]          # (conv1's own fp32 map stays for an identity shortcut of the first block)
+    for L in stages:
+        sck = {None: 0, "identity": 1, "conv": 2}[L["shortcut"]]
+        L["kernel"] = ("k_code8res_add<%d,%d>" % (L["k"], sck)) if L["kind"] == "add" else "k_code8res_conv<%d,%d>" % (L["k"], L["stride"])
+        report.append(dict(name=L["name"], kind=L["kind"], K=L["cin"] * L["k"] * L["k"], blocks=(L["cin"] + 15) // 16, kernel=L["kernel"], stride=L["stride"],
+                           shortcut=L["shortcut"], outputs=list(L["outputs"])))
+    report.append(dict(name="avg_pool", kind="last", K=cin, blocks=0, kernel="the model's own avg_pool and fc (fp32)", stride=1, shortcut=None, outputs=["f32"]))
+    return stages, report
+
+
+class Byte8ResPlan(_Plan):
+    """What ``dorefa_compile_bytes`` returns for the reference's ResNet of BasicBlocks: the model's own conv1 (fp32) -> ``mn_code8_quant_map`` -> per block
+    ``mn_code8res_conv_fwd`` (its first conv, stride 1 or 2) and ``mn_code8res_add_fwd`` (its second conv, BatchNorm, shortcut, add and ReLU in one launch) -> the
+    model's own avg_pool and fc on the last block's fp32 map.  Eval only; owns the packed tables and one set of maps per input shape.  ``layers[i]`` keeps what stage i
+    was packed from (``w``, ``chan``; an add stage with a conv shortcut also ``w_s``, ``chan_s``) for the tests' judge.  ``keep_stages``: forward leaves a copy of every
+    stage's maps in ``stage_codes`` / ``stage_f32`` -- entry 0 the stem's, entry i + 1 stage i's, None where a stage does not write that map."""
+
+    who = "dorefa_compile_bytes"
+
+    def __init__(self, conv1, stages, avg_pool, fc, report):
+        super().__init__(conv1, stages, None, [avg_pool, fc], True, report)
+        self.stage_codes, self.stage_f32 = [], []
+
+    def _plan_buffers(self, shape, device):
+        """The stem's byte map, then per stage its geometry (the shortcut conv's as well) and the maps it writes, for one conv1 output shape."""
+        from micronet_amd import _lib
+        N, Cc, H, W = shape
+        if Cc != self.layers[0]["cin"]:
+            raise _err("dorefa_compile_bytes: conv1 produced %d channels, the first block reads %d" % (Cc, self.layers[0]["cin"]))
+        bufs, Hi, Wi = [], H, W
+        for L in self.layers:
+            g = _block_geom(L, N, H, W)
+            if L["kind"] == "conv":
+                Hi, Wi, H, W = H, W, (H - 1) // L["stride"] + 1, (W - 1) // L["stride"] + 1          # (Hi, Wi: the block's input map, which a conv shortcut reads)
+            gs = _lib.ConvGeom(N, L["s_cin"], Hi, Wi, L["cout"], 1, 1, L["s_stride"], L["s_stride"], 0, 0, 1, 1, 1, 0) if L["shortcut"] == "conv" else None
+            bufs.append(dict(g=g, gs=gs, codes=_code_map(N, L["cout"], H * W, device) if "bytes" in L["outputs"] else None,
+                             f32=torch.empty((N, L["cout"], H, W), dtype=torch.float32, device=device) if "f32" in L["outputs"] else None))
+        return _code_map(N, Cc, shape[2] * shape[3], device), bufs
+
+    @torch.no_grad()
+    def forward(self, x):
+        from micronet_amd import ops
+        a = self.first(x)
+        if not (type(a) is torch.Tensor and a.is_cuda and a.dtype == torch.float32 and a.dim() == 4):
+            raise _err("dorefa_compile_bytes: conv1 did not produce a float32 GPU map (the input must be a float32 GPU tensor; no CPU fallback)")
+        a = a.contiguous()
+        N, Cc, H, W = a.shape
+        with torch.cuda.device(a.device):
+            b0, bufs = self._shape_buffers(a.shape, a.device)
+            st = ops._s()
+            ops._call("mn_code8_quant_map", ops._p(a), N, Cc, H * W, ops._p(b0), st)
+            codes, f32, block_in = b0, a, (b0, a)          # the current byte map and fp32 map; (bytes, fp32) of the block's input
+            for L, ws in zip(self.layers, bufs):
+                if L["kind"] == "conv":
+                    block_in = (codes, f32)
+                    ops._call("mn_code8res_conv_fwd", C.byref(ws["g"]), ops._p(L["table"]), ops._p(codes), ops._p(ws["codes"]), st)
+                elif L["shortcut"] == "identity":
+                    ops._call("mn_code8res_add_fwd", C.byref(ws["g"]), ops._p(L["table"]), ops._p(codes), 1, ops._p(block_in[1]), None, None, None, ops._p(ws["codes"]),
+                              ops._p(ws["f32"]), st)
+                else:
+                    ops._call("mn_code8res_add_fwd", C.byref(ws["g"]), ops._p(L["table"]), ops._p(codes), 2, None, C.byref(ws["gs"]), ops._p(L["table_s"]),
+                              ops._p(block_in[0]), ops._p(ws["codes"]), ops._p(ws["f32"]), st)
+                codes, f32 = ws["codes"], ws["f32"]
+            if self.keep_stages:
+                keep = lambda t: None if t is None else t.clone()
+                self.stage_codes = [b0.clone()] + [keep(ws["codes"]) for ws in bufs]
+                self.stage_f32 = [a.clone()] + [keep(ws["f32"]) for ws in bufs]
+        y = self.tail[0](f32)          # (a new tensor: the plan's own map is never handed out)
+        return self.tail[1](y.view(y.size(0), -1))
+
+
+@torch.no_grad()
+def _compile_bytes_res(model, byte_ends=False):
+    from micronet_amd import _lib, ops
+    from micronet_amd.quantization.wqaq.dorefa.quantize import _weight_is_coded
+    who, B = "dorefa_compile_bytes", BYTE_BITS
+    stages, report = _walk_bytes_res(model, byte_ends)
+    _require_gpu(model, who)
+    if model.training:
+        raise _err("%s: the model is in training mode (model.eval(): the plan computes the eval-mode function)" % who)
+
+    def packed(nm, L, conv, bn):
+        """(stored weights, [9][O] constants, table) of one conv + BatchNorm: the constants of ``_bn_chan_constants`` with alpha = fl(1/255 * 1/255) and the conv's bias."""
+        if not _weight_is_coded(conv):
+            raise _err("%s: %s: the stored weights were not found on the 8-bit grid (2k - 255) / 255 (run inference.prequantize_weights on the GPU model first)" % (who, nm))
+        dev = conv.weight.device
+        chan = _bn_chan_constants(bn, conv.out_channels, ops._chk(bn.weight.detach(), "weight"), ops._chk(bn.bias.detach(), "bias"))
+        chan[0], chan[1] = _code8_identity_chan(conv, dev)[:2]
+        chan[6], chan[7] = chan[0] * chan[3], (chan[1] - chan[2]) * chan[3]
+        g, w = _block_geom(L), conv.weight.detach().float().contiguous()
+        table = torch.empty(int(_lib.get_lib().mn_code8res_conv_table_bytes(C.byref(g), B, B, B)) // 4, dtype=torch.int32, device=dev)
+        ops._call("mn_code8res_conv_pack", C.byref(g), ops._p(w), ops._p(chan), B, B, B, ops._p(table), ops._s())
+        return w, chan, table
+
+    tables = []
+    with torch.cuda.device(stages[0]["conv"].weight.device):
+        for L in stages:
+            L["w"], L["chan"], L["table"] = packed(L["name"], L, L.pop("conv"), L.pop("bn"))
+            tables.append((L["name"], L["table"]))
+            if L["shortcut"] == "conv":
+                Ls = dict(cin=L["s_cin"], cout=L["cout"], k=1, pad=0, stride=L["s_stride"])
+                L["w_s"], L["chan_s"], L["table_s"] = packed(L["s_name"], Ls, L.pop("sconv"), L.pop("sbn"))
+                tables.append((L["s_name"], L["table_s"]))
+        counters = torch.stack([t[:8] for _, t in tables]).cpu()          # (compile time: the one place a host read-back is allowed, one read for every table)
+    for (nm, _), row in zip(tables, counters):
+        if int(row[0]):
+            raise _err("%s: %s: %d output channels with a non-finite (or beyond 1e9) BatchNorm constant" % (who, nm, int(row[0])))
+        if int(row[7]):
+            raise _err("%s: %s: %d table rows with a weight off the 8-bit grid" % (who, nm, int(row[7])))
+    return Byte8ResPlan(model.conv1, stages, model.avg_pool, model.fc, report)
 
 
 # ------------------------------------------------------------------------------------------------ int8 deployment of the BN-folded IAO graph (csrc/qgemm_iao8.h)
