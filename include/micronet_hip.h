@@ -1160,6 +1160,26 @@ int mn_code8res_conv_fwd(const mn_conv_geom* g, const uint32_t* table, const int
 int mn_code8res_add_supported(const mn_conv_geom* g, int shortcut, const mn_conv_geom* gs, int a_bits_in, int w_bits, int a_bits_out);
 int mn_code8res_add_fwd(const mn_conv_geom* g, const uint32_t* table, const int8_t* in_codes, int shortcut, const float* res_f32, const mn_conv_geom* gs,
                         const uint32_t* table_s, const int8_t* sc_codes, int8_t* out_codes, float* out_f32, mn_stream_t stream);
+/* What plain nin adds to the W8A8 byte plan (csrc/qgemm_codes_w8_tile.h; inference.dorefa_compile_bytes(model, tile_blocks=True)).  Map, acc, the chain, pack's arguments
+ * and the table's header words are those of mn_code8conv_*.
+ *   conv5   : the dense 5x5 hidden block on an LDS-resident halo tile: a block stages its input tile (several whole images of at most 256 pixels together, else a band of
+ *             rows at full width) with a halo of 2 ONCE, 0x80 bytes where the map or the batch ends, and its k-loop reads LDS alone.  Covered (mn_code8conv5_supported,
+ *             which table_bytes / pack / fwd follow): widths 8 / 8 / 8; KH = KW = 5, stride 1, padding 2, dilation 1, groups 1, g->in_shuffle 0 / 1, C % 16 == 0, any O;
+ *             C * 25 <= 33025; W <= 256 and ceil(C/16) * 5 * (W + 4) <= 3071 (one output row with its halo in 48 KB of LDS); any H, any N.  No pool is folded.
+ *             out_codes [N][ceil(O/16)][H*W][16], every 16-byte block stored once and whole, positions >= O and bad out_order entries 0x80.  Not covered: MN_ENOTSUP;
+ *             null / misaligned pointer (table and maps 16-byte aligned), an invalid geometry or an output that overlaps the input: MN_EINVAL; nothing is written in
+ *             either case.  mn_last_kernel(): k_code8conv5<5>.
+ *   maxpool : map_in [N][ceil(C/16)][H*W][16] -> map_out [N][ceil(C/16)][Ho*Wo][16], the maximum code per channel over the in-map cells of the window, floor mode
+ *             (Ho = (H + 2 pad - k) / stride + 1); tail channels stay 0x80.  Covered: (k, stride, pad) = (2, 2, 0) and (3, 2, 1); anything else MN_ENOTSUP.  Null /
+ *             misaligned / empty argument, an image smaller than the window or an output that overlaps the input (no in-place call): MN_EINVAL.  Nothing is written in
+ *             either case.  mn_last_kernel(): k_code8_maxpool.
+ * No entry allocates. */
+int mn_code8conv5_supported(const mn_conv_geom* g, int a_bits_in, int w_bits, int a_bits_out);
+int64_t mn_code8conv5_table_bytes(const mn_conv_geom* g, int a_bits_in, int w_bits, int a_bits_out);
+int mn_code8conv5_pack(const mn_conv_geom* g, const float* w, const float* chan, int a_bits_in, int w_bits, int a_bits_out, const int32_t* out_order, uint32_t* table,
+                       mn_stream_t stream);
+int mn_code8conv5_fwd(const mn_conv_geom* g, const uint32_t* table, const int8_t* in_codes, int8_t* out_codes, mn_stream_t stream);
+int mn_code8_maxpool(const int8_t* map_in, int64_t N, int64_t C, int64_t H, int64_t W, int k, int stride, int pad, int8_t* map_out, mn_stream_t stream);
 /* ------------------------------------------------------------------ int8 deployment of the BN-folded IAO hidden blocks: byte codes on v_mfma_i32_16x16x64_i8
  * What a hidden stage of a BN-folded, pre-quantised IAO net computes in eval mode -- [channel shuffle] -> QuantConv2d -> ReLU -> [QuantMaxPool2d 2x2 / 2] -> the next
  * conv's activation quantizer, every quantizer symmetric (zero point 0), code widths 2 .. 8 -- on byte codes:

@@ -24,7 +24,8 @@
 //                  in SLOTS of 16 channels, slot = tap * chunks + chunk (chunks = ceil(C / groups / 16)), four slots per k-step.  A 1x1 block is the one-tap case.
 //   weight table : (private layout, 16-byte aligned: the set / tile table of qgemm_mfma_sets.h, a set = four 16-byte output blocks) 16 header words -- [0] rows whose
 //                  constants fail qa_chan_finite, [1] k-steps, [2] tile slots per set, [3] tile stride, [4] sets, [5] chunks, [6] 8 | 8 << 8 | 8 << 16, [7] bad
-//                  out_order entries + rows with a weight off the grid, [8] T -- then one word per slot (dy + 1 | (dx + 1) << 2 | chunk << 4, bit 31: a padding slot),
+//                  out_order entries + rows with a weight off the grid, [8] T -- then one word per slot (dy + 1 | (dx + 1) << 2 | chunk << 4, bit 31: a padding slot; the 5x5 tables
+//                  of qgemm_codes_w8_tile.h: dy + 2 | (dx + 2) << 3 | chunk << 6),
 //                  then the tile count of every set, then the tiles:
 //                    [0] first 16-channel block of the tile's group, [1] 1: first tile of its group in the set, [16 ..) the nine QaCh rows of 16 output rows each,
 //                    [160 ..) Kc[16], [176 ..) dest[16] (position in the set, -1: a dead row), [192 ..) per k-step 64 lanes x 16 bytes in the A-operand order of
@@ -111,8 +112,9 @@ __global__ __launch_bounds__(256) void k_code8_wpack(W8Geom m, const float* __re
         for (int i = tid; i < 4 * m.nsteps; i += 256) {
             const bool real = i < m.nslots;
             const int tap = real ? i / m.chunks : 0, chunk = real ? i - tap * m.chunks : 0;
-            const int dy = m.KS == 3 ? tap / 3 : 1, dx = m.KS == 3 ? tap % 3 : 1;
-            tab[m.slot_off + i] = real ? (uint32_t)(dy | (dx << 2) | (chunk << 4)) : PADSLOT;
+            const int dy = m.KS == 1 ? 1 : tap / m.KS, dx = m.KS == 1 ? 1 : tap % m.KS;
+            const int word = m.KS == 5 ? dy | (dx << 3) | (chunk << 6) : dy | (dx << 2) | (chunk << 4);          // (5x5: qgemm_codes_w8_tile.h, three bits per tap offset)
+            tab[m.slot_off + i] = real ? (uint32_t)word : PADSLOT;
         }
         if (tid == 0) {
             tab[1] = (uint32_t)m.nsteps; tab[2] = (uint32_t)m.slots; tab[3] = (uint32_t)m.tstride; tab[4] = (uint32_t)m.nsets; tab[5] = (uint32_t)m.chunks;

@@ -1127,6 +1127,11 @@ def _code8conv_kernel_name(k, pool):
     return "k_code8conv<%d,%d>" % (k, pool)
 
 
+def _code8conv5_kernel_name(k):
+    """The kernel mn_code8conv5_fwd reports for a dense 5x5 block (csrc/qgemm_codes_w8_tile.h)."""
+    return "k_code8conv5<%d>" % k
+
+
 def pack_code_map(t):
     """uint8 8-bit activation codes [N, C, H, W] (or an 8-bit QActTensor) -> the byte map of the W8A8 blocks: int8 [N, ceil(C / 16), H * W, 16], byte = code - 128,
     tail channels 0x80 (the code 0)."""
@@ -1156,7 +1161,8 @@ def unpack_code_map(m, C_, H, W):
 
 class Byte8Plan(_Plan):
     """What ``dorefa_compile_bytes`` returns: first block (fp32 conv + BatchNorm + ReLU + the next conv's 8-bit quantizer, the model's own module) -> byte-map pack -> n
-    byte blocks (2x2 max-pools folded in) -> unpack -> last block and tail (the model's own modules).  Eval only; owns the packed weight tables (and the per-channel
+    byte blocks (2x2 max-pools folded in; with ``tile_blocks`` also the dense 5x5 block on an LDS tile, and a max-pool ``prepare()`` did not fuse run on the byte map
+    behind its block, through one more mid map per such pool) -> unpack -> last block and tail (the model's own modules).  Eval only; owns the packed weight tables (and the per-channel
     constants they were packed from: ``layers[i]["chan"]``) and one set of byte maps [N, ceil(C / 16), H * W, 16] (byte = code - 128) per input shape.
     ``keep_stages``: forward leaves a copy of every stage's map in ``stage_codes``.  ``byte_ends``: the first conv's kernel writes the first stage's map itself
     (no fp32 map, no uint8 codes, no pack; ``first_chan`` holds the first block's [9][O] constants) and the last conv reads the last stage's map (no unpack, no
@@ -1183,27 +1189,45 @@ class Byte8Plan(_Plan):
             if not lib.mn_conv2d_first_bytes_supported(C.byref(g0)):
                 raise _err("dorefa_compile_bytes(byte_ends=True): %s.conv: a %d x %d x %d x %d input is not covered by mn_conv2d_first_bytes (W %% 4 == 0, H * W %% 32 == 0, "
                            "the image strip in LDS)" % (self.report[0]["name"], N, conv.in_channels, H, W))
-        bufs, geoms = [_code_map(N, Cc, H * W, device)], []
+        bufs, geoms, mids = [_code_map(N, Cc, H * W, device)], [], []
         for L in self.layers:
             geoms.append(_block_geom(L, N, H, W))
+            if L.get("tile") and not lib.mn_code8conv5_supported(C.byref(geoms[-1]), BYTE_BITS, BYTE_BITS, BYTE_BITS):
+                raise _err("dorefa_compile_bytes(tile_blocks=True): %s.conv: a %d-channel map %d pixels wide is beyond the LDS bound of mn_code8conv5_supported (W <= 256 and "
+                           "ceil(C / 16) * 5 * (W + 4) <= 3071: one output row with its halo in 48 KB)" % (L["name"], Cc, W))
             if L["pool"]:
                 if H % 2 or W % 2:
                     raise _err("dorefa_compile_bytes: %s: the 2x2 max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
                 H, W = H // 2, W // 2
+            ksp = L.get("pool_ksp")          # (tile_blocks) a pool the block does not fold: the block at full size into a mid map, then mn_code8_maxpool
+            if ksp:
+                if min(H, W) + 2 * ksp[2] < ksp[0]:
+                    raise _err("dorefa_compile_bytes: %s: the max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
+                mids.append((_code_map(N, L["cout"], H * W, device), H, W))
+                H, W = (H + 2 * ksp[2] - ksp[0]) // ksp[1] + 1, (W + 2 * ksp[2] - ksp[0]) // ksp[1] + 1
+            else:
+                mids.append(None)
             bufs.append(_code_map(N, L["cout"], H * W, device))
             Cc = L["cout"]
         if not self.byte_ends:
-            return bufs, geoms, torch.empty((N, Cc, H, W), dtype=torch.uint8, device=device)
+            return bufs, geoms, torch.empty((N, Cc, H, W), dtype=torch.uint8, device=device), mids
         gl = _block_geom(self.last_layer, N, H, W)
         if not lib.mn_code8conv_f32_supported(C.byref(gl)):
             raise _err("dorefa_compile_bytes(byte_ends=True): %s.conv: a %d-channel %d x %d map is not covered by mn_code8conv_fwd_f32" % (self.report[-1]["name"], Cc, H, W))
-        return bufs, geoms, (g0, gl, torch.empty((N, gl.O, H, W), dtype=torch.float32, device=device))          # (the classifier's fp32 output in place of the uint8 buffer)
+        return bufs, geoms, (g0, gl, torch.empty((N, gl.O, H, W), dtype=torch.float32, device=device)), mids          # (the classifier's fp32 output in place of the uint8 buffer)
 
-    def _run_layers(self, bufs, geoms, st):
-        """One launch per hidden block; ``keep_stages``: a copy of every stage's map."""
+    def _run_layers(self, bufs, geoms, mids, st):
+        """One launch per hidden block (two where a max-pool runs on the map behind it); ``keep_stages``: a copy of every stage's (post-pool) map."""
         from micronet_amd import ops
         for i, L in enumerate(self.layers):
-            ops._call("mn_code8conv_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(bufs[i + 1]), int(L["pool"]), st)
+            out = bufs[i + 1] if mids[i] is None else mids[i][0]
+            if L.get("tile"):
+                ops._call("mn_code8conv5_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(out), st)
+            else:
+                ops._call("mn_code8conv_fwd", C.byref(geoms[i]), ops._p(L["table"]), ops._p(bufs[i]), ops._p(out), int(L["pool"]), st)
+            if mids[i] is not None:
+                (m, h, w), (pk, ps, pp) = mids[i], L["pool_ksp"]
+                ops._call("mn_code8_maxpool", ops._p(m), m.shape[0], L["cout"], h, w, pk, ps, pp, ops._p(bufs[i + 1]), st)
         if self.keep_stages:
             self.stage_codes = [b.clone() for b in bufs]
 
@@ -1215,11 +1239,11 @@ class Byte8Plan(_Plan):
             raise _err("dorefa_compile_bytes(byte_ends=True): the input must be a float32 GPU tensor [N, %d, H, W] (no CPU fallback)" % conv.in_channels)
         x = x.contiguous()
         with torch.cuda.device(x.device):
-            bufs, geoms, (g0, gl, y) = self._shape_buffers((x.shape[0], conv.out_channels, x.shape[2], x.shape[3]), x.device)
+            bufs, geoms, (g0, gl, y), mids = self._shape_buffers((x.shape[0], conv.out_channels, x.shape[2], x.shape[3]), x.device)
             st = ops._s()
             ops._call("mn_conv2d_first_bytes", C.byref(g0), ops._p(x), ops._p(ops._chk(conv.weight.detach(), "weight")), ops._p(ops._chk(conv.bias, "bias")),
                       ops._p(self.first_chan), ops._p(bufs[0]), st)
-            self._run_layers(bufs, geoms, st)
+            self._run_layers(bufs, geoms, mids, st)
             ops._call("mn_code8conv_fwd_f32", C.byref(gl), ops._p(self.last_layer["table"]), ops._p(bufs[-1]), ops._p(y), st)
         return self._finish(self._after_conv(self.last, self.last.conv, y))          # (BatchNorm + ReLU)
 
@@ -1236,10 +1260,10 @@ class Byte8Plan(_Plan):
         codes = a.codes.contiguous()
         N, Cc, H, W = codes.shape
         with torch.cuda.device(codes.device):
-            bufs, geoms, c8 = self._shape_buffers(codes.shape, codes.device)
+            bufs, geoms, c8, mids = self._shape_buffers(codes.shape, codes.device)
             st = ops._s()
             ops._call("mn_code8_pack_codes", ops._p(codes), N, Cc, H * W, ops._p(bufs[0]), st)
-            self._run_layers(bufs, geoms, st)
+            self._run_layers(bufs, geoms, mids, st)
             n_, c_, h_, w_ = c8.shape
             ops._call("mn_code8_unpack_codes", ops._p(bufs[-1]), n_, c_, h_ * w_, ops._p(c8), st)
         # (materialize: a consumer that does not read codes re-quantises 10 j s to j -- the middle of the code's bin)
@@ -1261,11 +1285,13 @@ def _check_byte_ends(first, nm_first, last, nm_last):
                 "at most 33025 input channels")
 
 
-def _walk_bytes(model, byte_ends=False):
+def _walk_bytes(model, byte_ends=False, tile_blocks=False):
     """The graph walk of ``dorefa_compile_bytes`` (no GPU needed): (first, layers, last, tail, flatten, report).  It accepts what ``_walk_codes`` accepts without its
     flags -- the first block on the fp32 first conv handing over codes, conv -> BatchNorm -> ReLU hidden blocks with fused 2x2 max-pools and channel shuffles folded
     into the producer, a last block -- at a_bits = w_bits = 8 in every quantised block.  ``byte_ends``: both ends must be covered by their byte-map kernels
-    (``_check_byte_ends``); the first and the last row of the report name them."""
+    (``_check_byte_ends``); the first and the last row of the report name them.  ``tile_blocks``: also admit what ``_walk_codes(tile_blocks=True)`` admits for plain
+    nin -- a dense 5x5 block ``mn_code8conv5_supported`` covers (``layer["tile"]``) and a max-pool ``prepare()`` did not fuse, run on the byte map behind its block
+    (``layer["pool_ksp"]``); without it the layer dicts have neither key."""
     from micronet_amd import _lib
     from micronet_amd.nn import Conv2dFirst
     from micronet_amd.quantization.wqaq.dorefa import quantize
@@ -1284,21 +1310,50 @@ def _walk_bytes(model, byte_ends=False):
                        "dorefa_compile_codes)" % (who, nm, ab, wb))
         if not conv.quant_inference:
             raise _err("%s: %s.conv is not a quant_inference=True layer (prepare(..., quant_inference=True), then prequantize_weights)" % (who, nm))
+    tiled = set()          # (tile_blocks) the hidden blocks mn_code8conv5_* runs
     for nm, blk in blocks[1:-1]:
         conv = blk.conv
         if tuple(conv.stride) != (1, 1) or tuple(conv.dilation) != (1, 1) or conv.padding_mode != "zeros" or isinstance(conv.padding, str):
             raise _err("%s: %s.conv: stride / dilation other than 1 (or non-zero padding mode) is not covered by the byte kernels" % (who, nm))
         if not _lib.get_lib().mn_code8conv_supported(C.byref(_conv_geom(conv)), B, B, B):
             ks, cg = tuple(conv.kernel_size), conv.in_channels // conv.groups
+            five = ks == (5, 5)
+            if tile_blocks and _lib.get_lib().mn_code8conv5_supported(C.byref(_conv_geom(conv)), B, B, B):
+                tiled.add(nm)
+                continue
+            if tile_blocks and five and conv.groups != 1:
+                raise _err("%s(tile_blocks=True): %s.conv: a grouped 5x5 block (groups %d) is not covered by mn_code8conv5_supported (dense only)" % (who, nm, conv.groups))
+            if tile_blocks and five and tuple(conv.padding) == (2, 2):
+                raise _err("%s(tile_blocks=True): %s.conv: a 5x5 block of %d input channels is beyond the bounds of mn_code8conv5_supported (C %% 16 == 0; C * 25 <= 33025: "
+                           "the exact int32 sum; ceil(C / 16) * 5 * (W + 4) <= 3071: one output row with its halo in 48 KB of LDS, at most 1216 channels on the narrowest "
+                           "map)" % (who, nm, conv.in_channels))
             raise _err("%s: %s.conv: geometry not covered by mn_code8conv_supported (%dx%d, padding %d, groups %d, %d channels per group: needs 1x1 / padding 0 that is "
-                       "dense or has C / groups %% 16 == 0, or 3x3 / padding 1 with C / groups %% 16 == 0, and C / groups * taps <= 33025)"
-                       % (who, nm, ks[0], ks[1], conv.padding[0], conv.groups, cg))
+                       "dense or has C / groups %% 16 == 0, or 3x3 / padding 1 with C / groups %% 16 == 0, and C / groups * taps <= 33025)%s"
+                       % (who, nm, ks[0], ks[1], conv.padding[0], conv.groups, cg,
+                          "; tile_blocks=True admits the dense 5x5 / padding 2 block of plain nin" if five and not tile_blocks else ""))
     first = last = None
     layers, tail, report = [], [], []
-    for name, child in seq.named_children():
+    kids = list(seq.named_children())
+    pending = None          # (tile_blocks) the standalone pool the walk has just passed: a quantised block must follow
+    for ki, (name, child) in enumerate(kids):
         nm = prefix + name
         if last is not None:
             tail.append(child)
+            continue
+        if tile_blocks and isinstance(child, nn.MaxPool2d) and not getattr(child, "_mn_fused_pool", False):
+            # ---- a max-pool prepare() did not fuse into the block in front of it: run on that block's byte map (mn_code8_maxpool)
+            ksp = _pool_kind(child)
+            if ksp is None:
+                raise _err("%s(tile_blocks=True): %s: max-pool (kernel %s, stride %s, padding %s, ceil_mode %s) is not covered by the byte kernels (2x2 / 2 / 0 and "
+                           "3x3 / 2 / 1, floor mode)" % (who, nm, child.kernel_size, child.stride, child.padding, child.ceil_mode))
+            if pending is not None or (layers and (layers[-1]["pool"] or layers[-1]["pool_ksp"])):
+                raise _err("%s(tile_blocks=True): %s: two max-pools in a row are not covered (one pool behind a byte block)" % (who, nm))
+            if not layers:
+                raise _err("%s(tile_blocks=True): %s: a max-pool directly behind the first block is not covered (its producer is not a byte block)" % (who, nm))
+            if not layers[-1]["wants_consumer"]:
+                raise _err("%s(tile_blocks=True): %s: the block in front of this max-pool already hands its codes to another consumer" % (who, nm))
+            layers[-1]["wants_consumer"], layers[-1]["pool_ksp"], layers[-1]["stage"] = False, ksp, name
+            pending = nm
             continue
         if isinstance(child, nn.MaxPool2d):
             if _pool_kind(child) != (2, 2, 0):
@@ -1313,10 +1368,17 @@ def _walk_bytes(model, byte_ends=False):
         conv, bn = child.conv, getattr(child, "bn", None)
         if not isinstance(bn, quantize.BatchNorm2dReLU):
             raise _err("%s: %s: conv -> BatchNorm -> ReLU not fused (prepare(..., fuse_bn_act=True, fuse_blocks=True))" % (who, nm))
+        if pending is not None:          # the consumer of a standalone pool: its activation quantizer is the one the producer's codes stand for
+            if not isinstance(conv, quantize.QuantConv2d) or conv.activation_quantizer.a_bits != B:
+                raise _err("%s(tile_blocks=True): %s: the block behind the max-pool %s must be a quantised conv reading %d-bit codes" % (who, nm, pending, B))
+            pending = None
         K = conv.in_channels // conv.groups * conv.kernel_size[0] * conv.kernel_size[1]
         if first is None:
             if type(conv) is not Conv2dFirst or getattr(child, "channel_shuffle_flag", 0):
                 raise _err("%s: %s: the first block must be the fp32 first conv" % (who, nm))
+            if tile_blocks and not bn.q_out_bits and ki + 1 < len(kids) and isinstance(kids[ki + 1][1], nn.MaxPool2d):
+                raise _err("%s(tile_blocks=True): %s: a max-pool directly behind the first block is not covered (its producer, %s, is not a byte block)"
+                           % (who, prefix + kids[ki + 1][0], nm))
             if bn.q_out_bits != B or bn.q_pool:
                 raise _err("%s: %s: the first block must hand over un-pooled 8-bit activation codes (it emits %s%s)"
                            % (who, nm, ("%d-bit codes" % bn.q_out_bits) if bn.q_out_bits else "fp32", ", pooled" if bn.q_pool else ""))
@@ -1332,7 +1394,12 @@ def _walk_bytes(model, byte_ends=False):
                             out_order="identity", stage=name)
             continue
         # ---- a hidden block: conv on bytes -> bn -> relu -> [pool] -> the next conv's quantizer
-        if bn.q_out_bits != B:
+        wants = False
+        if tile_blocks and not bn.q_out_bits and ki + 1 < len(kids) and isinstance(kids[ki + 1][1], nn.MaxPool2d) and not getattr(kids[ki + 1][1], "_mn_fused_pool", False):
+            # prepare() left the block emitting fp32 because an un-fused max-pool follows: it emits the codes of the conv behind that pool instead (checked when the
+            # walk gets there) -- exact, the pool sits behind the ReLU and the quantizer is non-decreasing
+            wants = True
+        elif bn.q_out_bits != B:
             raise _err("%s: %s: its output is not handed over as 8-bit codes to the next quantised conv" % (who, nm))
         if shuffle:
             _check_shuffle_divides(who, nm, conv, shuffle)
@@ -1341,13 +1408,25 @@ def _walk_bytes(model, byte_ends=False):
             layers[-1]["shuffle"] = shuffle          # folded into the producer's row order
         layers.append(dict(name=nm, conv=conv, bn=bn, k=conv.kernel_size[0], pad=conv.padding[0], cin=conv.in_channels, cout=conv.out_channels, groups=conv.groups,
                            pool=0, want_pool=bool(bn.q_pool), shuffle=0, stage=name))
+        if tile_blocks:
+            layers[-1].update(tile=nm in tiled, pool_ksp=None, wants_consumer=wants)
+    if pending is not None:
+        raise _err("%s(tile_blocks=True): %s: no quantised block behind this max-pool" % (who, pending))
     if first is None or last is None:
         raise _err("%s: module order not recognised (no %s block found)" % (who, "first" if first is None else "last"))
     for L in layers:
         if L.pop("want_pool") != bool(L["pool"]):
             raise _err("%s: %s: the block pools its output but no 2x2 max-pool follows it (or the reverse)" % (who, L["name"]))
+        kern, pooled = _code8conv_kernel_name(L["k"], L["pool"]), bool(L["pool"])
+        if tile_blocks:
+            if L.pop("wants_consumer"):
+                raise _err("%s(tile_blocks=True): %s: its output is not handed over as 8-bit codes to the next quantised conv" % (who, L["name"]))
+            if L["tile"]:
+                kern = _code8conv5_kernel_name(L["k"])
+            if L["pool_ksp"]:
+                kern, pooled = kern + ", k_code8_maxpool", "standalone"
         report.append(dict(name=L["name"], kind="byte", K=L["cin"] // L["groups"] * L["k"] * L["k"], blocks=(L["cin"] + 15) // 16,
-                           kernel=_code8conv_kernel_name(L["k"], L["pool"]), pooled=bool(L["pool"]),
+                           kernel=kern, pooled=pooled,
                            out_order=("shuffle %d" % L["shuffle"]) if L["shuffle"] > 1 else "identity", stage=L["stage"]))
     report.append(rep_last)
     if byte_ends:
@@ -1356,14 +1435,16 @@ def _walk_bytes(model, byte_ends=False):
     return first, layers, last, tail, flatten, report
 
 
-def dorefa_bytes_report(model, byte_ends=False):
-    """The ``report`` ``dorefa_compile_bytes(model, byte_ends)`` would carry -- one row per stage: name, kind ("first" / "byte" / "last"), K, blocks (16-channel blocks
-    of the stage's input map), kernel, pooled, out_order, stage -- from the graph walk alone: no GPU, nothing packed.  Raises like ``dorefa_compile_bytes``.  The
-    reference's ResNet of BasicBlocks: rows of name, kind ("first" / "quant" / "conv" / "add" / "last"), K, blocks, kernel, stride, shortcut ("identity" / "conv" / None)
-    and outputs (``_walk_bytes_res``)."""
+def dorefa_bytes_report(model, byte_ends=False, tile_blocks=False):
+    """The ``report`` ``dorefa_compile_bytes(model, byte_ends, tile_blocks)`` would carry -- one row per stage: name, kind ("first" / "byte" / "last"), K, blocks
+    (16-channel blocks of the stage's input map), kernel, pooled, out_order, stage -- from the graph walk alone: no GPU, nothing packed.  Raises like
+    ``dorefa_compile_bytes``.  ``tile_blocks`` as there: the dense 5x5 block reads ``k_code8conv5<5>``, a max-pool run on the byte map behind its block reads
+    ``pooled="standalone"`` and ``"<block kernel>, k_code8_maxpool"``, and its ``stage`` is the pool's.  The reference's ResNet of BasicBlocks: rows of name, kind
+    ("first" / "quant" / "conv" / "add" / "last"), K, blocks, kernel, stride, shortcut ("identity" / "conv" / None) and outputs (``_walk_bytes_res``; ``tile_blocks``
+    changes nothing there)."""
     if _is_ref_resnet(model):
         return _walk_bytes_res(model, byte_ends)[1]
-    return _walk_bytes(model, byte_ends)[5]
+    return _walk_bytes(model, byte_ends, tile_blocks)[5]
 
 
 def _code8_identity_chan(conv, dev):
@@ -1379,16 +1460,18 @@ def _code8_identity_chan(conv, dev):
 
 
 def _code8_pack(L, conv, chan, order=None):
-    """mn_code8conv_pack of a layer dict's geometry: the table of ``conv``'s stored weights with the constants ``chan``, rows in ``order``."""
+    """mn_code8conv_pack (a ``tile`` layer: mn_code8conv5_pack) of a layer dict's geometry: the table of ``conv``'s stored weights with the constants ``chan``, rows in
+    ``order``."""
     from micronet_amd import _lib, ops
     g, B = _block_geom(L), BYTE_BITS
-    table = torch.empty(int(_lib.get_lib().mn_code8conv_table_bytes(C.byref(g), B, B, B)) // 4, dtype=torch.int32, device=conv.weight.device)
-    ops._call("mn_code8conv_pack", C.byref(g), ops._p(conv.weight.detach().float().contiguous()), ops._p(chan), B, B, B, ops._p(order), ops._p(table), ops._s())
+    family = "mn_code8conv5" if L.get("tile") else "mn_code8conv"
+    table = torch.empty(int(getattr(_lib.get_lib(), family + "_table_bytes")(C.byref(g), B, B, B)) // 4, dtype=torch.int32, device=conv.weight.device)
+    ops._call(family + "_pack", C.byref(g), ops._p(conv.weight.detach().float().contiguous()), ops._p(chan), B, B, B, ops._p(order), ops._p(table), ops._s())
     return table
 
 
 @torch.no_grad()
-def dorefa_compile_bytes(model, byte_ends=False):
+def dorefa_compile_bytes(model, byte_ends=False, tile_blocks=False):
     """``model``: a DoReFa W8A8 net -- the reference's CPU configuration -- prepared with ``quant_inference=True`` after ``prequantize_weights``, on the GPU (the
     reference's ``nin_gc``, or an ``nn.Sequential`` of the same block kinds).  Returns a ``Byte8Plan`` that keeps ONE BYTE per hidden activation
     (``csrc/qgemm_codes_w8.h``: activation and weight codes as offset bytes on v_mfma_i32_16x16x64_i8, the block's BatchNorm + ReLU + [pool] + quantizer evaluated on
@@ -1396,7 +1479,14 @@ def dorefa_compile_bytes(model, byte_ends=False):
     one step.  Anything the byte kernels do not cover raises ``MicronetHipError`` naming the layer and the rule.  ``byte_ends=True``: the first conv
     writes the first stage's byte map in one launch (``mn_conv2d_first_bytes``) and the classifier conv reads the last stage's map (``mn_code8conv_fwd_f32``: the
     exact integer sum where the default path accumulates in fp32) -- no fp32 map, no uint8 codes, no pack / unpack launch; same bytes in every stage, logits within
-    the float contract.  Off by default until the gain is measured; with it off nothing changes.
+    the float contract.  Off by default until the gain is measured; with it off nothing changes.  ``tile_blocks=True``: also admits what plain ``nin`` needs -- a
+    dense 5x5 / padding 2 block with C % 16 == 0 and C * 25 <= 33025 on an LDS-resident halo tile (``mn_code8conv5_*``, ``csrc/qgemm_codes_w8_tile.h``; a map too wide
+    for one row with its halo in 48 KB of LDS raises at the first forward, naming the layer), and a 2x2 / 2 or 3x3 / 2 / 1 max-pool ``prepare()`` did not fuse,
+    directly behind a hidden block and in front of a quantised one, run on the byte map (``mn_code8_maxpool``; the block in front emits the codes of the conv behind
+    the pool: exact, the pool sits behind the ReLU and the quantizer is non-decreasing).  The layer dicts gain the keys ``"tile"`` and ``"pool_ksp"``, and
+    ``keep_stages`` keeps the post-pool maps.  Off by default; with it off nothing changes.  The two flags compose where the two end kernels cover the ends: plain
+    ``nin``'s first conv (5x5, 192 channels) is covered by ``mn_conv2d_first_bytes`` and its classifier by ``mn_code8conv_fwd_f32``; a first conv that is not keeps
+    the named refusal of ``byte_ends``.
 
     The reference's ``ResNet`` of ``BasicBlock``s (resnet18 / resnet34, any ``num_block``), W8A8, ``quant_inference=True``, pre-quantised, in eval mode, compiles to a
     ``Byte8ResPlan`` (``csrc/qgemm_codes_w8_res.h``): the model's own conv1, one launch that quantises its fp32 map to bytes, two launches per block (its first conv at
@@ -1407,7 +1497,7 @@ def dorefa_compile_bytes(model, byte_ends=False):
     from micronet_amd.quantization.wqaq.dorefa.quantize import _weight_is_coded
     if _is_ref_resnet(model):
         return _compile_bytes_res(model, byte_ends)
-    first, layers, last, tail, flatten, report = _walk_bytes(model, byte_ends)
+    first, layers, last, tail, flatten, report = _walk_bytes(model, byte_ends, tile_blocks)
     last_layer = None
     if byte_ends:          # the classifier as a layer dict of its own: packed and read back with the others
         conv = last.conv

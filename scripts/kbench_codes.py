@@ -27,6 +27,11 @@ follows the same procedure on W8A8 resnet18: the model's own eval forward (at 8 
 on fp32 maps -- the yardstick) against ``dorefa_compile_bytes(I)`` (a ``Byte8ResPlan``: two launches per block on byte maps), alternated in one process; the per-kernel
 times of k_code8_quant, k_code8res_conv and k_code8res_add, both launch counts and the largest logit difference are recorded.  No time is promised.
 
+    python scripts/kbench_codes.py --bytes-nin [--batches 256] [--warmup 5] [--iters 20] [--out profiles/codes_w8_nin.json]
+
+is that procedure on W8A8 PLAIN nin: the model's own eval forward against ``dorefa_compile_bytes(I, tile_blocks=True)`` (the dense 5x5 block on ``k_code8conv5``, the two
+3x3 / 2 max-pools on ``k_code8_maxpool``); the per-launch times of the k_code8conv* kernels and of k_code8_maxpool are recorded.  No time is promised.
+
     python scripts/kbench_codes.py --arch nin [--batches 256,1024] [--warmup 5] [--iters 20] [--out profiles/codes_nin.json]
 
 is the first protocol on PLAIN nin: ``P = dorefa_compile_codes(I, tile_blocks=True)`` (the dense 5x5 block on an LDS tile, the two 3x3 / 2 max-pools on planes).
@@ -157,19 +162,20 @@ def main_code_ends(args, byte=False):
     print("wrote", args.out)
 
 
-def main_bytes_resnet(args):
+def main_bytes_resnet(args, arch="resnet18", new_kernels=("k_code8_quant", "k_code8res_"), **compile_kw):
     """W8A8 resnet18: the model's own eval forward I (conv, BatchNorm, add, ReLU and quantizer launches on fp32 maps: the yardstick) against
-    P = dorefa_compile_bytes(I) (a Byte8ResPlan: two launches per block on byte maps), alternated in one process."""
+    P = dorefa_compile_bytes(I) (a Byte8ResPlan: two launches per block on byte maps), alternated in one process.  ``--bytes-nin``: the same procedure on W8A8 plain
+    nin with P = dorefa_compile_bytes(I, tile_blocks=True); ``new_kernels``: the kernels whose time per launch is listed."""
     from micronet.compression.quantization.wqaq.dorefa import quantize as Q
     from micronet_amd import _lib, inference
     from micronet_amd.train import build_model, synth_batch
     torch.manual_seed(0)
-    I = Q.prepare(build_model("resnet18"), inplace=True, a_bits=8, w_bits=8, quant_inference=True).cuda()
+    I = Q.prepare(build_model(arch), inplace=True, a_bits=8, w_bits=8, quant_inference=True).cuda()
     inference.prequantize_weights(I)
     I.eval()
-    P = inference.dorefa_compile_bytes(I)
+    P = inference.dorefa_compile_bytes(I, **compile_kw)
     lib = _lib.get_lib()
-    res = dict(model="resnet18", a_bits=8, w_bits=8, warmup=args.warmup, iters=args.iters, device=torch.cuda.get_device_name(0), report=P.report, batches={})
+    res = dict(model=arch, a_bits=8, w_bits=8, warmup=args.warmup, iters=args.iters, device=torch.cuda.get_device_name(0), report=P.report, batches={})
     with torch.no_grad():
         for bs in [int(v) for v in args.batches.split(",")]:
             x, _ = synth_batch(bs, device="cuda")
@@ -182,7 +188,7 @@ def main_bytes_resnet(args):
                 t1.append(timed(P, x))
             k0, k1 = profile(lib, _lib, I, x), profile(lib, _lib, P, x)
             med0, med1 = statistics.median(t0), statistics.median(t1)
-            new = {n: round(1e3 * v["ms"] / max(1, v["launches"]), 2) for n, v in k1.items() if n.startswith(("k_code8_quant", "k_code8res_"))}
+            new = {n: round(1e3 * v["ms"] / max(1, v["launches"]), 2) for n, v in k1.items() if n.startswith(new_kernels)}
             # (the exact integer sum against an fp32 accumulation: equal within the float contract, not to the bit)
             res["batches"][str(bs)] = dict(I_ms=q(t0), P_ms=q(t1), I_img_s=bs / med0 * 1e3, P_img_s=bs / med1 * 1e3, P_over_I=med0 / med1, new_us=new,
                                            max_abs_logit_diff=float((ref - got).abs().max()), max_abs_logit=float(ref.abs().max()),
@@ -374,6 +380,7 @@ def main():
     ap.add_argument("--code-ends", action="store_true", help="the default plan against dorefa_compile_codes(I, code_ends=True)")
     ap.add_argument("--byte-ends", action="store_true", help="W8A8: the default byte plan against dorefa_compile_bytes(I, byte_ends=True)")
     ap.add_argument("--bytes-resnet", action="store_true", help="W8A8 resnet18: the model's own eval forward against dorefa_compile_bytes(I) (a Byte8ResPlan)")
+    ap.add_argument("--bytes-nin", action="store_true", help="W8A8 plain nin: the model's own eval forward against dorefa_compile_bytes(I, tile_blocks=True)")
     ap.add_argument("--mfma-blocks", action="store_true", help="I, the default plan and dorefa_compile_codes(I, mfma_blocks=True)")
     ap.add_argument("--mfma-k3", action="store_true", help="I, the mfma_blocks plan and dorefa_compile_codes(I, mfma_blocks=True, mfma_k3=True); works with --arch nin")
     ap.add_argument("--arch", default="nin_gc", choices=("nin_gc", "nin"), help="nin: plain nin, compiled with tile_blocks=True")
@@ -382,6 +389,12 @@ def main():
                     help="with --bits 4: two --mfma-k3 results, of the parent commit and of this tree, recorded under two_bit_check")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.bytes_nin:
+        if args.bytes_resnet or args.byte_ends or args.code_ends or args.mfma_blocks or args.mfma_k3 or args.arch != "nin_gc" or args.bits != 2 or args.two_bit_check:
+            ap.error("--bytes-nin is its own protocol, on W8A8 plain nin")
+        if args.out is None:
+            args.out = os.path.join("profiles", "codes_w8_nin.json")
+        return main_bytes_resnet(args, "nin", ("k_code8conv", "k_code8_maxpool"), tile_blocks=True)
     if args.bytes_resnet:
         if args.byte_ends or args.code_ends or args.mfma_blocks or args.mfma_k3 or args.arch != "nin_gc" or args.bits != 2 or args.two_bit_check:
             ap.error("--bytes-resnet is its own protocol, on W8A8 resnet18")
