@@ -1347,6 +1347,30 @@ int mn_i8zconv_fwd(const mn_conv_geom* g, int a_bits, int w_bits, const uint32_t
 int mn_i8z_pack_codes(const float* x, int64_t N, int64_t C, int64_t HW, const mn_i8z_quant* q, const int32_t* out_order, int8_t* codes, mn_stream_t stream);
 int mn_i8z_unpack_codes(const int8_t* codes, int64_t N, int64_t C, int64_t HW, const mn_i8z_quant* q, float* y, mn_stream_t stream);
 
+/* What plain nin adds to the int8 deployment (csrc/qgemm_iao8_tile.h; inference.iao_compile_int8(model, tile_blocks=True)).  Codes, acc, the un-pooled chain, the
+ * table's header words and counters (0 and 7; scales in 8 .. 12) and pack's arguments are those of mn_i8conv_*; symmetric quantizers only.
+ *   conv5   : the dense 5x5 hidden block on an LDS-resident halo tile: a block stages its input tile (several whole images of at most 256 pixels together, else a band of
+ *             rows at full width) with a halo of 2 ONCE, zero bytes where the map or the batch ends, and its k-loop reads LDS alone.  Covered (mn_i8conv5_supported,
+ *             which table_bytes / pack / fwd follow): 2 <= a_bits, w_bits <= 8; KH = KW = 5, stride 1, padding 2, dilation 1, groups 1, g->in_shuffle 0 / 1,
+ *             C % 16 == 0, any O; C * 25 * 2^(a-1) * (2^(w-1) - 1) <= INT_MAX; W <= 256 and ceil(C/16) * 5 * (W + 4) <= 3071 (one output row with its halo in 48 KB of
+ *             LDS); any H, any N.  No pool is folded: pack takes no s_p (a block in front of a pool is packed with the POOL quantizer's scale as s_out, and
+ *             mn_i8_maxpool takes the codes on).  out_codes [N][ceil(O/16)][H*W][16], every 16-byte block stored once and whole, positions >= O and bad out_order
+ *             entries 0.  Not covered: MN_ENOTSUP; null / misaligned pointer (table and codes 16-byte aligned), an invalid geometry or an output that overlaps the
+ *             input: MN_EINVAL; nothing is written in either case.  mn_i8conv_supported goes on refusing 5x5.  mn_last_kernel(): k_i8conv5<5>.
+ *   maxpool : map_in [N][ceil(C/16)][H*W][16] -> map_out [N][ceil(C/16)][Ho*Wo][16], floor mode (Ho = (H + 2 pad - k) / stride + 1): per channel m = the largest code
+ *             over the in-map cells of the window, c = clamp(rha(fl(fl(float(m) * s_p) / s_out)), -2^(a-1), 2^(a-1) - 1) -- the pooled tail of mn_i8conv_fwd's chain,
+ *             map_in holding codes at the pool quantizer's scale s_p; tail channels stay 0.  Covered: (k, stride, pad) = (2, 2, 0) and (3, 2, 1), 2 <= a_bits <= 8;
+ *             anything else MN_ENOTSUP.  Null / misaligned / empty argument, a scale that is not finite and positive, an image smaller than the window or an output
+ *             that overlaps the input (no in-place call): MN_EINVAL.  Nothing is written in either case.  mn_last_kernel(): k_i8_maxpool.
+ * No entry allocates. */
+int mn_i8conv5_supported(const mn_conv_geom* g, int a_bits, int w_bits);
+int64_t mn_i8conv5_table_bytes(const mn_conv_geom* g, int a_bits, int w_bits);
+int mn_i8conv5_pack(const mn_conv_geom* g, const float* w, const float* s_w, int s_w_stride, const float* bias, float s_a, float s_out, int a_bits, int w_bits,
+                    const int32_t* out_order, uint32_t* table, mn_stream_t stream);
+int mn_i8conv5_fwd(const mn_conv_geom* g, int a_bits, int w_bits, const uint32_t* table, const int8_t* in_codes, int8_t* out_codes, mn_stream_t stream);
+int mn_i8_maxpool(const int8_t* map_in, int64_t N, int64_t C, int64_t H, int64_t W, int k, int stride, int pad, float s_p, float s_out, int a_bits, int8_t* map_out,
+                  mn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

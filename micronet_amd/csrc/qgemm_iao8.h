@@ -15,7 +15,8 @@
 //   weight table : (private layout, 16-byte aligned: the set / tile table of qgemm_mfma_sets.h, a set = four 16-byte output blocks) 16 header words -- [0] rows
 //                  with a non-finite al or b or a bad s_w, plus each of s_a, s_p, s_out that is non-finite or <= 0, [1] k-steps, [2] tile slots per set, [3] tile
 //                  stride, [4] sets, [5] chunks, [6] a_bits | w_bits << 8, [7] bad out_order entries + rows with a weight off the grid, [8] s_p, [9] s_out,
-//                  [10] qmin, [11] qmax, [12] s_a (fp32 bit patterns) -- then one word per slot (dy + 1 | (dx + 1) << 2 | chunk << 4), then the tile count of every
+//                  [10] qmin, [11] qmax, [12] s_a (fp32 bit patterns) -- then one word per slot (dy + 1 | (dx + 1) << 2 | chunk << 4; the 5x5 geometry of
+//                  qgemm_iao8_tile.h: dy | dx << 3 | chunk << 6 with dy, dx = 0 .. 4), then the tile count of every
 //                  set, then the tiles:
 //                    [0] first 16-channel block of the tile's group, [16 ..) al[16], [32 ..) b[16], [48 ..) dest[16] (position in the set, -1: a dead row),
 //                    [64 ..) per k-step 64 lanes x 16 bytes in the A-operand order of mn_mfma_i8 (lane = 16 kq + row).
@@ -80,8 +81,8 @@ __global__ __launch_bounds__(256) void k_i8conv_wpack(IGeom m, const float* __re
     if (set == 0) {
         for (int i = tid; i < 4 * m.nsteps; i += 256) {
             const int tap = i < m.nslots ? i / m.chunks : m.taps / 2, chunk = i < m.nslots ? i - tap * m.chunks : 0;          // a padding slot: the centre tap against zero bytes
-            const int dy = m.KS == 3 ? tap / 3 : 1, dx = m.KS == 3 ? tap % 3 : 1;
-            tab[m.slot_off + i] = (uint32_t)(dy | (dx << 2) | (chunk << 4));
+            const int dy = m.KS == 1 ? 1 : tap / m.KS, dx = m.KS == 1 ? 1 : tap % m.KS;
+            tab[m.slot_off + i] = (uint32_t)(m.KS == 5 ? dy | (dx << 3) | (chunk << 6) : dy | (dx << 2) | (chunk << 4));          // (5x5: qgemm_iao8_tile.h, three bits per tap offset)
         }
         if (tid == 0) {
             tab[1] = (uint32_t)m.nsteps; tab[2] = (uint32_t)m.slots; tab[3] = (uint32_t)m.tstride; tab[4] = (uint32_t)m.nsets; tab[5] = (uint32_t)m.chunks;

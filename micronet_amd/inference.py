@@ -1804,10 +1804,20 @@ def _iao8_check_weights(conv, nm, who="iao_compile_int8", zero_points=False):
     return wq
 
 
-def _walk_iao8(model, input_hw=(32, 32), byte_ends=False, zero_points=False):
+_TILE_ZP = ("iao_compile_int8(tile_blocks=True): zero_points=True is not covered together with tile_blocks (the 5x5 tile block and the max-pool on code maps take "
+            "symmetric quantizers only)")
+_TILE_E2E = "iao_compile_int8(tile_blocks=True): end_to_end=True is not covered together with tile_blocks (plain nin's form is byte_ends=True)"
+_TILE_RESNET = "iao_compile_int8(tile_blocks=True): the reference ResNet tree has no 5x5 block and no un-folded max-pool; compile it without tile_blocks"
+_I8CONV5_RULE = ("dense 5x5 / stride 1 / padding 2 / dilation 1 with C % 16 == 0, C * 25 * 2^(a-1) * (2^(w-1) - 1) <= INT_MAX, W <= 256 and "
+                 "ceil(C / 16) * 5 * (W + 4) <= 3071: one output row with its halo in 48 KB of LDS")
+
+
+def _walk_iao8(model, input_hw=(32, 32), byte_ends=False, zero_points=False, tile_blocks=False):
     """The graph walk of ``iao_compile_int8`` (no GPU needed): (first, layers, last, tail, flatten, report, pack_shuffle, ends); ``ends``: None, or with ``byte_ends``
     the layer dicts (first, last) of the two end blocks.  ``zero_points``: asymmetric quantizers are admitted; a layer whose input, weight, pool or consumer quantizer
-    is asymmetric carries ``zp`` = True and takes the kernels of csrc/qgemm_iao8_zp.h."""
+    is asymmetric carries ``zp`` = True and takes the kernels of csrc/qgemm_iao8_zp.h.  ``tile_blocks``: also admit what plain nin adds (csrc/qgemm_iao8_tile.h) -- a
+    dense 5x5 block ``mn_i8conv5_supported`` covers (``layer["tile"]``), and a 3x3 / 2 / 1 ``QuantMaxPool2d`` behind a hidden block or a 2x2 / 2 / 0 one behind a 5x5
+    block as an un-folded stage of its own (``layer["pool_ksp"]``, a report row of kind ``int8_pool``); without it the layer dicts have neither key."""
     if zero_points and byte_ends:
         raise _err("iao_compile_int8(zero_points=True): byte_ends=True is not covered together with zero points (the int8 end kernels take symmetric quantizers only)")
     from micronet_amd import _lib
@@ -1843,7 +1853,11 @@ def _walk_iao8(model, input_hw=(32, 32), byte_ends=False, zero_points=False):
     layers, pack_shuffle = [], 0
     for nm, child in items[1:last_i]:
         if isinstance(child, nn.MaxPool2d):
-            ok = (type(child) is quantize.QuantMaxPool2d and _pool_kind(child) == (2, 2, 0))
+            ksp = _pool_kind(child)
+            ok = (type(child) is quantize.QuantMaxPool2d and (ksp == (2, 2, 0) or (tile_blocks and ksp == (3, 2, 1))))
+            if not ok and tile_blocks:
+                raise _err("iao_compile_int8(tile_blocks=True): %s (%s, kernel %s, stride %s, padding %s): only a 2x2 / 2 / 0 or 3x3 / 2 / 1 QuantMaxPool2d (floor mode) "
+                           "runs on the code map" % (nm, type(child).__name__, child.kernel_size, child.stride, child.padding))
             if not ok:
                 raise _err("iao_compile_int8: %s (%s, kernel %s, stride %s, padding %s): only a 2x2 / stride 2 QuantMaxPool2d is folded into the int8 block in front of it"
                            % (nm, type(child).__name__, child.kernel_size, child.stride, child.padding))
@@ -1851,14 +1865,22 @@ def _walk_iao8(model, input_hw=(32, 32), byte_ends=False, zero_points=False):
                 raise _err("%s: %s: a max-pool directly behind the first block is not covered (the pooled form of k_i8first is not built)" % (ends_who, nm))
             if not layers:
                 raise _err("iao_compile_int8: %s: a max-pool directly behind the first block is not covered (its producer is not an int8 block)" % nm)
-            if layers[-1]["pool"]:
+            if layers[-1]["pool"] or layers[-1].get("pool_ksp"):
                 raise _err("iao_compile_int8: %s: a second max-pool behind one block" % nm)
             _iao8_check_quantizer(child.activation_quantizer, nm + ".activation_quantizer", True, zero_points=zero_points)
-            layers[-1]["pool"], layers[-1]["pool_module"], layers[-1]["pool_name"] = 1, child, nm
+            layers[-1]["pool_module"], layers[-1]["pool_name"] = child, nm
+            if tile_blocks and (ksp == (3, 2, 1) or layers[-1]["tile"]):
+                layers[-1]["pool_ksp"] = ksp          # a stage of its own on the code map (mn_i8_maxpool); a 2x2 / 2 behind a 1x1 or 3x3 block stays folded
+            else:
+                layers[-1]["pool"] = 1
             continue
         conv = block_conv(nm, child)
         wq = _iao8_check_weights(conv, nm + ".conv", zero_points=zero_points)
-        if not _lib.get_lib().mn_i8conv_supported(C.byref(_conv_geom(conv)), conv.activation_quantizer.bits, wq.bits):
+        tile = bool(tile_blocks and tuple(conv.kernel_size) == (5, 5))
+        if tile and not _lib.get_lib().mn_i8conv5_supported(C.byref(_conv_geom(conv)), conv.activation_quantizer.bits, wq.bits):
+            raise _err("iao_compile_int8(tile_blocks=True): %s.conv: geometry not covered by mn_i8conv5_supported (5x5, stride %d, padding %d, dilation %d, groups %d, "
+                       "%d channels: " % (nm, _one(conv.stride), _one(conv.padding), _one(conv.dilation), conv.groups, conv.in_channels) + _I8CONV5_RULE + ")")
+        if not tile and not _lib.get_lib().mn_i8conv_supported(C.byref(_conv_geom(conv)), conv.activation_quantizer.bits, wq.bits):
             raise _err("iao_compile_int8: %s.conv: geometry not covered by mn_i8conv_supported (%dx%d, stride %d, padding %d, dilation %d, groups %d, %d channels per group: "
                        "1x1 / padding 0 with groups 1 or C / groups %% 16 == 0, or 3x3 / padding 1 with C / groups %% 16 == 0; stride 1)"
                        % (nm, conv.kernel_size[0], conv.kernel_size[1], _one(conv.stride), _one(conv.padding), _one(conv.dilation), conv.groups, conv.in_channels // conv.groups))
@@ -1871,6 +1893,8 @@ def _walk_iao8(model, input_hw=(32, 32), byte_ends=False, zero_points=False):
                 pack_shuffle = s                   # ... or into the pack behind the first block
         layers.append(dict(name=nm, conv=conv, k=conv.kernel_size[0], pad=conv.padding[0], cin=conv.in_channels, cout=conv.out_channels, groups=conv.groups, pool=0,
                            pool_module=None, pool_name=None, shuffle=0, w_bits=wq.bits, in_bits=conv.activation_quantizer.bits, per_channel=wq.scale.numel() > 1))
+        if tile_blocks:
+            layers[-1].update(tile=tile, pool_ksp=None)
     if not layers:
         raise _err("iao_compile_int8: no hidden block between %s and %s" % (nm_first, nm_last))
     # the consumer of every hidden block: the next hidden conv's activation quantizer, or the last conv's
@@ -1882,7 +1906,7 @@ def _walk_iao8(model, input_hw=(32, 32), byte_ends=False, zero_points=False):
         L["asym_out"] = is_asym(nxt.activation_quantizer)
         L["asym_p"] = is_asym(L["pool_module"].activation_quantizer) if L["pool"] else L["asym_out"]
         L["zp"] = bool(L["asym_a"] or L["asym_w"] or L["asym_out"] or L["asym_p"])
-        if L["pool"] and L["pool_module"].activation_quantizer.bits != L["a_bits"]:
+        if L["pool_module"] is not None and L["pool_module"].activation_quantizer.bits != L["a_bits"]:
             raise _err("iao_compile_int8: %s: the pool's quantizer has %d bits, its consumer %d: one code width per block"
                        % (L["pool_name"], L["pool_module"].activation_quantizer.bits, L["a_bits"]))
     report = [dict(name=nm_first, kind="first", kernel="the model's own block (fp32), %s" % ("k_i8z_pack" if layers[0]["asym_a"] else "k_i8_pack"),
@@ -1911,10 +1935,23 @@ def _walk_iao8(model, input_hw=(32, 32), byte_ends=False, zero_points=False):
                 raise _err("iao_compile_int8: %s: the 2x2 max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
             H, W = H // 2, W // 2
         table_bytes = _lib.get_lib().mn_i8zconv_table_bytes if L["zp"] else _lib.get_lib().mn_i8conv_table_bytes
+        kernel = _i8conv_kernel_name(L["k"], L["pool"], L["zp"])
+        if L.get("tile"):
+            if not _lib.get_lib().mn_i8conv5_supported(C.byref(_block_geom(L, 1, H, W)), L["a_bits"], L["w_bits"]):
+                raise _err("iao_compile_int8(tile_blocks=True): %s.conv: a %d-channel map %d pixels wide is beyond the LDS bound of mn_i8conv5_supported (%s)"
+                           % (L["name"], L["cin"], W, _I8CONV5_RULE))
+            table_bytes, kernel = _lib.get_lib().mn_i8conv5_table_bytes, "k_i8conv5<%d>" % L["k"]
         L["table_bytes"] = int(table_bytes(C.byref(g), L["a_bits"], L["w_bits"]))
-        report.append(dict(name=L["name"], kind="int8", kernel=_i8conv_kernel_name(L["k"], L["pool"], L["zp"]), k=L["k"], cin=L["cin"],
+        report.append(dict(name=L["name"], kind="int8", kernel=kernel, k=L["k"], cin=L["cin"],
                            cout=L["cout"], groups=L["groups"], pool=L["pool"], out_order=("shuffle %d" % L["shuffle"]) if L["shuffle"] else "identity", table_bytes=L["table_bytes"], act_bytes_in=nin,
                            act_bytes_out=_blocked(L["cout"], H, W)))
+        if L.get("pool_ksp"):          # the un-folded pool: a stage of its own on the block's code map, positions (the consumer's shuffle) unchanged
+            pk, ps, pp = L["pool_ksp"]
+            if min(H, W) + 2 * pp < pk:
+                raise _err("iao_compile_int8(tile_blocks=True): %s: the max-pool does not fit a %d x %d map" % (L["pool_name"], H, W))
+            H, W = _out_size(H, pk, ps, pp, 1), _out_size(W, pk, ps, pp, 1)
+            report.append(dict(name=L["pool_name"], kind="int8_pool", kernel="k_i8_maxpool", k=pk, cin=L["cout"], cout=L["cout"], groups=L["cout"], pool=0,
+                               out_order="identity", table_bytes=0, act_bytes_in=report[-1]["act_bytes_out"], act_bytes_out=_blocked(L["cout"], H, W)))
     report.append(dict(name=nm_last, kind="last", kernel="%s, the model's own block (fp32)" % ("k_i8z_unpack" if layers[-1]["asym_out"] else "k_i8_unpack"),
                        k=last_conv.kernel_size[0], cin=last_conv.in_channels, cout=last_conv.out_channels, groups=last_conv.groups, pool=0, out_order="identity", table_bytes=0,
                        act_bytes_in=_blocked(last_conv.in_channels, H, W) + 4 * last_conv.in_channels * H * W, act_bytes_out=4 * last_conv.out_channels * H * W))
@@ -1937,7 +1974,7 @@ def _walk_iao8(model, input_hw=(32, 32), byte_ends=False, zero_points=False):
     return first, layers, last, tail, flatten, report, pack_shuffle, ends
 
 
-def iao_int8_report(model, input_hw=(32, 32), byte_ends=False, zero_points=False, end_to_end=False):
+def iao_int8_report(model, input_hw=(32, 32), byte_ends=False, zero_points=False, end_to_end=False, tile_blocks=False):
     """The ``report`` ``iao_compile_int8(model, byte_ends)`` would carry -- one row per stage: layer, kernel, geometry, folded pool, the consumer's shuffle folded into
     the stage (``out_order``), table bytes and the activation bytes per image the stage reads and writes at an ``input_hw`` input -- from the graph walk alone: no GPU,
     nothing packed.  With ``byte_ends`` the two end rows are the kinds ``int8_first`` / ``int8_last`` and no fp32 map stands between the rows.  Raises like
@@ -1952,15 +1989,29 @@ def iao_int8_report(model, input_hw=(32, 32), byte_ends=False, zero_points=False
 
     ``end_to_end=True`` (the reference ResNet tree only): the walk of ``iao_compile_int8(model, end_to_end=True)``: row 0 is the kind ``int8_first`` on
     ``k_i8first2<KS,nout>``, the last row the kind ``int8_last`` on ``k_i8poolfc``, both with table bytes and activation bytes (fp32 image in, ``nout`` byte maps out;
-    bytes in, 4 O out); every row between them is the default report's."""
+    bytes in, 4 O out); every row between them is the default report's.
+
+    ``tile_blocks=True``: the walk of ``iao_compile_int8(model, tile_blocks=True)``, which plain nin needs: its dense 5x5 block reports ``k_i8conv5<5>``, and each of
+    its max-pools is a row of its own of the kind ``int8_pool`` on ``k_i8_maxpool`` (name: the pool's; ``k``: its window) behind its block's un-pooled row."""
+    _iao8_tile_keywords(model, zero_points, end_to_end, tile_blocks)
     if _is_ref_resnet(model):
         if zero_points:
             raise _err(_ZP_RESNET)
         return _walk_iao8_res(model, input_hw, byte_ends, end_to_end)[4]
-    report = _walk_iao8(model, input_hw, byte_ends, zero_points)[5]
+    report = _walk_iao8(model, input_hw, byte_ends, zero_points, tile_blocks)[5]
     if end_to_end:
         raise _err(_E2E_RESNET)
     return report
+
+
+def _iao8_tile_keywords(model, zero_points, end_to_end, tile_blocks):
+    """What ``tile_blocks=True`` does not compose with: one fixed message each."""
+    if tile_blocks and zero_points:
+        raise _err(_TILE_ZP)
+    if tile_blocks and end_to_end:
+        raise _err(_TILE_E2E)
+    if tile_blocks and _is_ref_resnet(model):
+        raise _err(_TILE_RESNET)
 
 
 _E2E_RESNET = "iao_compile_int8(end_to_end=True): covered for the reference ResNet tree only (nin_gc's form is byte_ends=True)"
@@ -2006,7 +2057,11 @@ class Int8Plan(_Plan):
 
     With ``byte_ends`` (``ends`` is set) neither end runs the model's own modules: ``mn_i8first_fwd`` takes the fp32 image to the first hidden block's codes, the hidden
     stages run unchanged, ``mn_i8conv_fwd_f32`` takes the last hidden codes to the fp32 map [N][O][H * W] of the model's tail: no ``k_i8_pack``, no ``k_i8_unpack``
-    and no fp32 activation map in between.  ``ends`` = (first, last) keeps what the two tables were packed from, as ``layers[i]`` does (the first also ``in_bits``)."""
+    and no fp32 activation map in between.  ``ends`` = (first, last) keeps what the two tables were packed from, as ``layers[i]`` does (the first also ``in_bits``).
+
+    A plan compiled with ``tile_blocks=True`` runs a dense 5x5 stage on ``mn_i8conv5_fwd`` (``layers[i]["tile"]``) and a stage with an un-folded max-pool
+    (``layers[i]["pool_ksp"]`` = (kernel, stride, padding)) as two launches: the block, packed at the pool quantizer's scale ``s_p``, into a mid map at full size,
+    then ``mn_i8_maxpool`` from ``s_p`` to ``s_out``; the stage's buffer, ``stage_codes`` entry and ``run_stage`` result are the pooled map."""
 
     who = "iao_compile_int8"
 
@@ -2022,19 +2077,36 @@ class Int8Plan(_Plan):
         N, Cc, H, W = shape
         if Cc != self.layers[0]["cin"]:
             raise _err("iao_compile_int8: %s produced %d channels, %s reads %d" % (self.report[0]["name"], Cc, self.layers[0]["name"], self.layers[0]["cin"]))
-        bufs, geoms = [_code_map(N, Cc, H * W, device)], []
+        from micronet_amd import _lib
+        bufs, geoms, mids = [_code_map(N, Cc, H * W, device)], [], []
         if self.ends:
             geoms.append(_block_geom(self.ends[0], N, H, W))          # (stride 1, padding (k - 1) / 2: the image has the first block's H x W)
         for L in self.layers:
             geoms.append(_block_geom(L, N, H, W))
+            if L.get("tile") and not _lib.get_lib().mn_i8conv5_supported(C.byref(geoms[-1]), L["a_bits"], L["w_bits"]):
+                raise _err("iao_compile_int8(tile_blocks=True): %s.conv: a %d-channel map %d pixels wide is beyond the LDS bound of mn_i8conv5_supported (%s)"
+                           % (L["name"], L["cin"], W, _I8CONV5_RULE))
             if L["pool"]:
                 if H % 2 or W % 2:
                     raise _err("iao_compile_int8: %s: the 2x2 max-pool behind it does not fit a %d x %d map" % (L["name"], H, W))
                 H, W = H // 2, W // 2
+            mids.append(None)
+            if L.get("pool_ksp"):          # (tile_blocks) an un-folded pool: the block at full size into a mid map, then mn_i8_maxpool
+                Ho, Wo = self._pooled(L, H, W)
+                mids[-1] = (_code_map(N, L["cout"], H * W, device), H, W)
+                H, W = Ho, Wo
             bufs.append(_code_map(N, L["cout"], H * W, device))
         if self.ends:
             geoms.append(_block_geom(self.ends[1], N, H, W))
-        return (bufs, geoms, torch.empty((N, (self.ends[1] if self.ends else self.layers[-1])["cout"], H, W), dtype=torch.float32, device=device))
+        return (bufs, geoms, torch.empty((N, (self.ends[1] if self.ends else self.layers[-1])["cout"], H, W), dtype=torch.float32, device=device), mids)
+
+    @staticmethod
+    def _pooled(L, H, W):
+        """The map size behind the un-folded pool of stage ``L``."""
+        pk, ps, pp = L["pool_ksp"]
+        if min(H, W) + 2 * pp < pk:
+            raise _err("iao_compile_int8(tile_blocks=True): %s: the max-pool does not fit a %d x %d map" % (L["pool_name"], H, W))
+        return _out_size(H, pk, ps, pp, 1), _out_size(W, pk, ps, pp, 1)
 
     def _first(self, g, x, out, st):
         """The first end (byte_ends): the fp32 image to the first hidden stage's codes."""
@@ -2042,11 +2114,19 @@ class Int8Plan(_Plan):
         Lf = self.ends[0]
         ops._call("mn_i8first_fwd", C.byref(g), Lf["in_bits"], Lf["a_bits"], Lf["w_bits"], ops._p(Lf["table"]), ops._p(x), ops._p(out), st)
 
-    def _stage(self, L, g, src, out, st):
-        """A hidden stage: the zero-point kernels where one of its quantizers is asymmetric."""
+    def _stage(self, L, g, src, out, st, mid=None):
+        """A hidden stage: the zero-point kernels where one of its quantizers is asymmetric; (tile_blocks) the 5x5 block on its LDS tile, and behind a block with an
+        un-folded pool -- written into ``mid`` = (map, H, W) -- the max-pool from the pool quantizer's codes to the consumer's."""
         from micronet_amd import ops
-        ops._call("mn_i8zconv_fwd" if L.get("zp") else "mn_i8conv_fwd", C.byref(g), L["a_bits"], L["w_bits"], ops._p(L["table"]), ops._p(src), ops._p(out),
-                  int(L["pool"]), st)
+        blk = out if mid is None else mid[0]
+        if L.get("tile"):
+            ops._call("mn_i8conv5_fwd", C.byref(g), L["a_bits"], L["w_bits"], ops._p(L["table"]), ops._p(src), ops._p(blk), st)
+        else:
+            ops._call("mn_i8zconv_fwd" if L.get("zp") else "mn_i8conv_fwd", C.byref(g), L["a_bits"], L["w_bits"], ops._p(L["table"]), ops._p(src), ops._p(blk),
+                      int(L["pool"]), st)
+        if mid is not None:
+            (m, h, w), (pk, ps, pp) = mid, L["pool_ksp"]
+            ops._call("mn_i8_maxpool", ops._p(m), m.shape[0], L["cout"], h, w, pk, ps, pp, L["s_p"], L["s_out"], L["a_bits"], ops._p(out), st)
 
     def _last(self, g, codes, y, st):
         """The last end (byte_ends): the last hidden codes to the fp32 map of the tail."""
@@ -2079,11 +2159,11 @@ class Int8Plan(_Plan):
         x = _iao8_ends_image(self.ends, x, "byte_ends")
         N, _, H, W = x.shape
         with torch.cuda.device(x.device):
-            bufs, geoms, y = self._shape_buffers((N, self.ends[0]["cout"], H, W), x.device)
+            bufs, geoms, y, mids = self._shape_buffers((N, self.ends[0]["cout"], H, W), x.device)
             st = ops._s()
             self._first(geoms[0], x, bufs[0], st)
             for i, L in enumerate(self.layers):
-                self._stage(L, geoms[i + 1], bufs[i], bufs[i + 1], st)
+                self._stage(L, geoms[i + 1], bufs[i], bufs[i + 1], st, mids[i])
             if self.keep_stages:
                 self.stage_codes = [b.clone() for b in bufs]
             self._last(geoms[-1], bufs[-1], y, st)
@@ -2095,10 +2175,11 @@ class Int8Plan(_Plan):
         L = self.layers[i]
         if not _is_code_map(codes, N, L["cin"], H * W):
             raise _err("iao_compile_int8: run_stage needs int8 GPU codes [N, ceil(C / 16), H * W, 16]")
-        Ho, Wo = (H // 2, W // 2) if L["pool"] else (H, W)
+        Ho, Wo = (H // 2, W // 2) if L["pool"] else self._pooled(L, H, W) if L.get("pool_ksp") else (H, W)
         out = _code_map(N, L["cout"], Ho * Wo, codes.device, fill=77)
+        mid = (_code_map(N, L["cout"], H * W, codes.device, fill=77), H, W) if L.get("pool_ksp") else None
         with torch.cuda.device(codes.device):
-            self._stage(L, _block_geom(L, N, H, W), codes.contiguous(), out, ops._s())
+            self._stage(L, _block_geom(L, N, H, W), codes.contiguous(), out, ops._s(), mid)
         return out
 
     @torch.no_grad()
@@ -2112,14 +2193,14 @@ class Int8Plan(_Plan):
         a = a.contiguous()
         N, Cc, H, W = a.shape
         with torch.cuda.device(a.device):
-            bufs, geoms, y = self._shape_buffers(a.shape, a.device)
+            bufs, geoms, y, mids = self._shape_buffers(a.shape, a.device)
             st = ops._s()
             if self.pack.get("q") is not None:
                 ops._call("mn_i8z_pack_codes", ops._p(a), N, Cc, H * W, C.byref(self.pack["q"]), ops._p(self.pack["order"]), ops._p(bufs[0]), st)
             else:
                 ops._call("mn_i8_pack_codes", ops._p(a), N, Cc, H * W, self.pack["s"], self.pack["a_bits"], ops._p(self.pack["order"]), ops._p(bufs[0]), st)
             for i, L in enumerate(self.layers):
-                self._stage(L, geoms[i], bufs[i], bufs[i + 1], st)
+                self._stage(L, geoms[i], bufs[i], bufs[i + 1], st, mids[i])
             if self.keep_stages:
                 self.stage_codes = [b.clone() for b in bufs]
             n_, c_, h_, w_ = y.shape
@@ -2167,7 +2248,7 @@ def _iao8_check_counters(who, nm, L, row, scales, zp=False):
 
 
 @torch.no_grad()
-def iao_compile_int8(model, byte_ends=False, zero_points=False, end_to_end=False):
+def iao_compile_int8(model, byte_ends=False, zero_points=False, end_to_end=False, tile_blocks=False):
     """``model``: the result of ``iao_model_bn_fuse`` + ``prequantize_weights`` on a symmetric IAO net, on the GPU (the reference's ``nin_gc``, or an ``nn.Sequential``
     of its block kinds).  Returns an ``Int8Plan`` that keeps every hidden activation as one int8 code and contracts on v_mfma_i32_16x16x64_i8
     (``csrc/qgemm_iao8.h``); the two ends stay on the model's own modules.  ``.report`` lists the stages.  Scales are read from the quantizer buffers and the table
@@ -2197,14 +2278,22 @@ def iao_compile_int8(model, byte_ends=False, zero_points=False, end_to_end=False
     pool, consumer -- is asymmetric runs on ``mn_i8zconv_fwd`` (``csrc/qgemm_iao8_zp.h``: bytes are code - h, the zero points enter as integer offsets of an exact
     int32 sum), every other stage on ``mn_i8conv_fwd`` as before, and a symmetric net gives the plan and report it gives without the keyword.  The table counters
     additionally refuse, naming the layer: a zero point that is not an integer of magnitude <= 65535, a sum that would not fit int32, and a 3x3 stage whose input
-    quantizer has no code for the value 0 ("zero padding has no byte").  Not covered, each raising: together with ``byte_ends=True``; the reference ResNet tree."""
+    quantizer has no code for the value 0 ("zero padding has no byte").  Not covered, each raising: together with ``byte_ends=True``; the reference ResNet tree.
+
+    ``tile_blocks=True``: plain ``nin`` compiles as well (``csrc/qgemm_iao8_tile.h``).  A dense 5x5 / padding 2 hidden block ``mn_i8conv5_supported`` covers runs on
+    ``mn_i8conv5_fwd`` (its input tile staged once in LDS); a 3x3 / 2 / 1 ``QuantMaxPool2d`` behind a hidden block, and a 2x2 / 2 / 0 one behind a 5x5 block, is a
+    stage of its own: the block in front is packed at the pool quantizer's scale and ``mn_i8_maxpool`` takes the window maximum of its codes to the consumer's scale
+    (``layers[i]["pool_ksp"]``; the stage's kept map is the pooled one).  A 2x2 / 2 pool behind a 1x1 or 3x3 block stays folded; ``byte_ends=True`` composes.  A 5x5
+    block outside the tile rule raises naming the layer and the rule; together with ``zero_points`` or ``end_to_end``, or for the reference ResNet tree, one fixed
+    message each.  Off by default: plan, report and messages are then what they were."""
     from micronet_amd import _lib, ops
+    _iao8_tile_keywords(model, zero_points, end_to_end, tile_blocks)
     if _is_ref_resnet(model):
         if zero_points:
             raise _err(_ZP_RESNET)
         return _compile_iao8_res(model, byte_ends, end_to_end)
     who = "iao_compile_int8(byte_ends=True)" if byte_ends else "iao_compile_int8"
-    first, layers, last, tail, flatten, report, pack_shuffle, ends = _walk_iao8(model, byte_ends=byte_ends, zero_points=zero_points)
+    first, layers, last, tail, flatten, report, pack_shuffle, ends = _walk_iao8(model, byte_ends=byte_ends, zero_points=zero_points, tile_blocks=tile_blocks)
     if end_to_end:
         raise _err(_E2E_RESNET)
     _require_gpu(model, "iao_compile_int8")
@@ -2240,6 +2329,15 @@ def iao_compile_int8(model, byte_ends=False, zero_points=False, end_to_end=False
                               _lib.I8ZQuant(L["s_out"], L["z_out"], L["asym_out"], L["a_bits"]))
                 ops._call("mn_i8zconv_pack", C.byref(_block_geom(L)), ops._p(L["w"]), ops._p(L["s_w"]), ops._p(L["z_w"]), 1 if L["per_channel"] else 0, ops._p(L["bias"]),
                           C.byref(qa), C.byref(qp), C.byref(qo), L["asym_w"], L["w_bits"], ops._p(L["out_order"]), ops._p(L["table"]), ops._s())
+            elif L.get("tile") or L.get("pool_ksp"):
+                # the block in front of an un-folded pool stops at the POOL quantizer's codes (mn_i8_maxpool takes them to the consumer's); no pool is folded
+                s_blk = L["s_p"] if L["pool_ksp"] else L["s_out"]
+                if L["tile"]:
+                    ops._call("mn_i8conv5_pack", C.byref(_block_geom(L)), ops._p(L["w"]), ops._p(L["s_w"]), 1 if L["per_channel"] else 0, ops._p(L["bias"]), L["s_a"], s_blk,
+                              L["a_bits"], L["w_bits"], ops._p(L["out_order"]), ops._p(L["table"]), ops._s())
+                else:
+                    ops._call("mn_i8conv_pack", C.byref(_block_geom(L)), ops._p(L["w"]), ops._p(L["s_w"]), 1 if L["per_channel"] else 0, ops._p(L["bias"]), L["s_a"], s_blk,
+                              s_blk, L["a_bits"], L["w_bits"], ops._p(L["out_order"]), ops._p(L["table"]), ops._s())
             else:
                 ops._call("mn_i8conv_pack", C.byref(_block_geom(L)), ops._p(L["w"]), ops._p(L["s_w"]), 1 if L["per_channel"] else 0, ops._p(L["bias"]), L["s_a"], L["s_p"],
                           L["s_out"], L["a_bits"], L["w_bits"], ops._p(L["out_order"]), ops._p(L["table"]), ops._s())

@@ -32,6 +32,12 @@ times of k_code8_quant, k_code8res_conv and k_code8res_add, both launch counts a
 is that procedure on W8A8 PLAIN nin: the model's own eval forward against ``dorefa_compile_bytes(I, tile_blocks=True)`` (the dense 5x5 block on ``k_code8conv5``, the two
 3x3 / 2 max-pools on ``k_code8_maxpool``); the per-launch times of the k_code8conv* kernels and of k_code8_maxpool are recorded.  No time is promised.
 
+    python scripts/kbench_codes.py --iao8-nin [--byte-ends] [--batches 256] [--warmup 5] [--iters 20] [--out profiles/iao8_nin_inference.json]
+
+is that procedure on the int8 IAO deployment of PLAIN nin: the net is trained for two steps at batch 32 (the observers need a range), folded and pre-quantised; its own
+eval forward (fp32 maps, each QuantMaxPool2d on F.max_pool2d) against ``iao_compile_int8(F, tile_blocks=True)`` (the dense 5x5 block on ``k_i8conv5``, the two 3x3 / 2
+max-pools on ``k_i8_maxpool``); ``--byte-ends`` adds ``byte_ends=True`` (default output profiles/iao8_nin_ends_inference.json).  No time is promised.
+
     python scripts/kbench_codes.py --arch nin [--batches 256,1024] [--warmup 5] [--iters 20] [--out profiles/codes_nin.json]
 
 is the first protocol on PLAIN nin: ``P = dorefa_compile_codes(I, tile_blocks=True)`` (the dense 5x5 block on an LDS tile, the two 3x3 / 2 max-pools on planes).
@@ -162,18 +168,43 @@ def main_code_ends(args, byte=False):
     print("wrote", args.out)
 
 
-def main_bytes_resnet(args, arch="resnet18", new_kernels=("k_code8_quant", "k_code8res_"), **compile_kw):
-    """W8A8 resnet18: the model's own eval forward I (conv, BatchNorm, add, ReLU and quantizer launches on fp32 maps: the yardstick) against
-    P = dorefa_compile_bytes(I) (a Byte8ResPlan: two launches per block on byte maps), alternated in one process.  ``--bytes-nin``: the same procedure on W8A8 plain
-    nin with P = dorefa_compile_bytes(I, tile_blocks=True); ``new_kernels``: the kernels whose time per launch is listed."""
+def _dorefa_bytes(arch, **compile_kw):
+    """(I, P): the W8A8 DoReFa net with its own eval forward, and its byte plan."""
     from micronet.compression.quantization.wqaq.dorefa import quantize as Q
-    from micronet_amd import _lib, inference
-    from micronet_amd.train import build_model, synth_batch
-    torch.manual_seed(0)
+    from micronet_amd import inference
+    from micronet_amd.train import build_model
     I = Q.prepare(build_model(arch), inplace=True, a_bits=8, w_bits=8, quant_inference=True).cuda()
     inference.prequantize_weights(I)
     I.eval()
-    P = inference.dorefa_compile_bytes(I, **compile_kw)
+    return I, inference.dorefa_compile_bytes(I, **compile_kw)
+
+
+def _iao8_nin(arch, **compile_kw):
+    """(F, P): the BN-folded, pre-quantised IAO net after two training steps (the observers need a range), and its int8 plan."""
+    import importlib
+    from micronet_amd import inference
+    from micronet_amd.train import build_model, make_optimizer, synth_batch, train_step
+    Q = importlib.import_module("micronet.compression.quantization.wqaq.iao.quantize")
+    T = Q.prepare(build_model(arch), inplace=True, a_bits=8, w_bits=8, q_type=0, q_level=0, weight_observer=0, bn_fuse=True).cuda().train()
+    opt = make_optimizer(T, 0.01, 1e-5)
+    xt, yt = synth_batch(32, device="cuda")
+    for _ in range(2):
+        train_step(T, opt, xt, yt)
+    Fm = inference.iao_model_bn_fuse(T.eval())
+    inference.prequantize_weights(Fm)
+    Fm.eval()
+    return Fm, inference.iao_compile_int8(Fm, **compile_kw)
+
+
+def main_bytes_resnet(args, arch="resnet18", new_kernels=("k_code8_quant", "k_code8res_"), build=_dorefa_bytes, **compile_kw):
+    """W8A8 resnet18: the model's own eval forward I (conv, BatchNorm, add, ReLU and quantizer launches on fp32 maps: the yardstick) against
+    P = dorefa_compile_bytes(I) (a Byte8ResPlan: two launches per block on byte maps), alternated in one process.  ``--bytes-nin``: the same procedure on W8A8 plain
+    nin with P = dorefa_compile_bytes(I, tile_blocks=True); ``--iao8-nin``: on the folded IAO plain nin with P = iao_compile_int8(F, tile_blocks=True) (``build`` makes
+    the pair); ``new_kernels``: the kernels whose time per launch is listed."""
+    from micronet_amd import _lib
+    from micronet_amd.train import synth_batch
+    torch.manual_seed(0)
+    I, P = build(arch, **compile_kw)
     lib = _lib.get_lib()
     res = dict(model=arch, a_bits=8, w_bits=8, warmup=args.warmup, iters=args.iters, device=torch.cuda.get_device_name(0), report=P.report, batches={})
     with torch.no_grad():
@@ -381,6 +412,8 @@ def main():
     ap.add_argument("--byte-ends", action="store_true", help="W8A8: the default byte plan against dorefa_compile_bytes(I, byte_ends=True)")
     ap.add_argument("--bytes-resnet", action="store_true", help="W8A8 resnet18: the model's own eval forward against dorefa_compile_bytes(I) (a Byte8ResPlan)")
     ap.add_argument("--bytes-nin", action="store_true", help="W8A8 plain nin: the model's own eval forward against dorefa_compile_bytes(I, tile_blocks=True)")
+    ap.add_argument("--iao8-nin", action="store_true", help="int8 IAO plain nin: the folded model's own eval forward against iao_compile_int8(F, tile_blocks=True); "
+                                                            "with --byte-ends: byte_ends=True as well")
     ap.add_argument("--mfma-blocks", action="store_true", help="I, the default plan and dorefa_compile_codes(I, mfma_blocks=True)")
     ap.add_argument("--mfma-k3", action="store_true", help="I, the mfma_blocks plan and dorefa_compile_codes(I, mfma_blocks=True, mfma_k3=True); works with --arch nin")
     ap.add_argument("--arch", default="nin_gc", choices=("nin_gc", "nin"), help="nin: plain nin, compiled with tile_blocks=True")
@@ -389,6 +422,12 @@ def main():
                     help="with --bits 4: two --mfma-k3 results, of the parent commit and of this tree, recorded under two_bit_check")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.iao8_nin:
+        if args.bytes_nin or args.bytes_resnet or args.code_ends or args.mfma_blocks or args.mfma_k3 or args.arch != "nin_gc" or args.bits != 2 or args.two_bit_check:
+            ap.error("--iao8-nin is its own protocol, on int8 IAO plain nin (with or without --byte-ends)")
+        if args.out is None:
+            args.out = os.path.join("profiles", "iao8_nin_ends_inference.json" if args.byte_ends else "iao8_nin_inference.json")
+        return main_bytes_resnet(args, "nin", ("k_i8conv", "k_i8_maxpool", "k_i8first", "k_i8_pack", "k_i8_unpack"), _iao8_nin, byte_ends=args.byte_ends, tile_blocks=True)
     if args.bytes_nin:
         if args.bytes_resnet or args.byte_ends or args.code_ends or args.mfma_blocks or args.mfma_k3 or args.arch != "nin_gc" or args.bits != 2 or args.two_bit_check:
             ap.error("--bytes-nin is its own protocol, on W8A8 plain nin")
