@@ -1160,6 +1160,36 @@ int mn_code8res_conv_fwd(const mn_conv_geom* g, const uint32_t* table, const int
 int mn_code8res_add_supported(const mn_conv_geom* g, int shortcut, const mn_conv_geom* gs, int a_bits_in, int w_bits, int a_bits_out);
 int mn_code8res_add_fwd(const mn_conv_geom* g, const uint32_t* table, const int8_t* in_codes, int shortcut, const float* res_f32, const mn_conv_geom* gs,
                         const uint32_t* table_s, const int8_t* sc_codes, int8_t* out_codes, float* out_f32, mn_stream_t stream);
+/* A ResNet's BasicBlocks on the W2A2 code plan (csrc/qgemm_codes_res.h; inference.dorefa_compile_codes on the reference's ResNet): the plane-map counterpart of the
+ * mn_code8res_* group.  Every map is mn_codes_pack_planes' at two planes: uint32 [N][ceil(C/32)][2][HW], tail bits 0.  acc = sum code * (2k - 3) on v_mfma_i32_16x16x64_i8,
+ * and the fp32 chain z = ((fl(acc) * alpha + bias - mean) * invstd) * gamma + beta of the [9][O] constants `chan` is evaluated on it (no thresholds): the range is
+ * C * KH * KW * 9 < 2^24, where fl(acc) is exact.  The table is private to this family (mn_coderes_conv_table_bytes; 16-byte aligned; rows in identity order); header
+ * word 0 counts rows with a non-finite constant, word 7 rows with a weight off the grid (2k - 3) / 3.
+ *   quant : fp32 NCHW x -> planes of the 2-bit DoReFa activation code rha(clamp(0.1 x, 0, 1) * 3) of mn_qa_fwd, tail channels 0 bits, in one launch.  x and planes 4-byte
+ *           aligned; N, C, HW > 0, else MN_EINVAL.  mn_last_kernel(): k_coderes_quant.
+ *   conv  : conv -> BatchNorm -> ReLU -> 2-bit code, planes in, planes out.  Covered (mn_coderes_conv_supported, which table_bytes / pack / fwd follow): widths 2 / 2 / 2;
+ *           groups 1, dilation 1, g->in_shuffle 0; 3x3 / padding 1 with C % 16 == 0 or 1x1 / padding 0 with any C; stride 1 or 2, the same in both directions; any O;
+ *           C * KH * KW * 9 < 2^24.  Output pixel (h, w) reads input pixel (stride h + dy, stride w + dx), Ho = (H - 1) / stride + 1; a tap outside the INPUT map reads the
+ *           code 0.  out_planes [N][ceil(O/32)][2][Ho*Wo], bits >= O are 0.  mn_last_kernel(): k_coderes_conv<KS,stride>.
+ *   add   : the block's end in one launch.  With acc_b the branch conv `g` (stride 1) on in_planes and `table`:
+ *             z = chain_b(acc_b) up to and including its BatchNorm (no ReLU);
+ *             r = shortcut == 1 ? res_f32[n][o][h][w] (the block's fp32 input, NCHW with O channels: needs O == C)
+ *               : chain_s(acc_s) up to its BatchNorm (shortcut == 2), acc_s the 1x1 / padding 0 / stride 1 | 2 conv `gs` on sc_planes (the block INPUT's map) and `table_s`;
+ *             a = relu(fl(z + r));   out_planes (if not null): the planes of code2(a), bits >= O 0;   out_f32 (if not null): a, NCHW [N][O][H][W], no tail.
+ *           gs must have the branch's N and O and an output map of the branch's H x W.  At least one output; an output that is not requested is not touched; the
+ *           arguments of the other shortcut kind are ignored.  mn_last_kernel(): k_coderes_add<KS,shortcut>.
+ * Not covered (other widths, groups != 1, stride 3, 5x5, a 3x3 with C % 16 != 0, shortcut outside 1 .. 2, an identity shortcut with O != C, a shortcut of another
+ * size, a strided branch conv in the add stage): MN_ENOTSUP.  Null / misaligned pointer (tables 16-byte, plane and fp32 maps 4-byte aligned), an invalid geometry, no
+ * output requested or an output that overlaps an input: MN_EINVAL.  Nothing is written in either case.  Every output word and element is stored once: no atomics, no
+ * read-modify-write.  No entry allocates. */
+int mn_coderes_quant_map(const float* x, int64_t N, int64_t C, int64_t HW, uint32_t* planes, mn_stream_t stream);
+int mn_coderes_conv_supported(const mn_conv_geom* g, int a_bits_in, int w_bits, int a_bits_out);
+int64_t mn_coderes_conv_table_bytes(const mn_conv_geom* g, int a_bits_in, int w_bits, int a_bits_out);
+int mn_coderes_conv_pack(const mn_conv_geom* g, const float* w, const float* chan, int a_bits_in, int w_bits, int a_bits_out, uint32_t* table, mn_stream_t stream);
+int mn_coderes_conv_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t* in_planes, uint32_t* out_planes, mn_stream_t stream);
+int mn_coderes_add_supported(const mn_conv_geom* g, int shortcut, const mn_conv_geom* gs, int a_bits_in, int w_bits, int a_bits_out);
+int mn_coderes_add_fwd(const mn_conv_geom* g, const uint32_t* table, const uint32_t* in_planes, int shortcut, const float* res_f32, const mn_conv_geom* gs,
+                       const uint32_t* table_s, const uint32_t* sc_planes, uint32_t* out_planes, float* out_f32, mn_stream_t stream);
 /* What plain nin adds to the W8A8 byte plan (csrc/qgemm_codes_w8_tile.h; inference.dorefa_compile_bytes(model, tile_blocks=True)).  Map, acc, the chain, pack's arguments
  * and the table's header words are those of mn_code8conv_*.
  *   conv5   : the dense 5x5 hidden block on an LDS-resident halo tile: a block stages its input tile (several whole images of at most 256 pixels together, else a band of

@@ -757,6 +757,7 @@ extern "C" int mn_bits_maxpool(const uint32_t* bits_in, int64_t N, int64_t Cw, i
 #include "qgemm_codes.h"          // mn_codes_* / mn_codeconv_*: the code-packed deployment of the k-bit blocks
 #include "qgemm_codes_mfma.h"     // mn_codeconv_mfma_*: the int8-MFMA form of the 1x1 hidden code blocks
 #include "qgemm_codes_mfma3.h"    // mn_codeconv_mfma3_*: the int8-MFMA form of the 3x3 hidden code blocks
+#include "qgemm_codes_res.h"      // mn_coderes_*: a ResNet's BasicBlocks on the W2A2 code plan (strided convs, the block end with its shortcut in one launch; the fp32 chain on the exact sum)
 #include "qgemm_codes_w8.h"       // mn_code8conv_* / mn_code8_*: the byte form of the DoReFa W8A8 hidden blocks (offset bytes on the i8 MFMA, the fp32 chain on the exact sum)
 #include "qgemm_codes_w8_ends.h"  // mn_code8conv_fwd_f32: the classifier of the W8A8 byte plan reads the byte map (K split over the waves of a block), fp32 out
 #include "qgemm_codes_w8_res.h"   // mn_code8_quant_map / mn_code8res_*: a ResNet's BasicBlocks on that plan (strided convs, the block end with its shortcut in one launch)

@@ -1000,8 +1000,21 @@ def dorefa_codes_report(model, code_ends=False, tile_blocks=False, mfma_blocks=F
     ``k_codeconv_tile`` is named so, a max-pool run on the planes behind its block reads ``pooled="standalone"`` and ``"<block kernel>, k_codes_maxpool"``.
     ``mfma_blocks`` as there: the ``kernel`` of a block on the MFMA form reads ``k_codeconv_mfma<0|1>``.  ``mfma_k3`` as there: a 3x3 block on its MFMA form reads
     ``k_codeconv_mfma3<0>``.  A W4A4 net (the width is the first hidden block's) reads ``planes = 4`` and the two MFMA kernels in every hidden row, with or without the
-    two flags; ``code_ends`` / ``tile_blocks`` and a block neither MFMA form covers raise."""
+    two flags; ``code_ends`` / ``tile_blocks`` and a block neither MFMA form covers raise.  The reference's ResNet of BasicBlocks at W2A2: the rows of
+    ``dorefa_bytes_report`` on a ResNet (name, kind "first" / "quant" / "conv" / "add" / "last", K, blocks, kernel, stride, shortcut, outputs) with the
+    ``k_coderes_*`` kernels and ``outputs`` reading "planes"; ``code_ends`` / ``tile_blocks`` raise, the two MFMA flags change nothing."""
+    if _is_ref_resnet(model):
+        _check_codes_res_flags(code_ends, tile_blocks)
+        return _walk_bytes_res(model, fam=_RES_CODES)[1]
     return _walk_codes(model, code_ends, tile_blocks, mfma_blocks, mfma_k3)[5]
+
+
+def _check_codes_res_flags(code_ends, tile_blocks):
+    """The two flags of ``dorefa_compile_codes`` a ResNet's plan does not take."""
+    if code_ends:
+        raise _err("dorefa_compile_codes(code_ends=True): conv1 / avg_pool: a ResNet's ends on planes (the stem writing planes, avg_pool + fc reading them) are not built")
+    if tile_blocks:
+        raise _err("dorefa_compile_codes(tile_blocks=True): a ResNet has neither a 5x5 block nor a max-pool on planes; its plan is int8 MFMA throughout")
 
 
 def _bn_chan_constants(bn, O, gamma, beta):
@@ -1041,9 +1054,19 @@ def dorefa_compile_codes(model, code_ends=False, tile_blocks=False, mfma_blocks=
     ``mfma_blocks`` / ``mfma_k3`` say and the layer dicts carry ``"mfma"`` / ``"mfma3"``: a 1x1 block must be dense with at most 145 input channels or have 32, 64, 96
     or 128 channels per group, a 3x3 / padding 1 block 16 channels per group and no folded pool (K * 15 * 15 <= 32767, the int16 range the thresholds are searched
     over).  Any other hidden block, ``code_ends=True`` and ``tile_blocks=True`` raise ``MicronetHipError`` naming the layer; so does a net of mixed widths or of any
-    other width.  The stored weights must lie on the 4-bit grid (2k - 15) / 15.  Nothing changes for a W2A2 net."""
+    other width.  The stored weights must lie on the 4-bit grid (2k - 15) / 15.  Nothing changes for a W2A2 net.
+
+    The reference's ``ResNet`` of ``BasicBlock``s (resnet18 / resnet34, any ``num_block``) at W2A2 -- default ``prepare(a_bits=2, w_bits=2, quant_inference=True)``,
+    pre-quantised, on the GPU, in eval mode -- compiles to a ``CodeResPlan`` (``csrc/qgemm_codes_res.h``): the model's own conv1, one launch that quantises its fp32 map
+    to planes, two launches per block (its first conv at stride 1 or 2; its second conv with BatchNorm, identity or conv shortcut, add and ReLU: the fp32 chain on
+    the exact int32 sum, 512-channel 3x3 layers included), the model's own avg_pool and fc.  A BottleNeck, another block structure, a W4A4 or mixed-width ResNet, a
+    conv that is not ``quant_inference``, weights off the grid (2k - 3) / 3, a BatchNorm without affine parameters or running statistics, training mode,
+    ``code_ends=True`` and ``tile_blocks=True`` raise, naming the layer or the flag; ``mfma_blocks`` / ``mfma_k3`` change nothing (the plan is MFMA throughout)."""
     from micronet_amd import _lib, ops
     from micronet_amd.quantization.wqaq.dorefa.quantize import _weight_is_coded
+    if _is_ref_resnet(model):
+        _check_codes_res_flags(code_ends, tile_blocks)
+        return _compile_bytes_res(model, fam=_RES_CODES)
     first, layers, last, tail, flatten, report = _walk_codes(model, code_ends, tile_blocks, mfma_blocks, mfma_k3)
     B = report[-1]["planes"]          # the net's code width: 2 or 4
     for L in layers:
@@ -1447,10 +1470,10 @@ def dorefa_bytes_report(model, byte_ends=False, tile_blocks=False):
     return _walk_bytes(model, byte_ends, tile_blocks)[5]
 
 
-def _code8_identity_chan(conv, dev):
+def _code8_identity_chan(conv, dev, n=255):
     """The [9][O] constants of a conv alone on 8-bit codes: alpha = fl(1/255 * 1/255), the fp32 product of the weight and the activation scale, the conv's bias, and
-    the rows of an identity BatchNorm."""
-    sc = torch.tensor(1.0 / 255.0, dtype=torch.float32, device=dev)
+    the rows of an identity BatchNorm.  ``n``: the largest code of another width (3: alpha = fl(1/3 * 1/3))."""
+    sc = torch.tensor(1.0 / n, dtype=torch.float32, device=dev)
     chan = torch.zeros((9, conv.out_channels), dtype=torch.float32, device=dev)
     chan[0], chan[3], chan[4], chan[8] = sc * sc, 1.0, 1.0, 1.0
     if conv.bias is not None:
@@ -1541,14 +1564,24 @@ def dorefa_compile_bytes(model, byte_ends=False, tile_blocks=False):
 
 
 # ------------------------------------------------------------------------------------------------ DoReFa W8A8 ResNets on bytes (csrc/qgemm_codes_w8_res.h)
-def _walk_bytes_res(model, byte_ends=False, input_hw=(32, 32)):
+# What the two residual plans differ in -- the W8A8 byte plan (csrc/qgemm_codes_w8_res.h) and the W2A2 code plan (csrc/qgemm_codes_res.h): the entry point's name, the one
+# width, the ABI family, the quantising launch, the kernels' prefix, what a code map is called in ``outputs``, and the words of the refusals.
+_RES_BYTES = dict(who="dorefa_compile_bytes", bits=8, abi="mn_code8res", quant="mn_code8_quant_map", kernel="k_code8res", quant_kernel="k_code8_quant", out="bytes",
+                  only="only W8A8 nets are deployed on bytes, every quantised conv at 8 bits", kernels="the byte kernels", bound="C * taps <= 33025")
+_RES_CODES = dict(who="dorefa_compile_codes", bits=2, abi="mn_coderes", quant="mn_coderes_quant_map", kernel="k_coderes", quant_kernel="k_coderes_quant", out="planes",
+                  only="only W2A2 ResNets are deployed on planes, every quantised conv at 2 bits", kernels="the residual code kernels", bound="C * taps * 9 < 2^24")
+
+
+def _walk_bytes_res(model, byte_ends=False, input_hw=(32, 32), fam=_RES_BYTES):
     """The graph walk of ``dorefa_compile_bytes`` on the reference's ResNet of BasicBlocks (no GPU needed): (stages, report).  Every block becomes two stages -- its
     first conv (``kind`` "conv": conv -> bn -> relu -> the second conv's codes, stride 1 or 2) and its end ("add": the second conv, its BatchNorm, the shortcut, the
     add and the ReLU in one launch).  An add stage writes the byte map when a block follows, and the fp32 map only when the next block's shortcut is the identity or
-    the consumer is avg_pool.  ``input_hw`` only sizes the maps the geometry rules are asked about."""
+    the consumer is avg_pool.  ``input_hw`` only sizes the maps the geometry rules are asked about.  ``fam=_RES_CODES``: the same walk for ``dorefa_compile_codes`` on a
+    W2A2 ResNet -- plane maps (``outputs`` reads "planes"), the ``mn_coderes_*`` rules and kernels; ``byte_ends`` is not asked there."""
     from micronet_amd import _lib
     from micronet_amd.quantization.wqaq.dorefa import quantize
-    who, B, lib = "dorefa_compile_bytes", BYTE_BITS, _lib.get_lib()
+    who, B, lib, out = fam["who"], fam["bits"], _lib.get_lib(), fam["out"]
+    conv_supported, add_supported = getattr(lib, fam["abi"] + "_conv_supported"), getattr(lib, fam["abi"] + "_add_supported")
     if byte_ends:
         raise _err("%s(byte_ends=True): conv1 / avg_pool: a ResNet's ends on bytes (the stem writing bytes, avg_pool + fc reading them) are not built" % who)
     stem = [m for m in model.conv1.children()]
@@ -1561,11 +1594,11 @@ def _walk_bytes_res(model, byte_ends=False, input_hw=(32, 32)):
             raise _err("%s: %s is not a DoReFa QuantConv2d" % (who, nm))
         ab, wb = conv.activation_quantizer.a_bits, conv.weight_quantizer.w_bits
         if (ab, wb) != (B, B):
-            raise _err("%s: %s has a_bits = %d, w_bits = %d; only W8A8 nets are deployed on bytes, every quantised conv at 8 bits" % (who, nm, ab, wb))
+            raise _err("%s: %s has a_bits = %d, w_bits = %d; %s" % (who, nm, ab, wb, fam["only"]))
         if not conv.quant_inference:
             raise _err("%s: %s is not a quant_inference=True layer (prepare(..., quant_inference=True), then prequantize_weights)" % (who, nm))
         if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
-            raise _err("%s: %s: padding mode %r is not covered by the byte kernels" % (who, nm, conv.padding_mode))
+            raise _err("%s: %s: padding mode %r is not covered by %s" % (who, nm, conv.padding_mode, fam["kernels"]))
 
     def check_bn(nm, bn):
         if not isinstance(bn, nn.BatchNorm2d) or not (bn.affine and bn.track_running_stats and bn.momentum is not None):
@@ -1573,11 +1606,11 @@ def _walk_bytes_res(model, byte_ends=False, input_hw=(32, 32)):
 
     def stage(nm, kind, conv, bn):
         return dict(name=nm, kind=kind, conv=conv, bn=bn, k=_one(conv.kernel_size), pad=_one(conv.padding), stride=_one(conv.stride), cin=conv.in_channels,
-                    cout=conv.out_channels, groups=conv.groups, shortcut=None, outputs=["bytes"])
+                    cout=conv.out_channels, groups=conv.groups, shortcut=None, outputs=[out])
 
     what = lambda c: "%dx%d, stride %s, padding %s, dilation %s, groups %d, %d input channels" % (c.kernel_size[0], c.kernel_size[1], c.stride, c.padding, c.dilation,
                                                                                                  c.groups, c.in_channels)
-    rule = "groups 1, dilation 1, 3x3 / padding 1 with C %% 16 == 0 or 1x1 / padding 0, stride 1 or 2 in both directions, C * taps <= 33025"
+    rule = "groups 1, dilation 1, 3x3 / padding 1 with C %% 16 == 0 or 1x1 / padding 0, stride 1 or 2 in both directions, " + fam["bound"]
     H, W = (_out_size(input_hw[i], c0.kernel_size[i], c0.stride[i], c0.padding[i], c0.dilation[i]) for i in (0, 1))
     stages, cin = [], c0.out_channels
     blocks = [("%s.%s" % (sn, bn_), b) for sn in _RESNET_STAGES for bn_, b in getattr(model, sn).named_children()]
@@ -1599,8 +1632,8 @@ def _walk_bytes_res(model, byte_ends=False, input_hw=(32, 32)):
             raise _err("%s: %s: the channel counts of the block do not chain (its input has %d channels)" % (who, nm, cin))
         A, E = stage(named[0][0], "conv", rf[0], rf[1]), stage(named[1][0], "add", rf[3], rf[4])
         ga = _block_geom(A, 1, H, W)
-        if not lib.mn_code8res_conv_supported(C.byref(ga), B, B, B):
-            raise _err("%s: %s: geometry not covered by mn_code8res_conv_supported (%s: %s)" % (who, A["name"], what(rf[0]), rule))
+        if not conv_supported(C.byref(ga), B, B, B):
+            raise _err("%s: %s: geometry not covered by %s_conv_supported (%s: %s)" % (who, A["name"], fam["abi"], what(rf[0]), rule))
         Hi, Wi, H, W = H, W, (H - 1) // A["stride"] + 1, (W - 1) // A["stride"] + 1
         E["shortcut"] = "conv" if sc else "identity"
         gs = None
@@ -1608,12 +1641,12 @@ def _walk_bytes_res(model, byte_ends=False, input_hw=(32, 32)):
             E["sconv"], E["sbn"], E["s_name"], E["s_cin"], E["s_stride"] = sc[0], sc[1], named[2][0], sc[0].in_channels, _one(sc[0].stride)
             gs = _lib.ConvGeom(1, cin, Hi, Wi, sc[0].out_channels, sc[0].kernel_size[0], sc[0].kernel_size[1], sc[0].stride[0], sc[0].stride[1], sc[0].padding[0],
                                sc[0].padding[1], sc[0].dilation[0], sc[0].dilation[1], sc[0].groups, 0)
-        if not lib.mn_code8res_add_supported(C.byref(_block_geom(E, 1, H, W)), 2 if sc else 1, C.byref(gs) if sc else None, B, B, B):
-            raise _err("%s: %s: the block's end is not covered by mn_code8res_add_supported (%s%s: %s; the conv in front of the add at stride 1, an identity shortcut "
+        if not add_supported(C.byref(_block_geom(E, 1, H, W)), 2 if sc else 1, C.byref(gs) if sc else None, B, B, B):
+            raise _err("%s: %s: the block's end is not covered by %s_add_supported (%s%s: %s; the conv in front of the add at stride 1, an identity shortcut "
                        "with as many channels as the block writes, a conv shortcut 1x1 / padding 0 whose map has the size of the residual's)"
-                       % (who, E["name"], what(rf[3]), ("; shortcut " + what(sc[0])) if sc else "", rule))
+                       % (who, E["name"], fam["abi"], what(rf[3]), ("; shortcut " + what(sc[0])) if sc else "", rule))
         if stages:          # the producer's outputs follow from this consumer
-            stages[-1]["outputs"] = ["bytes"] + ([] if sc else ["f32"])
+            stages[-1]["outputs"] = [out] + ([] if sc else ["f32"])
         stages += [A, E]
         cin = E["cout"]
     stages[-1]["outputs"] = ["f32"]          # avg_pool reads the fp32 map
@@ -1621,68 +1654,78 @@ def _walk_bytes_res(model, byte_ends=False, input_hw=(32, 32)):
         raise _err("%s: fc: in_features is %d, the last block writes %d channels" % (who, model.fc.in_features, cin))
     report = [dict(name="conv1", kind="first", K=c0.in_channels // c0.groups * c0.kernel_size[0] * c0.kernel_size[1], blocks=0, kernel="the model's own block (fp32)",
                    stride=_one(c0.stride), shortcut=None, outputs=["f32"]),
-              dict(name="conv1 -> " + stages[0]["name"], kind="quant", K=0, blocks=(c0.out_channels + 15) // 16, kernel="k_code8_quant", stride=1, shortcut=None,
-                   outputs=["bytes"])]          # (conv1's own fp32 map stays for an identity shortcut of the first block)
+              dict(name="conv1 -> " + stages[0]["name"], kind="quant", K=0, blocks=(c0.out_channels + 15) // 16, kernel=fam["quant_kernel"], stride=1, shortcut=None,
+                   outputs=[out])]          # (conv1's own fp32 map stays for an identity shortcut of the first block)
     for L in stages:
         sck = {None: 0, "identity": 1, "conv": 2}[L["shortcut"]]
-        L["kernel"] = ("k_code8res_add<%d,%d>" % (L["k"], sck)) if L["kind"] == "add" else "k_code8res_conv<%d,%d>" % (L["k"], L["stride"])
+        L["kernel"] = ("%s_add<%d,%d>" % (fam["kernel"], L["k"], sck)) if L["kind"] == "add" else "%s_conv<%d,%d>" % (fam["kernel"], L["k"], L["stride"])
         report.append(dict(name=L["name"], kind=L["kind"], K=L["cin"] * L["k"] * L["k"], blocks=(L["cin"] + 15) // 16, kernel=L["kernel"], stride=L["stride"],
                            shortcut=L["shortcut"], outputs=list(L["outputs"])))
     report.append(dict(name="avg_pool", kind="last", K=cin, blocks=0, kernel="the model's own avg_pool and fc (fp32)", stride=1, shortcut=None, outputs=["f32"]))
     return stages, report
 
 
-class Byte8ResPlan(_Plan):
-    """What ``dorefa_compile_bytes`` returns for the reference's ResNet of BasicBlocks: the model's own conv1 (fp32) -> ``mn_code8_quant_map`` -> per block
-    ``mn_code8res_conv_fwd`` (its first conv, stride 1 or 2) and ``mn_code8res_add_fwd`` (its second conv, BatchNorm, shortcut, add and ReLU in one launch) -> the
-    model's own avg_pool and fc on the last block's fp32 map.  Eval only; owns the packed tables and one set of maps per input shape.  ``layers[i]`` keeps what stage i
-    was packed from (``w``, ``chan``; an add stage with a conv shortcut also ``w_s``, ``chan_s``) for the tests' judge.  ``keep_stages``: forward leaves a copy of every
-    stage's maps in ``stage_codes`` / ``stage_f32`` -- entry 0 the stem's, entry i + 1 stage i's, None where a stage does not write that map."""
+def _res_map(fam, N, c, hw, device):
+    """A code map of a residual plan for c channels on hw pixels: the blocked byte map, or pack_codes' planes [N, ceil(c / 32), 2, hw] of int32."""
+    return _code_map(N, c, hw, device) if fam is _RES_BYTES else torch.empty((N, (c + 31) // 32, 2, hw), dtype=torch.int32, device=device)
 
-    who = "dorefa_compile_bytes"
+
+class _ResPlan(_Plan):
+    """What the two residual plans share (``fam``: ``_RES_BYTES`` / ``_RES_CODES``): the model's own conv1 (fp32) -> the family's quantising launch -> per block its
+    ``_conv_fwd`` and ``_add_fwd`` -> the model's own avg_pool and fc on the last block's fp32 map.  Eval only; owns the packed tables and one set of maps per input
+    shape.  ``layers[i]`` keeps what stage i was packed from (``w``, ``chan``; an add stage with a conv shortcut also ``w_s``, ``chan_s``) for the tests' judge.
+    ``keep_stages``: forward leaves a copy of every stage's maps in ``stage_codes`` / ``stage_f32`` -- entry 0 the stem's, entry i + 1 stage i's, None where a stage does
+    not write that map."""
+
+    fam = None
 
     def __init__(self, conv1, stages, avg_pool, fc, report):
         super().__init__(conv1, stages, None, [avg_pool, fc], True, report)
+        self.who = self.fam["who"]
         self.stage_codes, self.stage_f32 = [], []
 
     def _plan_buffers(self, shape, device):
-        """The stem's byte map, then per stage its geometry (the shortcut conv's as well) and the maps it writes, for one conv1 output shape."""
+        """The stem's code map, then per stage its geometry (the shortcut conv's as well) and the maps it writes, for one conv1 output shape."""
         from micronet_amd import _lib
         N, Cc, H, W = shape
         if Cc != self.layers[0]["cin"]:
-            raise _err("dorefa_compile_bytes: conv1 produced %d channels, the first block reads %d" % (Cc, self.layers[0]["cin"]))
+            raise _err("%s: conv1 produced %d channels, the first block reads %d" % (self.who, Cc, self.layers[0]["cin"]))
         bufs, Hi, Wi = [], H, W
         for L in self.layers:
             g = _block_geom(L, N, H, W)
             if L["kind"] == "conv":
                 Hi, Wi, H, W = H, W, (H - 1) // L["stride"] + 1, (W - 1) // L["stride"] + 1          # (Hi, Wi: the block's input map, which a conv shortcut reads)
             gs = _lib.ConvGeom(N, L["s_cin"], Hi, Wi, L["cout"], 1, 1, L["s_stride"], L["s_stride"], 0, 0, 1, 1, 1, 0) if L["shortcut"] == "conv" else None
-            bufs.append(dict(g=g, gs=gs, codes=_code_map(N, L["cout"], H * W, device) if "bytes" in L["outputs"] else None,
+            bufs.append(dict(g=g, gs=gs, codes=_res_map(self.fam, N, L["cout"], H * W, device) if self.fam["out"] in L["outputs"] else None,
                              f32=torch.empty((N, L["cout"], H, W), dtype=torch.float32, device=device) if "f32" in L["outputs"] else None))
-        return _code_map(N, Cc, shape[2] * shape[3], device), bufs
+        return _res_map(self.fam, N, Cc, shape[2] * shape[3], device), bufs
 
     @torch.no_grad()
     def forward(self, x):
         from micronet_amd import ops
+        from micronet_amd.sign_tensor import QActTensor
+        conv_fwd, add_fwd = self.fam["abi"] + "_conv_fwd", self.fam["abi"] + "_add_fwd"
         a = self.first(x)
+        if isinstance(a, QActTensor):          # a stem prepared to feed fused blocks hands over codes and, for an identity shortcut, the fp32 map beside them
+            a = a._mn_f32 if a._mn_f32 is not None else ops.QActToFloat.apply(a)
         if not (type(a) is torch.Tensor and a.is_cuda and a.dtype == torch.float32 and a.dim() == 4):
-            raise _err("dorefa_compile_bytes: conv1 did not produce a float32 GPU map (the input must be a float32 GPU tensor; no CPU fallback)")
+            raise _err("%s: conv1 did not produce a float32 GPU map (the input must be a float32 GPU tensor; no CPU fallback)" % self.who)
         a = a.contiguous()
         N, Cc, H, W = a.shape
         with torch.cuda.device(a.device):
             b0, bufs = self._shape_buffers(a.shape, a.device)
             st = ops._s()
-            ops._call("mn_code8_quant_map", ops._p(a), N, Cc, H * W, ops._p(b0), st)
-            codes, f32, block_in = b0, a, (b0, a)          # the current byte map and fp32 map; (bytes, fp32) of the block's input
+            ops._call(self.fam["quant"], ops._p(a), N, Cc, H * W, ops._p(b0), st)
+            codes, f32, block_in = b0, a, (b0, a)          # the current code map and fp32 map; (codes, fp32) of the block's input
             for L, ws in zip(self.layers, bufs):
                 if L["kind"] == "conv":
                     block_in = (codes, f32)
-                    ops._call("mn_code8res_conv_fwd", C.byref(ws["g"]), ops._p(L["table"]), ops._p(codes), ops._p(ws["codes"]), st)
+                    ops._call(conv_fwd, C.byref(ws["g"]), ops._p(L["table"]), ops._p(codes), ops._p(ws["codes"]), st)
                 elif L["shortcut"] == "identity":
-                    ops._call("mn_code8res_add_fwd", C.byref(ws["g"]), ops._p(L["table"]), ops._p(codes), 1, ops._p(block_in[1]), None, None, None, ops._p(ws["codes"]),
+                    ops._call(add_fwd, C.byref(ws["g"]), ops._p(L["table"]), ops._p(codes), 1, ops._p(block_in[1]), None, None, None, ops._p(ws["codes"]),
                               ops._p(ws["f32"]), st)
                 else:
-                    ops._call("mn_code8res_add_fwd", C.byref(ws["g"]), ops._p(L["table"]), ops._p(codes), 2, None, C.byref(ws["gs"]), ops._p(L["table_s"]),
+                    ops._call(add_fwd, C.byref(ws["g"]), ops._p(L["table"]), ops._p(codes), 2, None, C.byref(ws["gs"]), ops._p(L["table_s"]),
                               ops._p(block_in[0]), ops._p(ws["codes"]), ops._p(ws["f32"]), st)
                 codes, f32 = ws["codes"], ws["f32"]
             if self.keep_stages:
@@ -1693,45 +1736,69 @@ class Byte8ResPlan(_Plan):
         return self.tail[1](y.view(y.size(0), -1))
 
 
+class CodeResPlan(_ResPlan):
+    """What ``dorefa_compile_codes`` returns for the reference's ResNet of BasicBlocks at W2A2 (``csrc/qgemm_codes_res.h``): the model's own conv1 (fp32) ->
+    ``mn_coderes_quant_map`` -> per block ``mn_coderes_conv_fwd`` (its first conv, stride 1 or 2) and ``mn_coderes_add_fwd`` (its second conv, BatchNorm, shortcut, add
+    and ReLU in one launch) -> the model's own avg_pool and fc on the last block's fp32 map.  Every map between the stem and avg_pool is pack_codes' plane map; layer
+    dicts, ``keep_stages`` and the report are those of ``Byte8ResPlan``, ``outputs`` reading "planes"."""
+
+    fam = _RES_CODES
+
+
+class Byte8ResPlan(_ResPlan):
+    """What ``dorefa_compile_bytes`` returns for the reference's ResNet of BasicBlocks: the model's own conv1 (fp32) -> ``mn_code8_quant_map`` -> per block
+    ``mn_code8res_conv_fwd`` (its first conv, stride 1 or 2) and ``mn_code8res_add_fwd`` (its second conv, BatchNorm, shortcut, add and ReLU in one launch) -> the
+    model's own avg_pool and fc on the last block's fp32 map.  Eval only; owns the packed tables and one set of maps per input shape.  ``layers[i]`` keeps what stage i
+    was packed from (``w``, ``chan``; an add stage with a conv shortcut also ``w_s``, ``chan_s``) for the tests' judge.  ``keep_stages``: forward leaves a copy of every
+    stage's maps in ``stage_codes`` / ``stage_f32`` -- entry 0 the stem's, entry i + 1 stage i's, None where a stage does not write that map."""
+
+    fam = _RES_BYTES
+
+
 @torch.no_grad()
-def _compile_bytes_res(model, byte_ends=False):
+def _compile_bytes_res(model, byte_ends=False, fam=_RES_BYTES):
+    """The residual plan of ``fam`` (``_RES_BYTES``: a ``Byte8ResPlan``; ``_RES_CODES``: a ``CodeResPlan``) from the stages of ``_walk_bytes_res``."""
     from micronet_amd import _lib, ops
     from micronet_amd.quantization.wqaq.dorefa.quantize import _weight_is_coded
-    who, B = "dorefa_compile_bytes", BYTE_BITS
-    stages, report = _walk_bytes_res(model, byte_ends)
-    _require_gpu(model, who)
+    who, B = fam["who"], fam["bits"]
+    n = 2 ** B - 1
+    stages, report = _walk_bytes_res(model, byte_ends, fam=fam)
     if model.training:
         raise _err("%s: the model is in training mode (model.eval(): the plan computes the eval-mode function)" % who)
+    for L in stages:
+        for nm, conv in [(L["name"], L["conv"])] + ([(L["s_name"], L["sconv"])] if L["shortcut"] == "conv" else []):
+            if not _weight_is_coded(conv):
+                raise _err("%s: %s: the stored weights were not found on the %d-bit grid (2k - %d) / %d (run inference.prequantize_weights on the GPU model first)"
+                           % (who, nm, B, n, n))
+    _require_gpu(model, who)
 
-    def packed(nm, L, conv, bn):
-        """(stored weights, [9][O] constants, table) of one conv + BatchNorm: the constants of ``_bn_chan_constants`` with alpha = fl(1/255 * 1/255) and the conv's bias."""
-        if not _weight_is_coded(conv):
-            raise _err("%s: %s: the stored weights were not found on the 8-bit grid (2k - 255) / 255 (run inference.prequantize_weights on the GPU model first)" % (who, nm))
+    def packed(L, conv, bn):
+        """(stored weights, [9][O] constants, table) of one conv + BatchNorm: the constants of ``_bn_chan_constants`` with alpha = fl(1/n * 1/n) and the conv's bias."""
         dev = conv.weight.device
         chan = _bn_chan_constants(bn, conv.out_channels, ops._chk(bn.weight.detach(), "weight"), ops._chk(bn.bias.detach(), "bias"))
-        chan[0], chan[1] = _code8_identity_chan(conv, dev)[:2]
+        chan[0], chan[1] = _code8_identity_chan(conv, dev, n)[:2]
         chan[6], chan[7] = chan[0] * chan[3], (chan[1] - chan[2]) * chan[3]
         g, w = _block_geom(L), conv.weight.detach().float().contiguous()
-        table = torch.empty(int(_lib.get_lib().mn_code8res_conv_table_bytes(C.byref(g), B, B, B)) // 4, dtype=torch.int32, device=dev)
-        ops._call("mn_code8res_conv_pack", C.byref(g), ops._p(w), ops._p(chan), B, B, B, ops._p(table), ops._s())
+        table = torch.empty(int(getattr(_lib.get_lib(), fam["abi"] + "_conv_table_bytes")(C.byref(g), B, B, B)) // 4, dtype=torch.int32, device=dev)
+        ops._call(fam["abi"] + "_conv_pack", C.byref(g), ops._p(w), ops._p(chan), B, B, B, ops._p(table), ops._s())
         return w, chan, table
 
     tables = []
     with torch.cuda.device(stages[0]["conv"].weight.device):
         for L in stages:
-            L["w"], L["chan"], L["table"] = packed(L["name"], L, L.pop("conv"), L.pop("bn"))
+            L["w"], L["chan"], L["table"] = packed(L, L.pop("conv"), L.pop("bn"))
             tables.append((L["name"], L["table"]))
             if L["shortcut"] == "conv":
                 Ls = dict(cin=L["s_cin"], cout=L["cout"], k=1, pad=0, stride=L["s_stride"])
-                L["w_s"], L["chan_s"], L["table_s"] = packed(L["s_name"], Ls, L.pop("sconv"), L.pop("sbn"))
+                L["w_s"], L["chan_s"], L["table_s"] = packed(Ls, L.pop("sconv"), L.pop("sbn"))
                 tables.append((L["s_name"], L["table_s"]))
         counters = torch.stack([t[:8] for _, t in tables]).cpu()          # (compile time: the one place a host read-back is allowed, one read for every table)
     for (nm, _), row in zip(tables, counters):
         if int(row[0]):
             raise _err("%s: %s: %d output channels with a non-finite (or beyond 1e9) BatchNorm constant" % (who, nm, int(row[0])))
         if int(row[7]):
-            raise _err("%s: %s: %d table rows with a weight off the 8-bit grid" % (who, nm, int(row[7])))
-    return Byte8ResPlan(model.conv1, stages, model.avg_pool, model.fc, report)
+            raise _err("%s: %s: %d table rows with a weight off the %d-bit grid" % (who, nm, int(row[7]), B))
+    return (Byte8ResPlan if fam is _RES_BYTES else CodeResPlan)(model.conv1, stages, model.avg_pool, model.fc, report)
 
 
 # ------------------------------------------------------------------------------------------------ int8 deployment of the BN-folded IAO graph (csrc/qgemm_iao8.h)

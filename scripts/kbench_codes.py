@@ -27,6 +27,11 @@ follows the same procedure on W8A8 resnet18: the model's own eval forward (at 8 
 on fp32 maps -- the yardstick) against ``dorefa_compile_bytes(I)`` (a ``Byte8ResPlan``: two launches per block on byte maps), alternated in one process; the per-kernel
 times of k_code8_quant, k_code8res_conv and k_code8res_add, both launch counts and the largest logit difference are recorded.  No time is promised.
 
+    python scripts/kbench_codes.py --codes-resnet [--batches 256] [--warmup 5] [--iters 20] [--out profiles/codes_res.json]
+
+is that procedure on W2A2 resnet18: the model's own eval forward (its fused residual blocks) against ``dorefa_compile_codes(I)`` (a ``CodeResPlan``: two launches per block
+on plane maps); the per-launch times of k_coderes_quant, k_coderes_conv and k_coderes_add are recorded.  No time is promised.
+
     python scripts/kbench_codes.py --bytes-nin [--batches 256] [--warmup 5] [--iters 20] [--out profiles/codes_w8_nin.json]
 
 is that procedure on W8A8 PLAIN nin: the model's own eval forward against ``dorefa_compile_bytes(I, tile_blocks=True)`` (the dense 5x5 block on ``k_code8conv5``, the two
@@ -196,17 +201,28 @@ def _iao8_nin(arch, **compile_kw):
     return Fm, inference.iao_compile_int8(Fm, **compile_kw)
 
 
-def main_bytes_resnet(args, arch="resnet18", new_kernels=("k_code8_quant", "k_code8res_"), build=_dorefa_bytes, **compile_kw):
+def _dorefa_codes_res(arch):
+    """(I, P): the W2A2 DoReFa ResNet with its own eval forward (fused blocks), and its code plan (a CodeResPlan)."""
+    from micronet.compression.quantization.wqaq.dorefa import quantize as Q
+    from micronet_amd import inference
+    from micronet_amd.train import build_model
+    I = Q.prepare(build_model(arch), inplace=True, a_bits=2, w_bits=2, quant_inference=True).cuda()
+    inference.prequantize_weights(I)
+    I.eval()
+    return I, inference.dorefa_compile_codes(I)
+
+
+def main_bytes_resnet(args, arch="resnet18", new_kernels=("k_code8_quant", "k_code8res_"), build=_dorefa_bytes, bits=8, **compile_kw):
     """W8A8 resnet18: the model's own eval forward I (conv, BatchNorm, add, ReLU and quantizer launches on fp32 maps: the yardstick) against
     P = dorefa_compile_bytes(I) (a Byte8ResPlan: two launches per block on byte maps), alternated in one process.  ``--bytes-nin``: the same procedure on W8A8 plain
     nin with P = dorefa_compile_bytes(I, tile_blocks=True); ``--iao8-nin``: on the folded IAO plain nin with P = iao_compile_int8(F, tile_blocks=True) (``build`` makes
-    the pair); ``new_kernels``: the kernels whose time per launch is listed."""
+    the pair); ``--codes-resnet``: on W2A2 resnet18 with P = dorefa_compile_codes(I) (``bits`` = 2); ``new_kernels``: the kernels whose time per launch is listed."""
     from micronet_amd import _lib
     from micronet_amd.train import synth_batch
     torch.manual_seed(0)
     I, P = build(arch, **compile_kw)
     lib = _lib.get_lib()
-    res = dict(model=arch, a_bits=8, w_bits=8, warmup=args.warmup, iters=args.iters, device=torch.cuda.get_device_name(0), report=P.report, batches={})
+    res = dict(model=arch, a_bits=bits, w_bits=bits, warmup=args.warmup, iters=args.iters, device=torch.cuda.get_device_name(0), report=P.report, batches={})
     with torch.no_grad():
         for bs in [int(v) for v in args.batches.split(",")]:
             x, _ = synth_batch(bs, device="cuda")
@@ -411,6 +427,7 @@ def main():
     ap.add_argument("--code-ends", action="store_true", help="the default plan against dorefa_compile_codes(I, code_ends=True)")
     ap.add_argument("--byte-ends", action="store_true", help="W8A8: the default byte plan against dorefa_compile_bytes(I, byte_ends=True)")
     ap.add_argument("--bytes-resnet", action="store_true", help="W8A8 resnet18: the model's own eval forward against dorefa_compile_bytes(I) (a Byte8ResPlan)")
+    ap.add_argument("--codes-resnet", action="store_true", help="W2A2 resnet18: the model's own eval forward against dorefa_compile_codes(I) (a CodeResPlan)")
     ap.add_argument("--bytes-nin", action="store_true", help="W8A8 plain nin: the model's own eval forward against dorefa_compile_bytes(I, tile_blocks=True)")
     ap.add_argument("--iao8-nin", action="store_true", help="int8 IAO plain nin: the folded model's own eval forward against iao_compile_int8(F, tile_blocks=True); "
                                                             "with --byte-ends: byte_ends=True as well")
@@ -434,6 +451,12 @@ def main():
         if args.out is None:
             args.out = os.path.join("profiles", "codes_w8_nin.json")
         return main_bytes_resnet(args, "nin", ("k_code8conv", "k_code8_maxpool"), tile_blocks=True)
+    if args.codes_resnet:
+        if args.bytes_resnet or args.byte_ends or args.code_ends or args.mfma_blocks or args.mfma_k3 or args.arch != "nin_gc" or args.bits != 2 or args.two_bit_check:
+            ap.error("--codes-resnet is its own protocol, on W2A2 resnet18")
+        if args.out is None:
+            args.out = os.path.join("profiles", "codes_res.json")
+        return main_bytes_resnet(args, new_kernels=("k_coderes_",), build=_dorefa_codes_res, bits=2)
     if args.bytes_resnet:
         if args.byte_ends or args.code_ends or args.mfma_blocks or args.mfma_k3 or args.arch != "nin_gc" or args.bits != 2 or args.two_bit_check:
             ap.error("--bytes-resnet is its own protocol, on W8A8 resnet18")

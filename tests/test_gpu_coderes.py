@@ -1,0 +1,18 @@
+"""The residual stages of the DoReFa W2A2 code plan (csrc/qgemm_codes_res.h) on the MI355X, through the C ABI: the exact checks of tests/coderes_cases.py,
+which tests/test_coderes_emulated.py runs on the CPU emulation build."""
+import pytest
+
+import abi_driver
+import coderes_cases as R
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def be():
+    return abi_driver.Backend("gpu")
+
+
+@pytest.mark.parametrize("check, arg", [c[1:] for c in R.CHECKS], ids=[c[0] for c in R.CHECKS])
+def test_coderes(be, check, arg):
+    check(be, arg)
