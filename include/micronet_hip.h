@@ -168,6 +168,14 @@ int mn_iao_fq_maxpool2x2_fwd(const float* x, int64_t planes, int64_t H, int64_t 
                              mn_stream_t stream);
 int mn_iao_fq_maxpool2x2_bwd(const float* gy, const uint8_t* idx, const float* x, int64_t planes, int64_t H, int64_t W, const float* qp, int bits, int q_type,
                              int relu_mask, float* dx, mn_stream_t stream);
+/* ... and with the 3 x 3 / stride-2 / padding-1 max-pool of plain nin: max_pool2d(Q(x), 3, 2, 1), shapes and window rule of mn_maxpool3x3s2_f32_*; the argmax is that
+ * of Q(x).  mm as above with mn_iao_fq_maxpool3x3s2_mm_count.  Backward: the gathered gradient through the clip-STE at x [and the ReLU mask, relu_mask != 0]. */
+int mn_iao_fq_maxpool3x3s2_supported(int64_t H, int64_t W);
+int64_t mn_iao_fq_maxpool3x3s2_mm_count(int64_t planes, int64_t H, int64_t W);
+int mn_iao_fq_maxpool3x3s2_fwd(const float* x, int64_t planes, int64_t H, int64_t W, const float* qp, int bits, int q_type, float* y, uint8_t* idx, float* mm,
+                               mn_stream_t stream);
+int mn_iao_fq_maxpool3x3s2_bwd(const float* gy, const uint8_t* idx, const float* x, int64_t planes, int64_t H, int64_t W, const float* qp, int bits, int q_type,
+                               int relu_mask, float* dx, mn_stream_t stream);
 /* Streaming helpers of the BN-fused blocks (n % 4 == 0, 16-byte aligned): mn_add_relu_mask: out = (a [+ b]) * [x > 0] (b, x nullable) -- the sum of
  * QuantBNFuseConv2d's two input gradients (quantised path 947-955, statistics path 843-855) with the ReLU mask of the block in front, or a ReLU backward alone;
  * mn_relu_mm: y = relu(x) (in place allowed) + per-block (min, max) of y in mm (nullable, 2 * mn_relu_mm_count(n) floats) for mn_iao_observe_partials. */
@@ -376,6 +384,16 @@ int mn_bnsign_bwd(const float* da, const float* y, const float* save, const floa
 int mn_maxpool2x2_f32_supported(int64_t H, int64_t W);
 int mn_maxpool2x2_f32_fwd(const float* x, int64_t planes, int64_t H, int64_t W, float* y, uint8_t* idx, mn_stream_t stream);
 int mn_maxpool2x2_f32_bwd(const float* gy, const uint8_t* idx, int64_t planes, int64_t H, int64_t W, float* dx, mn_stream_t stream);
+/* nn.MaxPool2d(kernel_size=3, stride=2, padding=1) (models/nin.py): x / dx / a / din [planes][H][W] -> y / gy / idx / out / dout [planes][Ho][Wo], Ho = (H - 1) / 2 + 1,
+ * every H, W >= 1 with H * W <= 4096 or W <= 819, any alignment.  Padded cells are never candidates; row-major scan, a later cell wins iff v > m || v != v (ATen).
+ * idx = the argmax as its position 0..8 in the unclipped window; the backward GATHERS (every dx element written once, fixed summation order: bit-reproducible).
+ * sign8: +-1 codes in and out; the backward recomputes the winner (the first +1 in scan order, else the first in-map cell) from the input codes `a`. */
+int mn_maxpool3x3s2_f32_supported(int64_t H, int64_t W);
+int mn_maxpool3x3s2_f32_fwd(const float* x, int64_t planes, int64_t H, int64_t W, float* y, uint8_t* idx, mn_stream_t stream);
+int mn_maxpool3x3s2_f32_bwd(const float* gy, const uint8_t* idx, int64_t planes, int64_t H, int64_t W, float* dx, mn_stream_t stream);
+int mn_maxpool3x3s2_sign8_supported(int64_t H, int64_t W);
+int mn_maxpool3x3s2_sign8_fwd(const int8_t* a, int64_t planes, int64_t H, int64_t W, int8_t* out, mn_stream_t stream);
+int mn_maxpool3x3s2_sign8_bwd(const float* dout, const int8_t* a, int64_t planes, int64_t H, int64_t W, float* din, mn_stream_t stream);
 /* nn.AvgPool2d whose window covers the whole image (the tail of nin / nin_gc, models/nin_gc.py:139): x [planes][HW] -> y [planes] = sum / HW; backward gy / HW. */
 int mn_avgpool_global_fwd(const float* x, int64_t planes, int64_t HW, float* y, mn_stream_t stream);
 int mn_avgpool_global_bwd(const float* gy, int64_t planes, int64_t HW, float* dx, mn_stream_t stream);

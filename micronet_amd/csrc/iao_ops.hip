@@ -8,6 +8,7 @@
 //     first-call / moving-average update of max_val in the last launch: no host synchronisation.
 // All HBM-bound streaming work: float4 per lane, grid-stride loops.
 #include "common.h"
+#include "pool3s2.h"
 
 #include <math.h>
 
@@ -416,6 +417,36 @@ extern "C" int mn_iao_fq_maxpool2x2_bwd(const float* gy, const uint8_t* idx, con
                        r.qmin, r.qmax, relu_mask);
     mn_prof_end((hipStream_t)stream);
     MN_CHECK_LAUNCH("mn_iao_fq_maxpool2x2_bwd");
+    return MN_OK;
+}
+
+// ---------------------------------------------------------------- QuantMaxPool2d(3, 2, 1) (plain nin) in one pass per direction: k_pool3_f32_*<1> of pool3s2.h
+// forward: every staged cell is quantised once on its way into LDS (the qp snapshot and rounding of the 2 x 2 entry), the windows compare quantised values, so the
+// argmax is that of Q(x); backward: the gathered gradient through the clip-STE at x [and the ReLU mask [x > 0] in front].
+extern "C" int mn_iao_fq_maxpool3x3s2_supported(int64_t H, int64_t W) { P3Geom g; return p3_geom(1, H, W, &g); }
+extern "C" int64_t mn_iao_fq_maxpool3x3s2_mm_count(int64_t planes, int64_t H, int64_t W) { P3Geom g; return p3_geom(planes, H, W, &g) ? p3_grid(g) : 0; }
+extern "C" int mn_iao_fq_maxpool3x3s2_fwd(const float* x, int64_t planes, int64_t H, int64_t W, const float* qp, int bits, int q_type, float* y, uint8_t* idx, float* mm,
+                                          mn_stream_t stream) {
+    P3Geom g;
+    if (!x || !y || !idx || !qp || bits < 2 || bits > 24 || (q_type != 0 && q_type != 1) || !p3_geom(planes, H, W, &g))
+        MN_FAIL(MN_EINVAL, "mn_iao_fq_maxpool3x3s2_fwd: needs H * W <= %d or W <= %d, 2..24 bits", P3_TILE, P3_TILE / 5);
+    const IaoRange r = iao_range(bits, q_type, 1);
+    mn_set_last_kernel("k_pool3_f32_fwd<1>"); mn_prof_bytes((double)planes * (4.0 * H * W + 5.0 * g.Ho * g.Wo)); mn_prof_begin((hipStream_t)stream);
+    hipLaunchKernelGGL(k_pool3_f32_fwd<1>, dim3(p3_grid(g)), dim3(256), 0, (hipStream_t)stream, x, y, (unsigned char*)idx, g, qp, r.qmin, r.qmax, mm);
+    mn_prof_end((hipStream_t)stream);
+    MN_CHECK_LAUNCH("mn_iao_fq_maxpool3x3s2_fwd");
+    return MN_OK;
+}
+extern "C" int mn_iao_fq_maxpool3x3s2_bwd(const float* gy, const uint8_t* idx, const float* x, int64_t planes, int64_t H, int64_t W, const float* qp, int bits, int q_type,
+                                          int relu_mask, float* dx, mn_stream_t stream) {
+    P3Geom g;
+    if (!gy || !dx || !idx || !x || !qp || bits < 2 || bits > 24 || (q_type != 0 && q_type != 1) || !p3_geom(planes, H, W, &g))
+        MN_FAIL(MN_EINVAL, "mn_iao_fq_maxpool3x3s2_bwd: needs H * W <= %d or W <= %d, 2..24 bits", P3_TILE, P3_TILE / 5);
+    const IaoRange r = iao_range(bits, q_type, 1);
+    mn_set_last_kernel("k_pool3_f32_bwd<1>"); mn_prof_bytes((double)planes * (8.0 * H * W + 5.0 * g.Ho * g.Wo)); mn_prof_begin((hipStream_t)stream);
+    hipLaunchKernelGGL(k_pool3_f32_bwd<1>, dim3(p3_grid(g)), dim3(256), 0, (hipStream_t)stream, gy, (const unsigned char*)idx, x, dx, g, qp, r.qmin, r.qmax, relu_mask);
+    mn_prof_end((hipStream_t)stream);
+    MN_CHECK_LAUNCH("mn_iao_fq_maxpool3x3s2_bwd");
     return MN_OK;
 }
 

@@ -11,6 +11,8 @@
 // i.e. 3 + 5 passes instead of 5 + 8.  All kernels address the tensor as C channels x (N planes of HW contiguous floats),
 // float4 per lane, every lane busy whatever HW is.
 #include "qgemm_dev.h"
+#define P3_SIGN_FORM
+#include "pool3s2.h"
 
 // streaming loops: iterations are independent; MN_STREAM_2 handles two quads per trip -- both sets of loads are issued before the
 // first is consumed (twice the bytes in flight per thread; same per-thread accumulation order)
@@ -421,6 +423,47 @@ extern "C" int mn_maxpool2x2_f32_bwd(const float* gy, const uint8_t* idx, int64_
     hipLaunchKernelGGL(k_pool2_f32_bwd, dim3(mn_grid_for(nq, 256, 8192)), dim3(256), 0, (hipStream_t)stream, gy, (const unsigned char*)idx, dx, nq, (int)H, (int)W);
     mn_prof_end((hipStream_t)stream);
     MN_CHECK_LAUNCH("mn_maxpool2x2_f32_bwd");
+    return MN_OK;
+}
+
+// ---------------------------------------------------------------- 3x3 / stride-2 / padding-1 max-pool (plain nin, models/nin.py): kernels and tiling in pool3s2.h
+extern "C" int mn_maxpool3x3s2_f32_supported(int64_t H, int64_t W) { P3Geom g; return p3_geom(1, H, W, &g); }
+extern "C" int mn_maxpool3x3s2_f32_fwd(const float* x, int64_t planes, int64_t H, int64_t W, float* y, uint8_t* idx, mn_stream_t stream) {
+    P3Geom g;
+    if (!x || !y || !idx || !p3_geom(planes, H, W, &g)) MN_FAIL(MN_EINVAL, "mn_maxpool3x3s2_f32_fwd: needs H * W <= %d or W <= %d", P3_TILE, P3_TILE / 5);
+    mn_set_last_kernel("k_pool3_f32_fwd<0>"); mn_prof_bytes((double)planes * (4.0 * H * W + 5.0 * g.Ho * g.Wo)); mn_prof_begin((hipStream_t)stream);
+    hipLaunchKernelGGL(k_pool3_f32_fwd<0>, dim3(p3_grid(g)), dim3(256), 0, (hipStream_t)stream, x, y, (unsigned char*)idx, g, (const float*)nullptr, 0.f, 0.f, (float*)nullptr);
+    mn_prof_end((hipStream_t)stream);
+    MN_CHECK_LAUNCH("mn_maxpool3x3s2_f32_fwd");
+    return MN_OK;
+}
+extern "C" int mn_maxpool3x3s2_f32_bwd(const float* gy, const uint8_t* idx, int64_t planes, int64_t H, int64_t W, float* dx, mn_stream_t stream) {
+    P3Geom g;
+    if (!gy || !dx || !idx || !p3_geom(planes, H, W, &g)) MN_FAIL(MN_EINVAL, "mn_maxpool3x3s2_f32_bwd: needs H * W <= %d or W <= %d", P3_TILE, P3_TILE / 5);
+    mn_set_last_kernel("k_pool3_f32_bwd<0>"); mn_prof_bytes((double)planes * (4.0 * H * W + 5.0 * g.Ho * g.Wo)); mn_prof_begin((hipStream_t)stream);
+    hipLaunchKernelGGL(k_pool3_f32_bwd<0>, dim3(p3_grid(g)), dim3(256), 0, (hipStream_t)stream, gy, (const unsigned char*)idx, (const float*)nullptr, dx, g,
+                       (const float*)nullptr, 0.f, 0.f, 0);
+    mn_prof_end((hipStream_t)stream);
+    MN_CHECK_LAUNCH("mn_maxpool3x3s2_f32_bwd");
+    return MN_OK;
+}
+extern "C" int mn_maxpool3x3s2_sign8_supported(int64_t H, int64_t W) { P3Geom g; return p3_geom(1, H, W, &g); }
+extern "C" int mn_maxpool3x3s2_sign8_fwd(const int8_t* a, int64_t planes, int64_t H, int64_t W, int8_t* out, mn_stream_t stream) {
+    P3Geom g;
+    if (!a || !out || !p3_geom(planes, H, W, &g)) MN_FAIL(MN_EINVAL, "mn_maxpool3x3s2_sign8_fwd: needs H * W <= %d or W <= %d", P3_TILE, P3_TILE / 5);
+    mn_set_last_kernel("k_pool3_sign8_fwd"); mn_prof_bytes((double)planes * (1.0 * H * W + 1.0 * g.Ho * g.Wo)); mn_prof_begin((hipStream_t)stream);
+    hipLaunchKernelGGL(k_pool3_sign8_fwd, dim3(p3_grid(g)), dim3(256), 0, (hipStream_t)stream, (const signed char*)a, (signed char*)out, g);
+    mn_prof_end((hipStream_t)stream);
+    MN_CHECK_LAUNCH("mn_maxpool3x3s2_sign8_fwd");
+    return MN_OK;
+}
+extern "C" int mn_maxpool3x3s2_sign8_bwd(const float* dout, const int8_t* a, int64_t planes, int64_t H, int64_t W, float* din, mn_stream_t stream) {
+    P3Geom g;
+    if (!dout || !a || !din || !p3_geom(planes, H, W, &g)) MN_FAIL(MN_EINVAL, "mn_maxpool3x3s2_sign8_bwd: needs H * W <= %d or W <= %d", P3_TILE, P3_TILE / 5);
+    mn_set_last_kernel("k_pool3_sign8_bwd"); mn_prof_bytes((double)planes * (5.0 * H * W + 4.0 * g.Ho * g.Wo)); mn_prof_begin((hipStream_t)stream);
+    hipLaunchKernelGGL(k_pool3_sign8_bwd, dim3(p3_grid(g)), dim3(256), 0, (hipStream_t)stream, dout, (const signed char*)a, din, g);
+    mn_prof_end((hipStream_t)stream);
+    MN_CHECK_LAUNCH("mn_maxpool3x3s2_sign8_bwd");
     return MN_OK;
 }
 

@@ -1335,6 +1335,52 @@ class IaoFakeQuantMaxPool2x2(Function):
         return dx, None, None, None, None, None
 
 
+def iao_fq_maxpool3_supported(x, kernel_size, stride, padding, dilation, ceil_mode):
+    return (torch.is_tensor(x) and type(x) is torch.Tensor and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous() and x.numel() > 0
+            and _pool3_geometry(kernel_size, stride if stride is not None else kernel_size, padding, dilation, ceil_mode)
+            and bool(_lib_().mn_iao_fq_maxpool3x3s2_supported(x.shape[2], x.shape[3])))
+
+
+class IaoFakeQuantMaxPool3x3S2(Function):
+    """max_pool2d(Q(x), 3, 2, 1) (QuantMaxPool2d of plain nin) in one pass per direction, the hand-overs of ``IaoFakeQuantMaxPool2x2``: (min, max) partials of the
+    output and its quantizer grid to ``st``, the ReLU mask of the producing block in backward (``ReluToken``)."""
+
+    @staticmethod
+    def forward(ctx, x, qp, bits, q_type, want_mm, st):
+        x = _chk(x, "input")
+        N, Cc, H, W = x.shape
+        y = torch.empty(_pool3_out(x.shape), dtype=torch.float32, device=x.device)
+        idx = torch.empty(y.shape, dtype=torch.uint8, device=x.device)
+        mm, count = None, 0
+        with torch.cuda.device_of(x):
+            if want_mm:
+                count = int(_lib_().mn_iao_fq_maxpool3x3s2_mm_count(N * Cc, H, W))
+                mm = torch.empty(2 * count, dtype=torch.float32, device=x.device)
+            _call("mn_iao_fq_maxpool3x3s2_fwd", _p(x), N * Cc, H, W, _p(qp), bits, q_type, _p(y), _p(idx), _p(mm), _s())
+        ctx.save_for_backward(x, qp, idx)
+        ctx.cfg = (bits, q_type)
+        ctx.tok_in = getattr(x, "_mn_relu_token", None)
+        ctx.x_obj = x
+        st.__dict__["_mn_fwd_out"] = (mm, count) if want_mm else None
+        st.__dict__["_mn_fwd_grid"] = (qp, bits, q_type)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, qp, idx = ctx.saved_tensors
+        bits, q_type = ctx.cfg
+        g = _chk(g, "grad")
+        N, Cc, H, W = x.shape
+        dx = torch.empty_like(x)
+        pre = ctx.tok_in is not None and relu_premask_ok(ctx.x_obj)
+        with torch.cuda.device_of(x):
+            _call("mn_iao_fq_maxpool3x3s2_bwd", _p(g), _p(idx), _p(x), N * Cc, H, W, _p(qp), bits, q_type, int(pre), _p(dx), _s())
+        if pre:
+            ctx.tok_in.dx = dx
+        ctx.x_obj = None
+        return dx, None, None, None, None, None
+
+
 def hist_observe(x, percentile, first, momentum, max_val):
     """HistogramObserver.forward (ref 126-139) on the device: exact k-th smallest |x| + first-call / EMA update of ``max_val``."""
     x = _chk(x.detach(), "input")
@@ -1875,6 +1921,50 @@ def f32_pool_supported(x, kernel_size, stride, padding, dilation, ceil_mode):
             and padding in (0, (0, 0)) and dilation in (1, (1, 1)) and not ceil_mode and bool(_lib_().mn_maxpool2x2_f32_supported(x.shape[2], x.shape[3])))
 
 
+def _pool3_geometry(kernel_size, stride, padding, dilation, ceil_mode):
+    """nn.MaxPool2d(kernel_size=3, stride=2, padding=1) (models/nin.py), dilation 1, floor mode."""
+    same = lambda v, k: v in (k, (k, k), [k, k])
+    return same(kernel_size, 3) and same(stride, 2) and same(padding, 1) and same(dilation, 1) and not ceil_mode
+
+
+def _pool3_out(shape):
+    N, Cc, H, W = shape
+    return (N, Cc, (H - 1) // 2 + 1, (W - 1) // 2 + 1)
+
+
+class MaxPool3x3S2F32(Function):
+    """nn.MaxPool2d(3, 2, 1) on fp32 activations (csrc/pool3s2.h): the forward keeps the argmax of every window in one byte (0..8), the backward gathers from it --
+    every input gradient written once, no atomics (ATen scatters int64 indices with atomics into a zero-filled tensor)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = _chk(x, "input")
+        N, Cc, H, W = x.shape
+        y = torch.empty(_pool3_out(x.shape), dtype=torch.float32, device=x.device)
+        idx = torch.empty(y.shape, dtype=torch.uint8, device=x.device)
+        with torch.cuda.device_of(x):
+            _call("mn_maxpool3x3s2_f32_fwd", _p(x), N * Cc, H, W, _p(y), _p(idx), _s())
+        ctx.save_for_backward(idx)
+        ctx.shape = tuple(x.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        (idx,) = ctx.saved_tensors
+        g = _chk(g, "grad")
+        N, Cc, H, W = ctx.shape
+        dx = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
+        with torch.cuda.device_of(g):
+            _call("mn_maxpool3x3s2_f32_bwd", _p(g), _p(idx), N * Cc, H, W, _p(dx), _s())
+        return dx
+
+
+def f32_pool3_supported(x, kernel_size, stride, padding, dilation, ceil_mode):
+    return (torch.is_tensor(x) and type(x) is torch.Tensor and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous() and x.numel() > 0
+            and _pool3_geometry(kernel_size, stride if stride is not None else kernel_size, padding, dilation, ceil_mode)
+            and bool(_lib_().mn_maxpool3x3s2_f32_supported(x.shape[2], x.shape[3])))
+
+
 class SignToFloat(Function):
     """SignTensor -> the float32 +-1 tensor, with an identity backward (for consumers our kernels do not cover)."""
 
@@ -1937,6 +2027,38 @@ class SignMaxPool2x2(Function):
             # hand the POOLED gradient on: the fused block in front expands it inside its kernels (anything else materialises it)
             return LazyPoolGrad(codes.shape, codes.device, g, codes, _expand_pool_grad)
         return _expand_pool_grad(g, codes)
+
+
+def sign_pool3_supported(a, kernel_size, stride, padding, dilation, ceil_mode):
+    return (isinstance(a, SignTensor) and a.dim() == 4 and a.codes.is_cuda and a.codes.is_contiguous() and a.codes.numel() > 0
+            and _pool3_geometry(kernel_size, stride if stride is not None else kernel_size, padding, dilation, ceil_mode)
+            and bool(_lib_().mn_maxpool3x3s2_sign8_supported(a.shape[2], a.shape[3])))
+
+
+class SignMaxPool3x3S2(Function):
+    """nn.MaxPool2d(3, 2, 1) on packed sign activations (models/nin.py): int8 in, int8 out.  No argmax is kept: the backward recomputes every window's winner from
+    the input codes (the first +1 in scan order, else the first in-map cell -- ATen's routing) and gathers.  Its result is an ordinary dense fp32 gradient: the lazy
+    pooled-gradient hand-over of the 2x2 pool (``LazyPoolGrad``) assumes disjoint windows and is not used here."""
+
+    @staticmethod
+    def forward(ctx, a):
+        codes = a.codes
+        N, Cc, H, W = codes.shape
+        out = torch.empty(_pool3_out(codes.shape), dtype=torch.int8, device=codes.device)
+        with torch.cuda.device_of(codes):
+            _call("mn_maxpool3x3s2_sign8_fwd", _p(codes), N * Cc, H, W, _p(out), _s())
+        ctx.save_for_backward(codes)
+        return SignTensor(out)
+
+    @staticmethod
+    def backward(ctx, g):
+        (codes,) = ctx.saved_tensors
+        g = _chk(g, "grad")
+        N, Cc, H, W = codes.shape
+        din = torch.empty(codes.shape, dtype=torch.float32, device=codes.device)
+        with torch.cuda.device_of(codes):
+            _call("mn_maxpool3x3s2_sign8_bwd", _p(g), _p(codes), N * Cc, H, W, _p(din), _s())
+        return din
 
 
 # ------------------------------------------------------------------------------------------------ convolution

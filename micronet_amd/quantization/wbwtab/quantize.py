@@ -155,6 +155,8 @@ class MaxPool2dSign(nn.MaxPool2d):
     def forward(self, input):
         if not self.return_indices and ops.sign_pool_supported(input, self.kernel_size, self.stride, self.padding, self.dilation, self.ceil_mode):
             return ops.SignMaxPool2x2.apply(input)
+        if not self.return_indices and ops.sign_pool3_supported(input, self.kernel_size, self.stride, self.padding, self.dilation, self.ceil_mode):
+            return ops.SignMaxPool3x3S2.apply(input)          # 3x3 / stride 2 / padding 1 (plain nin)
         ops.note_fallback("MaxPool2dSign -> nn.MaxPool2d")
         return super().forward(input)
 

@@ -309,6 +309,8 @@ class MaxPool2dF32(nn.MaxPool2d):
             return input          # the fused block in front already pooled (max of the activation = max of its codes: the quantizer is monotone)
         if not self.return_indices and ops.f32_pool_supported(input, self.kernel_size, self.stride, self.padding, self.dilation, self.ceil_mode):
             return ops.MaxPool2x2F32.apply(input)
+        if not self.return_indices and ops.f32_pool3_supported(input, self.kernel_size, self.stride, self.padding, self.dilation, self.ceil_mode):
+            return ops.MaxPool3x3S2F32.apply(input)          # 3x3 / stride 2 / padding 1 (plain nin): byte argmax, gather backward
         ops.note_fallback("MaxPool2dF32 -> nn.MaxPool2d")
         return super().forward(input)
 

@@ -589,14 +589,17 @@ class QuantMaxPool2d(nn.MaxPool2d):
 
     def forward(self, input):
         aq = self.activation_quantizer
+        geom = (self.kernel_size, self.stride, self.padding, self.dilation, self.ceil_mode)
+        fused = ops.IaoFakeQuantMaxPool2x2 if ops.iao_fq_maxpool_supported(input, *geom) else \
+            ops.IaoFakeQuantMaxPool3x3S2 if ops.iao_fq_maxpool3_supported(input, *geom) else None          # (3x3 / stride 2 / padding 1: plain nin)
         if (not self.return_indices and aq.bits != 32 and 2 <= aq.bits <= 24 and isinstance(aq.observer, (ObserverBase, HistogramObserver))
-                and getattr(aq.observer, "q_level", "L") == "L" and ops.iao_fq_maxpool_supported(input, self.kernel_size, self.stride, self.padding, self.dilation, self.ceil_mode)):
-            # quantizer + 2 x 2 max-pool in one pass (and one in backward); leaves (min, max) partials of its output for the next layer's observer
+                and getattr(aq.observer, "q_level", "L") == "L" and fused is not None):
+            # quantizer + max-pool in one pass (and one in backward); leaves (min, max) partials of its output for the next layer's observer
             qp = aq.qparams(input)
             aq._last_qp = qp
             if qp is not None and qp.shape[0] == 1:
                 want_mm = self.training
-                out = ops.IaoFakeQuantMaxPool2x2.apply(input, qp, aq.bits, aq.q_type, want_mm, self)
+                out = fused.apply(input, qp, aq.bits, aq.q_type, want_mm, self)
                 mm = self.__dict__.pop("_mn_fwd_out", None)
                 if mm is not None:
                     out._mn_minmax = mm + (out._version,)
@@ -609,6 +612,8 @@ class QuantMaxPool2d(nn.MaxPool2d):
             q = aq(input)
         if not self.return_indices and ops.f32_pool_supported(q, self.kernel_size, self.stride, self.padding, self.dilation, self.ceil_mode):
             return ops.MaxPool2x2F32.apply(q)        # 2x2 / stride 2: byte argmax, scatter backward (same values and gradient routing as ATen)
+        if not self.return_indices and ops.f32_pool3_supported(q, self.kernel_size, self.stride, self.padding, self.dilation, self.ceil_mode):
+            return ops.MaxPool3x3S2F32.apply(q)      # 3x3 / stride 2 / padding 1 at 32 bits or behind a per-channel quantizer: byte argmax, gather backward
         ops.note_fallback("QuantMaxPool2d -> F.max_pool2d")
         return F.max_pool2d(q, self.kernel_size, self.stride, self.padding, self.dilation, self.ceil_mode, self.return_indices)
 
