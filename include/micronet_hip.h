@@ -674,6 +674,9 @@ int mn_qconv_bnsign_bwd_pooled(const mn_conv_geom* g, const mn_wq* wq, const int
  *   mn_qa_bwd_sums / _apply  dq = d loss / d (pooled) activation -> dgamma, dbeta, sums [2][C]; dy [N][C][H][W] (what conv backward consumes).
  *                            quant != 0: dq is the gradient w.r.t. the QUANTISED activation and the quantizer's clip-STE is applied here;
  *                            quant == 0: dq is the gradient w.r.t. the activation (consumer applied its own STE, or is not quantised).
+ *   pool (all mn_qa_* below): 0 = none; 1 = the 2x2 / stride 2 max-pool (H even, W % 8 == 0); 2 = the 3x3 / stride 2 / padding 1 max-pool in floor mode (H even,
+ *                            W % 8 == 0, H * W <= 4096: LDS-tiled kernels, csrc/qact_pool3.h) -- pooled maps are [N][C][H / 2][W / 2] either way, the winner of a window is
+ *                            its first maximum in row-major order, an element takes the gradient of every window it wins.  Any other value: MN_EINVAL.
  * Backward of the conv itself: mn_conv2d_bwd_data (no STE epilogue) and mn_conv2d_bwd_weight with aq->mode == MN_ACTQ_CODE8. */
 #define MN_QA_NCH 9
 int mn_qconv_bnq_supported(const mn_conv_geom* g, const mn_wq* wq, int a_bits_in);

@@ -22,7 +22,7 @@
 struct QaGeom {
     int N, C, H, W, HW, HW8, W8;
     FastDiv fd_hw8, fd_w8;
-    int64_t n8;             // 8-element groups per channel (no pool) / 4-window groups per channel (pool)
+    int64_t n8;             // 8-element groups per channel (no pool) / 4-window groups per channel (pool 1) / tiles per channel (pool 2: qact_pool3.h)
     float s;                // quantizer scale 1 / (2^a - 1)
     float inv_s;            // RN(1 / s) for the division-free clip-STE (qa_dz_m); 0: the IEEE division
     int nthr;               // > 0 (mn_qa_fwd on the integer stash, <= 3 bit codes): levels 2^a - 1 of the integer-threshold forward
@@ -356,6 +356,8 @@ __global__ __launch_bounds__(256) void k_qa_apply(const QaGeom g, const void* __
     }
 }
 
+#include "qact_pool3.h"          // POOL 2: the 3x3 / stride 2 / padding 1 max-pool, LDS-tiled (k_qa3_fwd, k_qa3_bwd)
+
 // ---------------------------------------------------------------- per-channel constants
 // from (mean, invstd) of a BatchNorm over fp32 y (the first block: save = what mn_bnrelu_fwd / k_bns_final_fwd wrote); alpha = 1, bias = 0
 __global__ void k_qa_chan_f32(int C, const float* __restrict__ save, const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ chan) {
@@ -424,11 +426,13 @@ void qa_launch_stats_prep_const(const double* part, int CB, int Cout, float wsca
 static int qa_geom(QaGeom* g, int64_t N, int64_t C, int64_t H, int64_t W, int bits, int pool, const char* what) {
     const int64_t HW = H * W;
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || HW % 8 || bits < 2 || bits > 8) MN_FAIL(MN_EINVAL, "%s: bad shape / bits (H*W must be a multiple of 8, 2 <= bits <= 8)", what);
+    if (pool < 0 || pool > 2) MN_FAIL(MN_EINVAL, "%s: pool must be 0 (none), 1 (2x2 / stride 2) or 2 (3x3 / stride 2 / padding 1)", what);
     if (pool && ((H & 1) || W % 8)) MN_FAIL(MN_EINVAL, "%s: pooled variant needs even H and W %% 8 == 0", what);
+    if (pool == 2 && HW > P3_TILE) MN_FAIL(MN_EINVAL, "%s: the 3x3 / stride 2 pooled variant needs H * W <= %d", what, P3_TILE);
     if (N * (HW / 8) >= ((int64_t)1 << 31)) MN_FAIL(MN_EINVAL, "%s: tensor too large", what);
     g->N = (int)N; g->C = (int)C; g->H = (int)H; g->W = (int)W; g->HW = (int)HW; g->HW8 = (int)(HW / 8); g->W8 = (int)(W / 8);
     g->fd_hw8 = make_fastdiv((uint32_t)g->HW8); g->fd_w8 = make_fastdiv((uint32_t)(g->W8 > 0 ? g->W8 : 1));
-    g->n8 = pool ? N * (H / 2) * (W / 8) : N * (HW / 8);
+    g->n8 = pool == 2 ? (N + P3_TILE / HW - 1) / (P3_TILE / HW) : pool ? N * (H / 2) * (W / 8) : N * (HW / 8);
     g->s = dorefa_scale(bits);
     g->inv_s = mn_qa_inv(g->s);
     g->nthr = 0;
@@ -436,15 +440,18 @@ static int qa_geom(QaGeom* g, int64_t N, int64_t C, int64_t H, int64_t W, int bi
     g->fin_part = nullptr; g->fin_S = 0; g->fin_dgamma = g->fin_dbeta = g->fin_sums = g->fin_dgamma_s = g->fin_dbeta_s = g->fin_sums_s = nullptr;
     return MN_OK;
 }
-static int qa_split(const QaGeom& g) {
+static int qa_split(const QaGeom& g, int pool = 0) {
     int64_t S = (2048 + g.C - 1) / g.C;
-    const int64_t maxS = (g.n8 + 255) / 256;
+    const int64_t maxS = pool == 2 ? g.n8 : (g.n8 + 255) / 256;          // (pool 2: a block takes a whole tile per step)
     if (S > maxS) S = maxS;
     if (S > 32) S = 32;
     if (S < 1) S = 1;
     return (int)S;
 }
-extern "C" int mn_qa_supported(int64_t H, int64_t W, int pool) { return (H * W) % 8 == 0 && (!pool || ((H & 1) == 0 && W % 8 == 0)); }
+extern "C" int mn_qa_supported(int64_t H, int64_t W, int pool) {
+    if (pool < 0 || pool > 2 || H <= 0 || W <= 0 || (H * W) % 8) return 0;
+    return !pool || ((H & 1) == 0 && W % 8 == 0 && (pool == 1 || H * W <= P3_TILE));
+}
 extern "C" int64_t mn_qa_ws_floats(int64_t C) { return C * 32 * 4 + 2 * C + 16; }
 extern "C" int mn_qa_chan_from_save(const float* save, const float* gamma, const float* beta, int64_t C, float* chan, mn_stream_t stream) {
     if (!save || !gamma || !beta || !chan || C <= 0) MN_FAIL(MN_EINVAL, "mn_qa_chan_from_save: bad arguments");
@@ -456,6 +463,9 @@ extern "C" int mn_qa_chan_from_save(const float* save, const float* gamma, const
     if (in_f32 == 2) { if (pool) hipLaunchKernelGGL((KERNEL<2, 1>), __VA_ARGS__); else hipLaunchKernelGGL((KERNEL<2, 0>), __VA_ARGS__); } \
     else if (in_f32) { if (pool) hipLaunchKernelGGL((KERNEL<1, 1>), __VA_ARGS__); else hipLaunchKernelGGL((KERNEL<1, 0>), __VA_ARGS__); } \
     else { if (pool) hipLaunchKernelGGL((KERNEL<0, 1>), __VA_ARGS__); else hipLaunchKernelGGL((KERNEL<0, 0>), __VA_ARGS__); }
+#define QA3_DISPATCH(KERNEL, X, ...)                                                                                     \
+    if (in_f32 == 2) hipLaunchKernelGGL((KERNEL<2, X>), __VA_ARGS__); else if (in_f32) hipLaunchKernelGGL((KERNEL<1, X>), __VA_ARGS__); \
+    else hipLaunchKernelGGL((KERNEL<0, X>), __VA_ARGS__);
 extern "C" int mn_qa_fwd(int in_f32, const void* in, const float* chan, int64_t N, int64_t C, int64_t H, int64_t W, int a_bits, int pool, uint8_t* codes, float* act_f32,
                          mn_stream_t stream) {
     QaGeom g;
@@ -465,11 +475,18 @@ extern "C" int mn_qa_fwd(int in_f32, const void* in, const float* chan, int64_t 
         MN_FAIL(MN_EINVAL, "mn_qa_fwd: null / misaligned tensor");
     hipStream_t s = (hipStream_t)stream;
     if (!in_f32 && codes && a_bits <= 3) g.nthr = (1 << a_bits) - 1;       // integer-threshold forward
-    const dim3 grid((unsigned)C, (unsigned)qa_split(g));
+    const dim3 grid((unsigned)C, (unsigned)qa_split(g, pool));
     const double nel = (double)N * C * H * W;
-    mn_set_last_kernel("k_qa_fwd<%d, %d>", in_f32, pool ? 1 : 0);
+    mn_set_last_kernel(pool == 2 ? "k_qa3_fwd<%d>" : "k_qa_fwd<%d, %d>", in_f32, pool ? 1 : 0);
     mn_prof_bytes(nel * (in_f32 ? 4.0 : 2.0) + (codes ? 1.0 : 0.0) * nel / (pool ? 4.0 : 1.0) + (act_f32 ? 4.0 : 0.0) * nel / (pool ? 4.0 : 1.0));
     mn_prof_begin(s);
+    if (pool == 2) {
+        if (codes) { QA3_DISPATCH(k_qa3_fwd, 0, grid, dim3(256), 0, s, g, in, chan, codes, (float*)nullptr) }
+        if (act_f32) { QA3_DISPATCH(k_qa3_fwd, 1, grid, dim3(256), 0, s, g, in, chan, (unsigned char*)nullptr, act_f32) }
+        mn_prof_end(s);
+        MN_CHECK_LAUNCH("mn_qa_fwd");
+        return MN_OK;
+    }
     if (in_f32 == 2) {
         if (codes) { if (pool) hipLaunchKernelGGL((k_qa_fwd<2, 1, 0>), grid, dim3(256), 0, s, g, in, chan, codes, (float*)nullptr); else hipLaunchKernelGGL((k_qa_fwd<2, 0, 0>), grid, dim3(256), 0, s, g, in, chan, codes, (float*)nullptr); }
         if (act_f32) { if (pool) hipLaunchKernelGGL((k_qa_fwd<2, 1, 1>), grid, dim3(256), 0, s, g, in, chan, (unsigned char*)nullptr, act_f32); else hipLaunchKernelGGL((k_qa_fwd<2, 0, 1>), grid, dim3(256), 0, s, g, in, chan, (unsigned char*)nullptr, act_f32); }
@@ -515,13 +532,14 @@ extern "C" int mn_qa_bwd_sums(int in_f32, const void* in, const float* chan, con
     if (rc) return rc;
     if (!in || !chan || !dq || !sums || !ws || (((uintptr_t)in) & 15) || !aligned16(dq) || (((uintptr_t)ws) & 7)) MN_FAIL(MN_EINVAL, "mn_qa_bwd_sums: null / misaligned tensor");
     hipStream_t s = (hipStream_t)stream;
-    const int S = qa_split(g);
+    const int S = qa_split(g, pool);
     const dim3 grid((unsigned)C, (unsigned)S);
     const double nel = (double)N * C * H * W;
-    mn_set_last_kernel("k_qa_partial<%d, %d>", in_f32, pool ? 1 : 0);
+    mn_set_last_kernel(pool == 2 ? "k_qa3_bwd<%d, 0>" : "k_qa_partial<%d, %d>", in_f32, pool ? 1 : 0);
     mn_prof_bytes(nel * (in_f32 ? 4.0 : 2.0) + 4.0 * nel / (pool ? 4.0 : 1.0));
     mn_prof_begin(s);
-    QA_DISPATCH(k_qa_partial, grid, dim3(256), 0, s, g, in, chan, dq, quant, (double*)ws)
+    if (pool == 2) { QA3_DISPATCH(k_qa3_bwd, 0, grid, dim3(256), 0, s, g, in, chan, dq, (const float*)nullptr, 0, quant, (float*)nullptr, (double*)ws) }
+    else { QA_DISPATCH(k_qa_partial, grid, dim3(256), 0, s, g, in, chan, dq, quant, (double*)ws) }
     mn_prof_end(s);
     hipLaunchKernelGGL(k_qa_final_bwd, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, s, (int)C, (const double*)ws, S, dgamma, dbeta, sums);
     MN_CHECK_LAUNCH("mn_qa_bwd_sums");
@@ -541,12 +559,13 @@ extern "C" int mn_qa_bwd_apply(int in_f32, const void* in, const float* chan, co
     if (rc) return rc;
     if (!in || !chan || !dq || !sums || !dy || (((uintptr_t)in) & 15) || !aligned16(dq) || !aligned16(dy)) MN_FAIL(MN_EINVAL, "mn_qa_bwd_apply: null / misaligned tensor");
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)C, (unsigned)qa_split(g));
+    const dim3 grid((unsigned)C, (unsigned)qa_split(g, pool));
     const double nel = (double)N * C * H * W;
-    mn_set_last_kernel("k_qa_apply<%d, %d>", in_f32, pool ? 1 : 0);
+    mn_set_last_kernel(pool == 2 ? "k_qa3_bwd<%d, 1>" : "k_qa_apply<%d, %d>", in_f32, pool ? 1 : 0);
     mn_prof_bytes(nel * (in_f32 ? 4.0 : 2.0) + 4.0 * nel / (pool ? 4.0 : 1.0) + 4.0 * nel);
     mn_prof_begin(s);
-    QA_DISPATCH(k_qa_apply, grid, dim3(256), 0, s, g, in, chan, dq, sums, training, quant, dy)
+    if (pool == 2) { QA3_DISPATCH(k_qa3_bwd, 1, grid, dim3(256), 0, s, g, in, chan, dq, sums, training, quant, dy, (double*)nullptr) }
+    else { QA_DISPATCH(k_qa_apply, grid, dim3(256), 0, s, g, in, chan, dq, sums, training, quant, dy) }
     mn_prof_end(s);
     MN_CHECK_LAUNCH("mn_qa_bwd_apply");
     return MN_OK;
@@ -561,19 +580,21 @@ extern "C" int mn_qa_bwd(int in_f32, const void* in, const float* chan, const fl
     if (rc) return rc;
     if (!in || !chan || !dq || !sums || !dy || !ws || (((uintptr_t)in) & 15) || !aligned16(dq) || !aligned16(dy) || (((uintptr_t)ws) & 7)) MN_FAIL(MN_EINVAL, "mn_qa_bwd: null / misaligned tensor");
     hipStream_t s = (hipStream_t)stream;
-    const int S = qa_split(g);
+    const int S = qa_split(g, pool);
     const dim3 grid((unsigned)C, (unsigned)S);
     const double nel = (double)N * C * H * W;
-    mn_set_last_kernel("k_qa_partial<%d, %d>", in_f32, pool ? 1 : 0);
+    mn_set_last_kernel(pool == 2 ? "k_qa3_bwd<%d, 0>" : "k_qa_partial<%d, %d>", in_f32, pool ? 1 : 0);
     mn_prof_bytes(nel * (in_f32 ? 4.0 : 2.0) + 4.0 * nel / (pool ? 4.0 : 1.0));
     mn_prof_begin(s);
-    QA_DISPATCH(k_qa_partial, grid, dim3(256), 0, s, g, in, chan, dq, quant, (double*)ws)
+    if (pool == 2) { QA3_DISPATCH(k_qa3_bwd, 0, grid, dim3(256), 0, s, g, in, chan, dq, (const float*)nullptr, 0, quant, (float*)nullptr, (double*)ws) }
+    else { QA_DISPATCH(k_qa_partial, grid, dim3(256), 0, s, g, in, chan, dq, quant, (double*)ws) }
     mn_prof_end(s);
     g.fin_part = (const double*)ws; g.fin_S = S; g.fin_dgamma = dgamma; g.fin_dbeta = dbeta; g.fin_sums = sums;
-    mn_set_last_kernel("k_qa_apply<%d, %d>", in_f32, pool ? 1 : 0);
+    mn_set_last_kernel(pool == 2 ? "k_qa3_bwd<%d, 1>" : "k_qa_apply<%d, %d>", in_f32, pool ? 1 : 0);
     mn_prof_bytes(nel * (in_f32 ? 4.0 : 2.0) + 4.0 * nel / (pool ? 4.0 : 1.0) + 4.0 * nel);
     mn_prof_begin(s);
-    QA_DISPATCH(k_qa_apply, grid, dim3(256), 0, s, g, in, chan, dq, (const float*)sums, training, quant, dy)
+    if (pool == 2) { QA3_DISPATCH(k_qa3_bwd, 1, grid, dim3(256), 0, s, g, in, chan, dq, (const float*)sums, training, quant, dy, (double*)nullptr) }
+    else { QA_DISPATCH(k_qa_apply, grid, dim3(256), 0, s, g, in, chan, dq, (const float*)sums, training, quant, dy) }
     mn_prof_end(s);
     MN_CHECK_LAUNCH("mn_qa_bwd");
     return MN_OK;

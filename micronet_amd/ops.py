@@ -2782,7 +2782,8 @@ class QActToFloat(Function):
 
 
 def qa_supported(shape, pool):
-    return len(shape) == 4 and bool(_lib_().mn_qa_supported(shape[2], shape[3], int(bool(pool))))
+    """``pool``: 0 none, 1 the 2x2 / stride 2 max-pool, 2 the 3x3 / stride 2 / padding 1 max-pool (a plane of at most 4096 elements)"""
+    return len(shape) == 4 and bool(_lib_().mn_qa_supported(shape[2], shape[3], int(pool)))
 
 
 def _bn_front(y, gamma, beta, running_mean, running_var, eps, momentum, training, nbt, first=None):
@@ -2824,7 +2825,8 @@ def _bn_front(y, gamma, beta, running_mean, running_var, eps, momentum, training
 
 
 class BNReLUQ(Function):
-    """relu(batch_norm(y)) [-> 2x2 max-pool] -> the k-bit activation quantizer of the NEXT QuantConv2d, fused (qact_kernels.hip).
+    """relu(batch_norm(y)) [-> max-pool: ``pool`` 1 = 2x2 / stride 2, 2 = 3x3 / stride 2 / padding 1] -> the k-bit activation quantizer of the NEXT QuantConv2d,
+    fused (qact_kernels.hip, qact_pool3.h).
     y is a ``LazyQConvOut`` (the conv runs here, on codes: 16-bit stash + exact integer statistics; fp32 y never exists) or a plain fp32 tensor (the
     block behind the un-quantised first conv).  Output: a ``QActTensor`` (codes of the ``out_bits`` quantizer; ``out_bits`` > 0) or the fp32 activation
     (``out_bits`` == 0: the consumer is not a quantised conv of ours).  Backward: two streaming passes over (gradient, stash)."""
@@ -2839,7 +2841,8 @@ class BNReLUQ(Function):
         Ho, Wo = (H // 2, W // 2) if pool else (H, W)
         qbits = out_bits if out_bits else 2          # the kernels want a valid width even when no code is produced
         ctx.save_for_backward(src, chan, gamma, beta)
-        ctx.cfg = (in_f32, N, Cc, H, W, qbits, int(bool(pool)), int(training), bool(out_bits))
+        pool = int(pool)
+        ctx.cfg = (in_f32, N, Cc, H, W, qbits, pool, int(training), bool(out_bits))
         ctx.first, ctx.gram = (rec, holder[1]) if rec is not None else (None, None)
         # the conv in front is a pointwise layer k_pwb covers: its backward forms this block's dy itself from (dq, stash) -- the apply pass and its fp32 dy disappear
         ctx.pwb_fold = bool(lazy and not pool and FUSE_PW_BWD and LAZY_BN_GRAD and _lib_().mn_conv2d_bwd_bnh_supported(
@@ -2848,7 +2851,7 @@ class BNReLUQ(Function):
         def materialize():
             act = torch.empty((N, Cc, Ho, Wo), dtype=torch.float32, device=dev)
             with torch.cuda.device(dev):
-                _call("mn_qa_fwd", in_f32, _p(src), _p(chan), N, Cc, H, W, qbits, int(bool(pool)), None, _p(act), _s())
+                _call("mn_qa_fwd", in_f32, _p(src), _p(chan), N, Cc, H, W, qbits, pool, None, _p(act), _s())
             return act
         ctx.mask4 = None
         if not out_bits:
@@ -2859,7 +2862,7 @@ class BNReLUQ(Function):
                 ctx.mask4 = torch.empty((N, Cc, (H * W) // 4), dtype=torch.uint8, device=dev)
                 _call("mn_qa_fwd_f32_mask", _p(src), _p(chan), N, Cc, H, W, qbits, _p(codes), _p(ctx.mask4), _s())
             else:
-                _call("mn_qa_fwd", in_f32, _p(src), _p(chan), N, Cc, H, W, qbits, int(bool(pool)), _p(codes), None, _s())
+                _call("mn_qa_fwd", in_f32, _p(src), _p(chan), N, Cc, H, W, qbits, pool, _p(codes), None, _s())
         out = QActTensor(codes, out_bits, materialize, pooled=bool(pool))
         ctx.up_rec = None
         if lazy and not pool and in_f32 == 0 and UP_SUMS_FOLD:          # (16-bit stash, no pool: the next block's one-launch backward may form this block's sums)

@@ -205,7 +205,7 @@ class BatchNorm2dReLU(nn.BatchNorm2d):
     after it; that ReLU becomes a ``ReLUAfterFusedBN`` (a no-op ``nn.ReLU``)."""
 
     q_out_bits = 0          # > 0 (set by prepare(fuse_blocks=True)): the only consumer is the a-bit activation quantizer of the next QuantConv2d ->
-    q_pool = False          # emit its codes (QActTensor), through the 2x2 max-pool behind the block when q_pool
+    q_pool = False          # emit its codes (QActTensor), through the max-pool behind the block when q_pool (True: 2x2 / stride 2; 2: 3x3 / stride 2 / padding 1)
     q_also_f32 = False      # the consumer is a fused residual block with an identity shortcut: emit the codes AND the fp32 activation (one pass, two autograd outputs)
     emit_minmax = False     # (set by the IAO prepare) leave per-block (min, max) of the output for the observer of the IAO layer that reads it
     iao_lazy_out = False    # (set by the IAO prepare) the only consumer is the next dense IAO QuantConv2d of the same Sequential: behind a conv that left its epilogue
@@ -228,7 +228,7 @@ class BatchNorm2dReLU(nn.BatchNorm2d):
         plain_ok = self.affine and ops.bnrelu_supported(input)
         use_batch = self.training or self.running_mean is None
         stats_ok = self.momentum is not None and (use_batch or self.track_running_stats)
-        pool = bool(self.q_pool and self.q_out_bits)
+        pool = int(self.q_pool) if self.q_out_bits else 0          # mn_qa_*'s pool: 0 / 1 / 2; a shape they refuse keeps the un-fused path and the pool module pools
         if (lazy or (plain_ok and self.q_out_bits)) and self.affine and stats_ok and ops.qa_supported(input.shape, pool):
             nbt = None
             if self.training and self.track_running_stats and self.num_batches_tracked is not None:
@@ -336,9 +336,10 @@ def _is_ref_block(module):
     return bool(getattr(module, "_mn_ordered_forward", False)) or (t.__name__ == "ConvBNReLU" and t.__module__.split(".")[-1] in ("nin", "nin_gc"))
 
 
-def _fuse_blocks(model, fold_shuffle=True):
+def _fuse_blocks(model, fold_shuffle=True, fuse_pool3=False):
     """Second pass of ``prepare(fuse_blocks=True)``: wherever a ``ConvBNReLU`` block's output feeds ONLY the activation quantizer of the next block's
-    QuantConv2d (directly, or through a 2x2 / stride-2 max-pool) inside an ``nn.Sequential``, the producing BatchNorm2dReLU emits that quantizer's
+    QuantConv2d (directly, through a 2x2 / stride-2 max-pool or -- ``fuse_pool3`` -- through a 3x3 / stride-2 / padding-1 one, ``q_pool`` = 2) inside an
+    ``nn.Sequential``, the producing BatchNorm2dReLU emits that quantizer's
     codes (``q_out_bits`` / ``q_pool``), and every QuantConv2d followed by a BatchNorm2dReLU in its block may leave its output un-computed
     (``lazy_for_bn``); the block's channel shuffle moves into the conv's addressing (``in_shuffle_groups``)."""
     def is_block(m):
@@ -346,6 +347,9 @@ def _fuse_blocks(model, fold_shuffle=True):
 
     def two(v):
         return v in (2, (2, 2), [2, 2])
+
+    def plain(p):
+        return p.dilation in (1, (1, 1)) and not p.ceil_mode and not p.return_indices
     for parent in model.modules():
         if not isinstance(parent, nn.Sequential):
             continue
@@ -360,16 +364,17 @@ def _fuse_blocks(model, fold_shuffle=True):
                     blk.conv.in_shuffle_groups = int(blk.shuffle_groups)
                     blk.channel_shuffle_flag = 0
             nxt = kids[i + 1] if i + 1 < len(kids) else None
-            pool = None
-            if isinstance(nxt, MaxPool2dF32) and two(nxt.kernel_size) and two(nxt.stride) and nxt.padding in (0, (0, 0)) and nxt.dilation in (1, (1, 1)) \
-                    and not nxt.ceil_mode and not nxt.return_indices:
+            pool, kind = None, True
+            if isinstance(nxt, MaxPool2dF32) and two(nxt.kernel_size) and two(nxt.stride) and nxt.padding in (0, (0, 0)) and plain(nxt):
                 pool, nxt = nxt, (kids[i + 2] if i + 2 < len(kids) else None)
+            elif fuse_pool3 and isinstance(nxt, MaxPool2dF32) and nxt.kernel_size in (3, (3, 3)) and two(nxt.stride) and nxt.padding in (1, (1, 1)) and plain(nxt):
+                pool, kind, nxt = nxt, 2, (kids[i + 2] if i + 2 < len(kids) else None)
             # (the streaming kernels read either stash width, pooled or not: mn_qa_* with in_kind 0 / 2)
             if nxt is not None and is_block(nxt) and isinstance(nxt.conv, QuantConv2d):
                 bits = nxt.conv.activation_quantizer.a_bits
                 if 2 <= bits <= 8 and 2 <= nxt.conv.weight_quantizer.w_bits <= 8:          # (8-bit codes: the wide kernels, 32-bit stash)
                     blk.bn.q_out_bits = int(bits)
-                    blk.bn.q_pool = pool is not None
+                    blk.bn.q_pool = kind if pool is not None else False
                     from micronet_amd.nn import Conv2dFirst
                     if isinstance(blk.conv, Conv2dFirst) and pool is None and not getattr(blk, "channel_shuffle_flag", 0):
                         blk.conv.lazy_for_bn = "qa"          # the first block: conv + BatchNorm + ReLU + quantizer in one kernel (ops.FirstConvBNReLUQ, knob MN_FIRST_FUSED_QA)
@@ -560,17 +565,19 @@ def add_quant_op(module, layer_counter, a_bits=8, w_bits=8, quant_inference=Fals
             add_quant_op(child, layer_counter, fuse_bn_act=fuse_bn_act, **kw)
 
 
-def prepare(model, inplace=False, a_bits=8, w_bits=8, quant_inference=False, fuse_bn_act=True, fuse_blocks=True, fold_shuffle=True):
+def prepare(model, inplace=False, a_bits=8, w_bits=8, quant_inference=False, fuse_bn_act=True, fuse_blocks=True, fold_shuffle=True, fuse_pool3=False):
     """Same rewrite as the reference (ref 312-320).  ``fuse_bn_act`` (ours, default on): a ``BatchNorm2d`` directly in front of a ``ReLU`` in a
     block that calls them in that order becomes ``BatchNorm2dReLU`` (one fused op) and the ReLU a no-op subclass; with it off the module
     graph is exactly the reference's.  ``fuse_blocks`` (ours, default on, needs ``fuse_bn_act``): conv + BatchNorm + ReLU (+ 2x2 max-pool) + the next
     layer's activation quantizer run as the fused k-bit block of ``_fuse_blocks`` -- activations travel as one-byte codes, the conv output as a
-    16-bit integer stash; numerically the same function (tests compare with it off).  ``fold_shuffle``: see ``_fuse_blocks``."""
+    16-bit integer stash; numerically the same function (tests compare with it off).  ``fold_shuffle``: see ``_fuse_blocks``.  ``fuse_pool3`` (default off,
+    needs ``fuse_blocks``): the 3x3 / stride-2 / padding-1 max-pools of plain ``nin`` are folded into the block in front as well -- a TRAINING graph: the
+    deployment compilers of ``micronet_amd.inference`` expect those pools un-fused."""
     if not inplace:
         model = copy.deepcopy(model)
     add_quant_op(model, [0], a_bits=a_bits, w_bits=w_bits, quant_inference=quant_inference, fuse_bn_act=fuse_bn_act)
     if fuse_bn_act and fuse_blocks:          # (quant_inference graphs too: their convs take the code kernels once the stored weights are on the grid)
-        _fuse_blocks(model, fold_shuffle=fold_shuffle)
+        _fuse_blocks(model, fold_shuffle=fold_shuffle, fuse_pool3=fuse_pool3)
         _fuse_residual_blocks(model)
     if fuse_bn_act:
         from micronet_amd.nn import fuse_tail
