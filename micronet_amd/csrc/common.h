@@ -424,9 +424,13 @@ static int make_pro(const mn_actq* aq, Pro* p, int need_bounds, const char* what
 
 
 // four consecutive elements of the streamed conv input at element offset `off` (a multiple of 4): fp32, or -- MN_ACTQ_SIGN8 --
-// int8 sign codes widened to +-1.0f (any negative byte is -1, anything else +1)
+// int8 sign codes widened to +-1.0f (any negative byte is -1, anything else +1), or -- MN_ACTQ_CODE8 -- k-bit activation codes j (unsigned bytes) widened to j
 template <int XMODE>
 __device__ __forceinline__ float4 mn_ld_x4(const float* base, int64_t off) {
+    if (XMODE == MN_ACTQ_CODE8) {
+        const uint32_t u = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(base) + off);
+        return make_float4((float)(u & 0xffu), (float)((u >> 8) & 0xffu), (float)((u >> 16) & 0xffu), (float)(u >> 24));
+    }
     if (XMODE == MN_ACTQ_SIGN8) {
         const uint32_t u = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(base) + off);
         return make_float4((u & 0x80u) ? -1.f : 1.f, (u & 0x8000u) ? -1.f : 1.f, (u & 0x800000u) ? -1.f : 1.f, (u & 0x80000000u) ? -1.f : 1.f);

@@ -89,6 +89,9 @@ int kk_bwd_data(const mn_conv_geom* g, const mn_actq* aq, const mn_wq* wq, const
 int kk_bwd_weight(const mn_conv_geom* g, const mn_actq* aq, const float* gy, const float* x, float* dw, float* dbias, void* ws,
                   int64_t ws_bytes, hipStream_t s);
 
+// k_kk_wgrad on k-bit activation codes (MN_ACTQ_CODE8): the dense 5 x 5 / stride 1 / padding 2 layers whose forward is k_q5_fwd (qgemm_q5.h)
+int kk_wgrad_code8_supported(const mn_conv_geom* g, int a_bits);
+
 // k x k forward on sign codes that writes the byte stash h instead of y (qgemm_kxk.hip); info: what k_pws_final_fwd / k_pws_chan_prep need
 struct KkH8Info { const uint16_t* codes; const float* rowscale; int Mpad, Kp, K; };
 int kk_h8_supported(const mn_conv_geom* g, const mn_wq* wq);

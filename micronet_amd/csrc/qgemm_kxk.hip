@@ -814,19 +814,27 @@ static void launch_kw(const KwPlan& pl, int xmode, hipStream_t s) {
     } else if (xmode == MN_ACTQ_SIGN8) {
         raise_lds_limit((const void*)k_kk_wgrad<MT, NTL, MN_ACTQ_SIGN8>, pl.lds);
         hipLaunchKernelGGL((k_kk_wgrad<MT, NTL, MN_ACTQ_SIGN8>), dim3(pl.grid), dim3(256), pl.lds, s, pl.p);
+    } else if (xmode == MN_ACTQ_CODE8) {          // bytes read as codes j (exact in bf16); s_a is applied by the reduce
+        raise_lds_limit((const void*)k_kk_wgrad<MT, NTL, MN_ACTQ_CODE8>, pl.lds);
+        hipLaunchKernelGGL((k_kk_wgrad<MT, NTL, MN_ACTQ_CODE8>), dim3(pl.grid), dim3(256), pl.lds, s, pl.p);
     } else {
         raise_lds_limit((const void*)k_kk_wgrad<MT, NTL, MN_ACTQ_NONE>, pl.lds);
         hipLaunchKernelGGL((k_kk_wgrad<MT, NTL, MN_ACTQ_NONE>), dim3(pl.grid), dim3(256), pl.lds, s, pl.p);
     }
 }
 
+int kk_wgrad_code8_supported(const mn_conv_geom* g, int a_bits) {
+    KwPlan kw;
+    return g && a_bits >= 2 && a_bits <= 8 && g->groups == 1 && g->in_shuffle <= 1 && g->KH == 5 && g->KW == 5 && g->stride_h == 1 && g->stride_w == 1 && g->pad_h == 2 &&
+           g->pad_w == 2 && g->dil_h == 1 && g->dil_w == 1 && plan_kk_wgrad(g, &kw);
+}
 int kk_supported(const mn_conv_geom* g, const mn_actq* aq, const mn_wq* wq, int which) {
     KkPlan pl;
     if (which >= 0 && which <= 2 && qd_iao_supported(g, aq, wq, which)) return 1;
     if (which == 0) return wq_codeable(wq) && aq_codeable(aq, 0) && plan_kk(g, 0, aq ? aq->mode : MN_ACTQ_NONE, &pl);
     if (which == 1) return wq_codeable(wq) && (plan_kk(g, 1, MN_ACTQ_NONE, &pl) ||
                                                ((!aq || aq->mode == MN_ACTQ_NONE || aq->mode == MN_ACTQ_CODE8 || aq->mode == MN_ACTQ_SIGN8) && qd_dgrad_native(g, wq)));
-    if (which == 2 && aq && aq->mode == MN_ACTQ_CODE8) return k3s_wgrad_code8_supported(g, aq->bits) || qd_wgrad_supported(g, aq->bits);
+    if (which == 2 && aq && aq->mode == MN_ACTQ_CODE8) return k3s_wgrad_code8_supported(g, aq->bits) || qd_wgrad_supported(g, aq->bits) || kk_wgrad_code8_supported(g, aq->bits);
     if (which == 2) { KwPlan kw; return aq_codeable(aq, 1) && (plan_kk_wgrad(g, &kw) || (aq && aq->mode == MN_ACTQ_SIGN8 && k3s_wgrad_supported(g))); }
     return 0;
 }
@@ -857,12 +865,13 @@ int kk_bwd_weight(const mn_conv_geom* g, const mn_actq* aq, const float* gy, con
         return qd_bwd_weight(g, gy, (const uint8_t*)x, dorefa_scale(aq->bits), dw, ws, ws_bytes, s);
     if (qd_iao_supported(g, aq, nullptr, 2) && ws_bytes >= qd_iao_ws_bytes(g, 2) && aligned16(gy) && aligned16(x))          // dense IAO layers
         return qd_iao_bwd_weight(g, aq, gy, x, dw, dbias, ws, ws_bytes, s);
-    if (aq && aq->mode == MN_ACTQ_CODE8) {        // k-bit activation codes: only the wave-private 3x3 kernel reads them
+    const int code8_kk = aq && aq->mode == MN_ACTQ_CODE8 && kk_wgrad_code8_supported(g, aq->bits);          // dense 5 x 5: k_kk_wgrad<1, 25, MN_ACTQ_CODE8> below
+    if (aq && aq->mode == MN_ACTQ_CODE8 && !code8_kk) {        // k-bit activation codes: otherwise only the wave-private 3x3 kernel reads them
         if (!k3s_wgrad_code8_supported(g, aq->bits) || ws_bytes < k3s_wgrad_ws_bytes(g)) MN_FAIL(MN_ENOTSUP, "mn_conv2d_bwd_weight(code8): geometry / bits not covered");
         return k3s_bwd_weight_code8(g, gy, (const uint8_t*)x, aq->bits, dorefa_scale(aq->bits), dw, dbias, ws, ws_bytes, s);
     }
     KwPlan pl;
-    if (!aq_codeable(aq, 1) || !plan_kk_wgrad(g, &pl) || !aligned16(gy) || !aligned16(x))
+    if ((!code8_kk && !aq_codeable(aq, 1)) || !plan_kk_wgrad(g, &pl) || !aligned16(gy) || (((uintptr_t)x) & (code8_kk ? 3 : 15)))
         MN_FAIL(MN_ENOTSUP, "mn_conv2d_bwd_weight(qgemm): geometry / quantizer combination not covered");
     if (!ws || ws_bytes < pl.ws_bytes || !aligned16(ws)) MN_FAIL(MN_ENOSPC, "mn_conv2d_bwd_weight(qgemm kxk): workspace too small");
     Pro pro;
@@ -877,7 +886,7 @@ int kk_bwd_weight(const mn_conv_geom* g, const mn_actq* aq, const float* gy, con
     else launch_kw<1, 25>(pl, pro.mode, s);
     mn_prof_end(s);
     qg_launch_wgrad_reduce(p.part, p.dbpart, dw, dbias, p.Z, p.G, p.Mg, p.Cg * p.T, p.Mgw, p.Cgw * p.T,
-                           pro.mode == MN_ACTQ_DOREFA ? pro.s : 1.f, pro.mode == MN_ACTQ_IAO ? pro.qp : (const float*)nullptr, s);
+                           (pro.mode == MN_ACTQ_DOREFA || pro.mode == MN_ACTQ_CODE8) ? pro.s : 1.f, pro.mode == MN_ACTQ_IAO ? pro.qp : (const float*)nullptr, s);
     MN_CHECK_LAUNCH("mn_conv2d_bwd_weight(qgemm kxk)");
     return MN_OK;
 }

@@ -1964,9 +1964,11 @@ static int64_t bnq_accmax(const mn_conv_geom* g, const mn_wq* wq, int a_bits) {
 static int bnq_int16_ok(const mn_conv_geom* g, const mn_wq* wq, int a_bits) { return bnq_accmax(g, wq, a_bits) <= 32767; }
 // the WIDE variant of the grouped kernels (XENC 2: bf16 j for j <= 255, 32-bit stash): 8-bit activation codes, or an accumulator beyond int16
 static int bnq_wide(const mn_conv_geom* g, const mn_wq* wq, int a_bits) { return a_bits == 8 || !bnq_int16_ok(g, wq, a_bits); }
+#include "qgemm_q5.h"          // dense 5 x 5 / padding 2 on the int8 matrix cores: k_q5_fwd
 extern "C" int mn_qconv_bnq_supported(const mn_conv_geom* g, const mn_wq* wq, int a_bits_in) {
     if (!g || !wq || wq->mode != MN_WQ_DOREFA || wq->bits < 2 || wq->bits > 8 || a_bits_in < 2 || a_bits_in > 8 || g->groups < 1 || g->C % g->groups || g->O % g->groups) return 0;
     if (qd_fwd_supported(g, wq, a_bits_in) && qd_dgrad_supported(g, wq) && qd_wgrad_supported(g, a_bits_in)) return 1;      // dense layers (ResNets): qgemm_dense.hip
+    if (g->KH == 5 && g->KW == 5) return q5_supported(g, wq, a_bits_in);          // dense 5 x 5 (plain nin): exact in int32, qgemm_q5.h
     const int wide = bnq_wide(g, wq, a_bits_in);
     if (wide && bnq_accmax(g, wq, a_bits_in) >= (1ll << 24)) return 0;          // fp32 accumulation of bf16 integer products must stay exact
     if (g->stride_h != 1 || g->stride_w != 1) return 0;
@@ -1986,6 +1988,7 @@ extern "C" int64_t mn_qconv_bnq_ws_bytes(const mn_conv_geom* g) {
     if (!g) return -1;
     if (qd_fwd_ws_bytes(g) > 0) return qd_fwd_ws_bytes(g);
     if (g->KH == 1 && g->KW == 1) return pws_ws_bytes(g);
+    if (q5_ws_bytes(g) > 0) return q5_ws_bytes(g);
     return ((int64_t)512 * g->O * 2 * 8 + 255) / 256 * 256 + (int64_t)g->O * 4 + 256;      // statistics partials [<= 512][O][2] doubles + the per-channel scale
 }
 __global__ void k_fill_f32(float* __restrict__ p, int n, float v) { const int i = blockIdx.x * blockDim.x + threadIdx.x; if (i < n) p[i] = v; }
@@ -2010,6 +2013,15 @@ extern "C" int mn_qconv_bnq_fwd_stash(const mn_conv_geom* g, const mn_wq* wq, co
     }
     const double npix = (double)g->N * g->H * g->W;
     const int wide = bnq_wide(g, wq, a_bits_in);          // XENC 2, 32-bit stash (mn_qconv_bnq_stash_bits)
+    if (g->KH == 5 && g->KW == 5) {          // dense 5 x 5 / padding 2: the stash and its exact statistics from k_q5_fwd, in training and in eval mode
+        const double* part; int nparts;
+        int rc = q5_fwd_stash(g, wq, x_codes, w, (void*)stash, wide, ws, ws_bytes, s, &part, &nparts);
+        if (rc) return rc;
+        qa_launch_stats_prep_const(part, nparts, (int)g->O, 1.0f / (float)((1ll << wq->bits) - 1), ascale, bias, npix, eps, momentum, training, running_mean, running_var,
+                                   save, gamma, beta, chan, (long long*)num_batches_tracked, s);
+        MN_CHECK_LAUNCH("mn_qconv_bnq_fwd_stash(5x5)");
+        return MN_OK;
+    }
     if (g->KH == 1 && g->KW == 1) {
         PwsPlan pl;
         int rc = pws_prepare(g, wq, (const int8_t*)x_codes, w, ws, ws_bytes, PWS_NT_FWD, &pl, s, "mn_qconv_bnq_fwd_stash");

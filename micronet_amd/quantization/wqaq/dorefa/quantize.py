@@ -121,6 +121,8 @@ def _aq_args(quantizer):
 
 
 class QuantConv2d(nn.Conv2d):
+    code_k5 = False                    # True (set by prepare(code_conv5=True)): a dense 5x5 conv reads a QActTensor's codes itself (k_q5_fwd); a class default, so old pickles load
+
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True,
                  padding_mode="zeros", a_bits=8, w_bits=8, quant_inference=False):
         super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, bias, padding_mode)
@@ -138,7 +140,8 @@ class QuantConv2d(nn.Conv2d):
         if isinstance(input, QActTensor):
             # the block in front already evaluated THIS conv's activation quantizer (codes, one byte per element)
             w_bits = self.weight_quantizer.w_bits
-            if (self.lazy_for_bn and _weight_is_coded(self) and input.bits == bits and mode == ops.ACTQ_DOREFA and
+            k5 = tuple(self.kernel_size) == (5, 5)          # (without the flag a 5x5 keeps the QActToFloat route below)
+            if (self.lazy_for_bn and _weight_is_coded(self) and input.bits == bits and mode == ops.ACTQ_DOREFA and (not k5 or getattr(self, "code_k5", False)) and
                     ops.qconv_bnq_supported(input, quant_weight, self.stride, self.padding, self.dilation, self.groups, w_bits, self.in_shuffle_groups)):
                 return ops.QConvCodeLazy.apply(input, quant_weight, self.bias, self.stride, self.padding, self.dilation, self.groups, w_bits,
                                                self.in_shuffle_groups or 0)
@@ -336,7 +339,7 @@ def _is_ref_block(module):
     return bool(getattr(module, "_mn_ordered_forward", False)) or (t.__name__ == "ConvBNReLU" and t.__module__.split(".")[-1] in ("nin", "nin_gc"))
 
 
-def _fuse_blocks(model, fold_shuffle=True, fuse_pool3=False):
+def _fuse_blocks(model, fold_shuffle=True, fuse_pool3=False, code_conv5=False):
     """Second pass of ``prepare(fuse_blocks=True)``: wherever a ``ConvBNReLU`` block's output feeds ONLY the activation quantizer of the next block's
     QuantConv2d (directly, through a 2x2 / stride-2 max-pool or -- ``fuse_pool3`` -- through a 3x3 / stride-2 / padding-1 one, ``q_pool`` = 2) inside an
     ``nn.Sequential``, the producing BatchNorm2dReLU emits that quantizer's
@@ -359,6 +362,8 @@ def _fuse_blocks(model, fold_shuffle=True, fuse_pool3=False):
                 continue
             if isinstance(blk.conv, QuantConv2d):
                 blk.conv.lazy_for_bn = True
+                if code_conv5 and tuple(blk.conv.kernel_size) == (5, 5) and blk.conv.groups == 1:
+                    blk.conv.code_k5 = True          # the dense 5x5 block runs on the codes of the block in front (mn_qconv_bnq_fwd_stash: k_q5_fwd)
                 if fold_shuffle and getattr(blk, "channel_shuffle_flag", 0) and getattr(blk, "shuffle_groups", 1) > 1 and \
                         blk.conv.in_channels % blk.shuffle_groups == 0:
                     blk.conv.in_shuffle_groups = int(blk.shuffle_groups)
@@ -565,19 +570,22 @@ def add_quant_op(module, layer_counter, a_bits=8, w_bits=8, quant_inference=Fals
             add_quant_op(child, layer_counter, fuse_bn_act=fuse_bn_act, **kw)
 
 
-def prepare(model, inplace=False, a_bits=8, w_bits=8, quant_inference=False, fuse_bn_act=True, fuse_blocks=True, fold_shuffle=True, fuse_pool3=False):
+def prepare(model, inplace=False, a_bits=8, w_bits=8, quant_inference=False, fuse_bn_act=True, fuse_blocks=True, fold_shuffle=True, fuse_pool3=False,
+            code_conv5=False):
     """Same rewrite as the reference (ref 312-320).  ``fuse_bn_act`` (ours, default on): a ``BatchNorm2d`` directly in front of a ``ReLU`` in a
     block that calls them in that order becomes ``BatchNorm2dReLU`` (one fused op) and the ReLU a no-op subclass; with it off the module
     graph is exactly the reference's.  ``fuse_blocks`` (ours, default on, needs ``fuse_bn_act``): conv + BatchNorm + ReLU (+ 2x2 max-pool) + the next
     layer's activation quantizer run as the fused k-bit block of ``_fuse_blocks`` -- activations travel as one-byte codes, the conv output as a
     16-bit integer stash; numerically the same function (tests compare with it off).  ``fold_shuffle``: see ``_fuse_blocks``.  ``fuse_pool3`` (default off,
     needs ``fuse_blocks``): the 3x3 / stride-2 / padding-1 max-pools of plain ``nin`` are folded into the block in front as well -- a TRAINING graph: the
-    deployment compilers of ``micronet_amd.inference`` expect those pools un-fused."""
+    deployment compilers of ``micronet_amd.inference`` expect those pools un-fused.  ``code_conv5`` (default off, needs ``fuse_blocks``): a dense 5x5 /
+    padding-2 QuantConv2d whose input arrives as codes (plain ``nin``'s 96 -> 192 layer behind the first pool: only with ``fuse_pool3``) joins the fused k-bit
+    block as well -- int8-MFMA forward on the codes, integer stash; 2..7-bit operands, otherwise (and with the flag off) the conv keeps the fp32 route."""
     if not inplace:
         model = copy.deepcopy(model)
     add_quant_op(model, [0], a_bits=a_bits, w_bits=w_bits, quant_inference=quant_inference, fuse_bn_act=fuse_bn_act)
     if fuse_bn_act and fuse_blocks:          # (quant_inference graphs too: their convs take the code kernels once the stored weights are on the grid)
-        _fuse_blocks(model, fold_shuffle=fold_shuffle, fuse_pool3=fuse_pool3)
+        _fuse_blocks(model, fold_shuffle=fold_shuffle, fuse_pool3=fuse_pool3, code_conv5=code_conv5)
         _fuse_residual_blocks(model)
     if fuse_bn_act:
         from micronet_amd.nn import fuse_tail
